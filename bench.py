@@ -11,7 +11,16 @@ A "step" = one pass of the hot path over one batch: device collate + forward + L
 dataset (features from the HIP feature builder) is resident in HBM before the timed region.
 Prints ONE JSON line on rank 0.
 
-`roofline` = the scatter-add (esc::agg_fwd_wave): algorithmic bytes per launch / the launch's execution window, measured live in
+A plain run sets up, warms up, times --steps steps and prints the headline (`value`, `ms_per_step`, ...).  Everything else
+(the roofline and per-kernel figures, the second scaling mode of an N > 1 run, the CPU baseline) needs --full:
+
+    python bench.py --gpus 1 --steps 30 --warmup 5 --full
+
+--dump-outputs DIR (e.g. bench_outputs) writes what the last timed step left for its caller as float32 .npy files (loss,
+gradients, updated parameters and BatchNorm running statistics; inputs are seeded, so two builds can be compared output for
+output).
+
+`roofline` (--full) = the scatter-add (esc::agg_fwd_wave): algorithmic bytes per launch / the launch's execution window, measured live in
 the timed region on the device wall clock (first workgroup in -> last wave out, esc_prof_span_*); the hipExtLaunchKernelGGL event
 pairs of all launches (= inter-kernel dispatch gap + kernel) and the committed rocprofv3 trace's average stand beside it
 (`event_pairs`, `rocprofv3_avg_us`; DESIGN.md section 5 has the evidence for that choice of clock).
@@ -43,8 +52,8 @@ def parse():
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--h", type=int, default=3)
     ap.add_argument("--lr", type=float, default=1e-2)
-    ap.add_argument("--cpu_seconds", type=float, default=20.0, help="budget of the cpu_baseline leg (0 = skip)")
-    ap.add_argument("--no_breakdown", action="store_true")
+    ap.add_argument("--cpu_seconds", type=float, default=20.0, help="budget of the cpu_baseline leg of --full (0 = skip)")
+    ap.add_argument("--no_breakdown", action="store_true", help="--full without the per-kernel breakdown steps")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak (default): --batch_size graphs per GPU and step; strong: ONE global batch of --batch_size graphs "
                          "per step, sliced by graph over the ranks (SURVEY 8e)")
@@ -55,6 +64,11 @@ def parse():
                     help="esc_engine_set_side_stream mode (default: the library's; 0 = everything on one stream)")
     ap.add_argument("--path", choices=("engine", "autograd"), default="engine",
                     help="engine: one esc_engine_train_step call per step; autograd: per-op torch.autograd path")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline and per-kernel figures (instrumented timed "
+                         "region), the other scaling mode (N > 1), the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, gradients, parameters, BatchNorm statistics) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -185,31 +199,35 @@ def main():
 
     for i in range(args.warmup):
         step(i)
-    # dominant-kernel timing with HIP events on the launch stream, inside the timed region
-    nv.prof_reset("agg_fwd")
-    # + the kernel's own first-wave-in -> last-wave-out window, stamped by the launches of the first 10 timed steps
-    try:
-        nv.prof_span_arm("agg_fwd", min(args.steps, 10) * max(args.layers - 1, 1))
-    except Exception as exc:                                    # the roofline then falls back to the event pairs (clock says so)
-        print("bench: in-kernel stamps unavailable (%s)" % exc, file=sys.stderr)
-    nv.prof_enable("agg_fwd", True)
+    if args.full:
+        # dominant-kernel timing with HIP events on the launch stream, inside the timed region
+        nv.prof_reset("agg_fwd")
+        # + the kernel's own first-wave-in -> last-wave-out window, stamped by the launches of the first 10 timed steps
+        try:
+            nv.prof_span_arm("agg_fwd", min(args.steps, 10) * max(args.layers - 1, 1))
+        except Exception as exc:                                    # the roofline then falls back to the event pairs (clock says so)
+            print("bench: in-kernel stamps unavailable (%s)" % exc, file=sys.stderr)
+        nv.prof_enable("agg_fwd", True)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(args.warmup + i, count=True)
+        loss = step(args.warmup + i, count=True)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    nv.prof_enable("agg_fwd", False)
-    n_agg, ms_agg = nv.prof_read("agg_fwd")
-    agg_launch_ms = nv.prof_read_all("agg_fwd")
-    try:
-        agg_span_us = [u for u in nv.prof_span_read("agg_fwd") if 0 < u < 1e4]      # (a wrapped / unset stamp is dropped)
-    except Exception:
-        agg_span_us = []
+    if args.dump_outputs and rank == 0:                      # before any further step changes the parameters
+        dump_outputs(args.dump_outputs, loss, opt, model)
+    if args.full:
+        nv.prof_enable("agg_fwd", False)
+        n_agg, ms_agg = nv.prof_read("agg_fwd")
+        agg_launch_ms = nv.prof_read_all("agg_fwd")
+        try:
+            agg_span_us = [u for u in nv.prof_span_read("agg_fwd") if 0 < u < 1e4]      # (a wrapped / unset stamp is dropped)
+        except Exception:
+            agg_span_us = []
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -223,7 +241,7 @@ def main():
     # ---- N > 1: the OTHER scaling mode, same K / W, barrier and max-over-ranks timing (SURVEY 8e slices ONE global batch of
     # --batch_size graphs over the ranks = "strong"; the headline default keeps --batch_size graphs per GPU = "weak") ------
     other = None
-    if world > 1:
+    if args.full and world > 1:
         other_mode = "strong" if args.scaling == "weak" else "weak"
         if other_mode == "strong" and rank != 0:           # strong: every rank slices the SAME split (rank 0's)
             g0 = build_count_dataset(0, args.graphs, h=args.h, use_rd=True, self_loop=True)
@@ -266,7 +284,7 @@ def main():
 
     # ---- per-family breakdown (separate instrumented steps, not part of `value`) -------------------
     breakdown = {}
-    if not args.no_breakdown:
+    if args.full and not args.no_breakdown:
         fams = ["agg_fwd", "agg_bwd", "bag_fwd", "bag_bwd", "linear", "norm", "collate"]
         for f in fams:
             nv.prof_reset(f)
@@ -283,7 +301,7 @@ def main():
     # the same Linear kernels with the step on ONE stream: each launch has the CUs to itself, so this is what the GEMM
     # kernels do alone; the figure above is what they do while the other pipeline's kernels share the machine
     linear_one_stream_ms = None
-    if not args.no_breakdown and args.path == "engine" and world == 1:
+    if args.full and not args.no_breakdown and args.path == "engine" and world == 1:
         nv.call("esc_engine_set_side_stream", 0)
         for i in range(2):
             step(i)
@@ -299,7 +317,7 @@ def main():
     # the dominant MFMA kernel on its own: the 128x128x32 tile family that runs the edge-row Linear layers (z_embedding.3 and
     # conv*.lin, forward and the fused dX+dW launch) — event pairs per launch inside the normal two-stream step
     edge_gemm = None
-    if not args.no_breakdown and args.path == "engine" and world == 1:
+    if args.full and not args.no_breakdown and args.path == "engine" and world == 1:
         nv.prof_reset("gemm_edge")
         nv.prof_enable("gemm_edge", True)
         for i in range(5):
@@ -321,6 +339,47 @@ def main():
     value = total_graphs / elapsed
     edges_agg_per_s = total_edges * args.layers / elapsed
 
+    out = {
+        "metric": "graphs/sec + edges-aggregated/sec, NestedGIN_eff h=3 bs=128 @1/2/4/8 GPU",
+        "value": round(value, 1), "unit": "graphs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_step, 3), "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "count_cycle-shaped random regular graphs (n in 10/15/20/30), target=triangles, "
+                               "NestedGIN_eff h=%d layers=%d hidden=%d, bs=%d per GPU (configs[1])"
+                               % (args.h, args.layers, args.hidden, args.batch_size),
+                   "global_batch": args.batch_size * (world if args.scaling == "weak" else 1),
+                   "parallelism": "dp%d graph-sharded" % world, "step_path": args.path,
+                   "rccl_ranks": (dist.get_world_size() if (world > 1 and dist.get_backend() == "nccl") else (1 if world == 1 else 0)),
+                   "ranks": world,
+                   "collective_backend": (dist.get_backend() if world > 1 else None),
+                   "grad_allreduce": ("two buckets: node-pipeline gradients during the edge backward tail, edge-pipeline gradients "
+                                      "+ node count after the join" if world > 1 else None),
+                   "nodes_per_batch": round(N_avg, 1), "edges_per_batch": round(E_avg, 1),
+                   "nnz_per_batch": round(stats["nnz"] / args.steps, 1)},
+        "edges_aggregated_per_s": round(edges_agg_per_s, 1),
+        "feature_build": {"graphs": args.graphs, "seconds": round(t_feat, 3),
+                          "note": "graph generation (networkx) + HIP create_subgraphs_many + host copies"},
+    }
+    if args.full:                     # rooflines, per-kernel figures, the CPU baseline and (N > 1) the other scaling mode
+        roofline, extra = full_figures(args, N_avg, E_avg, n_agg, ms_agg, agg_launch_ms, agg_span_us, breakdown,
+                                       linear_one_stream_ms, edge_gemm)
+        out["roofline"] = roofline
+        out["cpu_baseline"] = cpu_baseline(args, graphs) if (args.cpu_seconds > 0 and world == 1) else None   # rank 0, N=1 only
+        out["kernel_ms_per_step"] = {k: round(v["ms_per_step"], 4) for k, v in breakdown.items()}
+        if world > 1:                 # both scaling modes in one line: `value` is the --scaling one, the other rides along
+            this = dict(scaling=args.scaling, value=out["value"], unit="graphs/s", ms_per_step=out["ms_per_step"],
+                        edges_aggregated_per_s=out["edges_aggregated_per_s"], global_batch=out["config"]["global_batch"],
+                        graphs_per_rank_and_step=round(total_graphs / args.steps / world, 1))
+            out[args.scaling] = this
+            out[other["scaling"]] = other
+        out.update(extra)
+    print(json.dumps(out))
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_figures(args, N_avg, E_avg, n_agg, ms_agg, agg_launch_ms, agg_span_us, breakdown, linear_one_stream_ms, edge_gemm):
+    """--full: the scatter-add roofline from the timed region's instrumentation and the MFMA roofline from the breakdown."""
     # roofline of the scatter-add: the row-per-wave aggregate-forward kernel, launched by the (L-1) layers of
     # width `hidden` (the 10-wide first layer runs the narrow element kernel and is not in this average)
     alg_bytes = aggregate_bytes(N_avg, E_avg, args.hidden)
@@ -414,42 +473,28 @@ def main():
         else:
             extra["roofline_mfma"] = dict(kernel=allin["kernels"], bound="mfma", achieved=allin["achieved"], peak=MFMA_F32_PEAK_TF,
                                           unit="TFLOP/s", frac=allin["frac"], flops_per_step=allin["flops_per_step"], all_linear=allin)
-    cpu = cpu_baseline(args, graphs) if (args.cpu_seconds > 0 and world == 1) else None   # rank 0, N=1 only
+    return roofline, extra
 
-    out = {
-        "metric": "graphs/sec + edges-aggregated/sec, NestedGIN_eff h=3 bs=128 @1/2/4/8 GPU",
-        "value": round(value, 1), "unit": "graphs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_step, 3), "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "count_cycle-shaped random regular graphs (n in 10/15/20/30), target=triangles, "
-                               "NestedGIN_eff h=%d layers=%d hidden=%d, bs=%d per GPU (configs[1])"
-                               % (args.h, args.layers, args.hidden, args.batch_size),
-                   "global_batch": args.batch_size * (world if args.scaling == "weak" else 1),
-                   "parallelism": "dp%d graph-sharded" % world, "step_path": args.path,
-                   "rccl_ranks": (dist.get_world_size() if (world > 1 and dist.get_backend() == "nccl") else (1 if world == 1 else 0)),
-                   "ranks": world,
-                   "collective_backend": (dist.get_backend() if world > 1 else None),
-                   "grad_allreduce": ("two buckets: node-pipeline gradients during the edge backward tail, edge-pipeline gradients "
-                                      "+ node count after the join" if world > 1 else None),
-                   "nodes_per_batch": round(N_avg, 1), "edges_per_batch": round(E_avg, 1),
-                   "nnz_per_batch": round(stats["nnz"] / args.steps, 1)},
-        "edges_aggregated_per_s": round(edges_agg_per_s, 1),
-        "roofline": roofline,
-        "cpu_baseline": cpu,
-        "feature_build": {"graphs": args.graphs, "seconds": round(t_feat, 3),
-                          "note": "graph generation (networkx) + HIP create_subgraphs_many + host copies"},
-        "kernel_ms_per_step": {k: round(v["ms_per_step"], 4) for k, v in breakdown.items()},
-    }
-    if world > 1:                     # both scaling modes in one line: `value` is the --scaling one, the other rides along
-        this = dict(scaling=args.scaling, value=out["value"], unit="graphs/s", ms_per_step=out["ms_per_step"],
-                    edges_aggregated_per_s=out["edges_aggregated_per_s"], global_batch=out["config"]["global_batch"],
-                    graphs_per_rank_and_step=round(total_graphs / args.steps / world, 1))
-        out[args.scaling] = this
-        out[other["scaling"]] = other
-    out.update(extra)
-    print(json.dumps(out))
-    if world > 1:
-        dist.destroy_process_group()
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, loss, opt, model):
+    """What the last timed step left for its caller, as float32 DIR/<name>.npy: its loss, the gradients and the updated
+    parameters (the optimiser's flat buffers, model.parameters() order) and the BatchNorm running statistics (model.buffers()
+    order).  Should they exceed 64 MB together, every array is cut to a fixed, seeded sample of its elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    stats = [b.detach().reshape(-1).float() for b in model.buffers() if b.is_floating_point()]
+    arrays = {"loss": loss.detach().reshape(-1), "grad": opt.flat_grad.detach(), "params": opt.flat_param.detach(),
+              "bn_running_stats": torch.cat(stats) if stats else torch.zeros(0)}
+    total = sum(4 * a.numel() for a in arrays.values())
+    for name, a in arrays.items():
+        a = a.float().cpu().numpy().reshape(-1)
+        if total > DUMP_LIMIT_BYTES and a.size > 1:
+            keep = max(1, a.size * DUMP_LIMIT_BYTES // total)
+            a = a[np.sort(np.random.RandomState(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(args, graphs):

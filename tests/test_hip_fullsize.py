@@ -169,15 +169,23 @@ def test_train_step_against_fp64_oracle_at_full_size(E, world):
     twin = copy.deepcopy(mine)
     twin.engine_forward = False                  # per-op autograd path: a second implementation of the same step
     cpu = {k: b[k].cpu() for k in ("x", "edge_index", "pos_enc", "pos_index", "pos_batch", "batch", "y")}
-    ref.train()
-    pr = ref(cpu["x"], cpu["edge_index"], cpu["pos_enc"], cpu["pos_index"], cpu["pos_batch"], cpu["batch"])
-    lr = torch.nn.functional.l1_loss(pr, cpu["y"].view(-1, 1))
-    lr.backward()
-    ref64 = copy.deepcopy(ref).double()
-    ref64.zero_grad()
-    p64 = ref64(cpu["x"].double(), cpu["edge_index"], cpu["pos_enc"], cpu["pos_index"], cpu["pos_batch"], cpu["batch"])
-    l64 = torch.nn.functional.l1_loss(p64, cpu["y"].double().view(-1, 1))
-    l64.backward()
+    # The fp32 oracle's own error sets the bar of every gradient below, and it moves with the host's thread count (each count
+    # splits the CPU reductions differently: x_embedding.0.weight 7.0e-6 on 1 thread, 3.9e-6 on 16).  The oracles run on ONE
+    # thread, so that the bar is the same on every machine the test runs on.
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        ref.train()
+        pr = ref(cpu["x"], cpu["edge_index"], cpu["pos_enc"], cpu["pos_index"], cpu["pos_batch"], cpu["batch"])
+        lr = torch.nn.functional.l1_loss(pr, cpu["y"].view(-1, 1))
+        lr.backward()
+        ref64 = copy.deepcopy(ref).double()
+        ref64.zero_grad()
+        p64 = ref64(cpu["x"].double(), cpu["edge_index"], cpu["pos_enc"], cpu["pos_index"], cpu["pos_batch"], cpu["batch"])
+        l64 = torch.nn.functional.l1_loss(p64, cpu["y"].double().view(-1, 1))
+        l64.backward()
+    finally:
+        torch.set_num_threads(threads)
 
     eng = E.StepEngine(mine)
     mine.train()
