@@ -1053,15 +1053,19 @@ static Layout plan_layout_zinc(const esc_zinc_gin_t* m, int64_t N, int64_t E, in
     y.conv[l].Y0 = a.take(N * H); y.conv[l].Y1 = a.take(N * H); y.conv[l].A1 = a.take(N * H);
     y.conv[l].b0 = take_bn(a, H); y.conv[l].b1 = take_bn(a, H);
   }
-  y.cat = a.take(N * y.W); y.pooled = a.take(G * y.W); y.Yl = a.take(G * H); y.Al = a.take(G * H); y.bl = take_bn(a, H);
-  y.pred = a.take(G); y.dpred = a.take(G);
+  // readout rows: the G pooled rows, or (node_readout) the N node rows of cat itself — no pooled / dpool then
+  const bool nodes = m->node_readout != 0;
+  const int64_t R = nodes ? N : G;
+  y.cat = a.take(N * y.W); y.pooled = nodes ? nullptr : a.take(G * y.W); y.Yl = a.take(R * H); y.Al = a.take(R * H);
+  y.bl = take_bn(a, H);
+  y.pred = a.take(R); y.dpred = a.take(R);
   y.bn_scratch = a.take(esc_bn_scratch(H));
   y.col_stats = a.take(2 * ((E > N ? E : N) / 32 + 1) * H);
   y.col_stats_b = a.take(2 * (N / 32 + 1) * H);
   y.bn_scratch_e = a.take(esc_bn_scratch(H));
   y.col_stats_e = a.take(2 * (E / 32 + 1) * H);
   if (train) {
-    y.dcat = a.take(N * y.W); y.dpool = a.take(G * y.W); y.dAl = a.take(G * H);
+    y.dcat = a.take(N * y.W); y.dpool = nodes ? nullptr : a.take(G * y.W); y.dAl = a.take(R * H);
     y.bst_part = a.take(2 * (N / 4 + E / 64 + 4) * H);
     y.dT1 = a.take(N * H); y.dT2 = a.take(N * H); y.dagg = a.take(N * H); y.dX0 = a.take(N * C0);
     y.dZcat = a.take(E * y.Wz); y.dZemb = a.take(E * H); y.dAz = a.take(E * H);
@@ -1074,7 +1078,7 @@ static Layout plan_layout_zinc(const esc_zinc_gin_t* m, int64_t N, int64_t E, in
       sl += esc_linear_bwd_weight_scratch(E, C, y.Wz) + esc_linear_bwd_weight_scratch(N, H, H) +
             esc_linear_bwd_weight_scratch(N, H, C) + 3 * 64;                                       // conv.lin, nn.lin1, nn.lin0
     }
-    sl += esc_linear_bwd_weight_scratch(G, H, y.W) + esc_linear_bwd_weight_scratch(G, 1, H) + 2 * 64;   // lin1, lin2
+    sl += esc_linear_bwd_weight_scratch(R, H, y.W) + esc_linear_bwd_weight_scratch(R, 1, H) + 2 * 64;   // lin1, lin2
     y.slabs = a.take(sl);
   }
   y.total = a.off;
@@ -1156,11 +1160,16 @@ static int forward_zinc(const ZincCtx& z) {
     }
     ESC_TRY(mlp_forward(c, cv.nn, y.conv[l], y.agg[l], C, N, y.cat + (int64_t)l * H, W));
   }
-  // readout (:601-609): global_add_pool -> lin1 -> bn_lin1 -> ELU -> lin2
-  ESC_TRY(esc_segment_pool_fwd(y.cat, W, b->graph_ptr, G, W, 0, y.pooled, W, c.s));
-  ESC_TRY(linear_bn(c, y.pooled, W, m->lin1, nullptr, nullptr, G, y.Yl, m->bn_lin1, y.bl));
-  ESC_TRY(esc_affine_act(y.Yl, H, G, H, y.bl.scale, y.bl.shift, act, y.Al, H, c.s));
-  ESC_TRY(esc_linear_fwd(y.Al, H, m->lin2.w, H, m->lin2.b, nullptr, nullptr, G, 1, H, y.pred, 1, nullptr, c.s));
+  // readout (:601-609): global_add_pool -> lin1 -> bn_lin1 -> ELU -> lin2; node_readout: lin1 reads the N rows of cat directly
+  const int64_t R = m->node_readout ? N : G;
+  const float* rin = y.cat;
+  if (!m->node_readout) {
+    ESC_TRY(esc_segment_pool_fwd(y.cat, W, b->graph_ptr, G, W, 0, y.pooled, W, c.s));
+    rin = y.pooled;
+  }
+  ESC_TRY(linear_bn(c, rin, W, m->lin1, nullptr, nullptr, R, y.Yl, m->bn_lin1, y.bl));
+  ESC_TRY(esc_affine_act(y.Yl, H, R, H, y.bl.scale, y.bl.shift, act, y.Al, H, c.s));
+  ESC_TRY(esc_linear_fwd(y.Al, H, m->lin2.w, H, m->lin2.b, nullptr, nullptr, R, 1, H, y.pred, 1, nullptr, c.s));
   if (es.ok) ESC_TRY(chain(es.joined, es.stream, (hipStream_t)c.s));    // forward-only calls return ordered behind the edge stream
   return ESC_OK;
 }
@@ -1177,10 +1186,15 @@ static int backward_zinc(const ZincCtx& z) {
   edge_jobs.reserve(ESC_MAX_REDUCE_JOBS);
   if (es.ok && c.jobs) ce.jobs = &edge_jobs;
   if (es.ok) ESC_TRY(chain(es.z_ready, (hipStream_t)c.s, es.stream));
-  ESC_TRY(linear_backward(c, y.dpred, 1, y.Al, H, nullptr, nullptr, m->lin2, G, y.dAl, H, 0));
-  ESC_TRY(bn_backward(c, y.Yl, H, y.Al, H, y.dAl, H, G, y.bl, m->bn_lin1, y.dAl, H, y.bn_scratch));
-  ESC_TRY(linear_backward(c, y.dAl, H, y.pooled, W, nullptr, nullptr, m->lin1, G, y.dpool, W, 0));
-  ESC_TRY(esc_segment_pool_bwd(y.dpool, W, b->graph_ptr, G, W, 0, y.dcat, W, c.s));
+  const int64_t R = m->node_readout ? N : G;
+  ESC_TRY(linear_backward(c, y.dpred, 1, y.Al, H, nullptr, nullptr, m->lin2, R, y.dAl, H, 0));
+  ESC_TRY(bn_backward(c, y.Yl, H, y.Al, H, y.dAl, H, R, y.bl, m->bn_lin1, y.dAl, H, y.bn_scratch));
+  if (m->node_readout) {              // lin1's dX is the whole dcat (every column block: the layers below add into it)
+    ESC_TRY(linear_backward(c, y.dAl, H, y.cat, W, nullptr, nullptr, m->lin1, N, y.dcat, W, 0));
+  } else {
+    ESC_TRY(linear_backward(c, y.dAl, H, y.pooled, W, nullptr, nullptr, m->lin1, G, y.dpool, W, 0));
+    ESC_TRY(esc_segment_pool_bwd(y.dpool, W, b->graph_ptr, G, W, 0, y.dcat, W, c.s));
+  }
   std::vector<esc_sum_job> eps_jobs;
   for (int l = (int)L - 1; l >= 0; --l) {
     const esc_conv_t& cv = m->conv[l];
@@ -1238,7 +1252,9 @@ static int check_zinc(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, const f
               "esc_zinc: embedding widths must be multiples of 4");
   ESC_REQUIRE(m->conv[0].lin.in_dim == m->hidden + m->edge_emb.dim && m->conv[0].lin.out_dim == m->node_emb.dim,
               "esc_zinc: conv1.lin must map hidden + edge width to the node width");
-  ESC_REQUIRE(b->N >= 2 && b->E >= 2 && b->Z >= 0 && b->G >= 2, "esc_zinc: batch needs >= 2 nodes, edges and graphs (BatchNorm statistics)");
+  ESC_REQUIRE(m->node_readout == 0 || m->node_readout == 1, "esc_zinc: node_readout must be 0 or 1");
+  ESC_REQUIRE(b->N >= 2 && b->E >= 2 && b->Z >= 0 && b->G >= (m->node_readout ? 1 : 2),
+              "esc_zinc: batch needs >= 2 nodes, edges and %s (BatchNorm statistics)", m->node_readout ? "1 graph" : "graphs");
   ESC_REQUIRE(b->node_type && b->edge_type && b->graph_ptr && b->in_ptr && b->row_ptr &&
               (!train || ((b->y || !need_y) && b->out_ptr && b->col_ptr)), "esc_zinc: null batch arrays");
   ESC_REQUIRE(aligned16(ws), "esc_zinc: workspace must be 16-byte aligned");
@@ -1831,6 +1847,9 @@ int64_t esc_zinc_workspace_floats(const esc_zinc_gin_t* m, int64_t N, int64_t E,
   return plan_layout_zinc(m, N, E, Z, G, nullptr, true).total + 64;
 }
 
+// rows of pred / dpred / y: one per graph, or one per node (node_readout)
+static int64_t zinc_rows(const esc_zinc_gin_t* m, const esc_mol_batch_t* b) { return m->node_readout ? b->N : b->G; }
+
 static int copy_floats(float* dst, const float* src, int64_t n, void* stream, const char* what) {
   if (hipMemcpyAsync(dst, src, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
     set_error("%s: copy failed", what);
@@ -1850,9 +1869,10 @@ int esc_zinc_train_step(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, float
   jobs.reserve(ESC_MAX_REDUCE_JOBS);
   float* cursor = z.c.y.slabs;
   if (3 * m->num_layers + 3 <= ESC_MAX_REDUCE_JOBS) { z.c.jobs = &jobs; z.c.slab_cursor = &cursor; }
+  const int64_t R = zinc_rows(m, b);
   ESC_TRY(forward_zinc(z));
-  ESC_TRY(esc_l1_loss(z.c.y.pred, b->y, b->G, loss_denom > 0 ? loss_denom : b->G, 1.0f, loss, z.c.y.dpred, stream));
-  if (pred) ESC_TRY(copy_floats(pred, z.c.y.pred, b->G, stream, "esc_zinc_train_step"));
+  ESC_TRY(esc_l1_loss(z.c.y.pred, b->y, R, loss_denom > 0 ? loss_denom : R, 1.0f, loss, z.c.y.dpred, stream));
+  if (pred) ESC_TRY(copy_floats(pred, z.c.y.pred, R, stream, "esc_zinc_train_step"));
   return backward_zinc(z);
 }
 
@@ -1866,7 +1886,7 @@ int esc_zinc_forward_train(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, fl
   float* cursor = z.c.y.slabs;
   z.c.jobs = &jobs; z.c.slab_cursor = &cursor;
   ESC_TRY(forward_zinc(z));
-  return copy_floats(pred, z.c.y.pred, b->G, stream, "esc_zinc_forward_train");
+  return copy_floats(pred, z.c.y.pred, zinc_rows(m, b), stream, "esc_zinc_forward_train");
 }
 
 int esc_zinc_backward(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, float* workspace, const float* dpred, void* stream) {
@@ -1879,7 +1899,7 @@ int esc_zinc_backward(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, float* 
   jobs.reserve(ESC_MAX_REDUCE_JOBS);
   float* cursor = z.c.y.slabs;
   if (3 * m->num_layers + 3 <= ESC_MAX_REDUCE_JOBS) { z.c.jobs = &jobs; z.c.slab_cursor = &cursor; }
-  ESC_TRY(copy_floats(z.c.y.dpred, dpred, b->G, stream, "esc_zinc_backward"));
+  ESC_TRY(copy_floats(z.c.y.dpred, dpred, zinc_rows(m, b), stream, "esc_zinc_backward"));
   return backward_zinc(z);
 }
 
@@ -1890,7 +1910,7 @@ int esc_zinc_predict(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, float* w
   ESC_REQUIRE(pred, "esc_zinc_predict: null output");
   ZincCtx z = make_zinc(m, b, workspace, stream, false);
   ESC_TRY(forward_zinc(z));
-  return copy_floats(pred, z.c.y.pred, b->G, stream, "esc_zinc_predict");
+  return copy_floats(pred, z.c.y.pred, zinc_rows(m, b), stream, "esc_zinc_predict");
 }
 
 // ---- OGB molecule variant ------------------------------------------------------------------------------------------------

@@ -136,3 +136,53 @@ def build_feature_dataset(raw, h, use_rd=True, self_loop=False):
     for d in done:
         d.num_nodes = None
     return done
+
+
+def _ring_closing_edges(seed, n_lo=18, n_hi=30):
+    """Random tree on n in [n_lo, n_hi] nodes + 1-4 ring closures between tree nodes 2..5 apart (3- to 6-rings; a closure
+    may cut across an earlier ring, giving fused ring systems); both directions, sorted by (src, dst)."""
+    rng = np.random.RandomState(seed)
+    n = int(rng.randint(n_lo, n_hi + 1))
+    parent = [-1] + [int(rng.randint(0, i)) for i in range(1, n)]
+    und = {(parent[i], i) for i in range(1, n)}
+    depth = [0] * n
+    for i in range(1, n):
+        depth[i] = depth[parent[i]] + 1
+
+    def tree_dist(a, b):
+        d = 0
+        while a != b:
+            if depth[a] < depth[b]:
+                a, b = b, a
+            a, d = parent[a], d + 1
+        return d
+
+    for _ in range(int(rng.randint(1, 5))):
+        for _try in range(40):
+            a, b = sorted(map(int, rng.randint(0, n, size=2)))
+            if a != b and (a, b) not in und and 2 <= tree_dist(a, b) <= 5:
+                und.add((a, b))
+                break
+    both = sorted(und | {(b, a) for a, b in und})
+    return n, np.array(both, dtype=np.int64).T, rng
+
+
+def synthetic_zinc_cycle_graphs(first, count):
+    """ZINC cycle-counting layout (reference dataset_zinc_cycle.py:45-61): the ZINC node / edge fields of
+    synthetic_zinc_graphs (atom type in [0,28), bond type in [0,4), coalesced edges in both directions) on seeded
+    ring-closed trees, and y = float32 [n, 4]: the 3-, 4-, 5- and 6-cycles through every node, counted on the device
+    (cycles.cycle_counts)."""
+    from .cycles import cycle_counts
+    out = []
+    for g in range(first, first + count):
+        n, ei, rng = _ring_closing_edges(90000 + g)
+        x = torch.tensor(rng.randint(0, 28, size=n))
+        bond = rng.randint(0, 4, size=ei.shape[1])
+        key = {}
+        for k in range(ei.shape[1]):                       # same bond type in both directions
+            a, b = int(ei[0, k]), int(ei[1, k])
+            bond[k] = key.setdefault((min(a, b), max(a, b)), bond[k])
+        out.append(Data(x=x, edge_index=torch.tensor(ei), edge_attr=torch.tensor(bond), y=None, num_nodes=n))
+    for d, y in zip(out, cycle_counts(out)):
+        d.y = y
+    return out

@@ -56,7 +56,8 @@ class _ZincModel(ctypes.Structure):
     _fields_ = [("num_layers", c_int64), ("hidden", c_int64), ("z_rows", c_int64),
                 ("z_table", c_void_p), ("dz_table", c_void_p),
                 ("zbn0", _BN), ("zlin", _Linear), ("zbn1", _BN), ("node_emb", _Embed), ("edge_emb", _Embed),
-                ("conv", _Conv * MAX_LAYERS), ("lin1", _Linear), ("bn_lin1", _BN), ("lin2", _Linear)]
+                ("conv", _Conv * MAX_LAYERS), ("lin1", _Linear), ("bn_lin1", _BN), ("lin2", _Linear),
+                ("node_readout", c_int32), ("pad_", c_int32)]
 
 
 class _MolBatch(ctypes.Structure):
@@ -559,7 +560,13 @@ def describe_zinc(m, gp=_grad_ptr):
         c.nn, c.lin = _mlp(cv.nn, gp), _lin(cv.lin, gp)
         d.conv[i] = c
     d.lin1, d.bn_lin1, d.lin2 = _lin(m.lin1, gp), _bn(m.bn_lin1, gp), _lin(m.lin2, gp)
+    d.node_readout = int(bool(getattr(m, "node_readout", False)))
     return d
+
+
+def _zinc_rows(m, b):
+    """rows of pred / y: one per graph, or one per node for the cycle-counting model (node_readout)"""
+    return b.N if getattr(m, "node_readout", False) else b.G
 
 
 def zinc_engine_supports(m, data=None):
@@ -575,15 +582,19 @@ def zinc_engine_supports(m, data=None):
 
 
 def zinc_engine_ready(m, data):
-    """zinc_engine_supports and at least two graphs in this batch"""
+    """zinc_engine_supports and at least two graphs in this batch — two nodes for the node-level readout (zinc_cycle_models:
+    bn_lin1 normalises over the nodes)"""
     if not zinc_engine_supports(m, data):
         return False
     from .plan import graph_ptr_of
     from .run_graphcount import Z_TABLE_ROWS
-    return graph_ptr_of(data, plan_of(data, Z_TABLE_ROWS))[1] >= 2
+    plan = plan_of(data, Z_TABLE_ROWS)
+    if getattr(m, "node_readout", False):
+        return plan.num_nodes >= 2
+    return graph_ptr_of(data, plan)[1] >= 2
 
 
-def _zinc_batch(model, data, need_y):
+def _zinc_batch(model, data, need_y, y=None):
     from .plan import graph_ptr_of
     from .run_graphcount import Z_TABLE_ROWS
     dev = model.lin1.weight.device
@@ -615,12 +626,13 @@ def _zinc_batch(model, data, need_y):
             raise IndexError("ZINC engine: %s holds a type id outside the %d-row embedding table" % (key, rows))
         src._esc_zinc_checked = (src._version, rows)
     b.node_type, b.edge_type, b.graph_ptr = nt.data_ptr(), et.data_ptr(), gptr.data_ptr()
-    y = None
     if need_y:
-        y = data.y.reshape(-1)
+        y = (data.y if y is None else y).reshape(-1)
         y = y if (y.dtype == torch.float32 and y.is_contiguous()) else y.float().contiguous()
-        if y.numel() != G:
-            raise ValueError("ZINC engine: expected one target per graph")
+        if y.numel() != _zinc_rows(model, b):
+            raise ValueError("ZINC engine: expected one target per %s" % ("node" if getattr(model, "node_readout", False) else "graph"))
+        if y.device != dev:
+            y = y.to(dev)
         b.y = y.data_ptr()
     for f in ("in_ptr", "in_edge", "in_src", "out_ptr", "out_edge", "out_dst", "row_ptr", "bag_idx", "bag_val",
               "col_ptr", "col_row", "col_val", "col_col"):
@@ -658,14 +670,15 @@ class ZincStepEngine(_AddressGuard):
         _zinc_batch(self.model, data, False)
         return data
 
-    def train_step(self, data, loss_denom=None, return_pred=False):
-        """forward + L1 over the graphs + backward; gradients land in the parameters' .grad (overwritten)"""
+    def train_step(self, data, loss_denom=None, return_pred=False, y=None):
+        """forward + L1 over the graphs (the nodes, for the node-level readout) + backward; gradients land in the parameters'
+        .grad (overwritten).  `y`: the target column when it is not data.y itself (run_zinc_cycle: data.y[:, target])."""
         dev = self.model.lin1.weight.device
         self._guard_check()
-        b, keep = _zinc_batch(self.model, data, True)
+        b, keep = _zinc_batch(self.model, data, True, y)
         ws = self._workspace(b)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
-        pred = torch.empty(b.G, dtype=torch.float32, device=dev) if return_pred else None
+        pred = torch.empty(_zinc_rows(self.model, b), dtype=torch.float32, device=dev) if return_pred else None
         nv.call("esc_zinc_train_step", ctypes.byref(self._desc), ctypes.byref(b), ws.data_ptr(), int(loss_denom or 0),
                 loss.data_ptr(), nv.ptr(pred), nv.stream())
         self._mark_bucket_written()
@@ -679,7 +692,7 @@ class ZincStepEngine(_AddressGuard):
         self._guard_check()
         b, keep = _zinc_batch(self.model, data, False)
         ws = self._workspace(b)
-        pred = torch.empty(b.G, dtype=torch.float32, device=dev)
+        pred = torch.empty(_zinc_rows(self.model, b), dtype=torch.float32, device=dev)
         nv.call("esc_zinc_predict", ctypes.byref(self._desc), ctypes.byref(b), ws.data_ptr(), pred.data_ptr(), nv.stream())
         return pred.view(-1, 1)
 
@@ -700,7 +713,7 @@ class _ZincEngineNode(torch.autograd.Function):
         desc = cache.descriptor(0)
         need = nv.lib().esc_zinc_workspace_floats(ctypes.byref(desc), b.N, b.E, b.Z, b.G)
         ws = torch.empty(int(need), dtype=torch.float32, device=dev)
-        pred = torch.empty(b.G, dtype=torch.float32, device=dev)
+        pred = torch.empty(_zinc_rows(model, b), dtype=torch.float32, device=dev)
         nv.call("esc_zinc_forward_train", ctypes.byref(desc), ctypes.byref(b), ws.data_ptr(), pred.data_ptr(), nv.stream())
         if cache.counters:
             torch._foreach_add_(cache.counters, 1)
@@ -730,7 +743,7 @@ def zinc_engine_predict(model, data):
     need = nv.lib().esc_zinc_workspace_floats(ctypes.byref(desc), b.N, b.E, b.Z, b.G)
     dev = model.lin1.weight.device
     ws = torch.empty(int(need), dtype=torch.float32, device=dev)
-    pred = torch.empty(b.G, dtype=torch.float32, device=dev)
+    pred = torch.empty(_zinc_rows(model, b), dtype=torch.float32, device=dev)
     nv.call("esc_zinc_predict", ctypes.byref(desc), ctypes.byref(b), ws.data_ptr(), pred.data_ptr(), nv.stream())
     return pred.view(-1, 1)
 

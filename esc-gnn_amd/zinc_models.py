@@ -64,7 +64,14 @@ class NestedGIN_eff(torch.nn.Module):
             from .engine import zinc_engine_predict, zinc_engine_ready
             if zinc_engine_ready(self, data):
                 return zinc_engine_predict(self, data)     # eval-mode forward as one call (esc_zinc_predict)
-        x, edge_index, batch = self.node_type_embedding(data.x.view(-1)), data.edge_index, data.batch
+        o = global_add_pool(self._node_states(data), data.batch)
+        o = self.lin1(o)
+        o = self.bn_lin1(o) if o.size(0) > 1 else F.elu(o)      # reference :606-609 (dropout p = 0)
+        return self.lin2(o)
+
+    def _node_states(self, data):
+        """cat(xs) of the per-op path (reference :581-598): the embeddings, the edge term and the GINE layers"""
+        x, edge_index = self.node_type_embedding(data.x.view(-1)), data.edge_index
         plan = plan_of(data, Z_TABLE_ROWS)
         if "edge_pos" in data:
             z = ops.linear(data.edge_pos.float(), self.z_initial.weight.t().contiguous())
@@ -77,7 +84,4 @@ class NestedGIN_eff(torch.nn.Module):
         for conv in self.convs:
             h = conv(h, edge_index, z, plan)
             xs.append(h)
-        o = global_add_pool(torch.cat(xs, dim=1), batch)
-        o = self.lin1(o)
-        o = self.bn_lin1(o) if o.size(0) > 1 else F.elu(o)      # reference :606-609 (dropout p = 0)
-        return self.lin2(o)
+        return torch.cat(xs, dim=1)

@@ -526,7 +526,11 @@ int esc_engine_predict(const esc_nested_gin_t* m, const esc_batch_t* b, float* w
  * (the reference skips bn_lin1 for a single graph, :603-604 — that case stays on the per-op path).
  * Activations are materialised (the GEMM prologue of the counting engine is ReLU-only); the edge pipeline (bag, z_embedding,
  * edge terms and their backward) runs on the engine's second stream like the counting model's when the batch has >= 12 000
- * edges (below that one stream is faster). */
+ * edges (below that one stream is faster).
+ * node_readout = 1 is the cycle-counting twin (reference zinc_cycle_models.py:506, run_zinc_cycle.py): the same model without
+ * global_add_pool, so lin1 -> BatchNorm (statistics over the N nodes) -> ELU -> lin2 run on the node rows of cat(xs) and
+ * pred / dpred / y / the loss are per node: [N] wherever the graph-level mode has [G], the default loss denominator is N, and
+ * the batch needs >= 2 nodes (any number of graphs). */
 typedef struct esc_embed_t { const float* w; float* dw; int64_t rows, dim; } esc_embed_t;
 typedef struct esc_zinc_gin_t {
   int64_t num_layers, hidden, z_rows;
@@ -535,6 +539,7 @@ typedef struct esc_zinc_gin_t {
   esc_embed_t node_emb, edge_emb;                        /* node_type_embedding, edge_type_embedding */
   esc_conv_t conv[ESC_MAX_LAYERS];                       /* conv1, convs.*; conv.lin.in_dim = hidden + edge_emb.dim */
   esc_linear_t lin1; esc_bn_t bn_lin1; esc_linear_t lin2;
+  int32_t node_readout, pad_;                            /* 1: zinc_cycle_models.py — no pooling, one prediction per NODE */
 } esc_zinc_gin_t;
 typedef struct esc_mol_batch_t {
   int64_t N, E, Z, G;
@@ -545,7 +550,7 @@ typedef struct esc_mol_batch_t {
   const int32_t *row_ptr, *bag_idx, *bag_val, *col_ptr, *col_row, *col_val, *col_col;
 } esc_mol_batch_t;
 int64_t esc_zinc_workspace_floats(const esc_zinc_gin_t* m, int64_t N, int64_t E, int64_t Z, int64_t G);
-/* loss[0] = sum|pred-y| / loss_denom (loss_denom <= 0: G).  pred (may be NULL): float[G]. */
+/* loss[0] = sum|pred-y| / loss_denom (loss_denom <= 0: G, or N with node_readout).  pred (may be NULL): float[G] (or [N]). */
 int esc_zinc_train_step(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, float* workspace, int64_t loss_denom,
                         float* loss, float* pred, void* stream);
 int esc_zinc_forward_train(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, float* workspace, float* pred, void* stream);
@@ -709,6 +714,14 @@ int esc_features_fill(const int64_t* node_ptr, const int64_t* edge_ptr, int64_t 
                       int self_loop, const int64_t* out_edge_ptr, const int64_t* nnz_ptr, int64_t total_out_edges,
                       int64_t* out_src, int64_t* out_dst, int64_t* in_edge_of_out, int64_t* pos_enc,
                       int64_t* pos_index, int64_t* pos_batch, int32_t* status, void* work, void* stream);
+
+/* ---- cycle-counting labels (reference dataset_zinc_cycle.py:45-61; csrc/cycles.hip) ------------------------------------
+ * Same ragged, graph-local-id layout as esc_features_count (node_ptr / edge_ptr [G+1], src / dst [total_edges]).  Self loops
+ * are dropped and the edges symmetrised and de-duplicated; out[v][k-3] (float32 [total_nodes, 4], 16-byte aligned) is the
+ * number of undirected simple cycles of length k = 3..6 through v (isolated nodes: zeros).  status[G]: 0, ESC_ERANGE for a
+ * graph of more than 64 nodes (its rows are left untouched), ESC_EINVAL for an id or a range outside the arrays. */
+int esc_cycle_counts(const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* src, const int64_t* dst, int64_t G,
+                     int64_t total_nodes, int64_t total_edges, float* out, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }
