@@ -131,6 +131,11 @@ SIGNATURES = {
     "esc_engine_predict": [P, P, P, P, P],
     "esc_l1_loss": [P, P, I64, I64, F32, P, P, P],
     "esc_bce_logits_loss": [P, P, I64, I64, P, P, P],
+    "esc_log_softmax_fwd": [P, I64, I64, I64, P, I64, P],
+    "esc_log_softmax_bwd": [P, I64, P, I64, I64, I64, P, I64, P],
+    "esc_nll_loss": [P, I64, P, I64, I64, I64, F32, P, P, I64, P, P, P, P],
+    "esc_log_softmax_nll": [P, I64, P, I64, I64, I64, F32, P, I64, P, P, I64, P, P, P, P],
+    "esc_pdist": [P, I64, I64, I64, P, F32, P, P],
     "esc_adam_step": [P, P, P, P, I64, c_double, c_double, c_double, c_double, I64, P],
     "esc_adam_step_scaled": [P, P, P, P, I64, c_double, c_double, c_double, c_double, I64, P, P],
     "esc_collate_cols": [P, I64, P, I64, P, P, P, P],

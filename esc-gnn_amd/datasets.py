@@ -186,3 +186,73 @@ def synthetic_zinc_cycle_graphs(first, count):
     for d, y in zip(out, cycle_counts(out)):
         d.y = y
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# The expressiveness datasets (the two graph files the reference ships): SR25 and EXP.
+# ---------------------------------------------------------------------------------------------------------
+def _both_directions_sorted(pairs):
+    """to_undirected + coalesce: every pair in both directions, duplicates removed, sorted by (src, dst)"""
+    both = sorted({(int(a), int(b)) for a, b in pairs} | {(int(b), int(a)) for a, b in pairs})
+    if not both:
+        return torch.zeros((2, 0), dtype=torch.int64)
+    return torch.tensor(both, dtype=torch.int64).t().contiguous()
+
+
+def load_sr25(path):
+    """data/sr25/raw/sr251256.g6 (SRDataset.py:30-39): one graph6 record per line, read with networkx;
+    x = ones[n, 1], edge_index = to_undirected(edge list), y = None."""
+    import networkx as nx
+    graphs = nx.read_graph6(path)
+    if not isinstance(graphs, list):
+        graphs = [graphs]
+    out = []
+    for G in graphs:
+        n = G.number_of_nodes()
+        out.append(Data(x=torch.ones(n, 1), edge_index=_both_directions_sorted(G.edges()), y=None, num_nodes=n))
+    return out
+
+
+def load_exp_txt(path, limit=None):
+    """data/EXP/GRAPHSAT.txt (PlanarSATPairsDataset + run_exp.py:50-53).  Line 1: the number of graphs; per graph a
+    line `n label`, then n lines `node_label degree neighbour ...`.  x = one_hot(node_label, 2), y = int64 [1],
+    edges in both directions sorted by (src, dst)."""
+    if str(path).endswith(".pkl"):
+        raise ValueError("%s: the reference's .pkl raw files hold pickled torch_geometric objects and are not supported; "
+                         "pass the text file (GRAPHSAT.txt) instead" % path)
+    out = []
+    with open(path) as fh:
+        total = int(fh.readline())
+        count = total if limit is None else min(total, int(limit))
+        for _ in range(count):
+            n, label = (int(v) for v in fh.readline().split())
+            node_label, pairs = [], []
+            for i in range(n):
+                parts = [int(v) for v in fh.readline().split()]
+                node_label.append(parts[0])
+                pairs.extend((i, nb) for nb in parts[2:2 + parts[1]])
+            x = torch.nn.functional.one_hot(torch.tensor(node_label, dtype=torch.int64), num_classes=2).to(torch.float)
+            out.append(Data(x=x, edge_index=_both_directions_sorted(pairs), y=torch.tensor([label], dtype=torch.int64),
+                            num_nodes=n))
+    return out
+
+
+def build_expressive_dataset(raw, h=3):
+    """the pre_transform of run_sr.py:76-78 / run_exp.py:76-78: create_subgraphs(g, h, node_label='hop', use_rd=False,
+    self_loop=True) for every graph, on the HIP feature builder"""
+    return build_feature_dataset(raw, h, use_rd=False, self_loop=True)
+
+
+def exp_split(num_graphs, split, splits=10, modulo=4, mod_thresh=1):
+    """Index lists of fold `split` of the EXP protocol (run_exp.py:282-303): test = [split*n, (split+1)*n) with
+    n = num_graphs // splits, divided into `lrn` (index % modulo <= mod_thresh) and `exp` (the others); of the remaining
+    graphs, in order, the split-th tenth is the validation set and the rest the training set."""
+    n = num_graphs // splits
+    test = list(range(split * n, (split + 1) * n))
+    lrn = [i for i in test if i % modulo <= mod_thresh]
+    exp = [i for i in test if i % modulo > mod_thresh]
+    rest = [i for i in range(num_graphs) if not split * n <= i < (split + 1) * n]
+    m = len(rest) // splits
+    val = rest[split * m:(split + 1) * m]
+    train = rest[:split * m] + rest[(split + 1) * m:]
+    return dict(train=train, val=val, test=test, lrn=lrn, exp=exp)

@@ -663,3 +663,163 @@ class _SegmentBroadcast(Function):
 def segment_broadcast(rows, batch, size=None):
     size = rows.size(0) if size is None else int(size)
     return _SegmentBroadcast.apply(rows, _seg_ptr(batch, size), batch.numel())
+
+
+# ---- classification head (csrc/classify.hip) -------------------------------------------------------------------------
+class _LogSoftmax(Function):
+    """F.log_softmax(x, dim=1) (run_sr.py:211, run_exp.py:215): one wave per row, maximum taken off first."""
+
+    @staticmethod
+    def forward(ctx, x):
+        _dev(x)
+        x, ldx = _rows(x)
+        M, C = x.shape
+        y = torch.empty((M, C), dtype=torch.float32, device=x.device)
+        nv.call("esc_log_softmax_fwd", nv.ptr(x), ldx, M, C, nv.ptr(y), C, nv.stream())
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        dy, ldg = _rows(dy)
+        M, C = y.shape
+        dx = torch.empty((M, C), dtype=torch.float32, device=y.device)
+        nv.call("esc_log_softmax_bwd", nv.ptr(y), C, nv.ptr(dy), ldg, M, C, nv.ptr(dx), C, nv.stream())
+        return dx
+
+
+def log_softmax(x):
+    """row-wise log-softmax of a [M, C] tensor"""
+    return _LogSoftmax.apply(x)
+
+
+def _targets(target, M, dev):
+    if target.dtype != torch.int64:
+        raise TypeError("esc_gnn_amd: class targets must be int64, got %s" % target.dtype)
+    _on(dev, target)
+    target = target.contiguous().view(-1)
+    if target.numel() != M:
+        raise ValueError("%d targets for %d rows" % (target.numel(), M))
+    return target
+
+
+def _denom(reduction, denom):
+    if denom is not None:
+        return int(denom)
+    if reduction not in ("mean", "sum"):
+        raise ValueError("reduction must be 'mean' or 'sum', got %r" % (reduction,))
+    return 0 if reduction == "mean" else 1
+
+
+def _head_info(info, C):
+    """one read-back of the head's int32 pair (bad-target flag, correct count): raises on a target outside [0, C)"""
+    bad, correct = info.tolist()
+    if bad:
+        raise RuntimeError("Target out of bounds: class targets must lie in [0, %d)" % C)
+    return correct
+
+
+def _nll_raw(logp, target, denom, want_grad):
+    logp, ld = _rows(logp)
+    M, C = logp.shape
+    target = _targets(target, M, logp.device)
+    loss = torch.empty(1, dtype=torch.float32, device=logp.device)
+    info = torch.empty(2, dtype=torch.int32, device=logp.device)
+    dlogp = torch.empty((M, C), dtype=torch.float32, device=logp.device) if want_grad else None
+    rows = torch.empty(2 * M, dtype=torch.float32, device=logp.device)
+    nv.call("esc_nll_loss", nv.ptr(logp), ld, nv.ptr(target), M, C, denom, 1.0, nv.ptr(loss), nv.ptr(dlogp), C,
+            info[1:].data_ptr(), info.data_ptr(), nv.ptr(rows), nv.stream())
+    return loss.view(()), dlogp, _head_info(info, C)
+
+
+class _NllLoss(Function):
+    """F.nll_loss(logp, target, reduction=...) (run_exp.py:235,248), deterministic; the accuracy count of
+    run_exp.py:261-264 rides on the same launch."""
+
+    @staticmethod
+    def forward(ctx, logp, target, denom):
+        _dev(logp)
+        loss, dlogp, ctx.correct = _nll_raw(logp, target, denom, True)
+        ctx.save_for_backward(dlogp)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dlogp,) = ctx.saved_tensors
+        return dlogp * g, None, None
+
+
+def nll_loss(logp, target, reduction="mean", denom=None, return_correct=False):
+    """-sum_i logp[i, target_i] / denom; `denom` overrides the divisor that `reduction` implies.  A target outside
+    [0, C) raises RuntimeError.  return_correct: also the number of rows whose argmax equals the target."""
+    denom = _denom(reduction, denom)
+    if torch.is_grad_enabled() and logp.requires_grad:
+        loss = _NllLoss.apply(logp, target, denom)
+        correct = loss.grad_fn.correct
+    else:
+        _dev(logp)
+        loss, _, correct = _nll_raw(logp, target, denom, False)
+    return (loss, correct) if return_correct else loss
+
+
+def _head_raw(logits, target, denom, want_grad):
+    x, ldx = _rows(logits)
+    M, C = x.shape
+    dev = x.device
+    target = _targets(target, M, dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    info = torch.empty(2, dtype=torch.int32, device=dev)
+    logp = torch.empty((M, C), dtype=torch.float32, device=dev)
+    dx = torch.empty((M, C), dtype=torch.float32, device=dev) if want_grad else None
+    rows = torch.empty(2 * M, dtype=torch.float32, device=dev)
+    nv.call("esc_log_softmax_nll", nv.ptr(x), ldx, nv.ptr(target), M, C, denom, 1.0, nv.ptr(logp), C, nv.ptr(loss),
+            nv.ptr(dx), C, info[1:].data_ptr(), info.data_ptr(), nv.ptr(rows), nv.stream())
+    return loss.view(()), logp, dx, _head_info(info, C)
+
+
+class _LogSoftmaxNll(Function):
+    """nll_loss(log_softmax(logits), target) with its gradient (softmax - onehot) / denom in ONE launch; logp and the
+    loss equal the two-op composition bit for bit."""
+
+    @staticmethod
+    def forward(ctx, logits, target, denom):
+        _dev(logits)
+        loss, logp, dx, ctx.correct = _head_raw(logits, target, denom, True)
+        ctx.save_for_backward(dx)
+        ctx.mark_non_differentiable(logp)
+        return loss, logp
+
+    @staticmethod
+    def backward(ctx, g, _glogp):
+        (dx,) = ctx.saved_tensors
+        return dx * g, None, None
+
+
+def log_softmax_nll(logits, target, reduction="mean", denom=None, return_aux=False):
+    """The fused classification head: loss = nll_loss(log_softmax(logits), target).  return_aux: (loss, logp, correct)
+    with logp the (non-differentiable) log-probabilities and correct the number of rows whose argmax is the target."""
+    denom = _denom(reduction, denom)
+    if torch.is_grad_enabled() and logits.requires_grad:
+        loss, logp = _LogSoftmaxNll.apply(logits, target, denom)
+        correct = loss.grad_fn.correct
+    else:
+        _dev(logits)
+        loss, logp, _, correct = _head_raw(logits, target, denom, False)
+    return (loss, logp, correct) if return_aux else loss
+
+
+def pdist(x, threshold=None):
+    """torch.pdist(x, p=2) in the difference form (fp64 inside): [M*(M-1)/2] distances in row-major upper-triangle order.
+    With a threshold: (distances, number of entries < threshold) — the SR25 criterion of run_sr.py:241-242.  Not
+    differentiable (the drivers use it under no_grad)."""
+    _dev(x)
+    x, ldx = _rows(x.detach())
+    M, C = x.shape
+    if C == 0:
+        raise ValueError("pdist: rows have no columns")
+    out = torch.empty(M * (M - 1) // 2, dtype=torch.float32, device=x.device)
+    below = torch.empty(1, dtype=torch.int32, device=x.device) if threshold is not None else None
+    nv.call("esc_pdist", nv.ptr(x), ldx, M, C, nv.ptr(out), float(threshold if threshold is not None else 0.0),
+            nv.ptr(below), nv.stream())
+    return out if threshold is None else (out, int(below.item()))

@@ -424,6 +424,33 @@ int esc_l1_loss(const float* pred, const float* y, int64_t M, int64_t denom, flo
  * d loss / d pred, 0 at unlabeled entries. */
 int esc_bce_logits_loss(const float* pred, const float* y, int64_t M, int64_t denom, float* loss,
                         float* dpred, void* stream);
+/* ---- classification head (csrc/classify.hip; run_sr.py:211,241-242, run_exp.py:215,235,248,261-264) ----------------
+ * One wave per row, wave reductions in a fixed order: no result depends on the grid shape.  The row maximum is taken
+ * off before anything is exponentiated, sums run in fp64 and every output is rounded to fp32 once.
+ * logp[i, c] = x[i, c] - max_i - log(sum_c exp(x[i, c] - max_i))   (F.log_softmax(x, dim=1)); M = 0 is a no-op. */
+int esc_log_softmax_fwd(const float* logits, int64_t ld_x, int64_t M, int64_t C, float* logp, int64_t ld_p, void* stream);
+/* dlogits = dlogp - exp(logp) * rowsum(dlogp) */
+int esc_log_softmax_bwd(const float* logp, int64_t ld_p, const float* dlogp, int64_t ld_dy, int64_t M, int64_t C,
+                        float* dlogits, int64_t ld_dx, void* stream);
+/* F.nll_loss: loss[0] = -sum_i logp[i, target_i] / denom  (denom <= 0: M, reduction='mean'; denom = 1: 'sum').
+ * Deterministic: the row terms are added by the workgroup that finishes last, in an order that depends on M alone, in
+ * fp64.  dlogp (may be NULL) receives -grad_scale / denom at [i, target_i] and 0 elsewhere.  correct (may be NULL):
+ * number of rows whose first maximum (tensor.max(1)[1]) equals the target.  bad_target[0] (required) is set to 1 when a
+ * target lay outside [0, C) — that row then contributes nothing — and to 0 otherwise.  scratch: 2*M floats, 8-byte
+ * aligned (the per-row terms). */
+int esc_nll_loss(const float* logp, int64_t ld_p, const int64_t* target, int64_t M, int64_t C, int64_t denom, float grad_scale,
+                 float* loss, float* dlogp, int64_t ld_d, int32_t* correct, int32_t* bad_target, float* scratch, void* stream);
+/* The fused training head, the classification sibling of esc_linear_fwd_l1: log-softmax, NLL loss, accuracy count and
+ * dlogits = (softmax - onehot) * grad_scale / denom in ONE launch.  logp (may be NULL) and loss equal
+ * esc_log_softmax_fwd followed by esc_nll_loss bit for bit; dlogits may be NULL (evaluation).  scratch as esc_nll_loss. */
+int esc_log_softmax_nll(const float* logits, int64_t ld_x, const int64_t* target, int64_t M, int64_t C, int64_t denom,
+                        float grad_scale, float* logp, int64_t ld_p, float* loss, float* dlogits, int64_t ld_dx,
+                        int32_t* correct, int32_t* bad_target, float* scratch, void* stream);
+/* torch.pdist(x, p=2): out[k] = sqrt(sum_c (x[i,c] - x[j,c])^2) for i < j, k in row-major upper-triangle order
+ * (M*(M-1)/2 entries; M <= 1: none).  Difference form in fp64 — rows of magnitude 1e5 at distances of a few units keep
+ * their distance.  below (may be NULL): number of entries < threshold (the SR25 criterion, run_sr.py:241-242); counted in
+ * the same launch for M <= 128, by a second small launch of the same call above that. */
+int esc_pdist(const float* x, int64_t ld_x, int64_t M, int64_t C, float* out, float threshold, int32_t* below, void* stream);
 /* torch.optim.Adam (no amsgrad, no weight decay) over one flat buffer, torch's operation order;
  * `step` is the 1-based step number. */
 int esc_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
