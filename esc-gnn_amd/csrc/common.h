@@ -56,14 +56,31 @@ unsigned long long* prof_span_next(int kind);
 // ESC_TRACE_LAUNCH=1 (debugging a fault or a hang): every launch is announced on stderr and waited for
 bool trace_launch();
 
+// A cross-stream dependency on ONE kernel: hipEventRecord behind the launch puts a marker packet on the producer's stream, and the
+// next kernel of that stream waits for the marker (5-8 us of bubble per record in the step's kernel trace, on the chain that can
+// least afford it).  An event armed here becomes the stop event of this thread's NEXT launch instead: it is bound to the
+// kernel's own completion signal and nothing is queued behind the kernel.  take_launch_event() returns (and clears) what is
+// still armed — non-NULL after the call means no launch consumed it.  Not used while the stream is being captured.
+void arm_launch_event(hipEvent_t ev);
+hipEvent_t take_launch_event();
+
 template <typename... KArgs, typename... Args>
 inline void launch(int kind, void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t s,
                    Args... args) {
   hipEvent_t a = nullptr, b = nullptr;
-  if (prof_slot(kind, &a, &b))
+  hipEvent_t done = take_launch_event();
+  if (done != nullptr) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) { arm_launch_event(done); done = nullptr; }   // left armed: the caller records it
+  }
+  if (prof_slot(kind, &a, &b)) {
     hipExtLaunchKernelGGL(kernel, grid, block, (unsigned)lds, s, a, b, 0, static_cast<KArgs>(args)...);
-  else
+    if (done != nullptr) (void)hipEventRecord(done, s);
+  } else if (done != nullptr) {
+    hipExtLaunchKernelGGL(kernel, grid, block, (unsigned)lds, s, nullptr, done, 0, static_cast<KArgs>(args)...);
+  } else {
     hipLaunchKernelGGL(kernel, grid, block, (unsigned)lds, s, static_cast<KArgs>(args)...);
+  }
   if (trace_launch()) {
     const char* name = hipKernelNameRefByPtr(reinterpret_cast<const void*>(kernel), s);
     fprintf(stderr, "[esc] %s grid (%u,%u,%u) block %u lds %zu stream %p ...", name ? name : "?", grid.x, grid.y, grid.z, block.x, lds, (void*)s);

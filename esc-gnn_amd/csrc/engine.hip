@@ -249,9 +249,9 @@ struct EdgeStream {
              agg_done[ESC_MAX_LAYERS] = {};
   bool ok = false;
 };
-// 1: the weight gradient of the LAST conv.lin backward (l == 0, in the tail of the step) runs on the node stream.  Measured
-// neutral (1.038 vs 1.031-1.044 ms by the phase marks; so was doing the same for z_embedding's Linear): the node stream's
-// own reductions then become the end of the step.  Off.
+// 1 (default): the weight gradient of the LAST conv.lin backward (l == 0, in the tail of the step) runs on the node stream.
+// Measured neutral when it went in (1.038 vs 1.031-1.044 ms by the phase marks): the node stream's own reductions then become
+// the end of the step.  Doing the same for z_embedding's Linear costs 25-30 us (DESIGN.md *Step engine, fork and join*).
 static int g_split_last_lin = getenv("ESC_SPLIT_LAST_LIN") ? atoi(getenv("ESC_SPLIT_LAST_LIN")) : 1;
 static int g_edge_priority_low = 1;
 static int g_use_edge_stream = 1;     // esc_engine_set_side_stream() bit 1
@@ -308,6 +308,27 @@ static EdgeStream& edge_stream_for(int64_t edges) {
 // `waiter` continues only after everything queued on `src` so far
 static int chain(hipEvent_t ev, hipStream_t src, hipStream_t waiter) {
   if (hipEventRecord(ev, src) != hipSuccess || hipStreamWaitEvent(waiter, ev, 0) != hipSuccess) {
+    set_error("esc_engine: stream event failed");
+    return ESC_ELAUNCH;
+  }
+  return ESC_OK;
+}
+
+// The same dependency on the ONE kernel launched while an ArmedEvent lives.  hipEventRecord queues a marker packet behind the
+// kernel and the NEXT kernel of `src` waits for that marker: 6-8 us of bubble per record in the step's kernel trace, and the node
+// chain — the critical path of the backward — records once per layer.  An armed event is instead the stop event of the launch
+// itself (arm_launch_event, common.h): bound to the kernel's completion signal, nothing queued behind it.  chain_armed() falls back
+// to the record when no launch took the event (nothing launched, a stream being captured, on == false).  Only around calls that
+// launch exactly one kernel.  g_plain_events (bit 6 of esc_engine_set_side_stream) keeps every dependency a record: A/B runs.
+static int g_plain_events = 0;
+struct ArmedEvent {
+  ArmedEvent(hipEvent_t ev, bool on) : on_(on && !g_plain_events) { if (on_) arm_launch_event(ev); }
+  ~ArmedEvent() { if (on_) (void)take_launch_event(); }
+  bool on_;
+};
+static int chain_armed(hipEvent_t ev, const ArmedEvent& arm, hipStream_t src, hipStream_t waiter) {
+  const bool bound = arm.on_ && take_launch_event() == nullptr;
+  if ((!bound && hipEventRecord(ev, src) != hipSuccess) || (waiter != nullptr && hipStreamWaitEvent(waiter, ev, 0) != hipSuccess)) {
     set_error("esc_engine: stream event failed");
     return ESC_ELAUNCH;
   }
@@ -387,7 +408,7 @@ static void mark(int which, void* stream) {
 }
 
 static int g_bag_stats = getenv("ESC_BAG_STATS") ? atoi(getenv("ESC_BAG_STATS")) : 1;   // BatchNorm partials from the bag kernel's epilogue
-static int g_e0_early = getenv("ESC_E0_EARLY") ? atoi(getenv("ESC_E0_EARLY")) : 1;   // see forward()
+static int g_e0_early = getenv("ESC_E0_EARLY") ? atoi(getenv("ESC_E0_EARLY")) : 1;   // e_0 in front of the pass that materialises z_emb: see forward()
 static int g_fuse_finalize = 1; // ... and their merge by the GEMM's last workgroup (no bn_finalize launch)
 static int g_gemm_stats = 1;   // BatchNorm statistics from the producing GEMM's epilogue (no extra pass over Y)
 // Node-sized BatchNorms: partials merged in the consumer's prologue instead of a finalize launch (esc_engine_set_gemm_stats
@@ -667,8 +688,8 @@ static int forward(const Ctx& c) {
     ESC_TRY(chain(es.z_ready, (hipStream_t)c.s, es.stream));       // the batch arrays were produced on the caller's stream
     ce = edge_ctx(c, es.stream);
   }
-  // ESC bag (LDS-staged table slices); in training mode its epilogue leaves the BatchNorm partials of z_embedding's first
-  // BatchNorm, so the statistics pass over the E x H output is one finalize launch
+  // ESC bag (esc_bag_fwd_rows; the LDS-staged table slices are an option that is off by default); in training mode its epilogue
+  // leaves the BatchNorm partials of z_embedding's first BatchNorm, so the statistics pass over the E x H output is one finalize launch
   const int64_t bag_block = (c.train && !sync_on(ce) && g_bag_stats) ? esc_bag_fwd_stats_block_rows(m->z_table, m->z_rows, H, y.Zb, H, E) : 0;
   if (bag_block > 0) {
     ESC_TRY(esc_bag_fwd_rows(m->z_table, m->z_rows, H, b->row_ptr, b->bag_idx, b->bag_val, E, y.Zb, H, 0, ce.y.col_stats, ce.s));
@@ -687,12 +708,16 @@ static int forward(const Ctx& c) {
   }                                                                       // z_emb = relu(Yz*scale+shift)
   // The first edge term is narrow (in_dim columns: a bandwidth pass over z_emb): it applies z_embedding's last BatchNorm+ReLU to
   // its operand itself and runs BEFORE the pass that materialises z_emb for the wide layers — the node chain's first
-  // aggregate waits for e_0 only (same fmaf + max per element: e_0 is bit-identical either way)
+  // aggregate waits for e_0 only (same fmaf + max per element: e_0 is bit-identical either way).  It went there when node layer 0
+  // was the later pipeline; since the batched launch below the two are level (layer 0 ends with the batched GEMM), and launching
+  // e_0 from the node stream instead brings the GEMM forward by 10 us without moving the end of the forward (DESIGN.md *Step
+  // engine, fork and join*): it stays here.
   const bool e0_early = mat && g_e0_early && y.C0 <= 32 && L >= 1;
   if (e0_early) {
     const LdsFloorGuard cap(ce.on_edge_stream && g_cap_forward);
+    const ArmedEvent arm(es.e_ready[0], es.ok);
     ESC_TRY(esc_linear_fwd(y.Yz, H, m->conv[0].lin.w, H, m->conv[0].lin.b, y.zb1.scale, y.zb1.shift, E, y.C0, H, y.e[0], y.ld_e[0], nullptr, ce.s));
-    if (es.ok && hipEventRecord(es.e_ready[0], es.stream) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
+    if (es.ok) ESC_TRY(chain_armed(es.e_ready[0], arm, es.stream, nullptr));
   }
   if (mat) ESC_TRY(esc_affine_act(y.Yz, H, E, H, y.zb1.scale, y.zb1.shift, 1, y.Zemb, H, ce.s));
   // Per-layer launches (ESC_EDGE_BATCHED=0, L < 3, or activations not materialised): the edge terms run one layer ahead of the node
@@ -721,9 +746,11 @@ static int forward(const Ctx& c) {
     ESC_TRY(esc_table_pack(&tl, H, y.w_cat, ce.s));
     {
       const LdsFloorGuard cap(ce.on_edge_stream && g_cap_forward);
+      const ArmedEvent arm(es.e_ready[1], es.ok);          // the node chain's layers 1 .. L-1 start behind this launch
       ESC_TRY(esc_linear_fwd(y.Zemb, H, y.w_cat, H, y.w_cat + (L - 1) * H * H, nullptr, nullptr, E, (L - 1) * H, H, y.e_cat, (L - 1) * H, nullptr, ce.s));
+      if (es.ok) ESC_TRY(chain_armed(es.e_ready[1], arm, es.stream, nullptr));
     }
-    for (int l = 1; l < (int)L; ++l)
+    for (int l = 2; l < (int)L; ++l)
       if (es.ok && hipEventRecord(es.e_ready[l], es.stream) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
   }
   const int ahead = batched ? 0 : (es.ok ? g_edge_ahead : (int)L);          // one stream: all of them up front, in layer order
@@ -795,9 +822,13 @@ static int forward(const Ctx& c) {
   } else
   ESC_TRY(linear_bn(c, y.cat, W, m->lin1, fa ? y.cat_scale : nullptr, fa ? y.cat_shift : nullptr, N, y.Yl, m->bn_lin1, y.bl));
   // train_step: the head's launch leaves the L1 gradient of every prediction too, so the backward starts behind it and the loss
-  // launch (a single workgroup walking all predictions, 5-7 us) leaves the chain
-  if (c.l1_target != nullptr && esc_linear_fwd_l1_ok(y.Yl, H, m->lin2.w, H, y.bl.scale, y.bl.shift))
-    return esc_linear_fwd_l1(y.Yl, H, m->lin2.w, m->lin2.b, y.bl.scale, y.bl.shift, N, H, c.l1_target, c.l1_denom, 1.0f, y.pred, y.dpred, c.s);
+  // launch (a single workgroup walking all predictions, 5-7 us) leaves the chain: the edge stream continues behind the head
+  // (train_step_impl() puts the loss value there)
+  if (c.l1_target != nullptr && esc_linear_fwd_l1_ok(y.Yl, H, m->lin2.w, H, y.bl.scale, y.bl.shift)) {
+    const ArmedEvent arm(es.lin1_fork, es.ok);
+    ESC_TRY(esc_linear_fwd_l1(y.Yl, H, m->lin2.w, m->lin2.b, y.bl.scale, y.bl.shift, N, H, c.l1_target, c.l1_denom, 1.0f, y.pred, y.dpred, c.s));
+    return es.ok ? chain_armed(es.lin1_fork, arm, (hipStream_t)c.s, es.stream) : ESC_OK;
+  }
   return esc_linear_fwd(y.Yl, H, m->lin2.w, H, m->lin2.b, y.bl.scale, y.bl.shift, N, 1, H, y.pred, 1, nullptr, c.s);
 }
 
@@ -931,6 +962,7 @@ static int backward(const Ctx& c_in, Pending* defer) {
         hipStreamWaitEvent((hipStream_t)c.s, es.lin1_rest, 0) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
     // (bit 3) d(cat)[:, l*H:(l+1)*H] is final once this launch has added its share: it leaves the column sums of the PREVIOUS layer's
     // last BatchNorm backward, and that layer's MLP backward starts with the finalize
+    const ArmedEvent arm(es.de_ready[l], es.ok);        // d_e[l] comes out of the aggregate backward: one launch, whichever form
     const bool stats_here = fuse_node_act(c) && l > 0 && (g_bn_fuse_bwd & 8) && esc_gine_aggregate_bwd_deps_slots(C) == 1 && C <= 2048 &&
                             mlp_backward_fused(c, m->conv[l - 1].nn, y.conv[l - 1], y.agg[l - 1], l - 1 == 0 ? y.C0 : H, N, y.cat + (int64_t)l * H, W,
                                                y.dcat + (int64_t)l * H, W, y.dagg, l - 1 == 0 ? y.C0 : H, true);
@@ -947,7 +979,7 @@ static int backward(const Ctx& c_in, Pending* defer) {
       ESC_TRY(esc_gine_aggregate_bwd(hin, ld_h, y.e[l], y.ld_e[l], y.dagg, C, b->out_ptr, b->out_edge, b->out_dst, cv.eps, N, C,
                                      y.d_e[l], C, dx, W, 1, y.deps_part + (int64_t)l * 2 * N, c.s));
     eps_jobs.push_back(esc_sum_job{y.deps_part + (int64_t)l * 2 * N, N * esc_gine_aggregate_bwd_deps_slots(C), cv.deps});
-    if (es.ok) ESC_TRY(chain(es.de_ready[l], (hipStream_t)c.s, es.stream));   // lin_l backward: edge stream
+    if (es.ok) ESC_TRY(chain_armed(es.de_ready[l], arm, (hipStream_t)c.s, es.stream));   // lin_l backward: edge stream
     const float* zin = g_materialise_edge_act ? y.Zemb : y.Yz;
     const float* zsc = g_materialise_edge_act ? nullptr : y.zb1.scale;
     const float* zsh = g_materialise_edge_act ? nullptr : y.zb1.shift;
@@ -1679,6 +1711,7 @@ int esc_engine_set_side_stream(int on) {
   g_edge_ahead = (on & 32) ? 2 : 1;
   g_edge_priority_low = (on & 4) == 0;      // bit 2: give the edge stream the HIGHEST priority instead (experiments)
   g_use_side_stream = (on & 1) != 0;
+  g_plain_events = (on & 64) != 0;
   return ESC_OK;
 }
 
@@ -1771,8 +1804,7 @@ static int train_step_impl(const esc_nested_gin_t* m, const esc_batch_t* b, floa
                        esc_linear_fwd_l1_ok(c.y.Yl, m->hidden, m->lin2.w, m->hidden, c.y.bl.scale, c.y.bl.shift) != 0;
   if (head_l1) { c.l1_target = b->y; c.l1_denom = denom; }
   ESC_TRY(forward(c));
-  if (head_l1) {              // the loss VALUE: on the edge stream (idle here), ordered behind the head; the step's join covers it
-    ESC_TRY(chain(es.lin1_fork, (hipStream_t)stream, es.stream));
+  if (head_l1) {              // the loss VALUE: on the edge stream (idle here), ordered behind the head by forward(); the step's join covers it
     ESC_TRY(esc_l1_loss(c.y.pred, b->y, b->N, denom, 1.0f, loss, nullptr, es.stream));
   } else {
     ESC_TRY(esc_l1_loss(c.y.pred, b->y, b->N, denom, 1.0f, loss, c.y.dpred, stream));

@@ -77,6 +77,10 @@ int node_lds_floor() { return g_node_lds_floor; }
 void set_node_lds_floor(int bytes) { g_node_lds_floor = bytes < 0 ? 0 : (bytes > 160 * 1024 ? 160 * 1024 : bytes); }
 void set_edge_lds_floor(int bytes) { g_edge_lds_floor = bytes < 0 ? 0 : bytes; }
 
+static thread_local hipEvent_t g_launch_event = nullptr;
+void arm_launch_event(hipEvent_t ev) { g_launch_event = ev; }
+hipEvent_t take_launch_event() { hipEvent_t ev = g_launch_event; g_launch_event = nullptr; return ev; }
+
 static const bool g_trace_launch = getenv("ESC_TRACE_LAUNCH") != nullptr && atoi(getenv("ESC_TRACE_LAUNCH")) != 0;
 bool trace_launch() { return g_trace_launch; }
 static int g_bn_bwd_one = getenv("ESC_BN_BWD_ONE") ? atoi(getenv("ESC_BN_BWD_ONE")) : 0;

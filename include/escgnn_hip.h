@@ -491,7 +491,12 @@ typedef struct esc_batch_t {
  * of the backward tail; bit 5: edge terms two layers ahead of the node chain instead of one; bit 2: edge stream at the
  * highest instead of the lowest priority — both for experiments.)
  * bit 1 (default on): the edge-sized conv.lin GEMMs of all layers run on a second HIP stream, ordered against the
- * node chain by one event per dependency; bit 0 (default off): the x_embedding branch on a further stream.  Default 2. */
+ * node chain by one event per dependency; bit 0 (default off): the x_embedding branch on a further stream.  Default 2.
+ * bit 6 (value 64, default clear): how the counting engine signals a cross-stream dependency on a single kernel (the edge terms
+ * e_0 and e_1 .. e_{L-1}, the head in front of the loss, d_e of every layer's aggregate backward).  Clear: the event is the stop
+ * event of that kernel's launch, so nothing is queued behind the kernel on the producing stream.  Set: hipEventRecord behind the
+ * launch, as before; its marker packet holds up the producer's next kernel (about 16 us per flagship step over all of them).
+ * Same kernels, arguments and results either way (A/B runs: `bench.py --streams 66`). */
 int esc_engine_set_side_stream(int on);
 /* all three engines: smallest batch (in edges) whose edge pipeline runs on the second stream (default 12 000; 0 = always).
  * Smaller batches — ZINC at bs 128, the 16-graph per-rank slices of a strong-scaling run of the counting model — are launch-latency
