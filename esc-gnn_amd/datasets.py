@@ -34,18 +34,37 @@ def adjacency_to_data(A, y):
                 y=torch.as_tensor(y), num_nodes=n)
 
 
-def synthetic_count_graphs(first, count):
+COUNT_LABELS = ("triangle", "cycles", "graphlets", "graphlet_orbits")
+
+
+def synthetic_count_graphs(first, count, labels="triangle"):
+    """labels: "triangle" — y float32 [n], the triangles through the node (host arithmetic); "cycles" — y float32 [n, 4],
+    the 3..6-cycles (cycles.cycle_counts); "graphlets" — y float32 [n, 5], the copies of the five count_graphlet patterns
+    through the node; "graphlet_orbits" — y float32 [n, 11], the same per orbit (graphlets.py).  The last three are
+    counted on the device.  Graphs, edge order and x do not depend on `labels`."""
+    if labels not in COUNT_LABELS:
+        raise ValueError("labels=%r: one of %s" % (labels, ", ".join(COUNT_LABELS)))
     out = []
     for g in range(first, first + count):
         A = count_shape_adjacency(g)
         tri = (np.diagonal(A @ A @ A) / 2.0).astype(np.float32)
         out.append(adjacency_to_data(A, tri))
+    if labels == "triangle":
+        return out
+    if labels == "cycles":
+        from .cycles import cycle_counts as count
+    elif labels == "graphlets":
+        from .graphlets import graphlet_counts as count
+    else:
+        from .graphlets import graphlet_orbit_counts_float as count
+    for d, y in zip(out, count(out)):
+        d.y = y
     return out
 
 
-def build_count_dataset(first, count, h=3, use_rd=True, self_loop=True):
+def build_count_dataset(first, count, h=3, use_rd=True, self_loop=True, labels="triangle"):
     """Synthetic graphs + ESC features (HIP feature builder), as run_graphcount.py:404-408 configures it."""
-    raw = synthetic_count_graphs(first, count)
+    raw = synthetic_count_graphs(first, count, labels)
     done = create_subgraphs_many(raw, h, use_rd=use_rd, self_loop=self_loop)
     for d in done:
         d.num_nodes = None            # like the reference's new Data: num_nodes is inferred from x

@@ -129,6 +129,13 @@ _FLAGS = [  # (name, kwargs) — same names, types and defaults as the reference
     # additions (not in the reference): synthetic data when data/<dataset>/raw/data.mat is absent
     ("--synthetic_graphs", dict(type=int, default=5000, help="size of the synthetic count_cycle-shaped dataset")),
     ("--data_root", dict(default="data")),
+    ("--synthetic_labels", dict(default="triangle", choices=("triangle", "task"),
+                                help="labels of the synthetic dataset: the per-node triangle count whatever --dataset and "
+                                     "--target say, or the task's own (count_cycle: 3..6-cycles, count_graphlet: the five "
+                                     "graphlets, column --target), counted on the device; ignored with a real data.mat")),
+    ("--graphlet_orbit", dict(type=int, default=-1,
+                              help="with --synthetic_labels task on count_graphlet: count only the copies that hold the "
+                                   "node at the K-th orbit of the pattern (-1: at any position)")),
 ]
 
 
@@ -140,12 +147,38 @@ def build_parser():
     return ap
 
 
-def _load_splits(args):
+def _mat_path(args):
+    import os
+    return os.path.join(args.data_root, args.dataset, "raw", "data.mat")
+
+
+def task_label_column(dataset, target, orbit=-1):
+    """(labels, column) of `--synthetic_labels task`: the `labels` kind of datasets.synthetic_count_graphs and the column
+    of its y that --dataset / --target / --graphlet_orbit select.  ValueError for a name or an index outside the task."""
+    from .graphlets import GRAPHLET_NAMES, GRAPHLET_ORBITS
+    if dataset == "count_cycle":
+        if not 0 <= target <= 3:
+            raise ValueError("--target %d: count_cycle has targets 0..3 (the 3-, 4-, 5- and 6-cycles)" % target)
+        if not -1 <= orbit <= 0:
+            raise ValueError("--graphlet_orbit %d: a cycle has one orbit, valid values are -1..0" % orbit)
+        return "cycles", target
+    if dataset == "count_graphlet":
+        if not 0 <= target <= 4:
+            raise ValueError("--target %d: count_graphlet has targets 0..4 (%s)" % (target, ", ".join(GRAPHLET_NAMES)))
+        cols = GRAPHLET_ORBITS[target]
+        if not -1 <= orbit < len(cols):
+            raise ValueError("--graphlet_orbit %d: the %s of --target %d has orbits 0..%d (-1: any position)"
+                             % (orbit, GRAPHLET_NAMES[target], target, len(cols) - 1))
+        return ("graphlets", target) if orbit < 0 else ("graphlet_orbits", cols[orbit])
+    raise ValueError("--dataset %s: --synthetic_labels task knows count_cycle and count_graphlet" % dataset)
+
+
+def _load_splits(args, labels="triangle"):
     """train/val/test lists of pre-transformed Data (reference :404-430)."""
     import os
     from .datasets import build_count_dataset, load_count_mat
     from .utils_edge_efficient import create_subgraphs_many
-    mat = os.path.join(args.data_root, args.dataset, "raw", "data.mat")
+    mat = _mat_path(args)
     if os.path.exists(mat):
         splits = []
         for name in ("train", "val", "test"):
@@ -154,7 +187,7 @@ def _load_splits(args):
         return splits, True
     G = args.synthetic_graphs
     n_tr, n_val = int(0.3 * G), int(0.2 * G)              # 30/20/50 split by index
-    alld = build_count_dataset(0, G, h=args.h, use_rd=True, self_loop=True)
+    alld = build_count_dataset(0, G, h=args.h, use_rd=True, self_loop=True, labels=labels)
     return [alld[:n_tr], alld[n_tr:n_tr + n_val], alld[n_tr + n_val:]], False
 
 
@@ -178,6 +211,10 @@ def main(argv=None):
     if args.model != "NestedGIN_eff":
         print("Model not implemented")
         raise NotImplementedError
+    # the task's own labels on the synthetic dataset (a real data.mat carries its own): checked before anything is built
+    task = None
+    if args.synthetic_labels == "task" and not os.path.exists(_mat_path(args)):
+        task = task_label_column(args.dataset, int(args.target), int(args.graphlet_orbit))
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if not torch.cuda.is_available():
@@ -211,16 +248,21 @@ def main(argv=None):
     if rank == 0:
         print("---- Target: {} ----".format(target))
 
-    (tr, va, te), real = _load_splits(args)
+    (tr, va, te), real = _load_splits(args, "triangle" if task is None else task[0])
 
     def column(d):                                        # MyTransform (reference :35-37)
         y = d.y
+        if task is not None and not real:
+            return y[:, task[1]]
         return y[:, target] if (real and y.dim() == 2) else y.reshape(-1)
     for part in (tr, va, te):
         for d in part:
             d.y = column(d).float()
     y_train_val = torch.cat([d.y for d in tr + va])       # reference :441-447
     mean, std = y_train_val.mean(), y_train_val.std()
+    if task is not None and not float(std) > 0:
+        raise ValueError("--dataset %s --target %d: the label is constant over the train and validation graphs "
+                         "(std %s), there is nothing to fit" % (args.dataset, target, float(std)))
     for part in (tr, va, te):
         for d in part:
             d.y = (d.y - mean) / std

@@ -755,6 +755,17 @@ int esc_features_fill(const int64_t* node_ptr, const int64_t* edge_ptr, int64_t 
 int esc_cycle_counts(const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* src, const int64_t* dst, int64_t G,
                      int64_t total_nodes, int64_t total_edges, float* out, int32_t* status, void* stream);
 
+/* ---- graphlet-counting labels (count_graphlet targets 0..4; csrc/graphlets.hip) ----------------------------
+ * Same layout, normalisation and status codes as esc_cycle_counts.  out is int32 [total_nodes, ld_out], ld_out >= 11;
+ * out[v][c] is the number of copies (subgraphs isomorphic to the pattern, not necessarily induced, each counted once) in
+ * which v sits at orbit c.  Columns: tailed triangle 0 (the triangle node carrying the tail), 1 (another triangle node),
+ * 2 (the tail end); chordal cycle 3 (a chord endpoint), 4 (a non-chord node); 4-clique 5; 4-path 6 (an end), 7 (an inner
+ * node); triangle-rectangle 8 (the apex), 9 (a node of the shared edge), 10 (a rectangle-only node).  Columns past 10 are
+ * left untouched. */
+int esc_graphlet_counts(const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* src, const int64_t* dst, int64_t G,
+                        int64_t total_nodes, int64_t total_edges, int32_t* out, int64_t ld_out, int32_t* status,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
