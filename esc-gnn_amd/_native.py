@@ -9,21 +9,23 @@ from ctypes import c_double, c_float, c_int, c_int64, c_void_p, POINTER
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libescgnn_hip.so")
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 P, I64, I32, F32 = c_void_p, c_int64, c_int, c_float
 
 class CollateArgs(ctypes.Structure):
     """mirror of `esc_collate_args` (include/escgnn_hip.h)"""
-    _fields_ = ([(n, c_int64) for n in ("B", "x_dim", "y_dim", "n_cols")] +
+    _fields_ = ([(n, c_int64) for n in ("B", "x_dim", "y_dim", "n_cols", "N", "E", "Z")] +
                 [(n, c_void_p) for n in (
-                    "graph_ids", "offsets", "node_ptr", "edge_ptr", "nnz_ptr", "y_ptr", "x_all", "y_all",
+                    "stage", "x_all", "y_all",
                     "esrc_all", "edst_all", "pos_enc_all", "pos_index_all", "pos_batch_all",
-                    "in_ptr_all", "in_edge_all", "out_ptr_all", "out_edge_all", "row_ptr_all", "c_perm_all",
-                    "c_rank_all", "col_ptr", "col_prefix",
+                    "esrc32", "edst32", "pos_enc32", "pos_index32", "pos_batch32",
+                    "in_ptr32", "out_ptr32", "in_edge32", "in_src32", "out_edge32", "out_dst32", "row_ptr32",
+                    "c_col32", "c_row32", "c_val32", "c_rank_all", "col_total", "col_prefix",
                     "x", "y", "edge_index", "batch", "pos_enc", "pos_index", "pos_batch",
                     "in_ptr", "in_edge", "in_src", "out_ptr", "out_edge", "out_dst",
-                    "row_ptr", "bag_idx", "bag_val", "col_row", "col_val", "col_col", "edge_attr_all", "edge_attr")] +
+                    "row_ptr", "bag_idx", "bag_val", "col_ptr", "col_row", "col_val", "col_col",
+                    "edge_attr_all", "edge_attr")] +
                 [("ea_words", c_int64), ("x_long", c_void_p), ("graph_ptr", c_void_p)])
 
 class BnFuse(ctypes.Structure):
@@ -138,7 +140,7 @@ SIGNATURES = {
     "esc_pdist": [P, I64, I64, I64, P, F32, P, P],
     "esc_adam_step": [P, P, P, P, I64, c_double, c_double, c_double, c_double, I64, P],
     "esc_adam_step_scaled": [P, P, P, P, I64, c_double, c_double, c_double, c_double, I64, P, P],
-    "esc_collate_cols": [P, I64, P, I64, P, P, P, P],
+    "esc_collate_cols": [P, I64, P, I64, P, P, P],
     "esc_collate_fill": [POINTER(CollateArgs), P],
     "esc_engine_set_two_stream_min_edges": [I64],
     "esc_gine_aggregate_fwd_affine": [P, I64, P, P, P, I64, P, P, P, P, I64, I64, P, I64, P],

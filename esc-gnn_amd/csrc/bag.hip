@@ -363,7 +363,10 @@ __global__ __launch_bounds__(256) void bag_bwd_pass1(const float* __restrict__ d
 // ~36x reuse instead of streaming all 15.6 MB from HBM / Infinity Cache.  Placement affects speed only: every chunk is
 // still processed exactly once and writes its own slots.
 __global__ __launch_bounds__(256) void bag_bwd_classify(const int* __restrict__ c_row, int Z, int rows, int chunks,
-                                                        int* __restrict__ order, int* __restrict__ bucket_cnt) {
+                                                        int* __restrict__ order, int* __restrict__ bucket_cnt, BnCounters cnt) {
+  // the training forward's BatchNorm step counters ride on this launch (the first one on the caller's stream): one
+  // thread per counter, nobody else touches them during the step
+  if (blockIdx.x == 0 && (int)threadIdx.x < cnt.n) *cnt.p[threadIdx.x] += 1;
   // one thread per chunk, many workgroups (the scattered middle-row reads miss: one CU alone needs ~20 us for them);
   // per wave and key ONE device atomic reserves the slots, the list of bucket k is order[k*chunks ...] in arrival
   // order — which does not matter: every chunk is processed once and writes its own slots
@@ -558,21 +561,35 @@ static inline bool bag_local_schedule(int64_t Z, int64_t H, int64_t rows) {
   return rows > 0 && rows * H * (int64_t)sizeof(float) > (4 << 20) && esc::cdiv(Z, esc::BAG_CH) >= 64;
 }
 
-int esc_bag_bwd_classify(const int32_t* c_row, int64_t Z, int64_t H, int64_t rows, float* partials, void* stream) {
+}  // extern "C"
+
+// esc_bag_bwd_classify that also adds 1 to the given BatchNorm step counters; with counters the launch is always made
+// (one workgroup when there is no schedule to build), so a training forward counts exactly once whatever the batch size
+int esc::bag_bwd_classify_counted(const int32_t* c_row, int64_t Z, int64_t H, int64_t rows, float* partials, const BnCounters& cnt,
+                                  void* stream) {
   ESC_REQUIRE(Z == 0 || (c_row && partials), "esc_bag_bwd_classify: null pointer");
   ESC_REQUIRE(H > 0 && Z >= 0 && rows >= 0 && rows < (1LL << 28) && Z < (1LL << 31) - 64, "esc_bag_bwd_classify: bad sizes");
-  if (!bag_local_schedule(Z, H, rows)) return ESC_OK;        // esc_bag_bwd_table_rows will not use a schedule either
+  ESC_REQUIRE(cnt.n >= 0 && cnt.n <= ESC_MAX_BN_COUNTERS, "esc_bag_bwd_classify: bad counter list");
+  const bool sched = bag_local_schedule(Z, H, rows);
+  if (!sched && cnt.n == 0) return ESC_OK;                   // esc_bag_bwd_table_rows will not use a schedule either
   hipStream_t s = (hipStream_t)stream;
-  const int64_t chunks = esc::cdiv(Z, esc::BAG_CH);
-  int* order = reinterpret_cast<int*>(partials + 2 * chunks * H);       // [8][chunks]
-  int* bucket_cnt = order + 8 * chunks;                                 // [8]
-  if (hipMemsetAsync(bucket_cnt, 0, 8 * sizeof(int), s) != hipSuccess) {
+  const int64_t chunks = sched ? esc::cdiv(Z, esc::BAG_CH) : 0;
+  int* order = sched ? reinterpret_cast<int*>(partials + 2 * chunks * H) : nullptr;       // [8][chunks]
+  int* bucket_cnt = sched ? order + 8 * chunks : nullptr;                                 // [8]
+  if (sched && hipMemsetAsync(bucket_cnt, 0, 8 * sizeof(int), s) != hipSuccess) {
     esc::set_error("esc_bag_bwd_classify: memset failed");
     return ESC_ELAUNCH;
   }
-  esc::launch(ESC_K_BAG_BWD, esc::bag_bwd_classify, dim3((unsigned)esc::cdiv(chunks, 256)), dim3(256), 0, s, c_row, (int)Z, (int)rows, (int)chunks, order, bucket_cnt);
+  const int64_t blocks = chunks > 0 ? esc::cdiv(chunks, 256) : 1;
+  esc::launch(ESC_K_BAG_BWD, esc::bag_bwd_classify, dim3((unsigned)blocks), dim3(256), 0, s, c_row, (int)Z, (int)rows, (int)chunks, order, bucket_cnt, cnt);
   ESC_CHECK_LAUNCH("esc_bag_bwd_classify");
   return ESC_OK;
+}
+
+extern "C" {
+
+int esc_bag_bwd_classify(const int32_t* c_row, int64_t Z, int64_t H, int64_t rows, float* partials, void* stream) {
+  return esc::bag_bwd_classify_counted(c_row, Z, H, rows, partials, esc::BnCounters{}, stream);
 }
 
 int esc_bag_bwd_table(const float* dz, int64_t ld_dz, int64_t H, const int32_t* col_ptr,

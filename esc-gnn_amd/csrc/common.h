@@ -90,6 +90,14 @@ inline void launch(int kind, void (*kernel)(KArgs...), dim3 grid, dim3 block, si
   }
 }
 
+// BatchNorm step counters (num_batches_tracked, device int64 scalars) handed by value to the launch that increments them
+struct BnCounters {
+  int n = 0;
+  int64_t* p[ESC_MAX_BN_COUNTERS] = {};
+};
+int bag_bwd_classify_counted(const int32_t* c_row, int64_t Z, int64_t H, int64_t rows, float* partials, const BnCounters& cnt,
+                             void* stream);
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
 // wave-uniform value into an SGPR so that dependent loads become scalar loads

@@ -757,7 +757,12 @@ static int forward(const Ctx& c) {
   for (int l = e0_early ? 1 : 0; l < (int)L && l < ahead; ++l) ESC_TRY(edge_term(l));
   // ---- node pipeline (first, while it would otherwise wait for the first edge term: the chunk schedule of the bag
   // gradient, which depends on the batch's index arrays only)
-  if (c.train) ESC_TRY(esc_bag_bwd_classify(b->col_row, y.Z, H, E, y.bag_scratch, c.s));
+  if (c.train) {                                             // ... and the BatchNorm step counters, in that same launch
+    BnCounters cnt;
+    cnt.n = (int)m->n_counters;
+    for (int i = 0; i < cnt.n; ++i) cnt.p[i] = m->counters[i];
+    ESC_TRY(bag_bwd_classify_counted(b->col_row, y.Z, H, E, y.bag_scratch, cnt, c.s));
+  }
   // xs[0] = x_embedding(x) (reference :166) — side stream
   SideStream& ss = side_stream();
   if (ss.ok) {
@@ -1690,6 +1695,8 @@ static int check(const esc_nested_gin_t* m, const esc_batch_t* b, const float* w
   ESC_REQUIRE(b->N >= 2 && b->E >= 2 && b->Z >= 0, "esc_engine: batch needs >= 2 nodes and edges (BatchNorm statistics)");
   ESC_REQUIRE(b->x && b->in_ptr && b->row_ptr && (!train || ((b->y || !need_y) && b->out_ptr && b->col_ptr)), "esc_engine: null batch arrays");
   ESC_REQUIRE(aligned16(ws), "esc_engine: workspace must be 16-byte aligned");
+  ESC_REQUIRE(m->n_counters >= 0 && m->n_counters <= ESC_MAX_BN_COUNTERS, "esc_engine: bad BatchNorm counter list");
+  for (int64_t i = 0; i < m->n_counters; ++i) ESC_REQUIRE(m->counters[i] != nullptr, "esc_engine: null BatchNorm counter");
   return ESC_OK;
 }
 

@@ -15,6 +15,7 @@ from . import _native as nv
 from .plan import plan_of
 
 MAX_LAYERS = 16
+MAX_BN_COUNTERS = 2 * MAX_LAYERS + 8
 
 
 class _Linear(ctypes.Structure):
@@ -39,7 +40,8 @@ class _Model(ctypes.Structure):
     _fields_ = [("num_layers", c_int64), ("hidden", c_int64), ("in_dim", c_int64), ("z_rows", c_int64),
                 ("z_table", c_void_p), ("dz_table", c_void_p),
                 ("zbn0", _BN), ("zlin", _Linear), ("zbn1", _BN), ("xemb", _MLP),
-                ("conv", _Conv * MAX_LAYERS), ("lin1", _Linear), ("bn_lin1", _BN), ("lin2", _Linear)]
+                ("conv", _Conv * MAX_LAYERS), ("lin1", _Linear), ("bn_lin1", _BN), ("lin2", _Linear),
+                ("n_counters", c_int64), ("counters", c_void_p * MAX_BN_COUNTERS)]
 
 
 class _Batch(ctypes.Structure):
@@ -113,7 +115,22 @@ def describe(m, gp=_grad_ptr):
         c.nn, c.lin = _mlp(cv.nn, gp), _lin(cv.lin, gp)
         d.conv[i] = c
     d.lin1, d.bn_lin1, d.lin2 = _lin(m.lin1, gp), _bn(m.bn_lin1, gp), _lin(m.lin2, gp)
+    # the BatchNorm step counters: a training forward of the engine adds 1 to each inside its first launch
+    counters = _bn_counters(m)
+    if len(counters) > MAX_BN_COUNTERS:
+        raise ValueError("at most %d BatchNorm step counters" % MAX_BN_COUNTERS)
+    d.n_counters = len(counters)
+    for i, t in enumerate(counters):
+        if t.dtype != torch.int64 or t.device != m.lin1.weight.device:
+            raise RuntimeError("step engine: num_batches_tracked must be an int64 tensor on the model's device")
+        d.counters[i] = t.data_ptr()
     return d
+
+
+def _bn_counters(m):
+    """num_batches_tracked of every BatchNorm1d of the model that tracks running statistics"""
+    return [mod.num_batches_tracked for mod in m.modules()
+            if isinstance(mod, torch.nn.BatchNorm1d) and mod.num_batches_tracked is not None]
 
 
 def _bns(m, cache=None):
@@ -254,14 +271,12 @@ class StepEngine(_AddressGuard):
         self.model = model
         self._ws = None
         _arm_collective(model, model.lin1.weight.device)     # SyncBN: the engine exchanges the statistics itself
-        self._bn_counters = [m.num_batches_tracked for m in model.modules()
-                             if isinstance(m, torch.nn.BatchNorm1d) and m.num_batches_tracked is not None]
         self.refresh()
 
     def refresh(self):
         """(Re)read parameter / gradient / buffer addresses — call after the optimiser re-homed them."""
         m = self.model
-        d = describe(m)
+        d = describe(m)              # (also names the BatchNorm step counters: the engine's forward increments them)
         self._desc = d
         self._keep = [p for p in m.parameters()]
         self._open = None
@@ -308,8 +323,6 @@ class StepEngine(_AddressGuard):
                 int(loss_denom or 0), loss.data_ptr(), nv.ptr(pred), nv.stream())
         self._mark_bucket_written()
         self._open = (keep, ws) if _entry.endswith("_begin") else None     # operands stay alive until end_step
-        if self._bn_counters:
-            torch._foreach_add_(self._bn_counters, 1)
         return (loss.view(()), pred.view(-1, 1)) if return_pred else loss.view(())
 
     def begin_step(self, data, loss_denom=None, return_pred=False):
@@ -345,9 +358,9 @@ class _NodeCache(object):
         import numpy as np
         self.params = list(model.parameters())
         self.buffers = [b for b in model.buffers() if b.is_floating_point()]   # the template bakes the running-stat addresses in
-        self.key = tuple(t.data_ptr() for t in self.params + self.buffers)
         self.counters = [m.num_batches_tracked for m in model.modules()
                          if isinstance(m, torch.nn.BatchNorm1d) and m.num_batches_tracked is not None]
+        self.key = tuple(t.data_ptr() for t in self.params + self.buffers + self.counters)   # (the counting engine's template names the counters too)
         self.bns = [m for m in model.modules() if hasattr(m, "sync_group")]     # see _bns
         with torch.enable_grad():       # the AccumulateGrad node of the first parameter: _node_backward asks the engine about it
             p0 = self.params[0]
@@ -367,7 +380,7 @@ class _NodeCache(object):
         self.byte_offsets = np.asarray(offs, dtype=np.uint64)[self.slot_param] * np.uint64(4)
 
     def valid(self):
-        return self.key == tuple(t.data_ptr() for t in self.params + self.buffers)
+        return self.key == tuple(t.data_ptr() for t in self.params + self.buffers + self.counters)
 
     def descriptor(self, grad_base):
         import numpy as np
@@ -505,8 +518,7 @@ class _EngineNode(torch.autograd.Function):
         ws = torch.empty(int(need), dtype=torch.float32, device=dev)   # private: stays intact until the backward
         pred = torch.empty(b.N, dtype=torch.float32, device=dev)
         nv.call("esc_engine_forward_train", ctypes.byref(desc), ctypes.byref(b), ws.data_ptr(), pred.data_ptr(), nv.stream())
-        if cache.counters:
-            torch._foreach_add_(cache.counters, 1)
+        # (the BatchNorm step counters are in the descriptor: that call has incremented them)
         ctx.cache, ctx.b, ctx.keep, ctx.ws, ctx.n_in = cache, b, keep, ws, len(params)
         return pred.view(-1, 1)
 

@@ -83,6 +83,40 @@ class DeviceGraphStore(object):
         gc_ptr, self.c_perm_all = _stable_group(gc_key, G * N_COLS)
         self.c_rank_all = (torch.arange(Zz, device=dev) - gc_ptr[gc_key[self.c_perm_all]]).to(torch.int32)
         self.col_cnt_all = (gc_ptr[1:] - gc_ptr[:-1]).to(torch.int32).view(G, N_COLS).contiguous()
+        self._build_views()
+
+    # what the fill kernel reads: int32, graph-local, already in the order it is written in (built once; csrc/collate.hip)
+    _VIEWS = ("in_ptr32", "out_ptr32", "in_edge32", "in_src32", "out_edge32", "out_dst32", "row_ptr32",
+              "c_col32", "c_row32", "c_val32")
+    # int32 copies of the row-order arrays behind the reference-visible int64 outputs: kept only where every value fits
+    _NARROW = (("esrc32", "esrc_all"), ("edst32", "edst_all"), ("pos_enc32", "pos_enc_all"),
+               ("pos_index32", "pos_index_all"), ("pos_batch32", "pos_batch_all"))
+
+    def _build_views(self):
+        """The compact views of the fill kernel, from the int64 arrays and the sorted views above.  Plan outputs are int32
+        anyway (today's `(int)` conversion of value + offset), so their views keep the low 32 bits of the graph-local
+        value; an int64 output whose source does not fit int32 keeps reading the int64 array (its narrow copy is None)."""
+        dev, G = self.device, self.num_graphs
+
+        def low32(t):                       # the (int) conversion of an int64: low 32 bits, sign-extended
+            return (((t & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32).contiguous()
+
+        def per(hptr):
+            return torch.repeat_interleave(torch.arange(G, device=dev), (hptr[1:] - hptr[:-1]).to(dev))
+        gid_n, gid_e = per(self.h_node_ptr), per(self.h_edge_ptr)
+        e0_n, e0_e, z0_e = self.edge_ptr[gid_n], self.edge_ptr[gid_e], self.nnz_ptr[gid_e]
+        self.in_ptr32, self.out_ptr32 = low32(self.in_ptr_all[:-1] - e0_n), low32(self.out_ptr_all[:-1] - e0_n)
+        self.in_edge32, self.out_edge32 = low32(self.in_edge_all - e0_e), low32(self.out_edge_all - e0_e)
+        self.in_src32, self.out_dst32 = low32(self.esrc_all[self.in_edge_all]), low32(self.edst_all[self.out_edge_all])
+        self.row_ptr32 = low32(self.row_ptr_all[:-1] - z0_e)
+        perm = self.c_perm_all
+        self.c_col32, self.c_row32 = low32(self.pos_index_all[perm]), low32(self.pos_batch_all[perm])
+        self.c_val32 = low32(self.pos_enc_all[perm])
+        for name, src in self._NARROW:
+            t = getattr(self, src)
+            fits = t.numel() == 0 or (int(t.min()) >= -2 ** 31 and int(t.max()) < 2 ** 31)
+            setattr(self, name, t.to(torch.int32).contiguous() if fits else None)
+        self.__dict__.pop("_args_tpl", None)
 
     def _compute_int_ranges(self):
         """value range of the integer features, per column: batches gathered from this store are known to stay inside it,
@@ -159,6 +193,11 @@ class DeviceGraphStore(object):
         for k, v in blob.items():
             setattr(self, k, v if (k in cls._HOST or k in cls._META) else v.to(dev))
         self._compute_int_ranges()
+        if all(k in blob for k in cls._VIEWS):
+            for name, _ in cls._NARROW:                       # absent from a current blob = did not fit int32
+                self.__dict__.setdefault(name, None)
+        else:                                                 # a cache written before the compact views existed
+            self._build_views()
         return self
 
     def nbytes(self):
@@ -166,16 +205,12 @@ class DeviceGraphStore(object):
 
     def collate(self, graph_ids):
         """Batch.from_data_list over the selected graphs, on the device.  graph_ids: 1-D LongTensor/list."""
-        # host ids are the fast path: ids and offsets travel through pinned staging buffers with async copies, so the
-        # host never waits for the device inside a training loop (device ids cost a D2H synchronisation)
+        # host ids are the fast path: ids, per-graph ranges and running offsets travel as ONE pinned block with ONE async
+        # copy, so the host never waits for the device inside a training loop (device ids cost a D2H synchronisation)
         if torch.is_tensor(graph_ids) and graph_ids.is_cuda:
-            ids_d = graph_ids.to(torch.int64).contiguous()
-            ids_h = ids_d.cpu()
+            ids_h = graph_ids.to(torch.int64).reshape(-1).cpu()
         else:
             ids_h = torch.as_tensor(graph_ids, dtype=torch.int64).reshape(-1)
-            ids_p = torch.empty(ids_h.numel(), dtype=torch.int64, pin_memory=True)
-            ids_p.copy_(ids_h)
-            ids_d = ids_p.to(self.device, non_blocking=True)
         B = ids_h.numel()
         if B == 0:
             raise ValueError("collate: empty batch")
@@ -187,11 +222,21 @@ class DeviceGraphStore(object):
         if ptrs is None:
             ptrs = np.stack([t.numpy() for t in (self.h_node_ptr, self.h_edge_ptr, self.h_nnz_ptr, self.h_y_ptr)])
             self.__dict__["_np_ptrs"] = ptrs
-        offs = torch.zeros(4, B + 1, dtype=torch.int64, pin_memory=True)
+        # the staged block (int64 words): ids[B] | start[4][B] | count[4][B] | offsets[4][B+1]  — rows: node, edge, nnz, y
+        stage = torch.empty(13 * B + 4, dtype=torch.int64, pin_memory=True)
+        st = stage.numpy()
         idn = ids_h.numpy()
-        np.cumsum(ptrs[:, idn + 1] - ptrs[:, idn], axis=1, out=offs.numpy()[:, 1:])
-        N, E, Z, Y = (int(v) for v in offs.numpy()[:, B])
-        offs_d = offs.to(self.device, non_blocking=True)
+        st[:B] = idn
+        start, count = st[B:5 * B].reshape(4, B), st[5 * B:9 * B].reshape(4, B)
+        offs_np = st[9 * B:].reshape(4, B + 1)
+        np.take(ptrs, idn, axis=1, out=start)
+        np.subtract(ptrs[:, idn + 1], start, out=count)
+        offs_np[:, 0] = 0
+        np.cumsum(count, axis=1, out=offs_np[:, 1:])
+        N, E, Z, Y = (int(v) for v in offs_np[:, B])
+        stage_d = stage.to(self.device, non_blocking=True)
+        ids_d, offs_d = stage_d[:B], stage_d[9 * B:].view(4, B + 1)
+        offs = stage[9 * B:].view(4, B + 1)
         dev, i64, i32, f32 = self.device, torch.int64, torch.int32, torch.float32
         # categorical node features (ZINC / OGB) leave the fill kernel as int64; per-edge attribute rows are gathered by it too
         x = torch.empty((N, self.x_dim), dtype=i64 if self.x_is_int else f32, device=dev)
@@ -219,26 +264,25 @@ class DeviceGraphStore(object):
          col_ptr, col_total, col_prefix) = parts
         s = nv.stream()
         nv.call("esc_collate_cols", nv.ptr(self.col_cnt_all), N_COLS, nv.ptr(ids_d), B, nv.ptr(col_prefix),
-                nv.ptr(col_total), nv.ptr(col_ptr), s)
+                nv.ptr(col_total), s)
         tpl = self.__dict__.get("_args_tpl")
         if tpl is None:                 # the store's own arrays never move: their addresses are filled in once
             t0 = nv.CollateArgs()
             t0.x_dim, t0.y_dim, t0.n_cols = self.x_dim, self.y_dim, N_COLS
-            for name in ("node_ptr", "edge_ptr", "nnz_ptr", "y_ptr", "x_all", "y_all", "esrc_all", "edst_all", "pos_enc_all",
-                         "pos_index_all", "pos_batch_all", "in_ptr_all", "in_edge_all", "out_ptr_all", "out_edge_all",
-                         "row_ptr_all", "c_perm_all", "c_rank_all"):
-                setattr(t0, name, getattr(self, name).data_ptr())
+            for name in ("x_all", "y_all", "esrc_all", "edst_all", "pos_enc_all", "pos_index_all", "pos_batch_all",
+                         "c_rank_all") + self._VIEWS + tuple(n for n, _ in self._NARROW):
+                setattr(t0, name, nv.ptr(getattr(self, name)))
             tpl = bytes(t0)
             self.__dict__["_args_tpl"] = tpl
         a = nv.CollateArgs.from_buffer_copy(tpl)
-        a.B = B
-        a.graph_ids, a.offsets, a.col_ptr, a.col_prefix = ids_d.data_ptr(), offs_d.data_ptr(), col_ptr.data_ptr(), col_prefix.data_ptr()
+        a.B, a.N, a.E, a.Z = B, N, E, Z
+        a.stage, a.col_total, a.col_prefix = stage_d.data_ptr(), col_total.data_ptr(), col_prefix.data_ptr()
         a.x, a.y, a.edge_index, a.batch = x.data_ptr(), y.data_ptr(), edge_index.data_ptr(), batch.data_ptr()
         a.pos_enc, a.pos_index, a.pos_batch = pos_enc.data_ptr(), pos_index.data_ptr(), pos_batch.data_ptr()
         base32 = slab.data_ptr()        # the plan arrays are consecutive int32 ranges of one slab
         o = 0
         for name, s_ in zip(("in_ptr", "in_edge", "in_src", "out_ptr", "out_edge", "out_dst", "row_ptr", "bag_idx", "bag_val",
-                             "col_row", "col_val", "col_col"), sizes):
+                             "col_row", "col_val", "col_col", "col_ptr"), sizes):
             setattr(a, name, base32 + 4 * o)
             o += s_
         if self.x_is_int:
@@ -265,7 +309,7 @@ class DeviceGraphStore(object):
                          out_dst=out_dst, row_ptr=row_ptr, bag_idx=bag_idx, bag_val=bag_val, col_ptr=col_ptr,
                          col_row=col_row, col_val=col_val, col_col=col_col, num_nodes=N, num_edges=E, nnz=Z,
                          n_cols=N_COLS)
-        plan._keepalive = (slab, offs_d, ids_d)
+        plan._keepalive = (slab, stage_d)
         plan.graph_ptr, plan.num_graphs = graph_ptr, B       # node range of every graph (readout pooling)
         plan._batch_sig = _sig(batch)
         object.__setattr__(out, "_num_graphs", B)

@@ -468,6 +468,7 @@ int esc_adam_step_scaled(float* param, const float* grad, float* exp_avg, float*
  * (z_emb and the hidden MLP activations are never materialised) and layer outputs written straight
  * into the [N,(L+1)H] concatenation buffer.  Gradients are WRITTEN (not accumulated) into the d* slots. */
 #define ESC_MAX_LAYERS 16
+#define ESC_MAX_BN_COUNTERS (2 * ESC_MAX_LAYERS + 8)   /* two per GINE layer + z_embedding (2), x_embedding (2), bn_lin1 */
 typedef struct esc_linear_t { const float* w; const float* b; float* dw; float* db; int64_t in_dim, out_dim; } esc_linear_t;
 typedef struct esc_bn_t { const float* gamma; const float* beta; float* dgamma; float* dbeta;
                           float* running_mean; float* running_var; float eps, momentum; } esc_bn_t;
@@ -480,6 +481,11 @@ typedef struct esc_nested_gin_t {
   esc_mlp_t xemb;                                        /* x_embedding */
   esc_conv_t conv[ESC_MAX_LAYERS];                       /* conv1, convs.* */
   esc_linear_t lin1; esc_bn_t bn_lin1; esc_linear_t lin2;
+  /* num_batches_tracked of the model's BatchNorms (device int64 scalars): a TRAINING forward adds 1 to each inside its
+   * first launch on the caller's stream (esc_engine_train_step*, esc_engine_forward_train); esc_engine_predict and
+   * esc_engine_backward leave them alone.  n_counters = 0: nothing to count. */
+  int64_t n_counters;
+  int64_t* counters[ESC_MAX_BN_COUNTERS];
 } esc_nested_gin_t;
 typedef struct esc_batch_t {
   int64_t N, E, Z;
@@ -674,45 +680,54 @@ int esc_ogb_predict(const esc_ogb_gnn_t* m, const esc_ogb_batch_t* b, float* wor
 
 /* ---- a-5 collate (batch.py:25-149): gather B graphs out of the HBM-resident dataset store ------
  * The store keeps the reference's InMemoryDataset layout (per-key concatenation + slice pointers,
- * GraphCountDataset.py:119-120) plus views sorted ONCE at build time (suffix _all):
- *   in_ptr_all[nodes+1] / in_edge_all[edges]   edges grouped by (global) destination, stable
- *   out_ptr_all / out_edge_all                 edges grouped by source
- *   row_ptr_all[edges+1]                       first bag entry of each edge
- *   c_perm_all[nnz] / c_rank_all[nnz]          entries grouped by (graph, histogram bin) + rank inside the group
- *   col_cnt_all[graphs][n_cols]                entries per bin per graph
- * offsets = int64[4][B+1]: exclusive prefix sums of the selected graphs' node / edge / nnz / y-row
- * counts (computed by the host from its copy of the slice pointers).
+ * GraphCountDataset.py:119-120) plus views derived ONCE at build time.  Every view the fill reads is int32 and
+ * graph-LOCAL (low 32 bits of the int64 value), so a batch entry is one load + one add:
+ *   in_ptr32[nodes] / in_edge32[edges] / in_src32[edges]    edges grouped by destination, stable: first edge of a node,
+ *                                                           edge id, source node of the edge in that order
+ *   out_ptr32 / out_edge32 / out_dst32                      the same grouped by source
+ *   row_ptr32[edges]                                        first bag entry of each edge
+ *   c_col32 / c_row32 / c_val32 / c_rank_all [nnz]          bag entries in (graph, histogram bin) order: bin, edge, value
+ *                                                           and rank inside the (graph, bin) group
+ *   col_cnt_all[graphs][n_cols]                             entries per bin per graph
+ *   esrc32, edst32, pos_enc32, pos_index32, pos_batch32     int32 copies of the row-order arrays; NULL where a value
+ *                                                           does not fit int32 - the int64 output is then read from
+ *                                                           the int64 array (esrc_all ...), which is always given
+ * stage = ONE staged block per batch (int64 words, built by the host from its copy of the slice pointers, one copy):
+ *   ids[B] | start[4][B] | count[4][B] | offsets[4][B+1]
+ * rows of start / count / offsets: node, edge, nnz, y-row; start and count are the graph's range in the store,
+ * offsets the exclusive prefix sums of the counts over the batch.  N, E, Z = offsets[0..2][B].
  * Outputs: the reference's batch tensors (x, y, edge_index[2,E], batch, pos_enc, pos_index, pos_batch:
  * int64 index tensors bit-identical to Batch.from_data_list) and the compact int32 plan consumed by
  * esc_bag_* / esc_gine_aggregate_*. */
 typedef struct esc_collate_args {
   int64_t B, x_dim, y_dim, n_cols;
-  const int64_t* graph_ids;     /* [B] device */
-  const int64_t* offsets;       /* [4][B+1] device */
+  int64_t N, E, Z;              /* totals of the batch */
+  const int64_t* stage;         /* device copy of the staged block */
   /* store */
-  const int64_t *node_ptr, *edge_ptr, *nnz_ptr, *y_ptr;
   const float *x_all, *y_all;
   const int64_t *esrc_all, *edst_all, *pos_enc_all, *pos_index_all, *pos_batch_all;
-  const int64_t *in_ptr_all, *in_edge_all, *out_ptr_all, *out_edge_all, *row_ptr_all, *c_perm_all;
-  const int32_t* c_rank_all;
+  const int32_t *esrc32, *edst32, *pos_enc32, *pos_index32, *pos_batch32;      /* NULL: read the int64 array */
+  const int32_t *in_ptr32, *out_ptr32, *in_edge32, *in_src32, *out_edge32, *out_dst32, *row_ptr32;
+  const int32_t *c_col32, *c_row32, *c_val32, *c_rank_all;
   /* from esc_collate_cols */
-  const int32_t *col_ptr, *col_prefix;
+  const int32_t *col_total, *col_prefix;
   /* reference-visible outputs */
   float *x, *y;
   int64_t *edge_index, *batch, *pos_enc, *pos_index, *pos_batch;
-  /* plan outputs */
+  /* plan outputs (col_ptr[n_cols+1] = exclusive scan of col_total, done in the fill's prologue) */
   int32_t *in_ptr, *in_edge, *in_src, *out_ptr, *out_edge, *out_dst;
-  int32_t *row_ptr, *bag_idx, *bag_val, *col_row, *col_val, *col_col;
-  /* optional (ABI 3; NULL / 0 = absent) */
+  int32_t *row_ptr, *bag_idx, *bag_val, *col_ptr, *col_row, *col_val, *col_col;
+  /* optional (NULL / 0 = absent) */
   const void* edge_attr_all;    /* per-edge attribute rows of the store, ea_words 4-byte words each (edge_attr of ZINC / OGB) */
   void* edge_attr;              /* [E][ea_words] gathered like edge_index (Batch.from_data_list, batch.py:112-113: no offset) */
   int64_t ea_words;
   int64_t* x_long;              /* categorical node features: x written as int64 here instead of float into `x` */
   int32_t* graph_ptr;           /* [B+1] first node of every graph of the batch (= offsets row 0 as int32) */
 } esc_collate_args;
-/* column bookkeeping of the batch: col_prefix[B][n_cols], col_total[n_cols], col_ptr[n_cols+1] */
+/* column bookkeeping of the batch: col_prefix[B][n_cols] (entries of a bin in the earlier graphs of the batch) and
+ * col_total[n_cols]; graph_ids = the head of the staged block */
 int esc_collate_cols(const int32_t* col_cnt_all, int64_t n_cols, const int64_t* graph_ids, int64_t B,
-                     int32_t* col_prefix, int32_t* col_total, int32_t* col_ptr, void* stream);
+                     int32_t* col_prefix, int32_t* col_total, void* stream);
 int esc_collate_fill(const esc_collate_args* args /* host struct of device pointers */, void* stream);
 
 /* ---- a-1..a-4 feature build (utils_edge_efficient.py:20-152,201-294) -----------------------
