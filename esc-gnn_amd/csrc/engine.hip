@@ -1700,6 +1700,28 @@ static int check(const esc_nested_gin_t* m, const esc_batch_t* b, const float* w
   return ESC_OK;
 }
 
+static int copy_floats(float* dst, const float* src, int64_t n, void* stream, const char* what) {
+  if (hipMemcpyAsync(dst, src, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
+    set_error("%s: copy failed", what);
+    return ESC_ELAUNCH;
+  }
+  return ESC_OK;
+}
+
+// The deferred-reduction job list of a training entry: it lives in the entry's frame, the Ctx points at it.  Armed when the
+// step's `budget` of jobs fits (else the reductions stay inline); the forward_train entries only mark the main chain
+// (statistics from the GEMM epilogues) and arm it whatever the budget (`always`).
+struct JobList {
+  std::vector<esc_reduce_job> jobs;
+  float* cursor = nullptr;
+};
+
+static void arm_jobs(Ctx& c, JobList& l, float* slabs, int64_t budget, bool always = false) {
+  if (!always) l.jobs.reserve(ESC_MAX_REDUCE_JOBS);
+  l.cursor = slabs;
+  if (always || budget <= ESC_MAX_REDUCE_JOBS) { c.jobs = &l.jobs; c.slab_cursor = &l.cursor; }
+}
+
 }  // namespace esc
 
 using namespace esc;
@@ -1801,10 +1823,8 @@ static int train_step_impl(const esc_nested_gin_t* m, const esc_batch_t* b, floa
   if (rc) return rc;
   ESC_REQUIRE(loss, "esc_engine_train_step: null loss pointer");
   Ctx c{m, b, plan_layout(m, b->N, b->E, b->Z, workspace, true), stream, true};
-  std::vector<esc_reduce_job> jobs;
-  jobs.reserve(ESC_MAX_REDUCE_JOBS);
-  float* cursor = c.y.slabs;
-  if (3 * m->num_layers + 7 <= ESC_MAX_REDUCE_JOBS) { c.jobs = &jobs; c.slab_cursor = &cursor; }
+  JobList jobs;
+  arm_jobs(c, jobs, c.y.slabs, 3 * m->num_layers + 7);
   const int64_t denom = loss_denom > 0 ? loss_denom : b->N;
   EdgeStream& es = edge_stream_for(b->E);
   const bool head_l1 = g_l1_head && es.ok && m->hidden <= 1024 &&
@@ -1817,12 +1837,7 @@ static int train_step_impl(const esc_nested_gin_t* m, const esc_batch_t* b, floa
     ESC_TRY(esc_l1_loss(c.y.pred, b->y, b->N, denom, 1.0f, loss, c.y.dpred, stream));
   }
   mark(PH_NODE_FWD_DONE, stream);
-  if (pred) {
-    if (hipMemcpyAsync(pred, c.y.pred, sizeof(float) * (size_t)b->N, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
-      set_error("esc_engine_train_step: prediction copy failed");
-      return ESC_ELAUNCH;
-    }
-  }
+  if (pred) ESC_TRY(copy_floats(pred, c.y.pred, b->N, stream, "esc_engine_train_step"));
   return backward(c, defer);
 }
 
@@ -1836,15 +1851,10 @@ int esc_engine_forward_train(const esc_nested_gin_t* m, const esc_batch_t* b, fl
   if (rc) return rc;
   ESC_REQUIRE(pred, "esc_engine_forward_train: null output");
   Ctx c{m, b, plan_layout(m, b->N, b->E, b->Z, workspace, true), stream, true};
-  std::vector<esc_reduce_job> jobs;            // only marks the main chain (statistics from the GEMM epilogues)
-  float* cursor = c.y.slabs;
-  c.jobs = &jobs; c.slab_cursor = &cursor;
+  JobList jobs;
+  arm_jobs(c, jobs, c.y.slabs, 0, true);
   ESC_TRY(forward(c));
-  if (hipMemcpyAsync(pred, c.y.pred, sizeof(float) * (size_t)b->N, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
-    set_error("esc_engine_forward_train: prediction copy failed");
-    return ESC_ELAUNCH;
-  }
-  return ESC_OK;
+  return copy_floats(pred, c.y.pred, b->N, stream, "esc_engine_forward_train");
 }
 
 int esc_engine_backward(const esc_nested_gin_t* m, const esc_batch_t* b, float* workspace, const float* dpred,
@@ -1854,14 +1864,9 @@ int esc_engine_backward(const esc_nested_gin_t* m, const esc_batch_t* b, float* 
   if (rc) return rc;
   ESC_REQUIRE(dpred, "esc_engine_backward: null gradient");
   Ctx c{m, b, plan_layout(m, b->N, b->E, b->Z, workspace, true), stream, true};
-  std::vector<esc_reduce_job> jobs;
-  jobs.reserve(ESC_MAX_REDUCE_JOBS);
-  float* cursor = c.y.slabs;
-  if (3 * m->num_layers + 7 <= ESC_MAX_REDUCE_JOBS) { c.jobs = &jobs; c.slab_cursor = &cursor; }
-  if (hipMemcpyAsync(c.y.dpred, dpred, sizeof(float) * (size_t)b->N, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
-    set_error("esc_engine_backward: gradient copy failed");
-    return ESC_ELAUNCH;
-  }
+  JobList jobs;
+  arm_jobs(c, jobs, c.y.slabs, 3 * m->num_layers + 7);
+  ESC_TRY(copy_floats(c.y.dpred, dpred, b->N, stream, "esc_engine_backward"));
   return backward(c, nullptr);
 }
 
@@ -1873,11 +1878,7 @@ int esc_engine_predict(const esc_nested_gin_t* m, const esc_batch_t* b, float* w
   ESC_REQUIRE(pred, "esc_engine_predict: null output");
   Ctx c{m, b, plan_layout(m, b->N, b->E, b->Z, workspace, false), stream, false};
   ESC_TRY(forward(c));
-  if (hipMemcpyAsync(pred, c.y.pred, sizeof(float) * (size_t)b->N, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
-    set_error("esc_engine_predict: prediction copy failed");
-    return ESC_ELAUNCH;
-  }
-  return ESC_OK;
+  return copy_floats(pred, c.y.pred, b->N, stream, "esc_engine_predict");
 }
 
 // ---- ZINC variant ------------------------------------------------------------------------------------------------------
@@ -1889,14 +1890,6 @@ int64_t esc_zinc_workspace_floats(const esc_zinc_gin_t* m, int64_t N, int64_t E,
 // rows of pred / dpred / y: one per graph, or one per node (node_readout)
 static int64_t zinc_rows(const esc_zinc_gin_t* m, const esc_mol_batch_t* b) { return m->node_readout ? b->N : b->G; }
 
-static int copy_floats(float* dst, const float* src, int64_t n, void* stream, const char* what) {
-  if (hipMemcpyAsync(dst, src, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
-    set_error("%s: copy failed", what);
-    return ESC_ELAUNCH;
-  }
-  return ESC_OK;
-}
-
 int esc_zinc_train_step(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, float* workspace, int64_t loss_denom,
                         float* loss, float* pred, void* stream) {
   ESC_TRY(finish_pending(pending()));
@@ -1904,10 +1897,8 @@ int esc_zinc_train_step(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, float
   if (rc) return rc;
   ESC_REQUIRE(loss, "esc_zinc_train_step: null loss pointer");
   ZincCtx z = make_zinc(m, b, workspace, stream, true);
-  std::vector<esc_reduce_job> jobs;
-  jobs.reserve(ESC_MAX_REDUCE_JOBS);
-  float* cursor = z.c.y.slabs;
-  if (3 * m->num_layers + 3 <= ESC_MAX_REDUCE_JOBS) { z.c.jobs = &jobs; z.c.slab_cursor = &cursor; }
+  JobList jobs;
+  arm_jobs(z.c, jobs, z.c.y.slabs, 3 * m->num_layers + 3);
   const int64_t R = zinc_rows(m, b);
   ESC_TRY(forward_zinc(z));
   ESC_TRY(esc_l1_loss(z.c.y.pred, b->y, R, loss_denom > 0 ? loss_denom : R, 1.0f, loss, z.c.y.dpred, stream));
@@ -1921,9 +1912,8 @@ int esc_zinc_forward_train(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, fl
   if (rc) return rc;
   ESC_REQUIRE(pred, "esc_zinc_forward_train: null output");
   ZincCtx z = make_zinc(m, b, workspace, stream, true);
-  std::vector<esc_reduce_job> jobs;            // only marks the main chain (statistics from the GEMM epilogues)
-  float* cursor = z.c.y.slabs;
-  z.c.jobs = &jobs; z.c.slab_cursor = &cursor;
+  JobList jobs;
+  arm_jobs(z.c, jobs, z.c.y.slabs, 0, true);
   ESC_TRY(forward_zinc(z));
   return copy_floats(pred, z.c.y.pred, zinc_rows(m, b), stream, "esc_zinc_forward_train");
 }
@@ -1934,10 +1924,8 @@ int esc_zinc_backward(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, float* 
   if (rc) return rc;
   ESC_REQUIRE(dpred, "esc_zinc_backward: null gradient");
   ZincCtx z = make_zinc(m, b, workspace, stream, true);
-  std::vector<esc_reduce_job> jobs;
-  jobs.reserve(ESC_MAX_REDUCE_JOBS);
-  float* cursor = z.c.y.slabs;
-  if (3 * m->num_layers + 3 <= ESC_MAX_REDUCE_JOBS) { z.c.jobs = &jobs; z.c.slab_cursor = &cursor; }
+  JobList jobs;
+  arm_jobs(z.c, jobs, z.c.y.slabs, 3 * m->num_layers + 3);
   ESC_TRY(copy_floats(z.c.y.dpred, dpred, zinc_rows(m, b), stream, "esc_zinc_backward"));
   return backward_zinc(z);
 }
@@ -1959,12 +1947,6 @@ int64_t esc_ogb_workspace_floats(const esc_ogb_gnn_t* m, int64_t N, int64_t E, i
   return plan_layout_ogb(m, N, E, Z, G, atom_entries, bond_entries, nullptr, true).total + 64;
 }
 
-static void ogb_jobs(OgbCtx& z, std::vector<esc_reduce_job>& jobs, float*& cursor) {
-  jobs.reserve(ESC_MAX_REDUCE_JOBS);
-  cursor = z.o.slabs;
-  if (5 * z.m->num_layers + 2 <= ESC_MAX_REDUCE_JOBS) { z.c.jobs = &jobs; z.c.slab_cursor = &cursor; }
-}
-
 int esc_ogb_train_step(const esc_ogb_gnn_t* m, const esc_ogb_batch_t* b, float* workspace, int64_t loss_denom, float* loss,
                        float* logits, void* stream) {
   ESC_TRY(finish_pending(pending()));
@@ -1972,9 +1954,8 @@ int esc_ogb_train_step(const esc_ogb_gnn_t* m, const esc_ogb_batch_t* b, float* 
   if (rc) return rc;
   ESC_REQUIRE(loss, "esc_ogb_train_step: null loss pointer");
   OgbCtx z = make_ogb(m, b, workspace, stream, true);
-  std::vector<esc_reduce_job> jobs;
-  float* cursor = nullptr;
-  ogb_jobs(z, jobs, cursor);
+  JobList jobs;
+  arm_jobs(z.c, jobs, z.o.slabs, 5 * m->num_layers + 2);
   ESC_TRY(forward_ogb(z));
   ESC_TRY(esc_bce_logits_loss(z.o.logits, b->y, b->G * m->num_tasks, loss_denom, loss, z.o.dlogits, stream));
   if (logits) ESC_TRY(copy_floats(logits, z.o.logits, b->G * m->num_tasks, stream, "esc_ogb_train_step"));
@@ -1987,9 +1968,8 @@ int esc_ogb_forward_train(const esc_ogb_gnn_t* m, const esc_ogb_batch_t* b, floa
   if (rc) return rc;
   ESC_REQUIRE(logits, "esc_ogb_forward_train: null output");
   OgbCtx z = make_ogb(m, b, workspace, stream, true);
-  std::vector<esc_reduce_job> jobs;
-  float* cursor = z.o.slabs;
-  z.c.jobs = &jobs; z.c.slab_cursor = &cursor;
+  JobList jobs;
+  arm_jobs(z.c, jobs, z.o.slabs, 0, true);
   ESC_TRY(forward_ogb(z));
   return copy_floats(logits, z.o.logits, b->G * m->num_tasks, stream, "esc_ogb_forward_train");
 }
@@ -2000,9 +1980,8 @@ int esc_ogb_backward(const esc_ogb_gnn_t* m, const esc_ogb_batch_t* b, float* wo
   if (rc) return rc;
   ESC_REQUIRE(dlogits, "esc_ogb_backward: null gradient");
   OgbCtx z = make_ogb(m, b, workspace, stream, true);
-  std::vector<esc_reduce_job> jobs;
-  float* cursor = nullptr;
-  ogb_jobs(z, jobs, cursor);
+  JobList jobs;
+  arm_jobs(z.c, jobs, z.o.slabs, 5 * m->num_layers + 2);
   ESC_TRY(copy_floats(z.o.dlogits, dlogits, b->G * m->num_tasks, stream, "esc_ogb_backward"));
   return backward_ogb(z);
 }

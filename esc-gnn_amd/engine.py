@@ -1,12 +1,23 @@
-"""StepEngine — NestedGIN_eff training/eval step as ONE call into libescgnn_hip.so
-(esc_engine_train_step / esc_engine_predict, csrc/engine.hip).
+"""Step engines — a model's training / eval step as ONE call into libescgnn_hip.so (csrc/engine.hip).
 
 The autograd path (`model(batch)`; `loss.backward()`) stays the drop-in interface; this is the fast
 path for the same module: it reads the module's parameters, writes the same `.grad` slots
 (views of the optimiser's flat gradient bucket) and updates the same BatchNorm buffers, so
 checkpoints, `optimizer.step()` and the data-parallel all-reduce are unchanged.
+
+Three model FAMILIES run on it: the counting NestedGIN_eff (esc_engine_*), the ZINC NestedGIN_eff (esc_zinc_*) and
+the OGB molecule GNN (esc_ogb_*).  A family is one `_Family` record (COUNTING, ZINC, OGB below): the prefix of its C
+entry points, its descriptor builder and struct, its batch builder, and the few places where the families differ.
+Everything on the host is written once and reads that record:
+  _FamilyEngine   train_step / predict on a persistent workspace (StepEngine, ZincStepEngine, OgbStepEngine)
+  _EngineNode     `model(batch)` in training mode as one autograd node (*_engine_forward)
+  _predict        eval-mode forward as one call (*_engine_predict and the engines' predict)
+  _NodeCache      per-model descriptor template behind the last two
+A further family is a descriptor builder, a batch builder and one more record.
 """
+import collections
 import ctypes
+import functools
 from ctypes import c_float, c_int32, c_int64, c_uint64, c_void_p
 
 import torch
@@ -16,6 +27,20 @@ from .plan import plan_of
 
 MAX_LAYERS = 16
 MAX_BN_COUNTERS = 2 * MAX_LAYERS + 8
+# the index arrays of a batch plan (plan.py): the tail of every family's batch struct
+_PLAN_FIELDS = ("in_ptr", "in_edge", "in_src", "out_ptr", "out_edge", "out_dst", "row_ptr", "bag_idx", "bag_val",
+                "col_ptr", "col_row", "col_val", "col_col")
+_PLAN_POINTERS = [(n, c_void_p) for n in _PLAN_FIELDS]
+
+
+def _bind_plan(b, plan):
+    for f in _PLAN_FIELDS:
+        setattr(b, f, getattr(plan, f).data_ptr())
+
+
+def _f32c(t):
+    """`t` as contiguous float32 (itself when it already is)"""
+    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
 
 
 class _Linear(ctypes.Structure):
@@ -45,9 +70,7 @@ class _Model(ctypes.Structure):
 
 
 class _Batch(ctypes.Structure):
-    _fields_ = ([("N", c_int64), ("E", c_int64), ("Z", c_int64), ("x", c_void_p), ("y", c_void_p)] +
-                [(n, c_void_p) for n in ("in_ptr", "in_edge", "in_src", "out_ptr", "out_edge", "out_dst",
-                                         "row_ptr", "bag_idx", "bag_val", "col_ptr", "col_row", "col_val", "col_col")])
+    _fields_ = [("N", c_int64), ("E", c_int64), ("Z", c_int64), ("x", c_void_p), ("y", c_void_p)] + _PLAN_POINTERS
 
 
 class _Embed(ctypes.Structure):
@@ -64,9 +87,7 @@ class _ZincModel(ctypes.Structure):
 
 class _MolBatch(ctypes.Structure):
     _fields_ = ([("N", c_int64), ("E", c_int64), ("Z", c_int64), ("G", c_int64), ("node_type", c_void_p),
-                 ("edge_type", c_void_p), ("y", c_void_p), ("graph_ptr", c_void_p)] +
-                [(n, c_void_p) for n in ("in_ptr", "in_edge", "in_src", "out_ptr", "out_edge", "out_dst",
-                                         "row_ptr", "bag_idx", "bag_val", "col_ptr", "col_row", "col_val", "col_col")])
+                 ("edge_type", c_void_p), ("y", c_void_p), ("graph_ptr", c_void_p)] + _PLAN_POINTERS)
 
 
 def _grad_ptr(p):
@@ -253,299 +274,39 @@ class _AddressGuard(object):
         """train_step OVERWRITES the .grad storage through raw addresses, which torch's version counter does not see: a
         FlatBucket that still believes it is as zero_grad() left it would let a later `model(batch).backward()` write
         straight into it (overwriting this step's gradients instead of accumulating onto them)."""
-        from .parallel import _BUCKETS
-        g0 = self._guard_params[0].grad
-        base = getattr(g0, "_base", None) if g0 is not None else None
-        bucket = _BUCKETS.get(base.data_ptr()) if base is not None else None
+        bucket = _bucket_of(self._guard_params[0])
         if bucket is not None:
             bucket._clean_version = None
 
 
-class StepEngine(_AddressGuard):
-    def __init__(self, model):
-        if model.graph_pred or model.dropout != 0 or not model.use_cycle:
-            raise NotImplementedError("StepEngine covers the run_graphcount configuration "
-                                      "(graph_pred=False, dropout=0, use_cycle=True); use model(batch) otherwise")
-        if model.lin1.weight.device.type != "cuda":
-            raise RuntimeError("StepEngine runs on the HIP device only; there is no CPU fallback")
-        self.model = model
-        self._ws = None
-        _arm_collective(model, model.lin1.weight.device)     # SyncBN: the engine exchanges the statistics itself
-        self.refresh()
-
-    def refresh(self):
-        """(Re)read parameter / gradient / buffer addresses — call after the optimiser re-homed them."""
-        m = self.model
-        d = describe(m)              # (also names the BatchNorm step counters: the engine's forward increments them)
-        self._desc = d
-        self._keep = [p for p in m.parameters()]
-        self._open = None
-        self._guard_arm()
-
-    def _batch(self, data, need_y):
-        dev = (self.model if isinstance(self, StepEngine) else self).lin1.weight.device
-        if data.x.device != dev:
-            data.to(dev)
-        plan = plan_of(data)
-        if plan.in_ptr.device != dev:
-            raise RuntimeError("StepEngine: batch plan lives on %s, model on %s" % (plan.in_ptr.device, dev))
-        b = _Batch()
-        b.N, b.E, b.Z = plan.num_nodes, plan.num_edges, plan.nnz
-        x = data.x if data.x.is_contiguous() else data.x.contiguous()
-        b.x = x.data_ptr()
-        y = None
-        if need_y:
-            y = data.y.reshape(-1)
-            y = y if (y.dtype == torch.float32 and y.is_contiguous()) else y.float().contiguous()
-            if y.numel() != plan.num_nodes:
-                raise ValueError("StepEngine: expected one target per node")
-            b.y = y.data_ptr()
-        for f in ("in_ptr", "in_edge", "in_src", "out_ptr", "out_edge", "out_dst", "row_ptr", "bag_idx", "bag_val",
-                  "col_ptr", "col_row", "col_val", "col_col"):
-            setattr(b, f, getattr(plan, f).data_ptr())
-        return b, (x, y, plan)
-
-    def _workspace(self, b):
-        need = nv.lib().esc_engine_workspace_floats(ctypes.byref(self._desc), b.N, b.E, b.Z)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(int(need * 1.25), dtype=torch.float32, device=self.model.lin1.weight.device)
-        return self._ws
-
-    def train_step(self, data, loss_denom=None, return_pred=False, _entry="esc_engine_train_step"):
-        """forward + L1 + backward; gradients land in the parameters' .grad (overwritten). Returns loss (0-d)."""
-        dev = self.model.lin1.weight.device
-        self._guard_check()
-        b, keep = self._batch(data, True)
-        ws = self._workspace(b)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        pred = torch.empty(b.N, dtype=torch.float32, device=dev) if return_pred else None
-        nv.call(_entry, ctypes.byref(self._desc), ctypes.byref(b), ws.data_ptr(),
-                int(loss_denom or 0), loss.data_ptr(), nv.ptr(pred), nv.stream())
-        self._mark_bucket_written()
-        self._open = (keep, ws) if _entry.endswith("_begin") else None     # operands stay alive until end_step
-        return (loss.view(()), pred.view(-1, 1)) if return_pred else loss.view(())
-
-    def begin_step(self, data, loss_denom=None, return_pred=False):
-        """train_step up to (not including) the join with the edge stream: what the caller enqueues next on the current
-        stream — typically `store.collate(next_ids)` — overlaps the tail of the edge pipeline.  Call end_step() before
-        using the gradients / the loss."""
-        return self.train_step(data, loss_denom, return_pred, _entry="esc_engine_train_step_begin")
-
-    def end_step(self):
-        nv.call("esc_engine_train_step_end")
-        self._open = None
-
-    @torch.no_grad()
-    def predict(self, data):
-        dev = self.model.lin1.weight.device
-        self._guard_check()
-        b, keep = self._batch(data, False)
-        ws = self._workspace(b)
-        pred = torch.empty(b.N, dtype=torch.float32, device=dev)
-        nv.call("esc_engine_predict", ctypes.byref(self._desc), ctypes.byref(b), ws.data_ptr(), pred.data_ptr(),
-                nv.stream())
-        return pred.view(-1, 1)
+def _bucket_of(param):
+    """the FlatBucket (parallel.py) whose flat gradient `param.grad` is a view of, or None"""
+    from .parallel import _BUCKETS
+    g = param.grad
+    base = getattr(g, "_base", None) if g is not None else None
+    return _BUCKETS.get(base.data_ptr()) if base is not None else None
 
 
-class _NodeCache(object):
-    """Per-model host-side cache of the autograd node: the parameter list, the BatchNorm step counters and a template of
-    the model descriptor with the positions of its gradient pointers, so that a step costs two small numpy patches
-    instead of two descriptor builds (~0.5 ms of Python)."""
-
-    MARK = 0x5E5C00000000
-
-    def __init__(self, model):
-        import numpy as np
-        self.params = list(model.parameters())
-        self.buffers = [b for b in model.buffers() if b.is_floating_point()]   # the template bakes the running-stat addresses in
-        self.counters = [m.num_batches_tracked for m in model.modules()
-                         if isinstance(m, torch.nn.BatchNorm1d) and m.num_batches_tracked is not None]
-        self.key = tuple(t.data_ptr() for t in self.params + self.buffers + self.counters)   # (the counting engine's template names the counters too)
-        self.bns = [m for m in model.modules() if hasattr(m, "sync_group")]     # see _bns
-        with torch.enable_grad():       # the AccumulateGrad node of the first parameter: _node_backward asks the engine about it
-            p0 = self.params[0]
-            self.acc0 = p0.view_as(p0).grad_fn.next_functions[0][0] if p0.requires_grad else None
-        index = {id(p): i for i, p in enumerate(self.params)}
-        describe_fn = getattr(self, "_describe", describe)
-        self.template = describe_fn(model, lambda p: self.MARK + index[id(p)])
-        words = np.frombuffer(self.template, dtype=np.uint64)
-        hits = np.nonzero((words >= self.MARK) & (words < self.MARK + len(self.params)))[0]
-        self.slots = hits                                                  # word positions of the gradient pointers
-        self.slot_param = (words[hits] - self.MARK).astype(np.int64)      # ... and whose gradient each one is
-        offs, total = [], 0
-        for p in self.params:
-            offs.append(total)
-            total += -(-p.numel() // 16) * 16                             # 64-byte aligned slices of one flat buffer
-        self.offsets, self.total = offs, total
-        self.byte_offsets = np.asarray(offs, dtype=np.uint64)[self.slot_param] * np.uint64(4)
-
-    def valid(self):
-        return self.key == tuple(t.data_ptr() for t in self.params + self.buffers + self.counters)
-
-    def descriptor(self, grad_base):
-        import numpy as np
-        d = getattr(self, "_struct", _Model).from_buffer_copy(self.template)
-        np.frombuffer(d, dtype=np.uint64)[self.slots] = np.uint64(grad_base) + self.byte_offsets
-        return d
-
-    def descriptor_at(self, addresses):
-        """descriptor whose gradient slot of parameter i is addresses[i] (a FlatAdam bucket's own layout)"""
-        import numpy as np
-        d = getattr(self, "_struct", _Model).from_buffer_copy(self.template)
-        np.frombuffer(d, dtype=np.uint64)[self.slots] = np.asarray(addresses, dtype=np.uint64)[self.slot_param]
-        return d
-
-    def owning_bucket(self):
-        """the FlatAdam / FlatBucket that owns the parameters' .grad storage and lets the engines write into it, or None.  None
-        also when a parameter carries tensor hooks / post-accumulate hooks (DDP-style wrappers: they only fire on gradients
-        that come back through autograd) or does not require a gradient."""
-        from .parallel import _BUCKETS
-        g0 = self.params[0].grad
-        base = getattr(g0, "_base", None) if g0 is not None else None
-        bucket = _BUCKETS.get(base.data_ptr()) if base is not None else None
-        if bucket is None or not bucket.engine_direct:
-            return None
-        for p in self.params:
-            if not p.requires_grad or p._backward_hooks or getattr(p, "_post_accumulate_grad_hooks", None):
-                return None
-        return bucket
-
-    def direct_bucket(self):
-        """owning_bucket() that is moreover still clean (see FlatBucket.direct_grad_addresses), as a list of gradient
-        addresses — or None"""
-        bucket = self.owning_bucket()
-        return bucket.direct_grad_addresses(self.params) if bucket is not None else None
-
-    def node_inputs(self):
-        """The differentiable inputs of the engine's autograd node.  Normally every parameter (their gradients come back
-        through autograd).  When a FlatAdam / FlatBucket owns every .grad, only the FIRST parameter: the backward writes
-        (clean bucket) or adds (otherwise) the gradients into the bucket itself and returns none, so the graph carries one
-        edge instead of one AccumulateGrad per parameter — 104 of them cost the reference's loop ~0.25 ms of host time per
-        step (tools/measure/dropin_prof.py).  torch.autograd.grad through such a node reaches its one input only."""
-        return (self.params[0],) if self.owning_bucket() is not None else tuple(self.params)
-
-
-def _under_autograd_grad(cache):
-    """inside a backward: is this torch.autograd.grad (functional: nothing may be accumulated) rather than .backward()?  The autograd
-    engine refuses the question about a leaf's AccumulateGrad node exactly in that case."""
-    if cache.acc0 is None:
-        return False
-    try:
-        torch._C._will_engine_execute_node(cache.acc0)
-        return False
-    except RuntimeError as exc:
-        return "autograd.grad" in str(exc)
-    except Exception:
-        return False
-
-
-def _node_backward(ctx, dpred, entry):
-    """backward of the three engine nodes: gradients straight into a clean FlatAdam bucket, else returned (or, for a
-    node built on node_inputs()' short form, added into the bucket / the .grad tensors by hand)"""
-    cache = ctx.cache
-    if ctx.ws is None:
-        raise RuntimeError("esc_gnn_amd: this engine node's workspace was released by its first backward; a second "
-                           "backward through the same forward (retain_graph=True) needs the per-op path")
-    g = dpred.reshape(-1)
-    g = g if (g.dtype == torch.float32 and g.is_contiguous()) else g.float().contiguous()
-    slim = ctx.n_in < len(cache.params)
-    none = (None, None, None) + (None,) * ctx.n_in
-    if _under_autograd_grad(cache):
-        # torch.autograd.grad(...): a functional call — no .grad may change.  The gradients of the node's inputs are returned (all
-        # parameters, or the one a short-form node was built on; asking for another parameter of such a node is autograd's own
-        # "not used in the graph" error)
-        flat = torch.empty(cache.total, dtype=torch.float32, device=dpred.device)
-        desc = cache.descriptor(flat.data_ptr())
-        nv.call(entry, ctypes.byref(desc), ctypes.byref(ctx.b), ctx.ws.data_ptr(), g.data_ptr(), nv.stream())
-        ctx.ws = ctx.keep = None
-        grads = tuple(flat[o:o + p.numel()].view(p.shape) if p.requires_grad else None
-                      for p, o in zip(cache.params[:ctx.n_in], cache.offsets[:ctx.n_in]))
-        return (None, None, None) + grads
-
-    def run(desc):
-        nv.call(entry, ctypes.byref(desc), ctypes.byref(ctx.b), ctx.ws.data_ptr(), g.data_ptr(), nv.stream())
-        ctx.ws = ctx.keep = None
-
-    bucket = cache.owning_bucket()
-    direct = bucket.direct_grad_addresses(cache.params) if bucket is not None else None
-    if direct is not None:             # every .grad is a clean FlatAdam bucket view: write there, nothing to accumulate
-        run(cache.descriptor_at(direct))
-        return none
-    if slim:
-        # the bucket has been written since its zero_grad() (a second backward before the optimiser step): accumulate
-        offs = bucket.grad_offsets(cache.params) if bucket is not None else None
-        if offs is not None:           # ... in one pass over a scratch copy with the bucket's own layout
-            tmp = torch.zeros_like(bucket.flat_grad)
-            run(cache.descriptor_at([tmp.data_ptr() + 4 * o for o in offs]))
-            bucket.flat_grad.add_(tmp)
-            return none
-        flat = torch.zeros(cache.total, dtype=torch.float32, device=dpred.device)    # .grad was re-bound by the caller
-        run(cache.descriptor(flat.data_ptr()))
-        for p, o in zip(cache.params, cache.offsets):
-            gp = flat[o:o + p.numel()].view(p.shape)
-            if p.grad is None:
-                p.grad = gp
-            else:
-                p.grad.add_(gp)
-        return none
-    flat = torch.empty(cache.total, dtype=torch.float32, device=dpred.device)   # fresh: the views alias nothing older
-    run(cache.descriptor(flat.data_ptr()))
-    grads = tuple(flat[o:o + p.numel()].view(p.shape) if p.requires_grad else None
-                  for p, o in zip(cache.params, cache.offsets))
-    return (None, None, None) + grads
-
-
-def _node_cache(model):
-    c = model.__dict__.get("_esc_node_cache")
-    if c is None or not c.valid():
-        c = _NodeCache(model)
-        model.__dict__["_esc_node_cache"] = c
-    return c
-
-
-class _EngineNode(torch.autograd.Function):
-    """`model(batch)` of a training-mode NestedGIN_eff as ONE autograd node on the whole-step engine: forward =
-    esc_engine_forward_train, backward = esc_engine_backward with d(loss)/d(pred) of whatever loss the caller built.
-    The user's own loop (`loss = L1Loss()(model(data), y); loss.backward(); optimizer.step()`, reference
-    run_graphcount.py:494-505) then runs at engine speed instead of one autograd node per op."""
-
-    @staticmethod
-    def forward(ctx, model, data, cache, *params):
-        dev = model.lin1.weight.device
-        b, keep = StepEngine._batch(model, data, False)            # (used unbound: only reads the module)
-        desc = cache.descriptor(0)                                 # the forward writes no gradient
-        need = nv.lib().esc_engine_workspace_floats(ctypes.byref(desc), b.N, b.E, b.Z)
-        ws = torch.empty(int(need), dtype=torch.float32, device=dev)   # private: stays intact until the backward
-        pred = torch.empty(b.N, dtype=torch.float32, device=dev)
-        nv.call("esc_engine_forward_train", ctypes.byref(desc), ctypes.byref(b), ws.data_ptr(), pred.data_ptr(), nv.stream())
-        # (the BatchNorm step counters are in the descriptor: that call has incremented them)
-        ctx.cache, ctx.b, ctx.keep, ctx.ws, ctx.n_in = cache, b, keep, ws, len(params)
-        return pred.view(-1, 1)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dpred):
-        return _node_backward(ctx, dpred, "esc_engine_backward")
-
-
-@torch.no_grad()
-def engine_predict(model, data):
-    """eval-mode `model(batch)` of the counting model as one call (esc_engine_predict: running statistics, no gradient
-    state) — the validation / test passes of a training run are most of its batches"""
-    cache = _node_cache(model)
-    b, keep = StepEngine._batch(model, data, False)
-    desc = cache.descriptor(0)
-    need = nv.lib().esc_engine_workspace_floats(ctypes.byref(desc), b.N, b.E, b.Z)
-    ws = torch.empty(int(need), dtype=torch.float32, device=model.lin1.weight.device)
-    pred = torch.empty(b.N, dtype=torch.float32, device=model.lin1.weight.device)
-    nv.call("esc_engine_predict", ctypes.byref(desc), ctypes.byref(b), ws.data_ptr(), pred.data_ptr(), nv.stream())
-    return pred.view(-1, 1)
-
-
-def engine_forward(model, data, cache=None):
-    cache = cache if cache is not None else _node_cache(model)
-    _arm_collective(model, model.lin1.weight.device, cache)  # SyncBN: the engine needs its all-reduce
-    return _EngineNode.apply(model, data, cache, *cache.node_inputs())
+def _count_batch(model, data, need_y):
+    """esc_batch_t of a counting batch (`need_y`: with its one target per node), and what must outlive the call"""
+    dev = model.lin1.weight.device
+    if data.x.device != dev:
+        data.to(dev)
+    plan = plan_of(data)
+    if plan.in_ptr.device != dev:
+        raise RuntimeError("StepEngine: batch plan lives on %s, model on %s" % (plan.in_ptr.device, dev))
+    b = _Batch()
+    b.N, b.E, b.Z = plan.num_nodes, plan.num_edges, plan.nnz
+    x = data.x if data.x.is_contiguous() else data.x.contiguous()
+    b.x = x.data_ptr()
+    y = None
+    if need_y:
+        y = _f32c(data.y.reshape(-1))
+        if y.numel() != plan.num_nodes:
+            raise ValueError("StepEngine: expected one target per node")
+        b.y = y.data_ptr()
+    _bind_plan(b, plan)
+    return b, (x, y, plan)
 
 
 # ---- ZINC variant (zinc_models.NestedGIN_eff; csrc/engine.hip esc_zinc_*) ---------------------------------------------
@@ -607,6 +368,7 @@ def zinc_engine_ready(m, data):
 
 
 def _zinc_batch(model, data, need_y, y=None):
+    """esc_mol_batch_t of a ZINC batch; `y`: the targets of a training step when they are not data.y itself"""
     from .plan import graph_ptr_of
     from .run_graphcount import Z_TABLE_ROWS
     dev = model.lin1.weight.device
@@ -639,134 +401,14 @@ def _zinc_batch(model, data, need_y, y=None):
         src._esc_zinc_checked = (src._version, rows)
     b.node_type, b.edge_type, b.graph_ptr = nt.data_ptr(), et.data_ptr(), gptr.data_ptr()
     if need_y:
-        y = (data.y if y is None else y).reshape(-1)
-        y = y if (y.dtype == torch.float32 and y.is_contiguous()) else y.float().contiguous()
+        y = _f32c((data.y if y is None else y).reshape(-1))
         if y.numel() != _zinc_rows(model, b):
             raise ValueError("ZINC engine: expected one target per %s" % ("node" if getattr(model, "node_readout", False) else "graph"))
         if y.device != dev:
             y = y.to(dev)
         b.y = y.data_ptr()
-    for f in ("in_ptr", "in_edge", "in_src", "out_ptr", "out_edge", "out_dst", "row_ptr", "bag_idx", "bag_val",
-              "col_ptr", "col_row", "col_val", "col_col"):
-        setattr(b, f, getattr(plan, f).data_ptr())
+    _bind_plan(b, plan)
     return b, (nt, et, y, plan, gptr)
-
-
-class ZincStepEngine(_AddressGuard):
-    """Training / eval step of zinc_models.NestedGIN_eff as ONE call (esc_zinc_train_step / esc_zinc_predict): same
-    parameters, `.grad` slots and BatchNorm buffers as the module, like StepEngine for the counting model."""
-
-    def __init__(self, model):
-        if not zinc_engine_supports(model):
-            raise NotImplementedError("ZincStepEngine covers dropout 0, lin2 -> 1 output, BatchNorm on one sync group, on the HIP device")
-        self.model = model
-        self._ws = None
-        _arm_collective(model, model.lin1.weight.device)
-        self._bn_counters = [m.num_batches_tracked for m in model.modules()
-                             if isinstance(m, torch.nn.BatchNorm1d) and m.num_batches_tracked is not None]
-        self.refresh()
-
-    def refresh(self):
-        self._desc = describe_zinc(self.model)
-        self._guard_arm()
-
-    def _workspace(self, b):
-        need = nv.lib().esc_zinc_workspace_floats(ctypes.byref(self._desc), b.N, b.E, b.Z, b.G)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(int(need * 1.25), dtype=torch.float32, device=self.model.lin1.weight.device)
-        return self._ws
-
-    def prepare(self, data):
-        """per-batch plans a prefetching loader can build ahead (harness.prefetched): the collate's own plan is all this
-        model needs"""
-        _zinc_batch(self.model, data, False)
-        return data
-
-    def train_step(self, data, loss_denom=None, return_pred=False, y=None):
-        """forward + L1 over the graphs (the nodes, for the node-level readout) + backward; gradients land in the parameters'
-        .grad (overwritten).  `y`: the target column when it is not data.y itself (run_zinc_cycle: data.y[:, target])."""
-        dev = self.model.lin1.weight.device
-        self._guard_check()
-        b, keep = _zinc_batch(self.model, data, True, y)
-        ws = self._workspace(b)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        pred = torch.empty(_zinc_rows(self.model, b), dtype=torch.float32, device=dev) if return_pred else None
-        nv.call("esc_zinc_train_step", ctypes.byref(self._desc), ctypes.byref(b), ws.data_ptr(), int(loss_denom or 0),
-                loss.data_ptr(), nv.ptr(pred), nv.stream())
-        self._mark_bucket_written()
-        if self._bn_counters:
-            torch._foreach_add_(self._bn_counters, 1)
-        return (loss.view(()), pred.view(-1, 1)) if return_pred else loss.view(())
-
-    @torch.no_grad()
-    def predict(self, data):
-        dev = self.model.lin1.weight.device
-        self._guard_check()
-        b, keep = _zinc_batch(self.model, data, False)
-        ws = self._workspace(b)
-        pred = torch.empty(_zinc_rows(self.model, b), dtype=torch.float32, device=dev)
-        nv.call("esc_zinc_predict", ctypes.byref(self._desc), ctypes.byref(b), ws.data_ptr(), pred.data_ptr(), nv.stream())
-        return pred.view(-1, 1)
-
-
-class _ZincNodeCache(_NodeCache):
-    def __init__(self, model):
-        self._describe, self._struct = describe_zinc, _ZincModel
-        super().__init__(model)
-
-
-class _ZincEngineNode(torch.autograd.Function):
-    """`model(batch)` of a training-mode ZINC NestedGIN_eff as one autograd node (esc_zinc_forward_train / _backward)"""
-
-    @staticmethod
-    def forward(ctx, model, data, cache, *params):
-        dev = model.lin1.weight.device
-        b, keep = _zinc_batch(model, data, False)
-        desc = cache.descriptor(0)
-        need = nv.lib().esc_zinc_workspace_floats(ctypes.byref(desc), b.N, b.E, b.Z, b.G)
-        ws = torch.empty(int(need), dtype=torch.float32, device=dev)
-        pred = torch.empty(_zinc_rows(model, b), dtype=torch.float32, device=dev)
-        nv.call("esc_zinc_forward_train", ctypes.byref(desc), ctypes.byref(b), ws.data_ptr(), pred.data_ptr(), nv.stream())
-        if cache.counters:
-            torch._foreach_add_(cache.counters, 1)
-        ctx.cache, ctx.b, ctx.keep, ctx.ws, ctx.n_in = cache, b, keep, ws, len(params)
-        return pred.view(-1, 1)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dpred):
-        return _node_backward(ctx, dpred, "esc_zinc_backward")
-
-
-def _mol_cache(model, kind):
-    c = model.__dict__.get("_esc_node_cache")
-    if c is None or not c.valid():
-        c = kind(model)
-        model.__dict__["_esc_node_cache"] = c
-    return c
-
-
-@torch.no_grad()
-def zinc_engine_predict(model, data):
-    """eval-mode forward of the ZINC model as one call (esc_zinc_predict)"""
-    cache = _mol_cache(model, _ZincNodeCache)
-    b, keep = _zinc_batch(model, data, False)
-    desc = cache.descriptor(0)
-    need = nv.lib().esc_zinc_workspace_floats(ctypes.byref(desc), b.N, b.E, b.Z, b.G)
-    dev = model.lin1.weight.device
-    ws = torch.empty(int(need), dtype=torch.float32, device=dev)
-    pred = torch.empty(_zinc_rows(model, b), dtype=torch.float32, device=dev)
-    nv.call("esc_zinc_predict", ctypes.byref(desc), ctypes.byref(b), ws.data_ptr(), pred.data_ptr(), nv.stream())
-    return pred.view(-1, 1)
-
-
-def zinc_engine_forward(model, data):
-    c = model.__dict__.get("_esc_node_cache")
-    if c is None or not c.valid():
-        c = _ZincNodeCache(model)
-        model.__dict__["_esc_node_cache"] = c
-    _arm_collective(model, model.lin1.weight.device, c)
-    return _ZincEngineNode.apply(model, data, c, *c.node_inputs())
 
 
 # ---- OGB molecule variant (ogb_mol_gnn.GNN(gnn_type="gin_eff"); csrc/engine.hip esc_ogb_*) -----------------------------
@@ -796,10 +438,7 @@ class _BagPlan(ctypes.Structure):
 
 class _OgbBatch(ctypes.Structure):
     _fields_ = ([("N", c_int64), ("E", c_int64), ("Z", c_int64), ("G", c_int64), ("atoms", _BagPlan), ("bonds", _BagPlan),
-                 ("y", c_void_p), ("graph_ptr", c_void_p), ("zero_idx", c_void_p)] +
-                [(n, c_void_p) for n in ("in_ptr", "in_edge", "in_src", "out_ptr", "out_edge", "out_dst",
-                                         "row_ptr", "bag_idx", "bag_val", "col_ptr", "col_row", "col_val", "col_col")] +
-                [("seed", c_uint64)])
+                 ("y", c_void_p), ("graph_ptr", c_void_p), ("zero_idx", c_void_p)] + _PLAN_POINTERS + [("seed", c_uint64)])
 
 
 def ogb_engine_supports(m, data=None):
@@ -871,7 +510,9 @@ def _bag_plan(plan):
 _zero_idx = {}
 
 
-def _ogb_batch(model, data, need_y, seed):
+def _ogb_batch(model, data, need_y, seed=0):
+    """esc_ogb_batch_t of an OGB molecule batch, with its embedding plans; `seed`: of a training step's dropout masks
+    (_drop_seed; eval and prepare draw none)"""
     from .ogb_mol_gnn import ATOM_FEATURE_DIMS, BOND_FEATURE_DIMS
     from .ops import embed_plan
     from .plan import graph_ptr_of
@@ -899,14 +540,11 @@ def _ogb_batch(model, data, need_y, seed):
     b.graph_ptr, b.zero_idx, b.seed = gptr.data_ptr(), zero.data_ptr(), int(seed) & ((1 << 64) - 1)
     y = None
     if need_y:
-        y = data.y.reshape(G, -1)
-        y = y if (y.dtype == torch.float32 and y.is_contiguous()) else y.float().contiguous()
+        y = _f32c(data.y.reshape(G, -1))
         if y.size(1) != model.num_tasks:
             raise ValueError("OGB engine: expected [num_graphs, num_tasks] targets")
         b.y = y.data_ptr()
-    for f in ("in_ptr", "in_edge", "in_src", "out_ptr", "out_edge", "out_dst", "row_ptr", "bag_idx", "bag_val",
-              "col_ptr", "col_row", "col_val", "col_col"):
-        setattr(b, f, getattr(plan, f).data_ptr())
+    _bind_plan(b, plan)
     return b, (y, plan, gptr, pa, pb, zero)
 
 
@@ -925,80 +563,210 @@ def _drop_seed(model):
     return (torch.initial_seed() * 0x9E3779B97F4A7C15 + n) & ((1 << 64) - 1)
 
 
-class OgbStepEngine(_AddressGuard):
-    """Training / eval step of ogb_mol_gnn.GNN(gnn_type='gin_eff') as ONE call (esc_ogb_train_step / esc_ogb_predict)"""
+# ---- the families --------------------------------------------------------------------------------------------------------
+# What a family IS — the host path below knows nothing else about a model:
+#   prefix       of its C entry points: <prefix>workspace_floats / train_step / forward_train / backward / predict
+#   describe     (model, gp) -> the model descriptor, an instance of `struct`
+#   device       (model) -> the device the step runs on
+#   batch        (model, data, need_y, ...) -> (batch struct, the tensors that must outlive the call)
+#   sizes        (batch struct) -> the arguments of <prefix>workspace_floats after the descriptor
+#   pred_shape   (model, batch struct) -> shape of the predictions
+#   py_counters  Python adds 1 to the BatchNorm step counters after a training call (the counting family names them in
+#                its descriptor instead: the library increments them)
+#   dropout      a training call hands its batch the next seed of the model's dropout stream (_drop_seed)
+_Family = collections.namedtuple("_Family", "prefix describe struct device batch sizes pred_shape py_counters dropout")
 
-    def __init__(self, model):
-        if not ogb_engine_supports(model):
-            raise NotImplementedError("OgbStepEngine covers ogbg-mol* gin_eff with a virtual node, JK=last, sum/mean pooling")
-        self.model = model
-        self._ws = None
-        _arm_collective(model, model.graph_pred_linear.weight.device)
-        self._bn_counters = [m.num_batches_tracked for m in model.modules()
-                             if isinstance(m, torch.nn.BatchNorm1d) and m.num_batches_tracked is not None]
-        self.refresh()
-
-    def refresh(self):
-        self._desc = describe_ogb(self.model)
-        self._guard_arm()
-
-    def _workspace(self, b):
-        need = nv.lib().esc_ogb_workspace_floats(ctypes.byref(self._desc), b.N, b.E, b.Z, b.G, b.atoms.n_entries, b.bonds.n_entries)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(int(need * 1.25), dtype=torch.float32, device=self.model.graph_pred_linear.weight.device)
-        return self._ws
-
-    def prepare(self, data):
-        """builds (and caches on the batch's tensors) every index plan train_step / predict will ask for — the call a
-        prefetching loader makes on its side stream (harness.prefetched)"""
-        _ogb_batch(self.model, data, False, 0)
-        return data
-
-    def train_step(self, data, loss_denom=None, return_pred=False):
-        """forward + masked BCE-with-logits + backward; gradients land in the parameters' .grad (overwritten)"""
-        dev = self.model.graph_pred_linear.weight.device
-        self._guard_check()
-        b, keep = _ogb_batch(self.model, data, True, _drop_seed(self.model))
-        ws = self._workspace(b)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        pred = torch.empty((b.G, self.model.num_tasks), dtype=torch.float32, device=dev) if return_pred else None
-        nv.call("esc_ogb_train_step", ctypes.byref(self._desc), ctypes.byref(b), ws.data_ptr(), int(loss_denom or 0),
-                loss.data_ptr(), nv.ptr(pred), nv.stream())
-        self._mark_bucket_written()
-        if self._bn_counters:
-            torch._foreach_add_(self._bn_counters, 1)
-        return (loss.view(()), pred) if return_pred else loss.view(())
-
-    @torch.no_grad()
-    def predict(self, data):
-        dev = self.model.graph_pred_linear.weight.device
-        self._guard_check()
-        b, keep = _ogb_batch(self.model, data, False, 0)
-        ws = self._workspace(b)
-        pred = torch.empty((b.G, self.model.num_tasks), dtype=torch.float32, device=dev)
-        nv.call("esc_ogb_predict", ctypes.byref(self._desc), ctypes.byref(b), ws.data_ptr(), pred.data_ptr(), nv.stream())
-        return pred
+COUNTING = _Family("esc_engine_", describe, _Model, lambda m: m.lin1.weight.device, _count_batch,
+                   lambda b: (b.N, b.E, b.Z), lambda m, b: (b.N, 1), py_counters=False, dropout=False)
+ZINC = _Family("esc_zinc_", describe_zinc, _ZincModel, lambda m: m.lin1.weight.device, _zinc_batch,
+               lambda b: (b.N, b.E, b.Z, b.G), lambda m, b: (_zinc_rows(m, b), 1), py_counters=True, dropout=False)
+OGB = _Family("esc_ogb_", describe_ogb, _OgbModel, lambda m: m.graph_pred_linear.weight.device, _ogb_batch,
+              lambda b: (b.N, b.E, b.Z, b.G, b.atoms.n_entries, b.bonds.n_entries), lambda m, b: (b.G, m.num_tasks),
+              py_counters=True, dropout=True)
 
 
-class _OgbNodeCache(_NodeCache):
-    def __init__(self, model):
-        self._describe, self._struct = describe_ogb, _OgbModel
-        super().__init__(model)
+def _training_args(family, model):
+    """what a TRAINING call adds to the batch builder's arguments: the next seed of the dropout stream, consumed here"""
+    return {"seed": _drop_seed(model)} if family.dropout else {}
 
 
-class _OgbEngineNode(torch.autograd.Function):
-    """`model(batch)` of a training-mode OGB GNN as one autograd node (esc_ogb_forward_train / esc_ogb_backward)"""
+def _workspace_floats(family, desc, b):
+    """size of the workspace the family's step needs for this batch"""
+    return getattr(nv.lib(), family.prefix + "workspace_floats")(ctypes.byref(desc), *family.sizes(b))
+
+
+# ---- the host path, written once -------------------------------------------------------------------------------------------
+class _NodeCache(object):
+    """Per-model host-side cache of the autograd node: the parameter list, the BatchNorm step counters and a template of
+    the model descriptor with the positions of its gradient pointers, so that a step costs two small numpy patches
+    instead of two descriptor builds (~0.5 ms of Python)."""
+
+    MARK = 0x5E5C00000000
+
+    def __init__(self, model, family):
+        import numpy as np
+        self.family = family
+        self.params = list(model.parameters())
+        self.buffers = [b for b in model.buffers() if b.is_floating_point()]   # the template bakes the running-stat addresses in
+        self.counters = _bn_counters(model)
+        self.key = tuple(t.data_ptr() for t in self.params + self.buffers + self.counters)   # (the counting engine's template names the counters too)
+        self.bns = [m for m in model.modules() if hasattr(m, "sync_group")]     # see _bns
+        with torch.enable_grad():       # the AccumulateGrad node of the first parameter: _node_backward asks the engine about it
+            p0 = self.params[0]
+            self.acc0 = p0.view_as(p0).grad_fn.next_functions[0][0] if p0.requires_grad else None
+        index = {id(p): i for i, p in enumerate(self.params)}
+        self.template = family.describe(model, lambda p: self.MARK + index[id(p)])
+        words = np.frombuffer(self.template, dtype=np.uint64)
+        hits = np.nonzero((words >= self.MARK) & (words < self.MARK + len(self.params)))[0]
+        self.slots = hits                                                  # word positions of the gradient pointers
+        self.slot_param = (words[hits] - self.MARK).astype(np.int64)      # ... and whose gradient each one is
+        offs, total = [], 0
+        for p in self.params:
+            offs.append(total)
+            total += -(-p.numel() // 16) * 16                             # 64-byte aligned slices of one flat buffer
+        self.offsets, self.total = offs, total
+        self.byte_offsets = np.asarray(offs, dtype=np.uint64)[self.slot_param] * np.uint64(4)
+
+    def valid(self):
+        return self.key == tuple(t.data_ptr() for t in self.params + self.buffers + self.counters)
+
+    def descriptor(self, grad_base):
+        import numpy as np
+        d = self.family.struct.from_buffer_copy(self.template)
+        np.frombuffer(d, dtype=np.uint64)[self.slots] = np.uint64(grad_base) + self.byte_offsets
+        return d
+
+    def descriptor_at(self, addresses):
+        """descriptor whose gradient slot of parameter i is addresses[i] (a FlatAdam bucket's own layout)"""
+        import numpy as np
+        d = self.family.struct.from_buffer_copy(self.template)
+        np.frombuffer(d, dtype=np.uint64)[self.slots] = np.asarray(addresses, dtype=np.uint64)[self.slot_param]
+        return d
+
+    def owning_bucket(self):
+        """the FlatAdam / FlatBucket that owns the parameters' .grad storage and lets the engines write into it, or None.  None
+        also when a parameter carries tensor hooks / post-accumulate hooks (DDP-style wrappers: they only fire on gradients
+        that come back through autograd) or does not require a gradient."""
+        bucket = _bucket_of(self.params[0])
+        if bucket is None or not bucket.engine_direct:
+            return None
+        for p in self.params:
+            if not p.requires_grad or p._backward_hooks or getattr(p, "_post_accumulate_grad_hooks", None):
+                return None
+        return bucket
+
+    def direct_bucket(self):
+        """owning_bucket() that is moreover still clean (see FlatBucket.direct_grad_addresses), as a list of gradient
+        addresses — or None"""
+        bucket = self.owning_bucket()
+        return bucket.direct_grad_addresses(self.params) if bucket is not None else None
+
+    def node_inputs(self):
+        """The differentiable inputs of the engine's autograd node.  Normally every parameter (their gradients come back
+        through autograd).  When a FlatAdam / FlatBucket owns every .grad, only the FIRST parameter: the backward writes
+        (clean bucket) or adds (otherwise) the gradients into the bucket itself and returns none, so the graph carries one
+        edge instead of one AccumulateGrad per parameter — 104 of them cost the reference's loop ~0.25 ms of host time per
+        step (tools/measure/dropin_prof.py).  torch.autograd.grad through such a node reaches its one input only."""
+        return (self.params[0],) if self.owning_bucket() is not None else tuple(self.params)
+
+
+def _under_autograd_grad(cache):
+    """inside a backward: is this torch.autograd.grad (functional: nothing may be accumulated) rather than .backward()?  The autograd
+    engine refuses the question about a leaf's AccumulateGrad node exactly in that case."""
+    if cache.acc0 is None:
+        return False
+    try:
+        torch._C._will_engine_execute_node(cache.acc0)
+        return False
+    except RuntimeError as exc:
+        return "autograd.grad" in str(exc)
+    except Exception:
+        return False
+
+
+def _node_backward(ctx, dpred, entry):
+    """backward of the engine node (`entry`: the family's *_backward): gradients straight into a clean FlatAdam bucket, else returned (or, for a
+    node built on node_inputs()' short form, added into the bucket / the .grad tensors by hand)"""
+    cache = ctx.cache
+    if ctx.ws is None:
+        raise RuntimeError("esc_gnn_amd: this engine node's workspace was released by its first backward; a second "
+                           "backward through the same forward (retain_graph=True) needs the per-op path")
+    g = _f32c(dpred.reshape(-1))
+    slim = ctx.n_in < len(cache.params)
+    none = (None, None, None) + (None,) * ctx.n_in
+
+    def run(desc):
+        nv.call(entry, ctypes.byref(desc), ctypes.byref(ctx.b), ctx.ws.data_ptr(), g.data_ptr(), nv.stream())
+        ctx.ws = ctx.keep = None
+
+    if _under_autograd_grad(cache):
+        # torch.autograd.grad(...): a functional call — no .grad may change.  The gradients of the node's inputs are returned (all
+        # parameters, or the one a short-form node was built on; asking for another parameter of such a node is autograd's own
+        # "not used in the graph" error)
+        flat = torch.empty(cache.total, dtype=torch.float32, device=dpred.device)
+        run(cache.descriptor(flat.data_ptr()))
+        grads = tuple(flat[o:o + p.numel()].view(p.shape) if p.requires_grad else None
+                      for p, o in zip(cache.params[:ctx.n_in], cache.offsets[:ctx.n_in]))
+        return (None, None, None) + grads
+
+    bucket = cache.owning_bucket()
+    direct = bucket.direct_grad_addresses(cache.params) if bucket is not None else None
+    if direct is not None:             # every .grad is a clean FlatAdam bucket view: write there, nothing to accumulate
+        run(cache.descriptor_at(direct))
+        return none
+    if slim:
+        # the bucket has been written since its zero_grad() (a second backward before the optimiser step): accumulate
+        offs = bucket.grad_offsets(cache.params) if bucket is not None else None
+        if offs is not None:           # ... in one pass over a scratch copy with the bucket's own layout
+            tmp = torch.zeros_like(bucket.flat_grad)
+            run(cache.descriptor_at([tmp.data_ptr() + 4 * o for o in offs]))
+            bucket.flat_grad.add_(tmp)
+            return none
+        flat = torch.zeros(cache.total, dtype=torch.float32, device=dpred.device)    # .grad was re-bound by the caller
+        run(cache.descriptor(flat.data_ptr()))
+        for p, o in zip(cache.params, cache.offsets):
+            gp = flat[o:o + p.numel()].view(p.shape)
+            if p.grad is None:
+                p.grad = gp
+            else:
+                p.grad.add_(gp)
+        return none
+    flat = torch.empty(cache.total, dtype=torch.float32, device=dpred.device)   # fresh: the views alias nothing older
+    run(cache.descriptor(flat.data_ptr()))
+    grads = tuple(flat[o:o + p.numel()].view(p.shape) if p.requires_grad else None
+                  for p, o in zip(cache.params, cache.offsets))
+    return (None, None, None) + grads
+
+
+def _node_cache(model, family):
+    """the model's node cache, rebuilt when a parameter, a buffer or a step counter has moved"""
+    c = model.__dict__.get("_esc_node_cache")
+    if c is None or not c.valid():
+        c = model.__dict__["_esc_node_cache"] = _NodeCache(model, family)
+    return c
+
+
+def _private_workspace(family, desc, b, dev):
+    """exactly sized and the caller's own: an autograd node's must stay intact until its backward"""
+    return torch.empty(int(_workspace_floats(family, desc, b)), dtype=torch.float32, device=dev)
+
+
+class _EngineNode(torch.autograd.Function):
+    """`model(batch)` of a training-mode model as ONE autograd node on the whole-step engine: forward =
+    <prefix>forward_train, backward = <prefix>backward with d(loss)/d(pred) of whatever loss the caller built.
+    The user's own loop (`loss = L1Loss()(model(data), y); loss.backward(); optimizer.step()`, reference
+    run_graphcount.py:494-505) then runs at engine speed instead of one autograd node per op."""
 
     @staticmethod
     def forward(ctx, model, data, cache, *params):
-        dev = model.graph_pred_linear.weight.device
-        b, keep = _ogb_batch(model, data, False, _drop_seed(model))
-        desc = cache.descriptor(0)
-        need = nv.lib().esc_ogb_workspace_floats(ctypes.byref(desc), b.N, b.E, b.Z, b.G, b.atoms.n_entries, b.bonds.n_entries)
-        ws = torch.empty(int(need), dtype=torch.float32, device=dev)
-        pred = torch.empty((b.G, model.num_tasks), dtype=torch.float32, device=dev)
-        nv.call("esc_ogb_forward_train", ctypes.byref(desc), ctypes.byref(b), ws.data_ptr(), pred.data_ptr(), nv.stream())
-        if cache.counters:
+        fam = cache.family
+        dev = fam.device(model)
+        b, keep = fam.batch(model, data, False, **_training_args(fam, model))
+        desc = cache.descriptor(0)                                 # the forward writes no gradient
+        ws = _private_workspace(fam, desc, b, dev)
+        pred = torch.empty(fam.pred_shape(model, b), dtype=torch.float32, device=dev)
+        nv.call(fam.prefix + "forward_train", ctypes.byref(desc), ctypes.byref(b), ws.data_ptr(), pred.data_ptr(), nv.stream())
+        if fam.py_counters and cache.counters:
             torch._foreach_add_(cache.counters, 1)
         ctx.cache, ctx.b, ctx.keep, ctx.ws, ctx.n_in = cache, b, keep, ws, len(params)
         return pred
@@ -1006,27 +774,140 @@ class _OgbEngineNode(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dpred):
-        return _node_backward(ctx, dpred, "esc_ogb_backward")
+        return _node_backward(ctx, dpred, ctx.cache.family.prefix + "backward")
+
+
+def _engine_forward(family, model, data, cache=None):
+    """training-mode `model(batch)` as one autograd node; `cache`: the node cache, when the caller has just validated it"""
+    cache = cache if cache is not None else _node_cache(model, family)
+    _arm_collective(model, family.device(model), cache)      # SyncBN: the engine needs its all-reduce
+    return _EngineNode.apply(model, data, cache, *cache.node_inputs())
 
 
 @torch.no_grad()
-def ogb_engine_predict(model, data):
-    """eval-mode forward of the OGB model as one call (esc_ogb_predict: no dropout, running statistics)"""
-    cache = _mol_cache(model, _OgbNodeCache)
-    b, keep = _ogb_batch(model, data, False, 0)
-    desc = cache.descriptor(0)
-    need = nv.lib().esc_ogb_workspace_floats(ctypes.byref(desc), b.N, b.E, b.Z, b.G, b.atoms.n_entries, b.bonds.n_entries)
-    dev = model.graph_pred_linear.weight.device
-    ws = torch.empty(int(need), dtype=torch.float32, device=dev)
-    pred = torch.empty((b.G, model.num_tasks), dtype=torch.float32, device=dev)
-    nv.call("esc_ogb_predict", ctypes.byref(desc), ctypes.byref(b), ws.data_ptr(), pred.data_ptr(), nv.stream())
+def _predict(family, model, data, desc, workspace):
+    """the eval-mode forward as one call (<prefix>predict: running statistics, no dropout, no gradient state) on the
+    buffer `workspace(batch struct)` returns"""
+    b, keep = family.batch(model, data, False)
+    ws = workspace(b)
+    pred = torch.empty(family.pred_shape(model, b), dtype=torch.float32, device=ws.device)
+    nv.call(family.prefix + "predict", ctypes.byref(desc), ctypes.byref(b), ws.data_ptr(), pred.data_ptr(), nv.stream())
     return pred
 
 
-def ogb_engine_forward(model, data):
-    c = model.__dict__.get("_esc_node_cache")
-    if c is None or not c.valid():
-        c = _OgbNodeCache(model)
-        model.__dict__["_esc_node_cache"] = c
-    _arm_collective(model, model.graph_pred_linear.weight.device, c)
-    return _OgbEngineNode.apply(model, data, c, *c.node_inputs())
+def _engine_predict(family, model, data):
+    """eval-mode `model(batch)` under no_grad as one call — the validation / test passes of a training run are most of
+    its batches"""
+    desc = _node_cache(model, family).descriptor(0)
+    return _predict(family, model, data, desc, lambda b: _private_workspace(family, desc, b, family.device(model)))
+
+
+# the names the model modules import
+engine_forward, engine_predict = functools.partial(_engine_forward, COUNTING), functools.partial(_engine_predict, COUNTING)
+zinc_engine_forward, zinc_engine_predict = functools.partial(_engine_forward, ZINC), functools.partial(_engine_predict, ZINC)
+ogb_engine_forward, ogb_engine_predict = functools.partial(_engine_forward, OGB), functools.partial(_engine_predict, OGB)
+
+
+class _FamilyEngine(_AddressGuard):
+    """Training step (forward + loss + backward) and eval forward of one model, each as ONE native call on a persistent
+    workspace: same parameters, `.grad` slots and BatchNorm buffers as the module.  A subclass names its family and checks
+    that the model is one the family's entry points cover."""
+    family = None
+
+    def __init__(self, model):
+        self.model = model
+        self._ws = None
+        _arm_collective(model, self.family.device(model))     # SyncBN: the engine exchanges the statistics itself
+        self.refresh()
+
+    def refresh(self):
+        """(Re)read parameter / gradient / buffer addresses — call after the optimiser re-homed them."""
+        fam, m = self.family, self.model
+        self._desc = fam.describe(m)
+        self._dev = fam.device(m)
+        self._counters = _bn_counters(m) if fam.py_counters else []
+        self._open = None
+        self._guard_arm()
+
+    def _workspace(self, b):
+        need = _workspace_floats(self.family, self._desc, b)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(int(need * 1.25), dtype=torch.float32, device=self._dev)
+        return self._ws
+
+    def prepare(self, data):
+        """builds (and caches on the batch's tensors) every index plan train_step / predict will ask for — the call a
+        prefetching loader makes on its side stream (harness.prefetched)"""
+        self.family.batch(self.model, data, False)
+        return data
+
+    def _step(self, entry, data, loss_denom, return_pred, **target):
+        fam, m = self.family, self.model
+        self._guard_check()
+        b, keep = fam.batch(m, data, True, **target, **_training_args(fam, m))
+        ws = self._workspace(b)
+        loss = torch.empty(1, dtype=torch.float32, device=self._dev)
+        pred = torch.empty(fam.pred_shape(m, b), dtype=torch.float32, device=self._dev) if return_pred else None
+        nv.call(fam.prefix + entry, ctypes.byref(self._desc), ctypes.byref(b), ws.data_ptr(), int(loss_denom or 0),
+                loss.data_ptr(), nv.ptr(pred), nv.stream())
+        self._mark_bucket_written()
+        if self._counters:
+            torch._foreach_add_(self._counters, 1)
+        self._open = (keep, ws) if entry.endswith("_begin") else None     # operands stay alive until end_step
+        return (loss.view(()), pred) if return_pred else loss.view(())
+
+    def train_step(self, data, loss_denom=None, return_pred=False):
+        """forward + the family's loss (L1; OGB: masked BCE-with-logits) + backward; gradients land in the parameters'
+        .grad (overwritten).  Returns loss (0-d), and the predictions with `return_pred`."""
+        return self._step("train_step", data, loss_denom, return_pred)
+
+    def predict(self, data):
+        self._guard_check()
+        return _predict(self.family, self.model, data, self._desc, self._workspace)
+
+
+class StepEngine(_FamilyEngine):
+    """the counting NestedGIN_eff (run_graphcount): L1 over the nodes"""
+    family = COUNTING
+
+    def __init__(self, model):
+        if model.graph_pred or model.dropout != 0 or not model.use_cycle:
+            raise NotImplementedError("StepEngine covers the run_graphcount configuration "
+                                      "(graph_pred=False, dropout=0, use_cycle=True); use model(batch) otherwise")
+        if model.lin1.weight.device.type != "cuda":
+            raise RuntimeError("StepEngine runs on the HIP device only; there is no CPU fallback")
+        super().__init__(model)
+
+    def begin_step(self, data, loss_denom=None, return_pred=False):
+        """train_step up to (not including) the join with the edge stream: what the caller enqueues next on the current
+        stream — typically `store.collate(next_ids)` — overlaps the tail of the edge pipeline.  Call end_step() before
+        using the gradients / the loss."""
+        return self._step("train_step_begin", data, loss_denom, return_pred)
+
+    def end_step(self):
+        nv.call("esc_engine_train_step_end")
+        self._open = None
+
+
+class ZincStepEngine(_FamilyEngine):
+    """zinc_models.NestedGIN_eff (and the node-level zinc_cycle_models one): L1 over the graphs (the nodes)"""
+    family = ZINC
+
+    def __init__(self, model):
+        if not zinc_engine_supports(model):
+            raise NotImplementedError("ZincStepEngine covers dropout 0, lin2 -> 1 output, BatchNorm on one sync group, on the HIP device")
+        super().__init__(model)
+
+    def train_step(self, data, loss_denom=None, return_pred=False, y=None):
+        """`y`: the target column when it is not data.y itself (run_zinc_cycle: data.y[:, target])"""
+        return self._step("train_step", data, loss_denom, return_pred, y=y)
+
+
+class OgbStepEngine(_FamilyEngine):
+    """ogb_mol_gnn.GNN(gnn_type='gin_eff'): masked BCE-with-logits over [num_graphs, num_tasks]"""
+    family = OGB
+
+    def __init__(self, model):
+        if not ogb_engine_supports(model):
+            raise NotImplementedError("OgbStepEngine covers ogbg-mol* gin_eff with a virtual node, JK=last, sum/mean pooling")
+        super().__init__(model)

@@ -1,0 +1,114 @@
+"""The three step-engine families (counting, ZINC, OGB) share one host path: what that path must keep per family — who
+increments the BatchNorm step counters and when, when the OGB dropout stream advances, that a spent workspace refuses a
+second backward, and that `model(batch)` is the one engine node."""
+import pytest
+import torch
+
+from conftest import require_gpu
+
+DEV = "cuda:0"
+
+
+def _family(kind, seed=5):
+    """a fresh seeded model of the family, its engine class and two 16-graph batches (32 synthetic graphs, 2 layers)"""
+    import esc_gnn_amd as E
+    from esc_gnn_amd.datasets import (build_count_dataset, build_feature_dataset, synthetic_ogbmol_graphs,
+                                      synthetic_zinc_graphs)
+    torch.manual_seed(seed)
+    if kind == "ogb":
+        from esc_gnn_amd.engine import OgbStepEngine as Eng
+        from esc_gnn_amd.ogb_mol_gnn import GNN
+        graphs = build_feature_dataset(synthetic_ogbmol_graphs(0, 32), 2, use_rd=True, self_loop=True)
+        model = GNN("ogbg-molhiv", 1, num_layer=2, emb_dim=32, gnn_type="gin_eff", virtual_node=True, residual=True,
+                    drop_ratio=0.3, use_rd=True)
+    elif kind == "zinc":
+        from esc_gnn_amd.engine import ZincStepEngine as Eng
+        from esc_gnn_amd.zinc_models import NestedGIN_eff
+        graphs = build_feature_dataset(synthetic_zinc_graphs(0, 32), 2, use_rd=True, self_loop=False)
+        model = NestedGIN_eff(None, num_layers=2)
+    else:
+        from esc_gnn_amd.engine import StepEngine as Eng
+        graphs = build_count_dataset(0, 32, h=2)
+        model = E.NestedGIN_eff(None, 2, 64, use_rd=True, graph_pred=False, dropout=0, edge_nest=True, use_cycle=True)
+    store = E.DeviceGraphStore(graphs, torch.device(DEV))
+    return model.to(DEV).train(), Eng, [store.collate(torch.arange(16) + 16 * i) for i in range(2)]
+
+
+def _counters(model):
+    cs = [m.num_batches_tracked for m in model.modules() if isinstance(m, torch.nn.BatchNorm1d)]
+    assert len(cs) >= 1
+    return cs
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["zinc", "ogb"])
+def test_batchnorm_step_counters_and_dropout_stream(kind):
+    """one increment per BatchNorm per TRAINING call (train_step, the module as an autograd node), none by predict, the
+    backward or an eval forward; the OGB dropout stream advances with exactly the training calls, not with prepare"""
+    require_gpu()
+    model, Eng, (b, _) = _family(kind)
+    counters = _counters(model)
+
+    def expect(n):
+        assert all(int(c) == n for c in counters), (n, [int(c) for c in counters])
+    expect(0)
+    eng = Eng(model)
+    for _ in range(2):
+        eng.train_step(b)
+    expect(2)
+    eng.predict(b)
+    expect(2)
+    pred = model(b)
+    assert type(pred.grad_fn).__name__.startswith("_EngineNode")
+    expect(3)
+    pred.sum().backward()
+    expect(3)
+    model.eval()
+    with torch.no_grad():
+        model(b)
+    expect(3)
+    eng.prepare(b)
+    expect(3)
+    if kind == "ogb":
+        assert model.__dict__["_esc_drop_step"] == 3
+    else:
+        assert "_esc_drop_step" not in model.__dict__
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("extra", ["prepare", "predict"])
+def test_ogb_dropout_stream_ignores_prepare_and_predict(extra):
+    """two identically seeded models, one stepped with `extra` calls interleaved: bit-equal losses (dropout 0.3: a seed
+    consumed by prepare / predict would shift every later mask)"""
+    require_gpu()
+    import esc_gnn_amd as E
+    losses = []
+    for interleave in (False, True):
+        model, Eng, batches = _family("ogb", seed=7)
+        eng = Eng(model)
+        opt = E.optim.FlatAdam(model.parameters(), lr=1e-3)
+        run = []
+        for i in range(4):
+            b = batches[i % 2]
+            if interleave:
+                getattr(eng, extra)(b)
+            run.append(eng.train_step(b))
+            opt.step()
+        assert model.__dict__["_esc_drop_step"] == 4
+        losses.append(torch.stack(run).cpu())
+    assert torch.equal(losses[0], losses[1]), (losses[0] - losses[1]).abs().max()
+    assert len(set(losses[0].tolist())) > 1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["count", "zinc", "ogb"])
+def test_one_node_class_and_second_backward_refused(kind):
+    """`model(batch)` in training mode is the one engine node for every family; its workspace is released by the first
+    backward, so a second one through the same forward is refused on the host, before any native call"""
+    require_gpu()
+    model, _, (b, _) = _family(kind)
+    pred = model(b)
+    assert type(pred.grad_fn).__name__.startswith("_EngineNode")
+    pred.sum().backward(retain_graph=True)
+    with pytest.raises(RuntimeError, match="workspace was released"):
+        pred.sum().backward()

@@ -122,7 +122,7 @@ def test_zinc_cycle_model_against_reference_golden(E, step_engine):
     y = torch.tensor(z["labels"][:, int(z["target"])])
     out = m(E.Data(**{k: v.clone() for k, v in bt.items()}))
     assert out.shape == (bt["x"].numel(), 1)
-    assert (type(out.grad_fn).__name__ == "_ZincEngineNodeBackward") == step_engine
+    assert (type(out.grad_fn).__name__ == "_EngineNodeBackward") == step_engine
     loss = E.ops.l1_loss(out, y.to(DEV))
     loss.backward()
     _close(out, torch.tensor(z["pred"]), "zinc cycle predictions")
@@ -181,7 +181,7 @@ def test_zinc_cycle_full_size_step(E, bs, L):
     g64 = {n: p.grad for n, p in ref64.named_parameters()}
     # the training step through the engine node: predictions, loss, every gradient as accurate as the fp32 oracle
     out = mine(b)
-    assert type(out.grad_fn).__name__ == "_ZincEngineNodeBackward" and out.shape == (b.x.numel(), 1)
+    assert type(out.grad_fn).__name__ == "_EngineNodeBackward" and out.shape == (b.x.numel(), 1)
     loss = E.ops.l1_loss(out, y)
     loss.backward()
     scale = max(1.0, float(p64.abs().max()))
