@@ -9,7 +9,7 @@ from ctypes import c_double, c_float, c_int, c_int64, c_void_p, POINTER
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libescgnn_hip.so")
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 P, I64, I32, F32 = c_void_p, c_int64, c_int, c_float
 
@@ -107,7 +107,6 @@ SIGNATURES = {
     "esc_slab_reduce_jobs": [P, I32, P],
     "esc_linear_bwd_both_bn_ok": [P, I64, POINTER(BnBwdFused), P, I64, P, I64, I64, I64, I64, P, I64, P, POINTER(BnBwdNext)],
     "esc_linear_bwd_bn_block_rows": [I64, I64, I64],
-    "esc_linear_bwd_set_wgrad_stream": [P],
     "esc_linear_bwd_both_bn": [P, I64, POINTER(BnBwdFused), P, I64, P, P, P, I64, I64, I64, I64, P, I64, I32, P, I64, P, P, P,
                                POINTER(BnBwdNext), P],
     "esc_bn_bwd_coef": [P, I64, P, I64, P, I64, I64, I64, P, P, P, P, I32, P, P, P, P, P],
@@ -122,8 +121,6 @@ SIGNATURES = {
     "esc_affine_act": [P, I64, I64, I64, P, P, I32, P, I64, P],
     "esc_bn_eval_coef": [P, P, P, P, F32, I64, P, P, P],
     "esc_engine_set_side_stream": [I32],
-    "esc_engine_set_materialise_edge_act": [I32],
-    "esc_engine_set_gemm_stats": [I32],
     "esc_engine_workspace_floats": [P, I64, I64, I64],
     "esc_engine_train_step": [P, P, P, I64, P, P, P],
     "esc_engine_train_step_begin": [P, P, P, I64, P, P, P],

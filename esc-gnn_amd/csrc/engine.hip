@@ -14,7 +14,6 @@
 // use_cycle=True — the configuration run_graphcount.py:465 instantiates).
 #include "common.h"
 
-#include <cstring>
 #include <map>
 #include <vector>
 #include <cstdlib>
@@ -38,23 +37,17 @@ struct Layout {
   int64_t N, E, Z, H, L, C0, W;   // W = (L+1)*H
   // forward state
   float *Zb, *Yz; BnWs zb0, zb1;
-  float *A0, *Zemb;               // relu(BN(Zb)) and z_emb = relu(BN(Yz)), materialised when g_materialise_edge_act
+  float *A0, *Zemb;               // relu(BN(Zb)) and z_emb = relu(BN(Yz)), materialised (see forward())
   float* e[ESC_MAX_LAYERS]; float* agg[ESC_MAX_LAYERS]; MlpWs conv[ESC_MAX_LAYERS];
   int64_t ld_e[ESC_MAX_LAYERS];   // leading dimension of e[l]: C, or (L-1)*H when the H-wide edge terms are column blocks of ONE matrix
-  float *e_cat, *w_cat;           // g_edge_batched: [E, (L-1)*H] and the packed [(L-1)*H + (L-1), H] weights ++ biases
+  float *e_cat, *w_cat;           // batched edge terms: [E, (L-1)*H] and the packed [(L-1)*H + (L-1), H] weights ++ biases
   MlpWs xemb; float *cat, *Yl; BnWs bl; float *pred, *dpred;
-  float *Ypart;                   // readout: lin1 over the concat slices that are final before the last layer (g_readout_split)
   // backward scratch
   float *dcat, *dAl, *dT1, *dT2, *dagg, *dZemb, *dAz, *deps_part;
-  float *dT1_l[ESC_MAX_LAYERS], *dT2_l[ESC_MAX_LAYERS];   // per-layer copies: read by weight-gradient tiles that run behind the node chain (g_wgrad_stream)
   float* d_e[ESC_MAX_LAYERS];      // one per GINE layer: the edge stream consumes d_e[l] while the node chain moves on
   float *bn_scratch, *bag_scratch, *slabs;
   float *col_stats;               // GEMM-epilogue BatchNorm partials: float2[ceil(rows/32)][H]
-  float *col_stats_b;             // second set: a folded BatchNorm's partials live until its consumer has run
   float *bst_part;                // BatchNorm-backward column sums left by a dX epilogue / an aggregate backward: float2[slots][H]
-  float *bst_part_e;              // ... of the edge pipeline (z_embedding's first BatchNorm, from its Linear's dX epilogue)
-  // private scratch of the x_embedding branch (runs on a side stream next to the z/conv chain)
-  float *bn_scratch_x, *dT1x, *dT2x, *slabs_x;
   float *bn_scratch_e, *col_stats_e;   // the edge stream's own BatchNorm scratch / GEMM-epilogue partials
   // ZINC variant: node features from a table, [z_emb | edge type] edge-term input, pooled readout
   float *cat_scale, *cat_shift;     // (scale, shift) of the BatchNorm that produced each H-wide slice of cat: [(L+1)*H]
@@ -63,17 +56,6 @@ struct Layout {
   int64_t total;
 };
 
-// SURVEY section 7 step 6, built to be measured: the H-wide edge terms e_1 .. e_{L-1} = lin_l(z_emb) of ALL layers as ONE GEMM
-// [E, H] x [H, (L-1)*H] over packed weights (one launch of 119 x 6 tiles instead of three of 119 x 2), their outputs column blocks of
-// one matrix.  ESC_EDGE_BATCHED=1; see DESIGN.md for what it measured.
-// The readout Linear reduces over all (L+1)*H concat columns (K = 1280: 152 workgroups walking 40 K-steps, 33 us — the longest kernel of
-// the node forward).  L of its L+1 slices are final before the LAST layer starts: their share is computed on the idle edge stream while
-// that layer runs, and the launch on the node chain starts from it and only reduces over the last slice (esc_linear_fwd_from).
-static int g_l1_head = getenv("ESC_L1_HEAD") ? atoi(getenv("ESC_L1_HEAD")) : 1;     // see train_step_impl()
-static int g_ogb_bnb = getenv("ESC_OGB_BNB") ? atoi(getenv("ESC_OGB_BNB")) : 0;
-static int g_readout_split = getenv("ESC_READOUT_SPLIT") ? atoi(getenv("ESC_READOUT_SPLIT")) : 0;    // measured neutral (1.012-1.016 ms either way): off
-static int g_skip_waits = getenv("ESC_SKIP_WAITS") ? atoi(getenv("ESC_SKIP_WAITS")) : 1;   // -7 us of step time
-static int g_edge_batched = getenv("ESC_EDGE_BATCHED") ? atoi(getenv("ESC_EDGE_BATCHED")) : 1;
 static BnWs take_bn(Arena& a, int64_t C) { BnWs w; w.mean = a.take(C); w.invstd = a.take(C); w.scale = a.take(C); w.shift = a.take(C); w.nglob = a.take(16); w.coef = a.take(2 * C); return w; }
 
 static Layout plan_layout(const esc_nested_gin_t* m, int64_t N, int64_t E, int64_t Z, float* base, bool train) {
@@ -83,7 +65,10 @@ static Layout plan_layout(const esc_nested_gin_t* m, int64_t N, int64_t E, int64
   y.N = N; y.E = E; y.Z = Z; y.H = H; y.L = L; y.C0 = C0; y.W = (L + 1) * H;
   y.Zb = a.take(E * H); y.Yz = a.take(E * H); y.zb0 = take_bn(a, H); y.zb1 = take_bn(a, H);
   y.A0 = a.take(E * H); y.Zemb = a.take(E * H);
-  const bool batched = g_edge_batched && L >= 3;            // (two or more H-wide edge terms)
+  // the H-wide edge terms e_1 .. e_{L-1} = lin_l(z_emb) of ALL layers as ONE GEMM [E, H] x [H, (L-1)*H]
+  // over packed weights (one launch of 119 x 6 tiles instead of three of 119 x 2), their outputs column blocks of one matrix; see
+  // DESIGN.md for what it measured.
+  const bool batched = L >= 3;                              // (two or more H-wide edge terms)
   if (batched) { y.e_cat = a.take(E * (L - 1) * H); y.w_cat = a.take(((L - 1) * H + (L - 1)) * H); }
   for (int l = 0; l < L; ++l) {
     const int64_t C = l == 0 ? C0 : H;
@@ -95,7 +80,6 @@ static Layout plan_layout(const esc_nested_gin_t* m, int64_t N, int64_t E, int64
   }
   y.xemb.Y0 = a.take(N * H); y.xemb.Y1 = a.take(N * H); y.xemb.b0 = take_bn(a, H); y.xemb.b1 = take_bn(a, H);
   y.cat = a.take(N * y.W); y.Yl = a.take(N * H); y.bl = take_bn(a, H);
-  y.Ypart = a.take(N * H);
   y.cat_scale = a.take(y.W); y.cat_shift = a.take(y.W);       // the slices' BatchNorm coefficients side by side (readout prologue)
   if (base) {
     y.xemb.b1.scale = y.cat_scale; y.xemb.b1.shift = y.cat_shift;
@@ -103,18 +87,12 @@ static Layout plan_layout(const esc_nested_gin_t* m, int64_t N, int64_t E, int64
   }
   y.pred = a.take(N); y.dpred = a.take(N);
   y.bn_scratch = a.take(esc_bn_scratch(H));
-  y.bn_scratch_x = a.take(esc_bn_scratch(H));
   y.col_stats = a.take(2 * ((E > N ? E : N) / 32 + 1) * H);
-  y.col_stats_b = a.take(2 * (N / 32 + 1) * H);
   y.bn_scratch_e = a.take(esc_bn_scratch(H));
   y.col_stats_e = a.take(2 * (E / 32 + 1) * H);
   if (train) {
     y.bst_part = a.take(2 * (N / 4 + 2) * H);
-    y.bst_part_e = a.take(2 * (E / 64 + 2) * H);
-    y.dT1x = a.take(N * H); y.dT2x = a.take(N * H);
-    y.slabs_x = a.take(esc_linear_bwd_weight_scratch(N, H, H));
     y.dcat = a.take(N * y.W); y.dAl = a.take(N * H); y.dT1 = a.take(N * H); y.dT2 = a.take(N * H);
-    for (int l = 0; l < L; ++l) { y.dT1_l[l] = a.take(N * H); y.dT2_l[l] = a.take(N * H); }
     y.dagg = a.take(N * H); y.dZemb = a.take(E * H); y.dAz = a.take(E * H);
     for (int l = 0; l < L; ++l) y.d_e[l] = a.take(E * (l == 0 ? C0 : H));
     y.deps_part = a.take(2 * N * (L > 0 ? L : 1));        // one vector per GINE layer, summed together at the end
@@ -151,22 +129,11 @@ struct Ctx {
   float** slab_cursor = nullptr;
   bool on_edge_stream = false;
   int act = 1;                                   // 1 ReLU (counting model), 2 ELU (ZINC): materialised activations
-  void* wgrad = nullptr;                         // != NULL: the node chain's weight-gradient tiles go to this stream (backward())
-  const float* l1_target = nullptr;              // train_step: the prediction head also leaves d L1 / d pred (forward(), g_l1_head)
+  const float* l1_target = nullptr;              // train_step: the prediction head also leaves d L1 / d pred (forward(), train_step_impl())
   int64_t l1_denom = 0;
 };
-// While it lives, node-sized Linear backwards launched for `c` put their dW tiles on c.wgrad (esc_linear_bwd_set_wgrad_stream)
-struct WgradScope {
-  explicit WgradScope(const Ctx& c) : on_(c.wgrad != nullptr && !c.on_edge_stream && c.jobs != nullptr) { if (on_) (void)esc_linear_bwd_set_wgrad_stream(c.wgrad); }
-  ~WgradScope() { if (on_) (void)esc_linear_bwd_set_wgrad_stream(nullptr); }
-  bool on_;
-};
 
-// dX + dW tiles now, slab reduce deferred (or immediate when the context has no job list)
-static int g_edge_ahead = 1;      // edge terms one layer ahead of the node chain (bit 5 of esc_engine_set_side_stream: two)
-static int g_cap_tail = 0;        // bit 4: ... and the z_embedding GEMM of the backward tail
-static int g_cap_forward = 1;     // the occupancy cap also applies to the forward's edge GEMMs (bit 3: backward only)
-struct LdsFloorGuard {            // occupancy cap for the GEMMs launched while it lives (edge stream only)
+struct LdsFloorGuard {            // occupancy cap for the GEMMs launched while it lives (edge stream only, forward and backward)
   explicit LdsFloorGuard(bool on) : on_(on && edge_lds_floor() > 0) { if (on_) set_gemm_lds_floor(edge_lds_floor()); }
   ~LdsFloorGuard() { if (on_) set_gemm_lds_floor(0); }
   bool on_;
@@ -177,19 +144,18 @@ struct LdsFloorGuard {            // occupancy cap for the GEMMs launched while 
 // ASKS for 66 KB (dynamic LDS it does not use) is only placed on CUs without an edge workgroup: in the backward — dual launches of 392
 // workgroups beside 57-us edge launches of 478 — that is worth 15 us of the node chain (phase marks: node backward 477 -> 462 us,
 // step 0.995 -> 0.980 ms; bench 1.048 -> 1.031 ms); 60 000 bytes (still co-resident) changes nothing, 82 000 (one node workgroup per
-// CU) costs 50 us, and in the forward (152-workgroup launches) the same request costs 8 us.  ESC_NODE_LDS_FLOOR_FWD / _BWD, bytes.
-static int g_node_floor_fwd = getenv("ESC_NODE_LDS_FLOOR_FWD") ? atoi(getenv("ESC_NODE_LDS_FLOOR_FWD")) : 0;
-static int g_node_floor_bwd = getenv("ESC_NODE_LDS_FLOOR_BWD") ? atoi(getenv("ESC_NODE_LDS_FLOOR_BWD")) : 66 * 1024;
+// CU) costs 50 us, and in the forward (152-workgroup launches) the same request costs 8 us: the backward only.
+static constexpr int kNodeLdsFloorBwd = 66 * 1024;      // bytes
 struct NodeFloorGuard {
   explicit NodeFloorGuard(int bytes) : on_(bytes > 0) { if (on_) set_node_lds_floor(bytes); }
   ~NodeFloorGuard() { if (on_) set_node_lds_floor(0); }
   bool on_;
 };
 
+// dX + dW tiles now, slab reduce deferred (or immediate when the context has no job list)
 static int linear_backward(const Ctx& c, const float* dY, int64_t ld_dy, const float* X, int64_t ld_x, const float* sc,
                            const float* sh, const esc_linear_t& lin, int64_t M, float* dX, int64_t ld_dx, int accumulate) {
   const LdsFloorGuard cap(c.on_edge_stream);
-  const WgradScope side(c);
   const int64_t N = lin.out_dim, K = lin.in_dim;
   if (c.jobs == nullptr)
     return esc_linear_bwd_both(dY, ld_dy, X, ld_x, sc, sh, lin.w, K, M, N, K, dX, ld_dx, accumulate, lin.dw, K, lin.db,
@@ -203,11 +169,12 @@ static int linear_backward(const Ctx& c, const float* dY, int64_t ld_dy, const f
 
 // ---- BatchNorm(+ReLU) backward folded into the Linear backward behind it (r03; esc_linear_bwd_both_bn) ------------------
 // The node chain's backward was, per Linear -> BatchNorm -> ReLU pair, partial -> finalize -> apply -> dX+dW: four dependent
-// launches.  The apply now happens while the GEMM stages its dY operand (bit 0) and the column sums of an MLP's FIRST
-// BatchNorm come out of the dX epilogue of its second Linear (bit 1): partial/finalize -> dX+dW -> finalize -> dX+dW.
-// ESC_BN_FUSE_BWD=0 restores the elementwise launches (A/B runs, bisecting).
-static int g_bn_fuse_bwd = getenv("ESC_BN_FUSE_BWD") ? atoi(getenv("ESC_BN_FUSE_BWD")) : 11;      // bit 2: the edge tail, see backward() (measured: no gain, off)
-static int g_bn_fuse_elu = getenv("ESC_BN_FUSE_ELU") ? atoi(getenv("ESC_BN_FUSE_ELU")) : 0;
+// launches.  The apply now happens while the GEMM stages its dY operand and the column sums of an MLP's FIRST BatchNorm come
+// out of the dX epilogue of its second Linear: partial/finalize -> dX+dW -> finalize -> dX+dW.  The three fusions in force
+// (the former ESC_BN_FUSE_BWD = 11, bits 0, 1, 3; the forms they replace stay for the shapes and modes they do not serve):
+static constexpr bool kBnBwdApplyInGemm = true;    // a BatchNorm backward's apply rides on the dY staging of the Linear backward behind it
+static constexpr bool kBnBwdSumsFromDx = true;     // its column sums come out of the dX epilogue of the Linear backward in front of it
+static constexpr bool kBnBwdSumsFromAgg = true;    // ... or out of the aggregate backward that completes its output gradient
 static esc_bn_bwd_fused bn_fused(const float* x, int64_t ld_x, const BnWs& w, int relu) {
   return esc_bn_bwd_fused{x, ld_x, w.mean, w.invstd, w.scale, w.shift, w.coef, relu};
 }
@@ -215,7 +182,6 @@ static int linear_backward_bn(const Ctx& c, const float* dOut, int64_t ld_dout, 
                               const float* sc, const float* sh, const esc_linear_t& lin, int64_t M, float* dX, int64_t ld_dx,
                               int accumulate, const esc_bn_bwd_next* next) {
   const LdsFloorGuard cap(c.on_edge_stream);
-  const WgradScope side(c);
   const int64_t N = lin.out_dim, K = lin.in_dim;
   if (c.jobs == nullptr)
     return esc_linear_bwd_both_bn(dOut, ld_dout, &f, X, ld_x, sc, sh, lin.w, K, M, N, K, dX, ld_dx, accumulate, lin.dw, K, lin.db, c.y.slabs,
@@ -227,33 +193,15 @@ static int linear_backward_bn(const Ctx& c, const float* dOut, int64_t ld_dout, 
                                 &c.jobs->back(), next, c.s);
 }
 
-// The x_embedding MLP depends only on x (forward) / on d(cat)[:, 0:H] (backward): five to eight small,
-// latency-bound launches that overlap perfectly with the edge-sized work of the main chain.  They run on a
-// second HIP stream with their own scratch, forked and joined with events (a capturable fork/join).
-struct SideStream {
-  hipStream_t stream = nullptr;
-  hipEvent_t fork_f = nullptr, join_f = nullptr, fork_b = nullptr, join_b = nullptr;
-  bool ok = false;
-};
-// Edge-sized activations: the affine+ReLU prologue costs the edge-row GEMMs ~25 % (VALU-bound staging), more
-// than the two extra elementwise passes that materialise them once; node-sized MLP activations stay fused.
-static int g_materialise_edge_act = 1;
-static int g_use_side_stream = 0;     // esc_engine_set_side_stream(); measured neutral-to-negative on MI355X r01
-
 // The edge-sized conv.lin GEMMs (e_l = lin_l(z_emb) forward; dX/dW of lin_l backward) depend on the node chain only
 // through e_l / d_e_l: they run on a second HIP stream and fill the CUs that the latency-bound node-sized launches
 // (152 workgroups on 256 CUs) leave idle.  One event per dependency, no host synchronisation.
 struct EdgeStream {
   hipStream_t stream = nullptr;
-  hipEvent_t z_ready = nullptr, joined = nullptr, lin1_fork = nullptr, lin1_rest = nullptr, tail_dz = nullptr, e_ready[ESC_MAX_LAYERS] = {}, de_ready[ESC_MAX_LAYERS] = {},
+  hipEvent_t z_ready = nullptr, joined = nullptr, lin1_fork = nullptr, lin1_rest = nullptr, e_ready[ESC_MAX_LAYERS] = {}, de_ready[ESC_MAX_LAYERS] = {},
              agg_done[ESC_MAX_LAYERS] = {};
   bool ok = false;
 };
-// 1 (default): the weight gradient of the LAST conv.lin backward (l == 0, in the tail of the step) runs on the node stream.
-// Measured neutral when it went in (1.038 vs 1.031-1.044 ms by the phase marks): the node stream's own reductions then become
-// the end of the step.  Doing the same for z_embedding's Linear costs 25-30 us (DESIGN.md *Step engine, fork and join*).
-static int g_split_last_lin = getenv("ESC_SPLIT_LAST_LIN") ? atoi(getenv("ESC_SPLIT_LAST_LIN")) : 1;
-static int g_edge_priority_low = 1;
 static int g_use_edge_stream = 1;     // esc_engine_set_side_stream() bit 1
 static int current_device() {
   int dev = 0;
@@ -269,25 +217,11 @@ static EdgeStream& edge_stream() {
     // lowest priority: when workgroup slots free up, the latency-critical node chain is served first
     int least = 0, greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-    // ESC_EDGE_CU_MASK (experiment, DESIGN.md *Step engine, r03* (vi)): the edge stream on a subset of the CUs.  "low:N" = the first N
-    // mask bits (the driver deals mask bits round-robin over the 8 XCDs: N/8 CUs of every XCD), "xcd:K" = the CUs of XCDs 0..K-1.
-    bool good = false;
-    if (const char* mk = getenv("ESC_EDGE_CU_MASK")) {
-      uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      const int n = atoi(strchr(mk, ':') ? strchr(mk, ':') + 1 : "0");
-      for (int i = 0; i < 256; ++i) {
-        const bool on = strncmp(mk, "xcd", 3) == 0 ? (i % 8) < n : i < n;
-        if (on) mask[i / 32] |= 1u << (i % 32);
-      }
-      good = n > 0 && hipExtStreamCreateWithCUMask(&es.stream, 8, mask) == hipSuccess;
-    } else {
-      good = hipStreamCreateWithPriority(&es.stream, hipStreamNonBlocking, g_edge_priority_low ? least : greatest) == hipSuccess;
-    }
+    bool good = hipStreamCreateWithPriority(&es.stream, hipStreamNonBlocking, least) == hipSuccess;
     good = good && hipEventCreateWithFlags(&es.z_ready, hipEventDisableTiming) == hipSuccess;
     good = good && hipEventCreateWithFlags(&es.joined, hipEventDisableTiming) == hipSuccess;
     good = good && hipEventCreateWithFlags(&es.lin1_fork, hipEventDisableTiming) == hipSuccess;
     good = good && hipEventCreateWithFlags(&es.lin1_rest, hipEventDisableTiming) == hipSuccess;
-    good = good && hipEventCreateWithFlags(&es.tail_dz, hipEventDisableTiming) == hipSuccess;
     for (int l = 0; l < ESC_MAX_LAYERS; ++l) {
       good = good && hipEventCreateWithFlags(&es.e_ready[l], hipEventDisableTiming) == hipSuccess;
       good = good && hipEventCreateWithFlags(&es.de_ready[l], hipEventDisableTiming) == hipSuccess;
@@ -335,57 +269,12 @@ static int chain_armed(hipEvent_t ev, const ArmedEvent& arm, hipStream_t src, hi
   return ESC_OK;
 }
 
-static SideStream& side_stream() {
-  static thread_local std::map<int, SideStream> per_device;
-  static thread_local SideStream off;   // ok == false
-  if (!g_use_side_stream) return off;
-  SideStream& ss = per_device[current_device()];
-  if (!ss.ok && ss.stream == nullptr) {
-    bool good = hipStreamCreateWithFlags(&ss.stream, hipStreamNonBlocking) == hipSuccess;
-    hipEvent_t* evs[4] = {&ss.fork_f, &ss.join_f, &ss.fork_b, &ss.join_b};
-    for (auto e : evs) good = good && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
-    ss.ok = good;
-  }
-  return ss;
-}
-// The node chain's backward waits for a Linear's dX only; its dW tiles (the larger half of the dual launch: 240 of 392 workgroups
-// at 2400 rows) are needed by the optimiser.  With this on they run on a third, lowest-priority stream behind the chain
-// (esc_linear_bwd_set_wgrad_stream), the scratch rows they read are per-layer copies, and the node-side slab reduce joins it.
-static int g_wgrad_stream = getenv("ESC_WGRAD_STREAM") ? atoi(getenv("ESC_WGRAD_STREAM")) : 0;
-struct WgradStream {
-  hipStream_t stream = nullptr;
-  hipEvent_t joined = nullptr;
-  bool ok = false;
-};
-static WgradStream& wgrad_stream() {
-  static thread_local std::map<int, WgradStream> per_device;
-  static thread_local WgradStream off;   // ok == false
-  if (!g_wgrad_stream) return off;
-  WgradStream& ws = per_device[current_device()];
-  if (!ws.ok && ws.stream == nullptr) {
-    int least = 0, greatest = 0;
-    (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-    bool good = hipStreamCreateWithPriority(&ws.stream, hipStreamNonBlocking, least) == hipSuccess;
-    good = good && hipEventCreateWithFlags(&ws.joined, hipEventDisableTiming) == hipSuccess;
-    ws.ok = good;
-  }
-  return ws;
-}
 static Ctx edge_ctx(const Ctx& c, hipStream_t edge) {       // same job list / slab cursor: host-side bookkeeping only
   Ctx x = c;
   x.s = edge;
   x.on_edge_stream = true;
-  x.wgrad = nullptr;
   x.y.bn_scratch = c.y.bn_scratch_e;
   x.y.col_stats = c.y.col_stats_e;
-  return x;
-}
-static Ctx side_ctx(const Ctx& c, hipStream_t side) {
-  Ctx x = c;
-  x.s = side;
-  x.y.bn_scratch = c.y.bn_scratch_x;
-  x.y.dT1 = c.y.dT1x; x.y.dT2 = c.y.dT2x; x.y.slabs = c.y.slabs_x;
-  x.jobs = nullptr; x.slab_cursor = nullptr; x.wgrad = nullptr;
   return x;
 }
 
@@ -407,30 +296,11 @@ static void mark(int which, void* stream) {
   (void)hipEventRecord(e, (hipStream_t)stream);
 }
 
-static int g_bag_stats = getenv("ESC_BAG_STATS") ? atoi(getenv("ESC_BAG_STATS")) : 1;   // BatchNorm partials from the bag kernel's epilogue
-static int g_e0_early = getenv("ESC_E0_EARLY") ? atoi(getenv("ESC_E0_EARLY")) : 1;   // e_0 in front of the pass that materialises z_emb: see forward()
-static int g_fuse_finalize = 1; // ... and their merge by the GEMM's last workgroup (no bn_finalize launch)
-static int g_gemm_stats = 1;   // BatchNorm statistics from the producing GEMM's epilogue (no extra pass over Y)
-// Node-sized BatchNorms: partials merged in the consumer's prologue instead of a finalize launch (esc_engine_set_gemm_stats
-// bit 2 / ESC_BN_FOLD=1).  Measured on MI355X (cfg1, untraced, same box): 1.154 ms with it vs 1.144 ms without — with the
-// host running ahead a finalize launch costs the node chain ~5 us, and so does the redundant merge in every consumer
-// workgroup (77 KB of partials + 38 fp64 merges: GEMM 8.5 -> 13.3 us, affine pass 4.4 -> 10 us).  Off by default.
 // The LAST BatchNorm+ReLU of every node MLP is not materialised: the Linear writes its pre-BatchNorm rows straight into the
 // concat slice and the consumers apply relu(x*scale+shift) as they read them — the next layer's aggregate (forward and
 // backward, esc_gine_aggregate_*_affine) and the readout GEMM (prologue over all (L+1)*H columns).  One elementwise launch
-// less per layer on the dependent node chain.  ESC_FUSE_NODE_ACT=0 / esc_engine_set_gemm_stats bit 4 switch it off.
-static int g_ogb_prologue = getenv("ESC_OGB_PROLOGUE") ? atoi(getenv("ESC_OGB_PROLOGUE")) : 1;        // OGB node MLP: BN+ReLU of the hidden layer in lin1's GEMM prologue
-static int g_ogb_split_tail = getenv("ESC_OGB_SPLIT_TAIL") ? atoi(getenv("ESC_OGB_SPLIT_TAIL")) : 0;    // OGB engine: weight gradients of the tail's two edge-row Linears on the node stream
-static int g_ogb_bonds_on_node = getenv("ESC_OGB_BONDS_ON_NODE") ? atoi(getenv("ESC_OGB_BONDS_ON_NODE")) : 1;   // 4.34 -> 4.31 ms/step
-static int g_fuse_drop_bwd = getenv("ESC_FUSE_DROP_BWD") ? atoi(getenv("ESC_FUSE_DROP_BWD")) : 1;     // dropout backward inside the BatchNorm backward (OGB engine)
-static int g_fuse_node_act = getenv("ESC_FUSE_NODE_ACT") ? atoi(getenv("ESC_FUSE_NODE_ACT")) : 1;
-static int g_fold = getenv("ESC_BN_FOLD") ? atoi(getenv("ESC_BN_FOLD")) : 0;     // 1: both BatchNorms of an MLP merged by their consumers; 2: only the last one (by the affine pass)
-static bool fuse_node_act(const Ctx& c) { return g_fuse_node_act && !g_fold && c.act == 1 && c.y.H >= 64 && c.y.H % 4 == 0 && c.y.cat_scale != nullptr; }
-
-static esc_bn_fold make_fold(const float* partials, int64_t rows, int64_t block_rows, int64_t C, const esc_bn_t& bn, const BnWs& w) {
-  return esc_bn_fold{partials, rows, block_rows, C, bn.eps, bn.momentum, bn.gamma, bn.beta, w.mean, w.invstd, w.scale, w.shift,
-                     bn.running_mean, bn.running_var};
-}
+// less per layer on the dependent node chain.
+static bool fuse_node_act(const Ctx& c) { return c.act == 1 && c.y.H >= 64 && c.y.H % 4 == 0 && c.y.cat_scale != nullptr; }
 
 // ---- SyncBN (esc_engine_set_collective): statistics over all ranks of a graph-sharded step ----------------------------
 struct Collective {
@@ -486,7 +356,7 @@ static int bn_backward_drop(const Ctx& c, const float* X, int64_t ldx, const flo
                      ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(dY) | reinterpret_cast<uintptr_t>(dX) |
                        reinterpret_cast<uintptr_t>(w.mean) | reinterpret_cast<uintptr_t>(w.invstd) | reinterpret_cast<uintptr_t>(bn.gamma) |
                        reinterpret_cast<uintptr_t>(bn.beta) | reinterpret_cast<uintptr_t>(scratch)) & 15) == 0 &&
-                     (reinterpret_cast<uintptr_t>(mask) & 3) == 0 && g_fuse_drop_bwd;
+                     (reinterpret_cast<uintptr_t>(mask) & 3) == 0;
   if (fused)
     return esc_bn_bwd_dropout(X, ldx, dY, lddy, M, C, w.mean, w.invstd, bn.gamma, bn.beta, c.act, mask, p, on_output, dX, lddx,
                               bn.dgamma, bn.dbeta, scratch, c.s);
@@ -501,12 +371,13 @@ static int bn_backward_drop(const Ctx& c, const float* X, int64_t ldx, const flo
 // Y = X*W^T + b followed by BatchNorm coefficient computation (training: batch statistics; eval: running ones)
 static int linear_bn(const Ctx& c, const float* X, int64_t ld_x, const esc_linear_t& lin, const float* sc, const float* sh,
                      int64_t M, float* Y, const esc_bn_t& bn, const BnWs& w, int64_t ld_y = 0) {
-  const LdsFloorGuard cap(c.on_edge_stream && g_cap_forward);
+  const LdsFloorGuard cap(c.on_edge_stream);
   const int64_t H = lin.out_dim, K = lin.in_dim;          // (the BatchNorm is as wide as the Linear's output)
   if (ld_y <= 0) ld_y = H;
   const bool sync = sync_on(c);     // statistics over all ranks: local ones first (no running update, no coefficients), then the exchange
-  const bool fused = c.train && g_gemm_stats && H > 32 && c.jobs != nullptr;   // main chain only (col_stats is shared scratch)
-  if (fused && g_fuse_finalize && M > 1 && !sync) {    // statistics AND their merge ride on the GEMM launch
+  // BatchNorm statistics from the producing GEMM's epilogue (no extra pass over Y): main chain only (col_stats is shared scratch)
+  const bool fused = c.train && H > 32 && c.jobs != nullptr;
+  if (fused && M > 1 && !sync) {    // ... and their merge by the GEMM's last workgroup (no bn_finalize launch)
     esc_bn_fuse f{bn.eps, bn.momentum, w.mean, w.invstd, bn.running_mean, bn.running_var, bn.gamma, bn.beta, w.scale, w.shift};
     return esc_linear_bn_fwd(X, ld_x, lin.w, K, lin.b, sc, sh, M, H, K, Y, ld_y, c.y.col_stats, &f, c.s);
   }
@@ -540,33 +411,12 @@ static int bn_coeffs(const Ctx& c, const float* X, int64_t ld, int64_t M, const 
 }
 
 // Linear, BN, ReLU, Linear, BN, ReLU  (reference :65-73, :78-87) -> out (materialised, ld_out)
-// node-sized training-mode MLPs: no finalize launches — each BatchNorm's partials are merged by its consumer
-static bool fold_ok(const Ctx& c, int64_t M) {
-  const int64_t H = c.y.H;
-  return c.act == 1 && c.train && g_fold && !sync_on(c) && g_gemm_stats && esc_linear_fold_available() && c.jobs != nullptr && !c.on_edge_stream && M > 1 && M <= 4096 && H % 32 == 0 &&
-         H > 32 && H <= 1024;
-}
-
 static int mlp_forward(const Ctx& c, const esc_mlp_t& p, const MlpWs& w, const float* A, int64_t ld_a, int64_t M,
                        float* out, int64_t ld_out, bool pre_out = false) {
   const int64_t H = c.y.H;
   if (pre_out) {                              // `out` receives the PRE-BatchNorm rows of lin1; w.b1 holds the coefficients
     ESC_TRY(linear_bn(c, A, ld_a, p.lin0, nullptr, nullptr, M, w.Y0, p.bn0, w.b0));
     return linear_bn(c, w.Y0, H, p.lin1, w.b0.scale, w.b0.shift, M, out, p.bn1, w.b1, ld_out);
-  }
-  if (fold_ok(c, M) && g_fold == 2) {         // only the MLP's last BatchNorm: its finalize launch folds into the affine pass
-    ESC_TRY(linear_bn(c, A, ld_a, p.lin0, nullptr, nullptr, M, w.Y0, p.bn0, w.b0));
-    ESC_TRY(esc_linear_fwd(w.Y0, H, p.lin1.w, H, p.lin1.b, w.b0.scale, w.b0.shift, M, H, H, w.Y1, H, c.y.col_stats_b, c.s));
-    const esc_bn_fold f1 = make_fold(c.y.col_stats_b, M, esc_linear_stats_block_rows(w.Y0, H, p.lin1.w, H, M, H, H), H, p.bn1, w.b1);
-    return esc_affine_act_fold(w.Y1, H, M, H, &f1, 1, out, ld_out, c.s);
-  }
-  if (fold_ok(c, M)) {
-    const int64_t K0 = p.lin0.in_dim;
-    ESC_TRY(esc_linear_fwd(A, ld_a, p.lin0.w, K0, p.lin0.b, nullptr, nullptr, M, H, K0, w.Y0, H, c.y.col_stats, c.s));
-    const esc_bn_fold f0 = make_fold(c.y.col_stats, M, esc_linear_stats_block_rows(A, ld_a, p.lin0.w, K0, M, H, K0), H, p.bn0, w.b0);
-    ESC_TRY(esc_linear_fwd_fold(w.Y0, H, p.lin1.w, H, p.lin1.b, &f0, M, H, H, w.Y1, H, c.y.col_stats_b, c.s));
-    const esc_bn_fold f1 = make_fold(c.y.col_stats_b, M, esc_linear_stats_block_rows(w.Y0, H, p.lin1.w, H, M, H, H), H, p.bn1, w.b1);
-    return esc_affine_act_fold(w.Y1, H, M, H, &f1, 1, out, ld_out, c.s);
   }
   ESC_TRY(linear_bn(c, A, ld_a, p.lin0, nullptr, nullptr, M, w.Y0, p.bn0, w.b0));
   if (w.A1) {                                 // activation other than ReLU: the hidden activation is written once
@@ -579,24 +429,20 @@ static int mlp_forward(const Ctx& c, const esc_mlp_t& p, const MlpWs& w, const f
 }
 
 // given dOut (grad of the materialised output `out`), produce parameter grads and, if dA != NULL, dA
-// Which of an MLP's two Linear backwards take the fused form (see g_bn_fuse_bwd)?  ReLU MLPs whose hidden activation was never
-// materialised (counting model) and ELU MLPs with a materialised one (ZINC), statistics of this rank only, shapes the fused
-// kernels serve; lin0 only together with lin1.
+// Which of an MLP's two Linear backwards take the fused form (see kBnBwdApplyInGemm)?  ReLU MLPs whose hidden activation was never
+// materialised (counting model), statistics of this rank only, shapes the fused kernels serve; lin0 only together with lin1.
 struct MlpFuse { bool lin1 = false, lin0 = false; };
 static MlpFuse mlp_fuse_plan(const Ctx& c, const esc_mlp_t& p, const MlpWs& w, const float* A, int64_t ld_a, int64_t M, const float* out,
                              int64_t ld_out, const float* dOut, int64_t ld_dout, const float* dA, int64_t ld_da, bool pre_out) {
   const Layout& y = c.y;
   const int64_t H = y.H;
   MlpFuse f;
-  if (!((g_bn_fuse_bwd & 1) && c.train && !sync_on(c) && y.bst_part != nullptr && p.lin1.in_dim == H && p.lin1.out_dim == H)) return f;
-  // (ELU: built and tested, but the exp in the operand staging costs more than the two launches it saves — ZINC config 4: 1.14 ms
-  // fused against 1.10 ms per step; ESC_BN_FUSE_ELU=1 enables it)
-  if (!((c.act == 1 && w.A1 == nullptr) || (c.act == 2 && w.A1 != nullptr && !pre_out && g_bn_fuse_elu))) return f;
+  if (!(kBnBwdApplyInGemm && c.train && !sync_on(c) && y.bst_part != nullptr && p.lin1.in_dim == H && p.lin1.out_dim == H)) return f;
+  if (!(c.act == 1 && w.A1 == nullptr)) return f;     // (ELU models keep the elementwise launches: DESIGN.md *Retired step-engine switches*)
   const esc_bn_bwd_fused f1 = bn_fused(pre_out ? out : w.Y1, pre_out ? ld_out : H, w.b1, c.act), f0 = bn_fused(w.Y0, H, w.b0, c.act);
   const esc_bn_bwd_next n0{y.bst_part, w.Y0, H, w.b0.mean, w.b0.invstd, w.b0.scale, w.b0.shift, c.act};
   const float* slab_probe = c.jobs ? *c.slab_cursor : y.slabs;
-  const float* xh = w.A1 ? w.A1 : w.Y0;                    // lin1's input: the materialised activation, or its pre-BatchNorm rows
-  f.lin1 = esc_linear_bwd_both_bn_ok(dOut, ld_dout, &f1, xh, H, p.lin1.w, H, M, H, H, y.dT2, H, slab_probe, (g_bn_fuse_bwd & 2) ? &n0 : nullptr) != 0;
+  f.lin1 = esc_linear_bwd_both_bn_ok(dOut, ld_dout, &f1, w.Y0, H, p.lin1.w, H, M, H, H, y.dT2, H, slab_probe, &n0) != 0;   // (lin1's input: Y0's pre-BatchNorm rows)
   f.lin0 = f.lin1 && esc_linear_bwd_both_bn_ok(y.dT2, H, &f0, A, ld_a, p.lin0.w, p.lin0.in_dim, M, H, p.lin0.in_dim, dA, ld_da, slab_probe, nullptr) != 0;
   return f;
 }
@@ -618,7 +464,6 @@ static int mlp_backward(const Ctx& c, const esc_mlp_t& p, const MlpWs& w, const 
     const int64_t ld_x1 = pre_out ? ld_out : H;
     const esc_bn_bwd_fused f1 = bn_fused(x1, ld_x1, w.b1, c.act), f0 = bn_fused(w.Y0, H, w.b0, c.act);
     esc_bn_bwd_next n0{y.bst_part, w.Y0, H, w.b0.mean, w.b0.invstd, w.b0.scale, w.b0.shift, c.act};
-    const bool stats = (g_bn_fuse_bwd & 2) != 0;
     // (activation derivatives are recomputed from the pre-BatchNorm rows everywhere — Y == NULL — so that the sums and the
     // fused apply see the same values)
     if (have_slots > 0)
@@ -626,13 +471,8 @@ static int mlp_backward(const Ctx& c, const esc_mlp_t& p, const MlpWs& w, const 
     else
       ESC_TRY(esc_bn_bwd_coef(x1, ld_x1, nullptr, 0, dOut, ld_dout, M, H, w.b1.mean, w.b1.invstd, p.bn1.gamma, p.bn1.beta, c.act, w.b1.coef,
                               p.bn1.dgamma, p.bn1.dbeta, y.bn_scratch, c.s));
-    if (w.A1) ESC_TRY(linear_backward_bn(c, dOut, ld_dout, f1, w.A1, H, nullptr, nullptr, p.lin1, M, y.dT2, H, 0, stats ? &n0 : nullptr));
-    else      ESC_TRY(linear_backward_bn(c, dOut, ld_dout, f1, w.Y0, H, w.b0.scale, w.b0.shift, p.lin1, M, y.dT2, H, 0, stats ? &n0 : nullptr));
-    if (stats)
-      ESC_TRY(esc_bn_bwd_coef_from_partials(y.bst_part, cdiv(M, esc_linear_bwd_bn_block_rows(M, H, H)), M, H, w.b0.coef, p.bn0.dgamma, p.bn0.dbeta, c.s));
-    else
-      ESC_TRY(esc_bn_bwd_coef(w.Y0, H, nullptr, 0, y.dT2, H, M, H, w.b0.mean, w.b0.invstd, p.bn0.gamma, p.bn0.beta, c.act, w.b0.coef,
-                              p.bn0.dgamma, p.bn0.dbeta, y.bn_scratch, c.s));
+    ESC_TRY(linear_backward_bn(c, dOut, ld_dout, f1, w.Y0, H, w.b0.scale, w.b0.shift, p.lin1, M, y.dT2, H, 0, &n0));
+    ESC_TRY(esc_bn_bwd_coef_from_partials(y.bst_part, cdiv(M, esc_linear_bwd_bn_block_rows(M, H, H)), M, H, w.b0.coef, p.bn0.dgamma, p.bn0.dbeta, c.s));
     if (fuse.lin0) return linear_backward_bn(c, y.dT2, H, f0, A, ld_a, nullptr, nullptr, p.lin0, M, dA, ld_da, 0, nullptr);
     // lin0's shape is not served by the fused kernels (e.g. a 32-wide input): the apply as its own pass, then the plain backward
     ESC_TRY(esc_bn_bwd_apply(w.Y0, H, nullptr, 0, y.dT2, H, M, H, w.b0.mean, w.b0.invstd, p.bn0.gamma, p.bn0.beta, c.act, w.b0.coef, y.dT2, H, c.s));
@@ -640,27 +480,6 @@ static int mlp_backward(const Ctx& c, const esc_mlp_t& p, const MlpWs& w, const 
   }
   if (pre_out) ESC_TRY(bn_backward(c, out, ld_out, nullptr, 0, dOut, ld_dout, M, w.b1, p.bn1, y.dT1, H, y.bn_scratch));   // `out` = pre-BN rows
   else         ESC_TRY(bn_backward(c, w.Y1, H, out, ld_out, dOut, ld_dout, M, w.b1, p.bn1, y.dT1, H, y.bn_scratch));
-  // bit 1 alone: the elementwise apply launches stay, only the column sums of BatchNorm 0 come out of lin1's dX epilogue
-  if ((g_bn_fuse_bwd & 3) == 2 && c.train && c.act == 1 && w.A1 == nullptr && !sync_on(c) && y.bst_part != nullptr && p.lin1.in_dim == H && p.lin1.out_dim == H) {
-    esc_bn_bwd_next n0{y.bst_part, w.Y0, H, w.b0.mean, w.b0.invstd, w.b0.scale, w.b0.shift, 1};
-    const float* slab_probe = c.jobs ? *c.slab_cursor : y.slabs;
-    if (esc_linear_bwd_both_bn_ok(y.dT1, H, nullptr, w.Y0, H, p.lin1.w, H, M, H, H, y.dT2, H, slab_probe, &n0)) {
-      const LdsFloorGuard cap(c.on_edge_stream);
-      float* slabs = y.slabs;
-      esc_reduce_job* job = nullptr;
-      if (c.jobs) {
-        slabs = *c.slab_cursor;
-        *c.slab_cursor += (esc_linear_bwd_weight_scratch(M, H, H) + 63) & ~63LL;
-        c.jobs->emplace_back();
-        job = &c.jobs->back();
-      }
-      ESC_TRY(esc_linear_bwd_both_bn(y.dT1, H, nullptr, w.Y0, H, w.b0.scale, w.b0.shift, p.lin1.w, H, M, H, H, y.dT2, H, 0, p.lin1.dw, H, p.lin1.db,
-                                     slabs, job, &n0, c.s));
-      ESC_TRY(esc_bn_bwd_coef_from_partials(y.bst_part, cdiv(M, esc_linear_bwd_bn_block_rows(M, H, H)), M, H, w.b0.coef, p.bn0.dgamma, p.bn0.dbeta, c.s));
-      ESC_TRY(esc_bn_bwd_apply(w.Y0, H, nullptr, 0, y.dT2, H, M, H, w.b0.mean, w.b0.invstd, p.bn0.gamma, p.bn0.beta, 1, w.b0.coef, y.dT2, H, c.s));
-      return linear_backward(c, y.dT2, H, A, ld_a, nullptr, nullptr, p.lin0, M, dA, ld_da, 0);
-    }
-  }
   if (w.A1) {
     ESC_TRY(linear_backward(c, y.dT1, H, w.A1, H, nullptr, nullptr, p.lin1, M, y.dT2, H, 0));
     ESC_TRY(bn_backward(c, w.Y0, H, w.A1, H, y.dT2, H, M, w.b0, p.bn0, y.dT2, H, y.bn_scratch));
@@ -682,7 +501,6 @@ static int forward(const Ctx& c) {
   // edge-sized kernels are as latency-bound as the node chain and the events cost more than the overlap returns (bs 16: 0.68 ms on
   // one stream, 0.84 on two; bs 64: 0.85 / 0.89; bs 128: 1.25 / 1.04).
   EdgeStream& es = edge_stream_for(E);
-  const NodeFloorGuard node_floor(es.ok && c.train ? g_node_floor_fwd : 0);
   Ctx ce = c;
   if (es.ok) {
     ESC_TRY(chain(es.z_ready, (hipStream_t)c.s, es.stream));       // the batch arrays were produced on the caller's stream
@@ -690,7 +508,7 @@ static int forward(const Ctx& c) {
   }
   // ESC bag (esc_bag_fwd_rows; the LDS-staged table slices are an option that is off by default); in training mode its epilogue
   // leaves the BatchNorm partials of z_embedding's first BatchNorm, so the statistics pass over the E x H output is one finalize launch
-  const int64_t bag_block = (c.train && !sync_on(ce) && g_bag_stats) ? esc_bag_fwd_stats_block_rows(m->z_table, m->z_rows, H, y.Zb, H, E) : 0;
+  const int64_t bag_block = (c.train && !sync_on(ce)) ? esc_bag_fwd_stats_block_rows(m->z_table, m->z_rows, H, y.Zb, H, E) : 0;
   if (bag_block > 0) {
     ESC_TRY(esc_bag_fwd_rows(m->z_table, m->z_rows, H, b->row_ptr, b->bag_idx, b->bag_val, E, y.Zb, H, 0, ce.y.col_stats, ce.s));
     ESC_TRY(esc_bn_stats_from_partials_rows(ce.y.col_stats, E, H, bag_block, m->zbn0.eps, m->zbn0.momentum, y.zb0.mean, y.zb0.invstd,
@@ -699,42 +517,37 @@ static int forward(const Ctx& c) {
     ESC_TRY(esc_bag_fwd_rows(m->z_table, m->z_rows, H, b->row_ptr, b->bag_idx, b->bag_val, E, y.Zb, H, 0, nullptr, ce.s));
     ESC_TRY(bn_coeffs(ce, y.Zb, H, E, m->zbn0, y.zb0));
   }
-  const bool mat = g_materialise_edge_act != 0;
-  if (mat) {
-    ESC_TRY(esc_affine_act(y.Zb, H, E, H, y.zb0.scale, y.zb0.shift, 1, y.A0, H, ce.s));
-    ESC_TRY(linear_bn(ce, y.A0, H, m->zlin, nullptr, nullptr, E, y.Yz, m->zbn1, y.zb1));
-  } else {
-    ESC_TRY(linear_bn(ce, y.Zb, H, m->zlin, y.zb0.scale, y.zb0.shift, E, y.Yz, m->zbn1, y.zb1));
-  }                                                                       // z_emb = relu(Yz*scale+shift)
+  // Edge-sized activations are materialised: the affine+ReLU prologue costs the edge-row GEMMs ~25 % (VALU-bound staging), more
+  // than the two extra elementwise passes that write them once; node-sized MLP activations stay fused.
+  ESC_TRY(esc_affine_act(y.Zb, H, E, H, y.zb0.scale, y.zb0.shift, 1, y.A0, H, ce.s));
+  ESC_TRY(linear_bn(ce, y.A0, H, m->zlin, nullptr, nullptr, E, y.Yz, m->zbn1, y.zb1));       // z_emb = relu(Yz*scale+shift)
   // The first edge term is narrow (in_dim columns: a bandwidth pass over z_emb): it applies z_embedding's last BatchNorm+ReLU to
   // its operand itself and runs BEFORE the pass that materialises z_emb for the wide layers — the node chain's first
   // aggregate waits for e_0 only (same fmaf + max per element: e_0 is bit-identical either way).  It went there when node layer 0
   // was the later pipeline; since the batched launch below the two are level (layer 0 ends with the batched GEMM), and launching
   // e_0 from the node stream instead brings the GEMM forward by 10 us without moving the end of the forward (DESIGN.md *Step
   // engine, fork and join*): it stays here.
-  const bool e0_early = mat && g_e0_early && y.C0 <= 32 && L >= 1;
+  const bool e0_early = y.C0 <= 32 && L >= 1;
   if (e0_early) {
-    const LdsFloorGuard cap(ce.on_edge_stream && g_cap_forward);
+    const LdsFloorGuard cap(ce.on_edge_stream);
     const ArmedEvent arm(es.e_ready[0], es.ok);
     ESC_TRY(esc_linear_fwd(y.Yz, H, m->conv[0].lin.w, H, m->conv[0].lin.b, y.zb1.scale, y.zb1.shift, E, y.C0, H, y.e[0], y.ld_e[0], nullptr, ce.s));
     if (es.ok) ESC_TRY(chain_armed(es.e_ready[0], arm, es.stream, nullptr));
   }
-  if (mat) ESC_TRY(esc_affine_act(y.Yz, H, E, H, y.zb1.scale, y.zb1.shift, 1, y.Zemb, H, ce.s));
-  // Per-layer launches (ESC_EDGE_BATCHED=0, L < 3, or activations not materialised): the edge terms run one layer ahead of the node
-  // chain — e_{l+1} is queued behind the aggregate of layer l and overlaps that layer's MLP, so that a bandwidth-bound aggregate never
-  // shares the HBM with an edge-sized GEMM (r01: 1.255 -> 1.225 ms against two layers ahead).  The default since r03 is the batched
-  // launch below.
+  ESC_TRY(esc_affine_act(y.Yz, H, E, H, y.zb1.scale, y.zb1.shift, 1, y.Zemb, H, ce.s));
+  // Per-layer launches (L < 3): the edge terms run one layer ahead of the node chain — e_{l+1} is queued behind the aggregate of
+  // layer l and overlaps that layer's MLP, so that a bandwidth-bound aggregate never shares the HBM with an edge-sized GEMM
+  // (r01: 1.255 -> 1.225 ms against two layers ahead).  From L = 3 on the batched launch below takes their place.
   auto edge_term = [&](int l) -> int {
-    const LdsFloorGuard cap(ce.on_edge_stream && g_cap_forward);
+    const LdsFloorGuard cap(ce.on_edge_stream);
     const esc_conv_t& cv = m->conv[l];
     const int64_t C = l == 0 ? y.C0 : H;
-    if (mat) ESC_TRY(esc_linear_fwd(y.Zemb, H, cv.lin.w, H, cv.lin.b, nullptr, nullptr, E, C, H, y.e[l], y.ld_e[l], nullptr, ce.s));
-    else     ESC_TRY(esc_linear_fwd(y.Yz, H, cv.lin.w, H, cv.lin.b, y.zb1.scale, y.zb1.shift, E, C, H, y.e[l], y.ld_e[l], nullptr, ce.s));
+    ESC_TRY(esc_linear_fwd(y.Zemb, H, cv.lin.w, H, cv.lin.b, nullptr, nullptr, E, C, H, y.e[l], y.ld_e[l], nullptr, ce.s));
     if (es.ok && hipEventRecord(es.e_ready[l], es.stream) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
     return ESC_OK;
   };
   mark(PH_START, c.s);
-  const bool batched = y.e_cat != nullptr && mat;
+  const bool batched = y.e_cat != nullptr;
   if (batched) {                                            // e_1 .. e_{L-1} in one launch over the packed weights
     if (!e0_early) ESC_TRY(edge_term(0));
     esc_table_list tl{};
@@ -745,7 +558,7 @@ static int forward(const Ctx& c) {
     }
     ESC_TRY(esc_table_pack(&tl, H, y.w_cat, ce.s));
     {
-      const LdsFloorGuard cap(ce.on_edge_stream && g_cap_forward);
+      const LdsFloorGuard cap(ce.on_edge_stream);
       const ArmedEvent arm(es.e_ready[1], es.ok);          // the node chain's layers 1 .. L-1 start behind this launch
       ESC_TRY(esc_linear_fwd(y.Zemb, H, y.w_cat, H, y.w_cat + (L - 1) * H * H, nullptr, nullptr, E, (L - 1) * H, H, y.e_cat, (L - 1) * H, nullptr, ce.s));
       if (es.ok) ESC_TRY(chain_armed(es.e_ready[1], arm, es.stream, nullptr));
@@ -753,7 +566,7 @@ static int forward(const Ctx& c) {
     for (int l = 2; l < (int)L; ++l)
       if (es.ok && hipEventRecord(es.e_ready[l], es.stream) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
   }
-  const int ahead = batched ? 0 : (es.ok ? g_edge_ahead : (int)L);          // one stream: all of them up front, in layer order
+  const int ahead = batched ? 0 : (es.ok ? 1 : (int)L);          // one stream: all of them up front, in layer order
   for (int l = e0_early ? 1 : 0; l < (int)L && l < ahead; ++l) ESC_TRY(edge_term(l));
   // ---- node pipeline (first, while it would otherwise wait for the first edge term: the chunk schedule of the bag
   // gradient, which depends on the batch's index arrays only)
@@ -763,31 +576,16 @@ static int forward(const Ctx& c) {
     for (int i = 0; i < cnt.n; ++i) cnt.p[i] = m->counters[i];
     ESC_TRY(bag_bwd_classify_counted(b->col_row, y.Z, H, E, y.bag_scratch, cnt, c.s));
   }
-  // xs[0] = x_embedding(x) (reference :166) — side stream
-  SideStream& ss = side_stream();
-  if (ss.ok) {
-    if (hipEventRecord(ss.fork_f, (hipStream_t)c.s) != hipSuccess || hipStreamWaitEvent(ss.stream, ss.fork_f, 0) != hipSuccess) {
-      set_error("esc_engine: side-stream fork failed");
-      return ESC_ELAUNCH;
-    }
-    const Ctx cx = side_ctx(c, ss.stream);
-    ESC_TRY(mlp_forward(cx, m->xemb, y.xemb, b->x, y.C0, N, y.cat, W, fuse_node_act(c)));
-    (void)hipEventRecord(ss.join_f, ss.stream);
-  } else {
-    ESC_TRY(mlp_forward(c, m->xemb, y.xemb, b->x, y.C0, N, y.cat, W, fuse_node_act(c)));
-  }
-  // (readout split: see g_readout_split; the conditions are linear_bn's for statistics from the GEMM epilogue + a finalize launch)
-  const bool ro_split = g_readout_split && es.ok && !ss.ok && c.train && L >= 2 && fuse_node_act(c) && !sync_on(c) && g_gemm_stats && c.jobs != nullptr &&
-                        !(fold_ok(c, N) && H <= 256) && L * H <= 1280 &&
-                        esc_linear_fwd_from_ok(y.cat + L * H, W, m->lin1.w + L * H, W, N, H, H, 1) != 0;
+  // xs[0] = x_embedding(x) (reference :166)
+  ESC_TRY(mlp_forward(c, m->xemb, y.xemb, b->x, y.C0, N, y.cat, W, fuse_node_act(c)));
   // GINE layers (reference :161, :167-175): xs[l+1] -> cat[:, (l+1)H : (l+2)H]
   for (int l = 0; l < L; ++l) {
     const esc_conv_t& cv = m->conv[l];
     const int64_t C = l == 0 ? y.C0 : H;
     const float* hin = l == 0 ? b->x : y.cat + (int64_t)l * H;
     const int64_t ld_h = l == 0 ? y.C0 : W;
-    // (batched edge terms: e_1 .. e_{L-1} come out of one launch, the wait in front of layer 1 covers the later layers)
-    if (es.ok && !(batched && l >= 2 && g_skip_waits) && hipStreamWaitEvent((hipStream_t)c.s, es.e_ready[l], 0) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
+    // (batched edge terms: e_1 .. e_{L-1} come out of one launch, the wait in front of layer 1 covers the later layers: -7 us of step time)
+    if (es.ok && !(batched && l >= 2) && hipStreamWaitEvent((hipStream_t)c.s, es.e_ready[l], 0) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
     if (fuse_node_act(c) && l > 0)          // hin = pre-BatchNorm rows of the previous layer: relu(x*scale+shift) on the fly
       ESC_TRY(esc_gine_aggregate_fwd_affine(hin, ld_h, y.cat_scale + (int64_t)l * H, y.cat_shift + (int64_t)l * H, y.e[l], y.ld_e[l], b->in_ptr,
                                             b->in_edge, b->in_src, cv.eps, N, C, y.agg[l], C, c.s));
@@ -798,33 +596,10 @@ static int forward(const Ctx& c) {
       ESC_TRY(edge_term(l + ahead));
     }
     ESC_TRY(mlp_forward(c, cv.nn, y.conv[l], y.agg[l], C, N, y.cat + (int64_t)(l + 1) * H, W, fuse_node_act(c)));
-    if (ro_split && l == (int)L - 2) {        // slices 0 .. L-1 of cat (and their BatchNorm coefficients) are final: their share of lin1
-      ESC_TRY(chain(es.lin1_fork, (hipStream_t)c.s, es.stream));
-      ESC_TRY(esc_linear_fwd(y.cat, W, m->lin1.w, W, nullptr, y.cat_scale, y.cat_shift, N, H, L * H, y.Ypart, H, nullptr, es.stream));
-      if (hipEventRecord(es.lin1_rest, es.stream) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
-    }
   }
   if (c.train) mark(PH_EDGE_FWD_DONE, ce.s);
-  // readout (reference :183-189) needs every slice of cat, including the side stream's
-  if (ss.ok && hipStreamWaitEvent((hipStream_t)c.s, ss.join_f, 0) != hipSuccess) {
-    set_error("esc_engine: side-stream join failed");
-    return ESC_ELAUNCH;
-  }
-  if (fold_ok(c, N) && H <= 256) {          // lin2 (a wave per row, H <= 256) merges bn_lin1's partials itself
-    ESC_TRY(esc_linear_fwd(y.cat, W, m->lin1.w, W, m->lin1.b, nullptr, nullptr, N, H, W, y.Yl, H, c.y.col_stats, c.s));
-    const esc_bn_fold f = make_fold(c.y.col_stats, N, esc_linear_stats_block_rows(y.cat, W, m->lin1.w, W, N, H, W), H, m->bn_lin1, y.bl);
-    return esc_linear_fwd_fold(y.Yl, H, m->lin2.w, H, m->lin2.b, &f, N, 1, H, y.pred, 1, nullptr, c.s);
-  }
+  // readout (reference :183-189)
   const bool fa = fuse_node_act(c);       // cat holds pre-BatchNorm rows: the readout GEMM applies every slice's BatchNorm+ReLU itself
-  if (ro_split) {
-    const int64_t K0 = L * H;
-    if (hipStreamWaitEvent((hipStream_t)c.s, es.lin1_rest, 0) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
-    ESC_TRY(esc_linear_fwd_from(y.Ypart, H, y.cat + K0, W, m->lin1.w + K0, W, m->lin1.b, y.cat_scale + K0, y.cat_shift + K0, N, H, H, y.Yl, H,
-                                c.y.col_stats, c.s));
-    ESC_TRY(esc_bn_stats_from_partials_rows(c.y.col_stats, N, H, esc_linear_stats_block_rows(y.cat + K0, W, m->lin1.w + K0, W, N, H, H), m->bn_lin1.eps,
-                                            m->bn_lin1.momentum, y.bl.mean, y.bl.invstd, m->bn_lin1.running_mean, m->bn_lin1.running_var,
-                                            m->bn_lin1.gamma, m->bn_lin1.beta, y.bl.scale, y.bl.shift, c.s));
-  } else
   ESC_TRY(linear_bn(c, y.cat, W, m->lin1, fa ? y.cat_scale : nullptr, fa ? y.cat_shift : nullptr, N, y.Yl, m->bn_lin1, y.bl));
   // train_step: the head's launch leaves the L1 gradient of every prediction too, so the backward starts behind it and the loss
   // launch (a single workgroup walking all predictions, 5-7 us) leaves the chain: the edge stream continues behind the head
@@ -862,31 +637,28 @@ static int finish_pending(Pending& p) {
   return ESC_OK;
 }
 
-static int backward(const Ctx& c_in, Pending* defer) {
-  Ctx c = c_in;
+static int backward(const Ctx& c, Pending* defer) {
   EdgeStream& es = edge_stream_for(c.y.E);
-  const NodeFloorGuard node_floor(es.ok ? g_node_floor_bwd : 0);
-  WgradStream& ws = wgrad_stream();
-  if (ws.ok && es.ok && c.jobs != nullptr && c.train && c.y.dT1_l[0] != nullptr) c.wgrad = ws.stream;
+  const NodeFloorGuard node_floor(es.ok ? kNodeLdsFloorBwd : 0);
   const esc_nested_gin_t* m = c.m;
   const esc_batch_t* b = c.b;
   const Layout& y = c.y;
   const int64_t N = y.N, E = y.E, H = y.H, L = y.L, W = y.W;
   // lin2 <- dpred
   ESC_TRY(linear_backward(c, y.dpred, 1, y.Yl, H, y.bl.scale, y.bl.shift, m->lin2, N, y.dAl, H, 0));
-  // bn_lin1 backward: folded into lin1's backward when the fused kernels serve its column blocks (see g_bn_fuse_bwd)
+  // bn_lin1 backward: folded into lin1's backward when the fused kernels serve its column blocks (see kBnBwdApplyInGemm)
   const bool split_lin1 = es.ok && c.jobs != nullptr && L >= 1;
   const esc_bn_bwd_fused fl = bn_fused(y.Yl, H, y.bl, 1);
   const bool fa_l = fuse_node_act(c);
   // the last layer's output gradient d(cat)[:, L*H:] is final once lin1's node-side block has written it: its dX tiles
-  // leave the column sums of that layer's last BatchNorm backward (bit 1)
+  // leave the column sums of that layer's last BatchNorm backward (kBnBwdSumsFromDx)
   const MlpWs& wl = y.conv[L > 0 ? L - 1 : 0];
   esc_bn_bwd_next nl{y.bst_part, y.cat + L * H, W, wl.b1.mean, wl.b1.invstd, wl.b1.scale, wl.b1.shift, 1};
   auto lin1_ok = [&](int64_t col0, int64_t ncols, const esc_bn_bwd_next* nx) {
     return esc_linear_bwd_both_bn_ok(y.dAl, H, &fl, y.cat + col0, W, m->lin1.w + col0, W, N, H, ncols, y.dcat + col0, W,
                                      c.jobs ? *c.slab_cursor : y.slabs, nx) != 0;
   };
-  const bool fuse_l = (g_bn_fuse_bwd & 1) && c.act == 1 && !sync_on(c) && y.bst_part != nullptr &&
+  const bool fuse_l = kBnBwdApplyInGemm && c.act == 1 && !sync_on(c) && y.bst_part != nullptr &&
                       (split_lin1 ? (lin1_ok(0, L * H, nullptr) && lin1_ok(L * H, H, nullptr)) : lin1_ok(0, W, nullptr));
   int64_t last_slots = 0;          // > 0: slots of bst_part that hold the last layer's BatchNorm-backward sums
   if (fuse_l)
@@ -904,9 +676,6 @@ static int backward(const Ctx& c_in, Pending* defer) {
       *c.slab_cursor += (esc_linear_bwd_weight_scratch(N, H, ncols) + 63) & ~63LL;
       c.jobs->emplace_back();
       const bool fa = fa_l;
-      Ctx cs = c;
-      if (stream != c.s) cs.wgrad = nullptr;
-      const WgradScope side(cs);
       if (fuse_l)
         return esc_linear_bwd_both_bn(y.dAl, H, &fl, y.cat + col0, W, fa ? y.cat_scale + col0 : nullptr, fa ? y.cat_shift + col0 : nullptr, m->lin1.w + col0, W,
                                       N, H, ncols, y.dcat + col0, W, 0, m->lin1.dw + col0, W, db, slabs, &c.jobs->back(), nx, stream);
@@ -920,7 +689,7 @@ static int backward(const Ctx& c_in, Pending* defer) {
     }
     if (hipEventRecord(es.lin1_rest, es.stream) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
     // (the last layer's MLP backward follows at once: does it take the fused form, and can this block leave its sums?)
-    const bool leave = fuse_l && fa_l && (g_bn_fuse_bwd & 2) && lin1_ok(K0, H, &nl) &&
+    const bool leave = fuse_l && fa_l && kBnBwdSumsFromDx && lin1_ok(K0, H, &nl) &&
                        mlp_backward_fused(c, m->conv[L - 1].nn, y.conv[L - 1], y.agg[L - 1], L == 1 ? y.C0 : H, N, y.cat + L * H, W, y.dcat + L * H, W,
                                           y.dagg, L == 1 ? y.C0 : H, true);
     ESC_TRY(part(c.s, K0, H, m->lin1.db, leave ? &nl : nullptr));
@@ -929,21 +698,6 @@ static int backward(const Ctx& c_in, Pending* defer) {
     ESC_TRY(linear_backward_bn(c, y.dAl, H, fl, y.cat, W, fa_l ? y.cat_scale : nullptr, fa_l ? y.cat_shift : nullptr, m->lin1, N, y.dcat, W, 0, nullptr));
   } else {
     ESC_TRY(linear_backward(c, y.dAl, H, y.cat, W, fa_l ? y.cat_scale : nullptr, fa_l ? y.cat_shift : nullptr, m->lin1, N, y.dcat, W, 0));
-  }
-  // x_embedding backward (input x needs no gradient): only reads d(cat)[:, 0:H] -> side stream
-  SideStream& ss = side_stream();
-  if (ss.ok) {
-    if (hipEventRecord(ss.fork_b, (hipStream_t)c.s) != hipSuccess || hipStreamWaitEvent(ss.stream, ss.fork_b, 0) != hipSuccess) {
-      set_error("esc_engine: side-stream fork failed");
-      return ESC_ELAUNCH;
-    }
-    if (split_lin1 && hipStreamWaitEvent(ss.stream, es.lin1_rest, 0) != hipSuccess) {      // d(cat)[:, 0:H] comes from there
-      set_error("esc_engine: stream event failed");
-      return ESC_ELAUNCH;
-    }
-    const Ctx cx = side_ctx(c, ss.stream);
-    ESC_TRY(mlp_backward(cx, m->xemb, y.xemb, b->x, y.C0, N, y.cat, W, y.dcat, W, nullptr, 0, fuse_node_act(c)));
-    (void)hipEventRecord(ss.join_b, ss.stream);
   }
   // GINE layers, last to first (the eps gradients are only needed by the optimiser: one reduce launch at the end)
   Ctx ce = es.ok ? edge_ctx(c, es.stream) : c;
@@ -957,18 +711,16 @@ static int backward(const Ctx& c_in, Pending* defer) {
     const int64_t C = l == 0 ? y.C0 : H;
     const float* hin = l == 0 ? b->x : y.cat + (int64_t)l * H;
     const int64_t ld_h = l == 0 ? y.C0 : W;
-    Ctx cl = c;
-    if (c.wgrad) { cl.y.dT1 = y.dT1_l[l]; cl.y.dT2 = y.dT2_l[l]; }     // still read by this layer's dW tiles when the next layer writes its own
-    ESC_TRY(mlp_backward(cl, cv.nn, y.conv[l], y.agg[l], C, N, y.cat + (int64_t)(l + 1) * H, W,
+    ESC_TRY(mlp_backward(c, cv.nn, y.conv[l], y.agg[l], C, N, y.cat + (int64_t)(l + 1) * H, W,
                          y.dcat + (int64_t)(l + 1) * H, W, y.dagg, C, fuse_node_act(c), l == (int)L - 1 ? last_slots : agg_slots));
     agg_slots = 0;
     float* dx = l == 0 ? nullptr : y.dcat + (int64_t)l * H;            // accumulate into the previous slice
     if (split_lin1 && l == (int)L - 1 &&                               // ... which the edge stream's lin1 blocks fill
         hipStreamWaitEvent((hipStream_t)c.s, es.lin1_rest, 0) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
-    // (bit 3) d(cat)[:, l*H:(l+1)*H] is final once this launch has added its share: it leaves the column sums of the PREVIOUS layer's
+    // (kBnBwdSumsFromAgg) d(cat)[:, l*H:(l+1)*H] is final once this launch has added its share: it leaves the column sums of the PREVIOUS layer's
     // last BatchNorm backward, and that layer's MLP backward starts with the finalize
     const ArmedEvent arm(es.de_ready[l], es.ok);        // d_e[l] comes out of the aggregate backward: one launch, whichever form
-    const bool stats_here = fuse_node_act(c) && l > 0 && (g_bn_fuse_bwd & 8) && esc_gine_aggregate_bwd_deps_slots(C) == 1 && C <= 2048 &&
+    const bool stats_here = fuse_node_act(c) && l > 0 && kBnBwdSumsFromAgg && esc_gine_aggregate_bwd_deps_slots(C) == 1 && C <= 2048 &&
                             mlp_backward_fused(c, m->conv[l - 1].nn, y.conv[l - 1], y.agg[l - 1], l - 1 == 0 ? y.C0 : H, N, y.cat + (int64_t)l * H, W,
                                                y.dcat + (int64_t)l * H, W, y.dagg, l - 1 == 0 ? y.C0 : H, true);
     if (stats_here) {
@@ -985,12 +737,12 @@ static int backward(const Ctx& c_in, Pending* defer) {
                                      y.d_e[l], C, dx, W, 1, y.deps_part + (int64_t)l * 2 * N, c.s));
     eps_jobs.push_back(esc_sum_job{y.deps_part + (int64_t)l * 2 * N, N * esc_gine_aggregate_bwd_deps_slots(C), cv.deps});
     if (es.ok) ESC_TRY(chain_armed(es.de_ready[l], arm, (hipStream_t)c.s, es.stream));   // lin_l backward: edge stream
-    const float* zin = g_materialise_edge_act ? y.Zemb : y.Yz;
-    const float* zsc = g_materialise_edge_act ? nullptr : y.zb1.scale;
-    const float* zsh = g_materialise_edge_act ? nullptr : y.zb1.shift;
-    if (l == 0 && es.ok && c.jobs && g_split_last_lin) {
+    const float* zin = y.Zemb;
+    if (l == 0 && es.ok && c.jobs) {
       // the LAST lin backward sits in the tail of the step: only its input gradient (which completes d(z_emb)) stays on
-      // the edge stream; the weight gradient runs on the node stream, which has nothing left to do
+      // the edge stream; the weight gradient runs on the node stream, which has nothing left to do.  Measured neutral when it
+      // went in (1.038 vs 1.031-1.044 ms by the phase marks): the node stream's own reductions then become the end of the
+      // step.  Doing the same for z_embedding's Linear costs 25-30 us (DESIGN.md *Step engine, fork and join*).
       {
         const LdsFloorGuard cap(true);
         ESC_TRY(esc_linear_bwd_input(y.d_e[l], C, cv.lin.w, H, E, C, H, y.dZemb, H, l == (int)L - 1 ? 0 : 1, es.stream));
@@ -998,64 +750,33 @@ static int backward(const Ctx& c_in, Pending* defer) {
       float* slabs = *c.slab_cursor;
       *c.slab_cursor += (esc_linear_bwd_weight_scratch(E, C, H) + 63) & ~63LL;
       c.jobs->emplace_back();
-      ESC_TRY(esc_linear_bwd_both_deferred(y.d_e[l], C, zin, H, zsc, zsh, cv.lin.w, H, E, C, H, nullptr, 0, 0, cv.lin.dw, H, cv.lin.db,
+      ESC_TRY(esc_linear_bwd_both_deferred(y.d_e[l], C, zin, H, nullptr, nullptr, cv.lin.w, H, E, C, H, nullptr, 0, 0, cv.lin.dw, H, cv.lin.db,
                                            slabs, &c.jobs->back(), c.s));
     } else {
-      ESC_TRY(linear_backward(ce, y.d_e[l], C, zin, H, zsc, zsh, cv.lin, E, y.dZemb, H, l == (int)L - 1 ? 0 : 1));
+      ESC_TRY(linear_backward(ce, y.d_e[l], C, zin, H, nullptr, nullptr, cv.lin, E, y.dZemb, H, l == (int)L - 1 ? 0 : 1));
     }
     if (es.ok && !edge_jobs.empty() && l > 0) {      // the edge stream now idles until d_e of the next layer: reduce these slabs there
       ESC_TRY(esc_slab_reduce_jobs(edge_jobs.data(), (int)edge_jobs.size(), es.stream));   // (l == 0: the tail of the step follows at
       edge_jobs.clear();                                                                    // once — its slabs wait for the final reduce)
     }
   }
-  if (!ss.ok) {
-    Ctx cx = c;
-    if (c.wgrad) { cx.y.dT1 = y.dT1x; cx.y.dT2 = y.dT2x; }
-    ESC_TRY(mlp_backward(cx, m->xemb, y.xemb, b->x, y.C0, N, y.cat, W, y.dcat, W, nullptr, 0, fuse_node_act(c)));
-  }
+  // x_embedding backward (input x needs no gradient): only reads d(cat)[:, 0:H]
+  ESC_TRY(mlp_backward(c, m->xemb, y.xemb, b->x, y.C0, N, y.cat, W, y.dcat, W, nullptr, 0, fuse_node_act(c)));
   // z_embedding + bag: the tail of the edge pipeline (d(z_emb) is complete in edge-stream order); it overlaps the
   // x_embedding backward queued above on the node stream
-  const bool mat = g_materialise_edge_act != 0;
-  // (the ReLU mask is recomputed from the pre-BN value even when the activation was materialised: one array less to read)
+  // (the ReLU mask is recomputed from the pre-BN value even though the activation was materialised: one array less to read)
   Ctx ct = ce;
-  ct.on_edge_stream = ce.on_edge_stream && g_cap_tail;    // the tail is the critical path: its GEMM runs at full occupancy
-  // The tail is serial edge-sized work behind the last d_e: both of z_embedding's BatchNorm backwards lose a pass when they
-  // ride on its Linear's backward (bit 2 of g_bn_fuse_bwd) — BatchNorm 1's apply on the staged dY, BatchNorm 0's column sums
-  // from the dX epilogue: coef (2 launches), dX+dW, finalize, apply instead of 3 + 1 + 3
-  if ((g_bn_fuse_bwd & 4) && mat && c.act == 1 && !sync_on(c) && y.bst_part_e != nullptr) {
-    const esc_bn_bwd_fused f1 = bn_fused(y.Yz, H, y.zb1, 1);
-    const esc_bn_bwd_next n0{y.bst_part_e, y.Zb, H, y.zb0.mean, y.zb0.invstd, y.zb0.scale, y.zb0.shift, 1};
-    const float* slab_probe = ct.jobs ? *ct.slab_cursor : y.slabs;
-    if (esc_linear_bwd_both_bn_ok(y.dZemb, H, &f1, y.A0, H, m->zlin.w, H, E, H, H, y.dAz, H, slab_probe, &n0)) {
-      ESC_TRY(esc_bn_bwd_coef(y.Yz, H, nullptr, 0, y.dZemb, H, E, H, y.zb1.mean, y.zb1.invstd, m->zbn1.gamma, m->zbn1.beta, 1, y.zb1.coef,
-                              m->zbn1.dgamma, m->zbn1.dbeta, ce.y.bn_scratch, ce.s));
-      ESC_TRY(linear_backward_bn(ct, y.dZemb, H, f1, y.A0, H, nullptr, nullptr, m->zlin, E, y.dAz, H, 0, &n0));
-      ESC_TRY(esc_bn_bwd_coef_from_partials(y.bst_part_e, cdiv(E, esc_linear_bwd_bn_block_rows(E, H, H)), E, H, y.zb0.coef, m->zbn0.dgamma,
-                                            m->zbn0.dbeta, ce.s));
-      ESC_TRY(esc_bn_bwd_apply(y.Zb, H, nullptr, 0, y.dAz, H, E, H, y.zb0.mean, y.zb0.invstd, m->zbn0.gamma, m->zbn0.beta, 1, y.zb0.coef, y.dAz, H, ce.s));
-      goto tail_bag;
-    }
-  }
+  ct.on_edge_stream = false;          // the tail is the critical path: its GEMM runs at full occupancy (no LdsFloorGuard cap)
   ESC_TRY(bn_backward(ce, y.Yz, H, nullptr, 0, y.dZemb, H, E, y.zb1, m->zbn1, y.dZemb, H, ce.y.bn_scratch));
-  if (mat) {
-    ESC_TRY(linear_backward(ct, y.dZemb, H, y.A0, H, nullptr, nullptr, m->zlin, E, y.dAz, H, 0));
-  } else {
-    ESC_TRY(linear_backward(ct, y.dZemb, H, y.Zb, H, y.zb0.scale, y.zb0.shift, m->zlin, E, y.dAz, H, 0));
-  }
+  ESC_TRY(linear_backward(ct, y.dZemb, H, y.A0, H, nullptr, nullptr, m->zlin, E, y.dAz, H, 0));
   ESC_TRY(bn_backward(ce, y.Zb, H, nullptr, 0, y.dAz, H, E, y.zb0, m->zbn0, y.dAz, H, ce.y.bn_scratch));
-tail_bag:
   ESC_TRY(esc_bag_bwd_table_rows(y.dAz, H, H, b->col_ptr, b->col_row, b->col_val, b->col_col, y.Z, m->z_rows, E,
                                  1, m->dz_table, y.bag_scratch, ce.s));
   mark(PH_NODE_BWD_DONE, c.s);
   mark(PH_EDGE_BWD_DONE, ce.s);
   // node-side reductions first (with an edge stream they overlap its tail), then join, then the edge-side ones
   if (!eps_jobs.empty()) ESC_TRY(esc_reduce_sum_jobs(eps_jobs.data(), (int)eps_jobs.size(), c.s));
-  if (c.wgrad) ESC_TRY(chain(ws.joined, ws.stream, (hipStream_t)c.s));          // the slabs of the dW tiles that ran behind the chain
   if (c.jobs && !c.jobs->empty()) ESC_TRY(esc_slab_reduce_jobs(c.jobs->data(), (int)c.jobs->size(), c.s));
-  if (ss.ok && hipStreamWaitEvent((hipStream_t)c.s, ss.join_b, 0) != hipSuccess) {
-    set_error("esc_engine: side-stream join failed");
-    return ESC_ELAUNCH;
-  }
   if (es.ok) {
     if (hipEventRecord(es.joined, es.stream) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
     Pending local;
@@ -1079,8 +800,8 @@ static Layout plan_layout_zinc(const esc_zinc_gin_t* m, int64_t N, int64_t E, in
   y.X0 = a.take(N * C0);
   y.Zb = a.take(E * H); y.Yz = a.take(E * H); y.zb0 = take_bn(a, H); y.zb1 = take_bn(a, H);
   y.A0 = a.take(E * H); y.Zcat = a.take(E * y.Wz);
-  const int64_t lb = C0 == H ? 0 : 1, nb = L - lb;            // the H-wide edge terms: layers lb .. L-1, batched into one GEMM (g_edge_batched)
-  const bool batched = g_edge_batched && nb >= 2;
+  const int64_t lb = C0 == H ? 0 : 1, nb = L - lb;            // the H-wide edge terms: layers lb .. L-1, batched into one GEMM (see plan_layout())
+  const bool batched = nb >= 2;
   if (batched) { y.e_cat = a.take(E * nb * H); y.w_cat = a.take(nb * H * y.Wz + nb * H); }
   for (int l = 0; l < L; ++l) {
     const int64_t C = l == 0 ? C0 : H;
@@ -1098,7 +819,6 @@ static Layout plan_layout_zinc(const esc_zinc_gin_t* m, int64_t N, int64_t E, in
   y.pred = a.take(R); y.dpred = a.take(R);
   y.bn_scratch = a.take(esc_bn_scratch(H));
   y.col_stats = a.take(2 * ((E > N ? E : N) / 32 + 1) * H);
-  y.col_stats_b = a.take(2 * (N / 32 + 1) * H);
   y.bn_scratch_e = a.take(esc_bn_scratch(H));
   y.col_stats_e = a.take(2 * (E / 32 + 1) * H);
   if (train) {
@@ -1152,7 +872,7 @@ static int forward_zinc(const ZincCtx& z) {
   ESC_TRY(esc_affine_act(y.Yz, H, E, H, y.zb1.scale, y.zb1.shift, act, y.Zcat, Wz, ce.s));
   ESC_TRY(esc_embed_fwd(m->edge_emb.w, m->edge_emb.rows, D, b->edge_type, E, y.Zcat + H, Wz, nullptr, ce.s));
   auto edge_term = [&](int l) -> int {
-    const LdsFloorGuard cap(ce.on_edge_stream && g_cap_forward);
+    const LdsFloorGuard cap(ce.on_edge_stream);
     const esc_conv_t& cv = m->conv[l];
     const int64_t C = l == 0 ? C0 : H;
     ESC_TRY(esc_linear_fwd(y.Zcat, Wz, cv.lin.w, Wz, cv.lin.b, nullptr, nullptr, E, C, Wz, y.e[l], y.ld_e[l], nullptr, ce.s));
@@ -1173,13 +893,13 @@ static int forward_zinc(const ZincCtx& z) {
     ESC_TRY(esc_table_pack(&tw, Wz, y.w_cat, ce.s));
     ESC_TRY(esc_table_pack(&tb, H, y.w_cat + (int64_t)nb * H * Wz, ce.s));
     {
-      const LdsFloorGuard cap(ce.on_edge_stream && g_cap_forward);
+      const LdsFloorGuard cap(ce.on_edge_stream);
       ESC_TRY(esc_linear_fwd(y.Zcat, Wz, y.w_cat, Wz, y.w_cat + (int64_t)nb * H * Wz, nullptr, nullptr, E, nb * H, Wz, y.e_cat, nb * H, nullptr, ce.s));
     }
     for (int l = lb; l < (int)L; ++l)
       if (es.ok && hipEventRecord(es.e_ready[l], es.stream) != hipSuccess) { set_error("esc_zinc: stream event failed"); return ESC_ELAUNCH; }
   }
-  const int ahead = batched ? 0 : (es.ok ? g_edge_ahead : (int)L);
+  const int ahead = batched ? 0 : (es.ok ? 1 : (int)L);
   for (int l = 0; l < (int)L && l < ahead; ++l) ESC_TRY(edge_term(l));
   // ---- node pipeline: x = node_type_embedding(data.x) (:581)
   ESC_TRY(esc_embed_fwd(m->node_emb.w, m->node_emb.rows, C0, b->node_type, N, y.X0, C0, nullptr, c.s));
@@ -1249,29 +969,9 @@ static int backward_zinc(const ZincCtx& z) {
   ESC_TRY(esc_embed_bwd(y.dX0, C0, b->node_type, N, m->node_emb.rows, C0, m->node_emb.dw, c.s));
   // edge pipeline tail: edge-type table, z_embedding, bag
   ESC_TRY(esc_embed_bwd(y.dZcat + H, Wz, b->edge_type, E, m->edge_emb.rows, D, m->edge_emb.dw, ce.s));
-  // z_embedding's two BatchNorms ride on its Linear's backward when the fused kernels serve the shape (molecule batches: a few
-  // thousand edge rows, the node-sized tile): coef, dX+dW (apply on the staged dY, the first BatchNorm's sums from the dX epilogue),
-  // finalize, apply — instead of 3 + 1 + 3 launches
-  bool z_fused = false;
-  if ((g_bn_fuse_bwd & 3) == 3 && g_bn_fuse_elu && !sync_on(c) && y.bst_part != nullptr) {
-    const esc_bn_bwd_fused f1 = bn_fused(y.Yz, H, y.zb1, c.act);
-    const esc_bn_bwd_next n0{y.bst_part, y.Zb, H, y.zb0.mean, y.zb0.invstd, y.zb0.scale, y.zb0.shift, c.act};
-    const float* slab_probe = ce.jobs ? *ce.slab_cursor : y.slabs;
-    if (esc_linear_bwd_both_bn_ok(y.dZcat, Wz, &f1, y.A0, H, m->zlin.w, H, E, H, H, y.dAz, H, slab_probe, &n0)) {
-      ESC_TRY(esc_bn_bwd_coef(y.Yz, H, nullptr, 0, y.dZcat, Wz, E, H, y.zb1.mean, y.zb1.invstd, m->zbn1.gamma, m->zbn1.beta, c.act, y.zb1.coef,
-                              m->zbn1.dgamma, m->zbn1.dbeta, ce.y.bn_scratch, ce.s));
-      ESC_TRY(linear_backward_bn(ce, y.dZcat, Wz, f1, y.A0, H, nullptr, nullptr, m->zlin, E, y.dAz, H, 0, &n0));
-      ESC_TRY(esc_bn_bwd_coef_from_partials(y.bst_part, cdiv(E, esc_linear_bwd_bn_block_rows(E, H, H)), E, H, y.zb0.coef, m->zbn0.dgamma,
-                                            m->zbn0.dbeta, ce.s));
-      ESC_TRY(esc_bn_bwd_apply(y.Zb, H, nullptr, 0, y.dAz, H, E, H, y.zb0.mean, y.zb0.invstd, m->zbn0.gamma, m->zbn0.beta, c.act, y.zb0.coef, y.dAz, H, ce.s));
-      z_fused = true;
-    }
-  }
-  if (!z_fused) {
-    ESC_TRY(bn_backward(ce, y.Yz, H, y.Zcat, Wz, y.dZcat, Wz, E, y.zb1, m->zbn1, y.dZemb, H, ce.y.bn_scratch));
-    ESC_TRY(linear_backward(ce, y.dZemb, H, y.A0, H, nullptr, nullptr, m->zlin, E, y.dAz, H, 0));
-    ESC_TRY(bn_backward(ce, y.Zb, H, y.A0, H, y.dAz, H, E, y.zb0, m->zbn0, y.dAz, H, ce.y.bn_scratch));
-  }
+  ESC_TRY(bn_backward(ce, y.Yz, H, y.Zcat, Wz, y.dZcat, Wz, E, y.zb1, m->zbn1, y.dZemb, H, ce.y.bn_scratch));
+  ESC_TRY(linear_backward(ce, y.dZemb, H, y.A0, H, nullptr, nullptr, m->zlin, E, y.dAz, H, 0));
+  ESC_TRY(bn_backward(ce, y.Zb, H, y.A0, H, y.dAz, H, E, y.zb0, m->zbn0, y.dAz, H, ce.y.bn_scratch));
   ESC_TRY(esc_bag_bwd_table_rows(y.dAz, H, H, b->col_ptr, b->col_row, b->col_val, b->col_col, y.Z, m->z_rows, E, 1,
                                  m->dz_table, y.bag_scratch, ce.s));
   if (es.ok && !edge_jobs.empty()) ESC_TRY(esc_slab_reduce_jobs(edge_jobs.data(), (int)edge_jobs.size(), es.stream));
@@ -1309,7 +1009,7 @@ static ZincCtx make_zinc(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, floa
 // materialised activations, dropout with its own counter-based stream.
 // =====================================================================================================================
 struct OgbLayer {
-  float *hin, *e, *agg, *Y0, *A1, *hc, *hb;       // hin = h + vn[batch]; Y0/A1 [N,2H]; hc pre-BN; hb after BN(+ReLU)
+  float *hin, *e, *agg, *Y0, *hc, *hb;            // hin = h + vn[batch]; Y0 [N,2H]; hc pre-BN; hb after BN(+ReLU)
   BnWs b0, bn;
   unsigned char* mask_h;
   float *tmp, *V0, *VA, *V1, *VB, *vn;             // virtual-node update (rows G); vn = the embedding ENTERING layer l
@@ -1323,7 +1023,6 @@ struct OgbLayout {
   float *Zb, *Zd, *A0, *Yz, *Yzd, *Zemb; BnWs zb0, zb1;
   unsigned char *mask_z0, *mask_z1;
   OgbLayer l[ESC_MAX_LAYERS];
-  float *e_cat, *w_cat; int64_t ld_e;     // g_edge_batched: every layer's edge term is a column block of ONE [E, L*H] matrix
   float *h[ESC_MAX_LAYERS + 1];
   float *pooled, *logits, *dlogits;
   // backward
@@ -1349,17 +1048,13 @@ static OgbLayout plan_layout_ogb(const esc_ogb_gnn_t* m, int64_t N, int64_t E, i
   y.Yz = a.take(E * H); y.Yzd = drop ? a.take(E * H) : y.Yz; y.Zemb = a.take(E * H);
   y.zb0 = take_bn(a, H); y.zb1 = take_bn(a, H);
   if (drop) { y.mask_z0 = take_bytes(a, E * H); y.mask_z1 = take_bytes(a, E * H); }
-  // see plan_layout(): the edge terms of layers 1 .. L-1 from one GEMM (layer 0's keeps its own launch: the first aggregate waits for it)
-  const bool batched = g_edge_batched >= 2 && L >= 3 && H % 4 == 0;
-  y.ld_e = batched ? (L - 1) * H : H;
-  if (batched) { y.e_cat = a.take(E * (L - 1) * H); y.w_cat = a.take((L - 1) * H * H + (L - 1) * H); }
   for (int l = 0; l < L; ++l) {
     OgbLayer& q = y.l[l];
     q.vn = a.take(G * H);
     q.hin = a.take(N * H);
-    q.e = (batched && l >= 1) ? y.e_cat + (int64_t)(l - 1) * H : a.take(E * H);
+    q.e = a.take(E * H);
     q.agg = a.take(N * H);
-    q.Y0 = a.take(N * H2); q.A1 = a.take(N * H2); q.hc = a.take(N * H); q.hb = nullptr;         // (hb is never materialised: BN -> ReLU -> dropout in one pass)
+    q.Y0 = a.take(N * H2); q.hc = a.take(N * H); q.hb = nullptr;         // (hb is never materialised: BN -> ReLU -> dropout in one pass)
     q.b0 = take_bn(a, H2); q.bn = take_bn(a, H);
     y.h[l + 1] = a.take(N * H);
     if (drop) q.mask_h = take_bytes(a, N * H);
@@ -1444,35 +1139,15 @@ static int forward_ogb(const OgbCtx& z) {
   ESC_TRY(esc_affine_act(y.Yzd, H, E, H, y.zb1.scale, y.zb1.shift, 1, y.Zemb, H, ce.s));
   // edge term of layer l = BondEncoder(edge_attr) + edge_encoder_pos(z_emb) (:352)
   auto edge_term = [&](int l) -> int {
-    const LdsFloorGuard cap(ce.on_edge_stream && g_cap_forward);
+    const LdsFloorGuard cap(ce.on_edge_stream);
     const esc_ogb_layer_t& q = m->layer[l];
-    const int64_t ld = (l == 0 || y.ld_e == H) ? H : y.ld_e;
-    ESC_TRY(esc_linear_fwd(y.Zemb, H, q.pos.w, H, q.pos.b, nullptr, nullptr, E, H, H, y.l[l].e, ld, nullptr, ce.s));
-    ESC_TRY(esc_bag_fwd_rows(y.Tcat + q.bond_row0 * H, m->bond_rows, H, b->bonds.row_ptr, b->bonds.idx, b->bonds.ones, E, y.l[l].e, ld, 1, nullptr, ce.s));
+    ESC_TRY(esc_linear_fwd(y.Zemb, H, q.pos.w, H, q.pos.b, nullptr, nullptr, E, H, H, y.l[l].e, H, nullptr, ce.s));
+    ESC_TRY(esc_bag_fwd_rows(y.Tcat + q.bond_row0 * H, m->bond_rows, H, b->bonds.row_ptr, b->bonds.idx, b->bonds.ones, E, y.l[l].e, H, 1, nullptr, ce.s));
     if (es.ok && hipEventRecord(es.e_ready[l], es.stream) != hipSuccess) { set_error("esc_ogb: stream event failed"); return ESC_ELAUNCH; }
     return ESC_OK;
   };
-  const bool batched = y.ld_e != H;
-  if (batched) {                        // layer 0's edge term first, then edge_encoder_pos of layers 1 .. L-1 in one launch + their bond sums
-    ESC_TRY(edge_term(0));
-    const int nb = (int)L - 1;
-    esc_table_list tl{};
-    tl.count = 2 * nb;
-    for (int l = 1; l < (int)L; ++l) {
-      tl.rows[l - 1] = (int32_t)H; tl.w[l - 1] = m->layer[l].pos.w;
-      tl.rows[nb + l - 1] = 1; tl.w[nb + l - 1] = m->layer[l].pos.b;
-    }
-    ESC_TRY(esc_table_pack(&tl, H, y.w_cat, ce.s));
-    {
-      const LdsFloorGuard cap(ce.on_edge_stream && g_cap_forward);
-      ESC_TRY(esc_linear_fwd(y.Zemb, H, y.w_cat, H, y.w_cat + (int64_t)nb * H * H, nullptr, nullptr, E, nb * H, H, y.e_cat, nb * H, nullptr, ce.s));
-    }
-    for (int l = 1; l < (int)L; ++l) {
-      ESC_TRY(esc_bag_fwd_rows(y.Tcat + m->layer[l].bond_row0 * H, m->bond_rows, H, b->bonds.row_ptr, b->bonds.idx, b->bonds.ones, E, y.l[l].e, y.ld_e, 1, nullptr, ce.s));
-      if (es.ok && hipEventRecord(es.e_ready[l], es.stream) != hipSuccess) { set_error("esc_ogb: stream event failed"); return ESC_ELAUNCH; }
-    }
-  }
-  const int ahead = batched ? 0 : (es.ok ? g_edge_ahead : (int)L);
+  // (per-layer launches, one layer ahead of the node chain as in forward(); one stream: all of them up front, in layer order)
+  const int ahead = es.ok ? 1 : (int)L;
   for (int l = 0; l < (int)L && l < ahead; ++l) ESC_TRY(edge_term(l));
   // ---- node pipeline: h0 = AtomEncoder(x) (:264-282); vn_0 = virtualnode_embedding(0) per graph (:701)
   ESC_TRY(esc_bag_fwd_rows(y.Tcat, m->atom_rows, H, b->atoms.row_ptr, b->atoms.idx, b->atoms.ones, N, y.h0, H, 0, nullptr, c.s));
@@ -1482,18 +1157,14 @@ static int forward_ogb(const OgbCtx& z) {
     const OgbLayer& w = y.l[l];
     ESC_TRY(esc_segment_broadcast_add(y.h[l], H, w.vn, H, b->graph_ptr, G, N, H, w.hin, H, c.s));                 // :739
     if (es.ok && hipStreamWaitEvent((hipStream_t)c.s, es.e_ready[l], 0) != hipSuccess) { set_error("esc_ogb: stream event failed"); return ESC_ELAUNCH; }
-    ESC_TRY(esc_gine_aggregate_fwd(w.hin, H, w.e, l == 0 ? H : y.ld_e, b->in_ptr, b->in_edge, b->in_src, q.eps, N, H, w.agg, H, c.s));
-    if (!batched && es.ok && l + ahead < (int)L) {
+    ESC_TRY(esc_gine_aggregate_fwd(w.hin, H, w.e, H, b->in_ptr, b->in_edge, b->in_src, q.eps, N, H, w.agg, H, c.s));
+    if (es.ok && l + ahead < (int)L) {
       ESC_TRY(chain(es.agg_done[l], (hipStream_t)c.s, es.stream));
       ESC_TRY(edge_term(l + ahead));
     }
     ESC_TRY(linear_bn(c, w.agg, H, q.lin0, nullptr, nullptr, N, w.Y0, q.bn0, w.b0));
-    if (g_ogb_prologue) {                       // relu(bn(Y0)) applied to the staged operand of lin1: A1 is never written
-      ESC_TRY(linear_bn(c, w.Y0, H2, q.lin1, w.b0.scale, w.b0.shift, N, w.hc, q.bn, w.bn));
-    } else {
-      ESC_TRY(esc_affine_act(w.Y0, H2, N, H2, w.b0.scale, w.b0.shift, 1, w.A1, H2, c.s));
-      ESC_TRY(linear_bn(c, w.A1, H2, q.lin1, nullptr, nullptr, N, w.hc, q.bn, w.bn));                              // + batch_norms[l] statistics
-    }
+    // relu(bn(Y0)) is applied to the staged operand of lin1 (the hidden activation is never written); + batch_norms[l] statistics
+    ESC_TRY(linear_bn(c, w.Y0, H2, q.lin1, w.b0.scale, w.b0.shift, N, w.hc, q.bn, w.bn));
     // batch_norm -> ReLU (not after the last layer) -> dropout (+ residual), :744-755, as one pass over hc
     ESC_TRY(esc_affine_act_dropout_fwd(w.hc, H, N, H, w.bn.scale, w.bn.shift, l == (int)L - 1 ? 0 : 1, p, drop_seed(z, 2 + 2 * l),
                                        m->residual ? w.hin : nullptr, H, y.h[l + 1], H, w.mask_h, c.s));
@@ -1544,8 +1215,8 @@ static int backward_ogb(const OgbCtx& z) {
     ESC_TRY(bn_backward_drop(last ? c0 : c, w.hc, H, dH, H, N, w.bn, q.bn, w.mask_h, p, 0, y.dT, H, y.bn_scratch));
     // The hidden BatchNorm's backward loses its partial-sum pass (2H-wide rows: the most expensive of its three launches): the
     // column sums come out of lin1's dX epilogue (esc_linear_bwd_both_bn with bn == NULL), then finalize + apply
-    bool hidden_done = false, hidden_fused = false;
-    if (g_ogb_prologue && (g_bn_fuse_bwd & 2) && !sync_on(c) && y.bst_part != nullptr) {
+    bool hidden_done = false;
+    if (kBnBwdSumsFromDx && !sync_on(c) && y.bst_part != nullptr) {
       const esc_bn_bwd_next n0{y.bst_part, w.Y0, H2, w.b0.mean, w.b0.invstd, w.b0.scale, w.b0.shift, 1};
       const float* slab_probe = c.jobs ? *c.slab_cursor : c.y.slabs;
       if (esc_linear_bwd_both_bn_ok(y.dT, H, nullptr, w.Y0, H2, q.lin1.w, H2, N, H, H2, y.dA1, H2, slab_probe, &n0)) {
@@ -1561,27 +1232,15 @@ static int backward_ogb(const OgbCtx& z) {
                                        q.lin1.db, slabs, job, &n0, c.s));
         ESC_TRY(esc_bn_bwd_coef_from_partials(y.bst_part, cdiv(N, esc_linear_bwd_bn_block_rows(N, H, H2)), N, H2, w.b0.coef, q.bn0.dgamma,
                                               q.bn0.dbeta, c.s));
-        // the apply of the hidden BatchNorm's backward rides on lin0's dX+dW launch (operand staging) when the fused kernels serve the shape
-        // (ESC_OGB_BNB=1; measured below)
-        {
-          const esc_bn_bwd_fused f0 = bn_fused(w.Y0, H2, w.b0, 1);
-          const float* probe = c.jobs ? *c.slab_cursor : c.y.slabs;
-          if (g_ogb_bnb && esc_linear_bwd_both_bn_ok(y.dA1, H2, &f0, w.agg, H, q.lin0.w, H, N, H2, H, y.dagg, H, probe, nullptr)) {
-            ESC_TRY(linear_backward_bn(c, y.dA1, H2, f0, w.agg, H, nullptr, nullptr, q.lin0, N, y.dagg, H, 0, nullptr));
-            hidden_fused = true;
-          } else {
-            ESC_TRY(esc_bn_bwd_apply(w.Y0, H2, nullptr, 0, y.dA1, H2, N, H2, w.b0.mean, w.b0.invstd, q.bn0.gamma, q.bn0.beta, 1, w.b0.coef, y.dA1, H2, c.s));
-          }
-        }
+        ESC_TRY(esc_bn_bwd_apply(w.Y0, H2, nullptr, 0, y.dA1, H2, N, H2, w.b0.mean, w.b0.invstd, q.bn0.gamma, q.bn0.beta, 1, w.b0.coef, y.dA1, H2, c.s));
         hidden_done = true;
       }
     }
     if (!hidden_done) {
-      if (g_ogb_prologue) ESC_TRY(linear_backward(c, y.dT, H, w.Y0, H2, w.b0.scale, w.b0.shift, q.lin1, N, y.dA1, H2, 0));
-      else                ESC_TRY(linear_backward(c, y.dT, H, w.A1, H2, nullptr, nullptr, q.lin1, N, y.dA1, H2, 0));
-      ESC_TRY(bn_backward(c, w.Y0, H2, nullptr, 0, y.dA1, H2, N, w.b0, q.bn0, y.dA1, H2, y.bn_scratch, H2));      // (ReLU mask from the pre-BatchNorm rows: A1 is not re-read)
+      ESC_TRY(linear_backward(c, y.dT, H, w.Y0, H2, w.b0.scale, w.b0.shift, q.lin1, N, y.dA1, H2, 0));
+      ESC_TRY(bn_backward(c, w.Y0, H2, nullptr, 0, y.dA1, H2, N, w.b0, q.bn0, y.dA1, H2, y.bn_scratch, H2));      // (ReLU mask from the pre-BatchNorm rows)
     }
-    if (!hidden_fused) ESC_TRY(linear_backward(c, y.dA1, H2, w.agg, H, nullptr, nullptr, q.lin0, N, y.dagg, H, 0));
+    ESC_TRY(linear_backward(c, y.dA1, H2, w.agg, H, nullptr, nullptr, q.lin0, N, y.dagg, H, 0));
     // virtual-node update of this layer: vn_{l+1} = dropout(mlp(add_pool(hin) + vn_l)) (+ vn_l)
     bool have_dhin = false;
     if (!last) {
@@ -1597,33 +1256,19 @@ static int backward_ogb(const OgbCtx& z) {
       float* t = dH; dH = dHin; dHin = t;          // d hin starts as d h_{l+1}: accumulate into that buffer
       have_dhin = true;
     }
-    ESC_TRY(esc_gine_aggregate_bwd(w.hin, H, w.e, l == 0 ? H : y.ld_e, y.dagg, H, b->out_ptr, b->out_edge, b->out_dst, q.eps, N, H, w.d_e, H,
+    ESC_TRY(esc_gine_aggregate_bwd(w.hin, H, w.e, H, y.dagg, H, b->out_ptr, b->out_edge, b->out_dst, q.eps, N, H, w.d_e, H,
                                    dHin, H, have_dhin ? 1 : 0, y.deps_part + (int64_t)l * 2 * N, c.s));
     eps_jobs.push_back(esc_sum_job{y.deps_part + (int64_t)l * 2 * N, N * esc_gine_aggregate_bwd_deps_slots(H), q.deps});
     // edge term: bond tables and edge_encoder_pos — edge stream
     if (es.ok) ESC_TRY(chain(es.de_ready[l], (hipStream_t)c.s, es.stream));
     // bond tables: on the edge stream — except for the LAST layer processed (l == 0), whose edge-term backward opens the tail of
     // the step: there the table gradient runs on the node stream (d_e is its own product; it has the atom tables' scratch to
-    // itself until the encoders below) and the edge stream goes straight to the Linear that completes d(z_emb)
-    const bool bonds_on_node = l == 0 && es.ok && g_ogb_bonds_on_node;
+    // itself until the encoders below) and the edge stream goes straight to the Linear that completes d(z_emb): 4.34 -> 4.31 ms/step
+    const bool bonds_on_node = l == 0 && es.ok;
     ESC_TRY(esc_bag_bwd_table(w.d_e, H, H, b->bonds.col_ptr, b->bonds.c_row, b->bonds.ones, b->bonds.c_col, b->bonds.n_entries,
                               m->bond_rows, y.dTcat + q.bond_row0 * H, bonds_on_node ? y.emb_scratch_n : y.emb_scratch,
                               bonds_on_node ? c.s : ce.s));
-    if (l == 0 && es.ok && c.jobs && g_ogb_split_tail) {
-      // the LAST edge-term backward starts the tail of the step: only its input gradient (which completes d(z_emb)) stays on
-      // the edge stream; the weight gradient runs on the node stream, which has little left to do (d_e is its own product)
-      {
-        const LdsFloorGuard cap(true);
-        ESC_TRY(esc_linear_bwd_input(w.d_e, H, q.pos.w, H, E, H, H, y.dZemb, H, last ? 0 : 1, es.stream));
-      }
-      float* slabs = *c.slab_cursor;
-      *c.slab_cursor += (esc_linear_bwd_weight_scratch(E, H, H) + 63) & ~63LL;
-      c.jobs->emplace_back();
-      ESC_TRY(esc_linear_bwd_both_deferred(w.d_e, H, y.Zemb, H, nullptr, nullptr, q.pos.w, H, E, H, H, nullptr, 0, 0, q.pos.dw, H, q.pos.db,
-                                           slabs, &c.jobs->back(), c.s));
-    } else {
-      ESC_TRY(linear_backward(ce, w.d_e, H, y.Zemb, H, nullptr, nullptr, q.pos, E, y.dZemb, H, last ? 0 : 1));
-    }
+    ESC_TRY(linear_backward(ce, w.d_e, H, y.Zemb, H, nullptr, nullptr, q.pos, E, y.dZemb, H, last ? 0 : 1));
     // d hin_l is complete: d h_l = d hin_l, d vn_l += add_pool(d hin_l)
     ESC_TRY(esc_segment_pool_fwd(dHin, H, b->graph_ptr, G, H, 0, y.poolG, H, c.s));
     ESC_TRY(esc_dropout_bwd(y.poolG, H, G, H, 0.f, nullptr, last ? nullptr : dvn_cur, H, dvn_cur, H, c.s));
@@ -1637,20 +1282,7 @@ static int backward_ogb(const OgbCtx& z) {
   ESC_TRY(esc_embed_bwd(dvn_next, H, b->zero_idx, G, 1, H, m->vn_dw, c.s));
   // z_embedding + bag: the tail of the edge pipeline (d(z_emb) is complete in edge-stream order)
   ESC_TRY(bn_backward_drop(ce, y.Yzd, H, y.dZemb, H, E, y.zb1, m->zbn1, y.mask_z1, p, 1, y.dYz, H, ce.y.bn_scratch));
-  if (es.ok && c.jobs && g_ogb_split_tail) {      // same split for z_embedding's Linear: dX continues the tail, dW on the node stream
-    ESC_TRY(chain(es.tail_dz, es.stream, (hipStream_t)c.s));           // d(Yz) is complete here in edge-stream order
-    {
-      const LdsFloorGuard cap(true);
-      ESC_TRY(esc_linear_bwd_input(y.dYz, H, m->zlin.w, H, E, H, H, y.dA0, H, 0, es.stream));
-    }
-    float* slabs = *c.slab_cursor;
-    *c.slab_cursor += (esc_linear_bwd_weight_scratch(E, H, H) + 63) & ~63LL;
-    c.jobs->emplace_back();
-    ESC_TRY(esc_linear_bwd_both_deferred(y.dYz, H, y.A0, H, nullptr, nullptr, m->zlin.w, H, E, H, H, nullptr, 0, 0, m->zlin.dw, H, m->zlin.db,
-                                         slabs, &c.jobs->back(), c.s));
-  } else {
-    ESC_TRY(linear_backward(ce, y.dYz, H, y.A0, H, nullptr, nullptr, m->zlin, E, y.dA0, H, 0));
-  }
+  ESC_TRY(linear_backward(ce, y.dYz, H, y.A0, H, nullptr, nullptr, m->zlin, E, y.dA0, H, 0));
   ESC_TRY(bn_backward_drop(ce, y.Zd, H, y.dA0, H, E, y.zb0, m->zbn0, y.mask_z0, p, 1, y.dA0, H, ce.y.bn_scratch));
   ESC_TRY(esc_bag_bwd_table_rows(y.dA0, H, H, b->col_ptr, b->col_row, b->col_val, b->col_col, y.Z, m->z_rows, E, 1,
                                  m->dz_table, y.bag_scratch, ce.s));
@@ -1733,13 +1365,10 @@ int esc_engine_set_two_stream_min_edges(int64_t edges) {
   return ESC_OK;
 }
 
+/* bit 1: the edge pipeline on a second stream; bit 6: every cross-stream dependency an event record (see ArmedEvent).  The other
+ * bits selected schedules that have been retired (DESIGN.md *Retired step-engine switches*) and are ignored. */
 int esc_engine_set_side_stream(int on) {
   g_use_edge_stream = (on & 2) != 0;
-  g_cap_forward = (on & 8) == 0;
-  g_cap_tail = (on & 16) != 0;
-  g_edge_ahead = (on & 32) ? 2 : 1;
-  g_edge_priority_low = (on & 4) == 0;      // bit 2: give the edge stream the HIGHEST priority instead (experiments)
-  g_use_side_stream = (on & 1) != 0;
   g_plain_events = (on & 64) != 0;
   return ESC_OK;
 }
@@ -1782,19 +1411,6 @@ int esc_engine_set_collective(esc_allreduce_fn fn, void* user, int rank, int wor
   return ESC_OK;
 }
 
-int esc_engine_set_gemm_stats(int on) {
-  g_fuse_finalize = (on & 2) == 0;       // bit 1: keep the statistics epilogue but finalize in a separate launch
-  g_fuse_node_act = (on & 16) == 0;      // bit 4: materialise the node MLPs' output activations again (one more launch per layer)
-  g_fold = (on & 8) ? 2 : ((on & 4) != 0);   // bit 2: node-sized BatchNorms are merged by their consumers; bit 3: only an MLP's last one
-  g_gemm_stats = (on & 1) != 0;
-  return ESC_OK;
-}
-
-int esc_engine_set_materialise_edge_act(int on) {
-  g_materialise_edge_act = on != 0;
-  return ESC_OK;
-}
-
 int64_t esc_engine_workspace_floats(const esc_nested_gin_t* m, int64_t N, int64_t E, int64_t Z) {
   if (!m || N < 0 || E < 0 || Z < 0) return -1;
   return plan_layout(m, N, E, Z, nullptr, true).total;
@@ -1827,7 +1443,7 @@ static int train_step_impl(const esc_nested_gin_t* m, const esc_batch_t* b, floa
   arm_jobs(c, jobs, c.y.slabs, 3 * m->num_layers + 7);
   const int64_t denom = loss_denom > 0 ? loss_denom : b->N;
   EdgeStream& es = edge_stream_for(b->E);
-  const bool head_l1 = g_l1_head && es.ok && m->hidden <= 1024 &&
+  const bool head_l1 = es.ok && m->hidden <= 1024 &&
                        esc_linear_fwd_l1_ok(c.y.Yl, m->hidden, m->lin2.w, m->hidden, c.y.bl.scale, c.y.bl.shift) != 0;
   if (head_l1) { c.l1_target = b->y; c.l1_denom = denom; }
   ESC_TRY(forward(c));

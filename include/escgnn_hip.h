@@ -325,15 +325,6 @@ int esc_linear_bwd_both_bn_ok(const float* dOut, int64_t ld_dout, const esc_bn_b
                               const float* slabs, const esc_bn_bwd_next* next);
 int64_t esc_linear_bwd_bn_block_rows(int64_t M, int64_t N, int64_t K);
 
-/* Weight-gradient tiles on a stream of their own (thread-local setting; NULL = off, the default).
- * Inside a training step the dependent chain waits for a Linear backward's dX only (the reference's autograd has the same
- * dependency structure: torch.nn.Linear's grad_weight feeds nothing but the optimiser, run_graphcount.py:497-505).  While
- * `stream` is set, the node-sized (64-row tile) launches of esc_linear_bwd_both_deferred / esc_linear_bwd_both_bn whose slab
- * reduce is DEFERRED (job != NULL) enqueue their dW tiles on `stream`, ordered behind everything queued so far on the launch
- * stream; the dX tiles stay where they were.  The caller (a) keeps dY / X / the BatchNorm operands of such a call unchanged
- * until `stream` has drained, and (b) orders esc_slab_reduce_jobs behind `stream`.  Results are bit-identical to the single
- * launch (same tiles, same slabs, same ordered reduce).  The step engine turns it on with ESC_WGRAD_STREAM=1. */
-int esc_linear_bwd_set_wgrad_stream(void* stream);
 int esc_linear_bwd_both_bn(const float* dOut, int64_t ld_dout, const esc_bn_bwd_fused* bn, const float* X, int64_t ld_x,
                            const float* in_scale, const float* in_shift, const float* W, int64_t ld_w, int64_t M,
                            int64_t N, int64_t K, float* dX, int64_t ld_dx, int accumulate, float* dW, int64_t ld_dw,
@@ -493,11 +484,9 @@ typedef struct esc_batch_t {
   const int32_t *in_ptr, *in_edge, *in_src, *out_ptr, *out_edge, *out_dst;
   const int32_t *row_ptr, *bag_idx, *bag_val, *col_ptr, *col_row, *col_val, *col_col;
 } esc_batch_t;
-/* (bit 3: do NOT apply the knob-10 occupancy cap to the forward's edge GEMMs; bit 4: apply it also to the z_embedding GEMM
- * of the backward tail; bit 5: edge terms two layers ahead of the node chain instead of one; bit 2: edge stream at the
- * highest instead of the lowest priority — both for experiments.)
- * bit 1 (default on): the edge-sized conv.lin GEMMs of all layers run on a second HIP stream, ordered against the
- * node chain by one event per dependency; bit 0 (default off): the x_embedding branch on a further stream.  Default 2.
+/* bit 1 (default on): the edge-sized conv.lin GEMMs of all layers run on a second HIP stream, ordered against the
+ * node chain by one event per dependency.  Default 2.  Bits 0, 2, 3, 4 and 5 selected schedules that have been retired
+ * (DESIGN.md *Retired step-engine switches*): they are accepted and ignored.
  * bit 6 (value 64, default clear): how the counting engine signals a cross-stream dependency on a single kernel (the edge terms
  * e_0 and e_1 .. e_{L-1}, the head in front of the loss, d_e of every layer's aggregate backward).  Clear: the event is the stop
  * event of that kernel's launch, so nothing is queued behind the kernel on the producing stream.  Set: hipEventRecord behind the
@@ -509,12 +498,6 @@ int esc_engine_set_side_stream(int on);
  * bound on both pipelines and the cross-stream events cost more than the overlap returns (counting model, bs 16: 0.68 ms on one
  * stream, 0.84 ms on two). */
 int esc_engine_set_two_stream_min_edges(int64_t edges);
-/* 1 (default): write relu(BN(.)) of the two EDGE-sized z_embedding activations once instead of re-applying the
- * affine+ReLU prologue in every consumer GEMM; 0: fully fused (less memory, slower on MI355X r01). */
-int esc_engine_set_materialise_edge_act(int on);
-/* 1 (default): BatchNorm statistics come from the producing GEMM's epilogue (col_stats) and are merged by that
- * launch's last workgroups (esc_linear_bn_fwd); 3: same epilogue, separate finalize launch; 0: a pass over Y */
-int esc_engine_set_gemm_stats(int on);
 /* ---- SyncBN inside the step engine: BatchNorm statistics over ALL ranks of a graph-sharded step ----------
  * The library links no communication stack: the host hands the engine ONE function that sums a device buffer over the
  * ranks, in place, ordered on the given HIP stream (RCCL via torch.distributed in esc_gnn_amd/engine.py; gloo in the

@@ -112,3 +112,58 @@ def test_one_node_class_and_second_backward_refused(kind):
     pred.sum().backward(retain_graph=True)
     with pytest.raises(RuntimeError, match="workspace was released"):
         pred.sum().backward()
+
+
+@pytest.fixture
+def schedule_knobs():
+    """always back to the library's defaults, whatever the test set"""
+    from esc_gnn_amd import _native as nv
+    yield nv
+    nv.call("esc_engine_set_side_stream", 2)
+    nv.call("esc_engine_set_two_stream_min_edges", 12000)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("live,with_retired", [(2, 2 | 1 | 4 | 8 | 16 | 32), (0, 61)], ids=["two_streams", "one_stream"])
+def test_retired_setter_bits_are_inert(schedule_knobs, live, with_retired):
+    """esc_engine_set_side_stream honours bit 1 (edge stream) and bit 6 (event records) only: bits 0, 2, 3, 4 and 5 selected
+    schedules that no longer exist.  Two train_steps from the same seed with and without them: loss, predictions and every
+    parameter gradient are bitwise equal.  Smallest counting shape on which every live fusion runs: L = 3 (batched edge
+    GEMM), H = 64 (node activations applied by their consumers), batches of 3 graphs, second stream forced on."""
+    require_gpu()
+    import esc_gnn_amd as E
+    from esc_gnn_amd.datasets import build_count_dataset
+    nv = schedule_knobs
+    bs, L, H = 3, 3, 64
+    graphs = build_count_dataset(100, 2 * bs, h=3, use_rd=True, self_loop=True)
+    gen = torch.Generator().manual_seed(bs)
+    for g in graphs:
+        g.x = torch.randn(g.x.shape, generator=gen)
+        g.y = torch.randn(g.x.size(0), generator=gen)
+    store = E.DeviceGraphStore(graphs, torch.device(DEV))
+    batches = [store.collate(torch.arange(bs) + bs * i) for i in range(2)]
+
+    def run(mode):
+        nv.call("esc_engine_set_side_stream", mode)
+        nv.call("esc_engine_set_two_stream_min_edges", 0)
+        torch.manual_seed(0)
+        m = E.NestedGIN_eff(None, L, H, use_rd=True, graph_pred=False, dropout=0, edge_nest=True, use_cycle=True).to(DEV)
+        with torch.no_grad():
+            for p in m.parameters():
+                p.add_(0.01 * torch.randn_like(p))
+        eng = E.StepEngine(m.train())
+        out = []
+        for b in batches:
+            loss, pred = eng.train_step(b, return_pred=True)
+            out.append((loss.clone(), pred.clone(), [p.grad.clone() for p in m.parameters()]))
+        torch.cuda.synchronize()
+        return out
+
+    ref, got = run(live), run(with_retired)
+    for i, ((lr, pr, gr), (lg, pg, gg)) in enumerate(zip(ref, got)):
+        assert bool(torch.isfinite(lr)) and bool(torch.isfinite(pr).all()), i
+        assert len(gr) == len(gg) and any(float(g.abs().max()) > 0.0 for g in gr), i
+        assert torch.equal(lr, lg), (i, float(lr), float(lg))
+        assert torch.equal(pr, pg), (i, int((pr != pg).sum()))
+        for k, (a, c) in enumerate(zip(gr, gg)):
+            assert torch.equal(a, c), (i, k, int((a != c).sum()))
