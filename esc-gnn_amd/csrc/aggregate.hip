@@ -419,7 +419,7 @@ int esc_gine_aggregate_fwd(const float* x, int64_t ld_x, const float* e, int64_t
   ESC_REQUIRE(N >= 0 && C > 0 && ld_x >= C && (!e || ld_e >= C) && ld_out >= C, "esc_gine_aggregate_fwd: bad sizes N=%ld C=%ld", (long)N, (long)C);
   ESC_REQUIRE(N < (1LL << 31) / 64, "esc_gine_aggregate_fwd: N too large");
   if (N == 0) return ESC_OK;
-  ESC_REQUIRE(in_edge && in_src, "esc_gine_aggregate_fwd: null edge arrays");
+  // (the edge arrays may be NULL: a batch of isolated nodes has none, and a row without edges never reads them)
   hipStream_t s = (hipStream_t)stream;
   if (C >= 64) {
     const bool vec = (C % 4 == 0) && (ld_x % 4 == 0) && (!e || ld_e % 4 == 0) && (ld_out % 4 == 0) &&
@@ -453,7 +453,6 @@ int esc_gine_aggregate_bwd(const float* x, int64_t ld_x, const float* e, int64_t
               "esc_gine_aggregate_bwd: bad sizes");
   ESC_REQUIRE(N < (1LL << 31) / 64, "esc_gine_aggregate_bwd: N too large");
   if (N == 0) return ESC_OK;
-  ESC_REQUIRE(out_edge && out_dst, "esc_gine_aggregate_bwd: null edge arrays");
   hipStream_t s = (hipStream_t)stream;
   const bool vec = (C % 4 == 0) && (ld_x % 4 == 0) && (!e || ld_e % 4 == 0) && (ld_g % 4 == 0) && (!d_e || ld_de % 4 == 0) &&
                    (!dx || ld_dx % 4 == 0) && esc::aligned16(x) && (!e || esc::aligned16(e)) && esc::aligned16(g) &&
@@ -480,7 +479,6 @@ int esc_gine_aggregate_fwd_affine(const float* x, int64_t ld_x, const float* x_s
               N < (1LL << 31) / 64, "esc_gine_aggregate_fwd_affine: needs C >= 64, C and the leading dimensions multiples of 4 (N=%ld C=%ld)", (long)N, (long)C);
   ESC_REQUIRE(esc::aligned16(x) && (!e || esc::aligned16(e)) && esc::aligned16(out), "esc_gine_aggregate_fwd_affine: pointers must be 16-byte aligned");
   if (N == 0) return ESC_OK;
-  ESC_REQUIRE(in_edge && in_src, "esc_gine_aggregate_fwd_affine: null edge arrays");
   unsigned long long* span = esc::prof_span_next(ESC_K_AGG_FWD);      // non-NULL only for launches armed by esc_prof_span_arm
   if (esc::agg_split(C) == 2 && span != nullptr)
     esc::launch(ESC_K_AGG_FWD, esc::agg_fwd_wave<2, true, true>, dim3((unsigned)esc::cdiv(2 * N, 4)), dim3(256), 0, (hipStream_t)stream, x, ld_x, e, ld_e, in_ptr,
@@ -507,7 +505,6 @@ int esc_gine_aggregate_bwd_affine(const float* x, int64_t ld_x, const float* x_s
   ESC_REQUIRE(esc::aligned16(x) && (!e || esc::aligned16(e)) && esc::aligned16(g) && (!d_e || esc::aligned16(d_e)) && (!dx || esc::aligned16(dx)),
               "esc_gine_aggregate_bwd_affine: pointers must be 16-byte aligned");
   if (N == 0) return ESC_OK;
-  ESC_REQUIRE(out_edge && out_dst, "esc_gine_aggregate_bwd_affine: null edge arrays");
   if (esc_gine_aggregate_bwd_deps_slots(C) == 2)
     esc::launch(ESC_K_AGG_BWD, esc::agg_bwd_wave<2, true>, dim3((unsigned)esc::cdiv(2 * N, 4)), dim3(256), 0, (hipStream_t)stream, x, ld_x, e, ld_e, g, ld_g,
                 out_ptr, out_edge, out_dst, eps, (int)N, (int)C, d_e, ld_de, dx, ld_dx, accumulate_dx, deps_part, x_scale, x_shift, 2, (const float*)nullptr, (const float*)nullptr, (float2*)nullptr);
@@ -536,7 +533,6 @@ int esc_gine_aggregate_bwd_affine_stats(const float* x, int64_t ld_x, const floa
   ESC_REQUIRE(esc::aligned16(x) && (!e || esc::aligned16(e)) && esc::aligned16(g) && (!d_e || esc::aligned16(d_e)) && esc::aligned16(dx) && esc::aligned16(partial),
               "esc_gine_aggregate_bwd_affine_stats: pointers must be 16-byte aligned");
   if (N == 0) return ESC_OK;
-  ESC_REQUIRE(out_edge && out_dst, "esc_gine_aggregate_bwd_affine_stats: null edge arrays");
   esc::launch(ESC_K_AGG_BWD, esc::agg_bwd_wave<4, true, true>, dim3((unsigned)esc::cdiv(N, 4)), dim3(256), (size_t)4 * C * sizeof(float2), (hipStream_t)stream,
               x, ld_x, e, ld_e, g, ld_g, out_ptr, out_edge, out_dst, eps, (int)N, (int)C, d_e, ld_de, dx, ld_dx, accumulate_dx, deps_part, x_scale,
               x_shift, 1, bn_mean, bn_invstd, reinterpret_cast<float2*>(partial));
