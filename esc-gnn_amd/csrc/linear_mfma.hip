@@ -568,27 +568,6 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_bwd_dual_kernel(DualArgs a)
   }
 }
 
-// sum `splits` slabs in fixed order: out[i] = sum_s slab[s][i] for the N*K weight-gradient elements and,
-// in the same launch, the N bias-gradient partials that follow them in every slab group
-__global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restrict__ slabs, int64_t n, int splits,
-                                                          int cols, float* __restrict__ out, int64_t ld_out,
-                                                          const float* __restrict__ db_part, int rows,
-                                                          float* __restrict__ db) {
-  ESC_PRIO();
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) {
-    float s = 0.f;
-#pragma unroll 4
-    for (int q = 0; q < splits; ++q) s += slabs[(size_t)q * n + i];
-    out[(i / cols) * ld_out + (i % cols)] = s;
-  } else if (db != nullptr && i - n < rows) {
-    const int64_t r = i - n;
-    float s = 0.f;
-    for (int q = 0; q < splits; ++q) s += db_part[(size_t)q * rows + r];
-    db[r] = s;
-  }
-}
-
 // every weight gradient of a training step reduced in ONE launch (the slabs are only needed by the optimiser):
 // block b belongs to the job whose [block_start, block_start+blocks) range contains it
 struct ReduceJobs {
@@ -731,6 +710,21 @@ static void tile_dims(int id, int* bm, int* bn, int* bk) {
 }
 
 static inline bool vec_ok(const void* p, int64_t ld) { return aligned16(p) && (ld % 4 == 0); }
+
+// (mean, M2) of every output column over R-row blocks of a finished Y: the col_stats contract for the one shape class whose GEMM
+// cannot write its partials at the block height esc_linear_stats_block_rows has promised (see linear_fwd_impl)
+__global__ __launch_bounds__(256) void col_stats_rows_kernel(const float* __restrict__ Y, int64_t ldy, int M, int N, int R,
+                                                             float2* __restrict__ col_stats) {
+  const int n = blockIdx.y * 256 + threadIdx.x;
+  if (n >= N) return;
+  const int r0 = blockIdx.x * R, rows = min(R, M - r0);
+  float s1 = 0.f;
+  for (int r = 0; r < rows; ++r) s1 += Y[(size_t)(r0 + r) * ldy + n];
+  const float mean = s1 / (float)rows;
+  float m2 = 0.f;
+  for (int r = 0; r < rows; ++r) { const float d = Y[(size_t)(r0 + r) * ldy + n] - mean; m2 = fmaf(d, d, m2); }
+  col_stats[(size_t)blockIdx.x * N + n] = make_float2(mean, m2);
+}
 
 // =================================================================================================
 // Narrow-output linears (N <= 4 output features, K <= 256): lin2 (H -> 1).  On the 128x32 MFMA tile this is 19
@@ -971,7 +965,7 @@ static inline bool dma_big(int64_t M, int64_t N) {
 }
 // 300 / 600-wide layers (ogbg-mol emb_dim 300, its 2H hidden layer): a 128-row x 160-column tile (r03) pads them by 6.7 % at 2.2x the
 // arithmetic intensity of the 64x64 tile they take (128-wide tiles would pad 300 by 28 %).  Built (reduction-major tiles with
-// 640-byte rows: one DMA piece per row, 40 of 64 lanes active), correct (tests/test_hip_ops.py) and MEASURED SLOWER
+// 640-byte rows: one DMA piece per row, 40 of 64 lanes active), correct (tests/test_hip_dense_dispatch.py, in a child process) and MEASURED SLOWER
 // (profiles/r03_kernel_roofline_tile160.txt): one workgroup per CU and 157 x 2 = 314 tiles for 256 CUs leave the second round of
 // workgroups on 58 CUs — 20000x300x300 forward 60.1 us against 51.5 us on the 128x64 tile, dX+dW 117 against 108 us, the
 // config-5 step 4.34 against 4.27 ms.  OFF by default; ESC_TILE160=1 enables it for experiments.
@@ -982,7 +976,7 @@ static inline bool use160(int64_t rows, int64_t cols) {
   return on && tile160_ok(cols) && cols % 128 != 0 && cdiv(rows, 128) * cdiv(cols, 160) >= min_wgs;
 }
 static inline hipError_t dma_check(hipError_t e, const char* what) {
-  if (e != hipSuccess) set_error("%s: %s", what, hipGetErrorString(e));
+  if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); (void)hipGetLastError(); }     // (do not leave it for the next call's launch check)
   return e;
 }
 // split-M plan of the weight gradient for a BMxBN output tile: ~one workgroup per CU, splits >= 128 rows deep
@@ -1133,6 +1127,18 @@ static int linear_fwd_impl(const float* X, int64_t ld_x, const float* W, int64_t
                                              bn->invstd, bn->running_mean, bn->running_var, bn->gamma, bn->beta, bn->scale,
                                              bn->shift, stream);
     }
+    // operands the LDS-DMA tiles serve, but a prologue beyond their K limit: esc_linear_stats_block_rows (which is not told about
+    // the prologue) has promised their row blocks, the register-staged tiles below write 32-row ones — take the partials from Y
+    const int64_t block_rows = col_stats ? esc_linear_stats_block_rows(X, ld_x, W, ld_w, M, N, K) : 32;
+    if (block_rows != 32) {
+      ESC_TRY_(linear_fwd_impl(X, ld_x, W, ld_w, bias, in_scale, in_shift, M, N, K, Y, ld_y, nullptr, nullptr, stream));
+      esc::launch(ESC_K_LINEAR, col_stats_rows_kernel, dim3((unsigned)cdiv(M, block_rows), (unsigned)cdiv(N, 256)), dim3(256), 0, s,
+                  Y, ld_y, (int)M, (int)N, (int)block_rows, reinterpret_cast<float2*>(col_stats));
+      ESC_CHECK_LAUNCH("esc_linear_fwd.col_stats");
+      if (bn == nullptr) return ESC_OK;
+      return esc_bn_stats_from_partials_rows(col_stats, M, N, block_rows, bn->eps, bn->momentum, bn->mean, bn->invstd, bn->running_mean,
+                                             bn->running_var, bn->gamma, bn->beta, bn->scale, bn->shift, stream);
+    }
   }
   GemmArgs g{};
   g.A = X; g.lda = ld_x; g.B = W; g.ldb = ld_w; g.C = Y; g.ldc = ld_y; g.bias = bias;
@@ -1272,7 +1278,7 @@ int esc_linear_bwd_input(const float* dY, int64_t ld_dy, const float* W, int64_t
     ESC_CHECK_LAUNCH("esc_linear_bwd_input.narrow");
     return ESC_OK;
   }
-  if ((g_use_dma & 4) && K <= small::SMALL_MAX && N % 4 == 0 && N <= 1024 && aligned16(dY) && ld_dy % 4 == 0) {
+  if ((g_use_dma & 4) && K <= small::SMALL_MAX && N % 4 == 0 && N <= small::SMALLN_DX_MAX_N && aligned16(dY) && ld_dy % 4 == 0) {
     const size_t lds = (size_t)(32 + small::SMALL_MAX) * (N + 4) * sizeof(float);
     static size_t raised_to = 64 * 1024;
     if (dma_check(dma::raise_lds(small::smalln_dx<small::SMALL_MAX>, lds, raised_to), "esc_linear_bwd_input") != hipSuccess) return ESC_ELAUNCH;
@@ -1324,9 +1330,12 @@ static void wgrad_plan_tile(int64_t M, int64_t N, int64_t K, int bm, int bn, int
 }
 
 int64_t esc_linear_bwd_weight_scratch(int64_t M, int64_t N, int64_t K) {
-  // upper bound over every tunable plan: at most ceil(M/128) splits; the tiny-dimension kernels (linear_small.h) cut the
-  // rows finer, their slabs are a few KB each
-  if ((K <= small::SMALL_MAX) != (N <= small::SMALL_MAX)) return (cdiv(M, small::ROWS_WGRAD) + 1) * (N * K + N);
+  // upper bound over every tunable plan: at most ceil(M/128) splits; the tiny-dimension kernels (linear_small.h) and the
+  // narrow both-kernel (linear_narrow_bwd: whenever N <= NARROW_N and K <= NARROW_K, K <= 16 included) cut the rows finer,
+  // their slabs are a few KB each
+  static_assert(NARROW_ROWS == small::ROWS_WGRAD, "one promise covers both 32-row plans");
+  if ((K <= small::SMALL_MAX) != (N <= small::SMALL_MAX) || (N <= NARROW_N && K <= NARROW_K))
+    return (cdiv(M, small::ROWS_WGRAD) + 1) * (N * K + N);
   return (cdiv(M, 128) + 1) * (N * K + N);
 }
 
@@ -1345,6 +1354,15 @@ static void fill_job(esc_reduce_job* j, const float* slabs, int64_t n, int split
                      const float* db_part, int64_t rows, float* db) {
   j->slabs = slabs; j->n = n; j->splits = splits; j->cols = cols; j->dw = dW; j->ld_dw = ld_dw;
   j->db_part = db_part; j->rows = rows; j->db = db;
+}
+
+// the ordered slab reduce of ONE weight gradient at once: the one-job form of esc_slab_reduce_jobs, so that the immediate and the
+// deferred form of every backward add the slabs in the same association and give the same bits
+static int reduce_now(const float* slabs, int64_t n, int splits, int64_t cols, float* dW, int64_t ld_dw, const float* db_part,
+                      int64_t rows, float* db, void* stream) {
+  esc_reduce_job j;
+  fill_job(&j, slabs, n, splits, cols, dW, ld_dw, db_part, rows, db);
+  return esc_slab_reduce_jobs(&j, 1, stream);
 }
 
 static int weight_impl(const float* dY, int64_t ld_dy, const float* X, int64_t ld_x, const float* in_scale,
@@ -1368,10 +1386,7 @@ static int weight_impl(const float* dY, int64_t ld_dy, const float* X, int64_t l
     ESC_CHECK_LAUNCH("esc_linear_bwd_weight.small");
     const int64_t n = N * K;
     if (defer) { fill_job(defer, slabs, n, splits, K, dW, ld_dw, db_part, N, db); return ESC_OK; }
-    esc::launch(ESC_K_LINEAR, slab_reduce_kernel, dim3((unsigned)cdiv(n + (db ? N : 0), 256)), dim3(256), 0, s, slabs, n,
-                splits, (int)K, dW, ld_dw, db_part, (int)N, db);
-    ESC_CHECK_LAUNCH("esc_linear_bwd_weight.reduce");
-    return ESC_OK;
+    return reduce_now(slabs, n, splits, K, dW, ld_dw, db_part, N, db, stream);
   }
   if (dma_bwd_ok(dY, ld_dy, X, ld_x, nullptr, 0, M, N, K, nullptr, 0, slabs, false, true)) {
     const bool big = M >= 8192 && tile128_ok(N) && tile128_ok(K);
@@ -1386,10 +1401,7 @@ static int weight_impl(const float* dY, int64_t ld_dy, const float* X, int64_t l
     if (dma_check(e, "esc_linear_bwd_weight") != hipSuccess) return ESC_ELAUNCH;
     const int64_t n = N * K;
     if (defer) { fill_job(defer, slabs, n, splits, K, dW, ld_dw, d.db_part, N, db); return ESC_OK; }
-    esc::launch(ESC_K_LINEAR, slab_reduce_kernel, dim3((unsigned)cdiv(n + (db ? N : 0), 256)), dim3(256), 0, s, slabs, n,
-                splits, (int)K, dW, ld_dw, d.db_part, (int)N, db);
-    ESC_CHECK_LAUNCH("esc_linear_bwd_weight.reduce");
-    return ESC_OK;
+    return reduce_now(slabs, n, splits, K, dW, ld_dw, d.db_part, N, db, stream);
   }
   wgrad_plan(M, N, K, &splits, &per);
   GemmArgs g{};
@@ -1406,10 +1418,7 @@ static int weight_impl(const float* dY, int64_t ld_dy, const float* X, int64_t l
   ESC_CHECK_LAUNCH("esc_linear_bwd_weight.tiles");
   const int64_t n = N * K;
   if (defer) { fill_job(defer, slabs, n, splits, K, dW, ld_dw, g.db_part, N, db); return ESC_OK; }
-  esc::launch(ESC_K_LINEAR, slab_reduce_kernel, dim3((unsigned)cdiv(n + (db ? N : 0), 256)), dim3(256), 0, s, slabs, n,
-              splits, (int)K, dW, ld_dw, g.db_part, (int)N, db);
-  ESC_CHECK_LAUNCH("esc_linear_bwd_weight.reduce");
-  return ESC_OK;
+  return reduce_now(slabs, n, splits, K, dW, ld_dw, g.db_part, N, db, stream);
 }
 
 }  // extern "C"
@@ -1501,10 +1510,7 @@ static int both_impl(const float* dY, int64_t ld_dy, const float* X, int64_t ld_
     ESC_CHECK_LAUNCH("esc_linear_bwd_both.narrow");
     const int64_t n = N * K;
     if (defer) { fill_job(defer, slabs, n, splits, K, dW, ld_dw, db_part, N, db); return ESC_OK; }
-    esc::launch(ESC_K_LINEAR, slab_reduce_kernel, dim3((unsigned)cdiv(n + (db ? N : 0), 256)), dim3(256), 0, s, slabs, n,
-                splits, (int)K, dW, ld_dw, db_part, (int)N, db);
-    ESC_CHECK_LAUNCH("esc_linear_bwd_both.narrow_reduce");
-    return ESC_OK;
+    return reduce_now(slabs, n, splits, K, dW, ld_dw, db_part, N, db, stream);
   }
   if (dX != nullptr && M > 0 && M < (1LL << 31) && ld_dw >= K && (in_scale == nullptr) == (in_shift == nullptr) &&
       dma_bwd_ok(dY, ld_dy, X, ld_x, W, ld_w, M, N, K, dX, ld_dx, slabs, true, true)) {
@@ -1526,10 +1532,7 @@ static int both_impl(const float* dY, int64_t ld_dy, const float* X, int64_t ld_
     if (dma_check(e, "esc_linear_bwd_both") != hipSuccess) return ESC_ELAUNCH;
     const int64_t n = N * K;
     if (defer) { fill_job(defer, slabs, n, splits, K, dW, ld_dw, a.dw.db_part, N, db); return ESC_OK; }
-    esc::launch(ESC_K_LINEAR, slab_reduce_kernel, dim3((unsigned)cdiv(n + (db ? N : 0), 256)), dim3(256), 0, s, slabs, n,
-                splits, (int)K, dW, ld_dw, a.dw.db_part, (int)N, db);
-    ESC_CHECK_LAUNCH("esc_linear_bwd_both.reduce");
-    return ESC_OK;
+    return reduce_now(slabs, n, splits, K, dW, ld_dw, a.dw.db_part, N, db, stream);
   }
   if (dX == nullptr || N <= 32 || K <= 32) {             // other narrow shapes keep their dedicated tiles
     int rc = weight_impl(dY, ld_dy, X, ld_x, in_scale, in_shift, M, N, K, dW, ld_dw, db, slabs, defer, stream);
@@ -1567,10 +1570,7 @@ static int both_impl(const float* dY, int64_t ld_dy, const float* X, int64_t ld_
   ESC_CHECK_LAUNCH("esc_linear_bwd_both.tiles");
   const int64_t n = N * K;
   if (defer) { fill_job(defer, slabs, n, splits, K, dW, ld_dw, w.db_part, N, db); return ESC_OK; }
-  esc::launch(ESC_K_LINEAR, slab_reduce_kernel, dim3((unsigned)cdiv(n + (db ? N : 0), 256)), dim3(256), 0, s, slabs, n,
-              splits, (int)K, dW, ld_dw, w.db_part, (int)N, db);
-  ESC_CHECK_LAUNCH("esc_linear_bwd_both.reduce");
-  return ESC_OK;
+  return reduce_now(slabs, n, splits, K, dW, ld_dw, w.db_part, N, db, stream);
 }
 
 
@@ -1585,7 +1585,7 @@ static inline bool bnb_operands_ok(const esc_bn_bwd_fused* b, int64_t M, int64_t
 }
 static inline bool bnb_big_shape(int64_t M, int64_t N, int64_t K) { return M >= 8192 && tile128_ok(N) && tile128_ok(K); }
 static inline bool in_range_big(int64_t N) { return N <= 640; }
-static inline bool bnb_small_shape(int64_t N, int64_t K) { return (g_use_dma & 4) && K <= small::SMALL_MAX && N > small::SMALL_MAX && N % 4 == 0 && N <= 1024; }
+static inline bool bnb_small_shape(int64_t N, int64_t K) { return (g_use_dma & 4) && K <= small::SMALL_MAX && N > small::SMALL_MAX && N % 4 == 0 && N <= small::SMALLN_DX_MAX_N; }
 
 int esc_linear_bwd_both_bn_ok(const float* dOut, int64_t ld_dout, const esc_bn_bwd_fused* bn, const float* X, int64_t ld_x,
                               const float* W, int64_t ld_w, int64_t M, int64_t N, int64_t K, const float* dX, int64_t ld_dx,
@@ -1642,10 +1642,7 @@ int esc_linear_bwd_both_bn(const float* dOut, int64_t ld_dout, const esc_bn_bwd_
       ESC_CHECK_LAUNCH("esc_linear_bwd_both_bn.smalln");
     }
     if (defer) { fill_job(defer, slabs, n, splits, K, dW, ld_dw, db_part, N, db); return ESC_OK; }
-    esc::launch(ESC_K_LINEAR, slab_reduce_kernel, dim3((unsigned)cdiv(n + (db ? N : 0), 256)), dim3(256), 0, s, slabs, n,
-                splits, (int)K, dW, ld_dw, db_part, (int)N, db);
-    ESC_CHECK_LAUNCH("esc_linear_bwd_both_bn.reduce");
-    return ESC_OK;
+    return reduce_now(slabs, n, splits, K, dW, ld_dw, db_part, N, db, stream);
   }
   const bool big = bnb_big_shape(M, N, K);
   int splits, per;
@@ -1670,10 +1667,7 @@ int esc_linear_bwd_both_bn(const float* dOut, int64_t ld_dout, const esc_bn_bwd_
   }
   if (dma_check(e, "esc_linear_bwd_both_bn") != hipSuccess) return ESC_ELAUNCH;
   if (defer) { fill_job(defer, slabs, n, splits, K, dW, ld_dw, a.dw.db_part, N, db); return ESC_OK; }
-  esc::launch(ESC_K_LINEAR, slab_reduce_kernel, dim3((unsigned)cdiv(n + (db ? N : 0), 256)), dim3(256), 0, s, slabs, n,
-              splits, (int)K, dW, ld_dw, a.dw.db_part, (int)N, db);
-  ESC_CHECK_LAUNCH("esc_linear_bwd_both_bn.reduce");
-  return ESC_OK;
+  return reduce_now(slabs, n, splits, K, dW, ld_dw, a.dw.db_part, N, db, stream);
 }
 
 }  // extern "C"

@@ -230,6 +230,8 @@ typedef struct esc_bn_fold {
   float* running_mean;       /* [C] in/out, may be NULL */
   float* running_var;        /* [C] in/out, may be NULL */
 } esc_bn_fold;
+/* (the answer holds with and without in_scale / in_shift: where only the prologue keeps a call off the kernels named here — K > 1280 —
+ * the forward still delivers its partials at this height) */
 int64_t esc_linear_stats_block_rows(const float* X, int64_t ld_x, const float* W, int64_t ld_w, int64_t M, int64_t N,
                                     int64_t K);
 int esc_linear_fold_available(void);        /* 0 while esc_tune_set(11, 0) keeps every GEMM on the r01 tiles */
@@ -276,7 +278,8 @@ int esc_linear_bwd_both(const float* dY, int64_t ld_dy, const float* X, int64_t 
                         float* dW, int64_t ld_dw, float* db, float* slabs, void* stream);
 
 /* deferred form: the tiles run now, the ordered slab reduce is described in *job; esc_slab_reduce_jobs then
- * finishes up to ESC_MAX_REDUCE_JOBS weight gradients in ONE launch (they are only needed by the optimiser).
+ * finishes up to ESC_MAX_REDUCE_JOBS weight gradients in ONE launch (they are only needed by the optimiser); dW / db have the bits
+ * of the immediate form (which is the one-job call of the same reduce).
  * Each deferred call needs its own `slabs` region, untouched until the reduce. */
 #define ESC_MAX_REDUCE_JOBS 48
 typedef struct esc_reduce_job {
@@ -308,7 +311,7 @@ int esc_slab_reduce_jobs(const esc_reduce_job* jobs /* host array */, int count,
  * Result: dX / dW / db equal esc_bn_bwd_apply followed by esc_linear_bwd_both[_deferred] (same arithmetic per element;
  * the operand is never written to memory).  job == NULL reduces the slabs at once.
  * esc_linear_bwd_both_bn_ok tells whether a shape is served (node-sized rows, 16-byte aligned operands, N <= 640 on
- * the MFMA tiles or K <= 16 on the narrow-input kernels); callers fall back to the unfused sequence otherwise.
+ * the MFMA tiles or K <= 16 with N <= 848 on the narrow-input kernels); callers fall back to the unfused sequence otherwise.
  * bn == NULL (with next != NULL): dOut is a plain dY — only the next BatchNorm's column sums are folded in. */
 typedef struct esc_bn_bwd_fused {
   const float* x; int64_t ld_x;
