@@ -23,7 +23,7 @@ def install_dropin():
     """Register this package's modules under the reference's top-level module names, so that an unmodified
     `from utils_edge_efficient import create_subgraphs`, `from batch import Batch`,
     `from dataloader import DataLoader`, `from kernel.gin import NestedGIN_eff`, `from zinc_models import *`,
-    `from zinc_cycle_models import *`,
+    `from zinc_cycle_models import *`, `from qm9_models import *`, `from distance import Distance`,
     `from ogb_mol_gnn import GNN` or `from modules.gine_operations import GINEPLUS` resolves here."""
     import sys
     import types
@@ -33,6 +33,9 @@ def install_dropin():
     sys.modules.setdefault("utils_edge_efficient", _uee)
     sys.modules.setdefault("zinc_models", _zinc)
     sys.modules.setdefault("zinc_cycle_models", _zinc_cycle)
+    from . import geometry as _geometry, qm9_models as _qm9
+    sys.modules.setdefault("qm9_models", _qm9)
+    sys.modules.setdefault("distance", _geometry)
     sys.modules.setdefault("ogb_mol_gnn", _ogb)
     mods = sys.modules.setdefault("modules", types.ModuleType("modules"))
     mods.gine_operations = _gine_ops

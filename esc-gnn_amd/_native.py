@@ -9,7 +9,7 @@ from ctypes import c_double, c_float, c_int, c_int64, c_void_p, POINTER
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libescgnn_hip.so")
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 P, I64, I32, F32 = c_void_p, c_int64, c_int, c_float
 
@@ -170,6 +170,10 @@ SIGNATURES = {
     "esc_features_fill": [P, P, I64, I64, I64, I64, I64, I32, I32, I32, P, P, I64, P, P, P, P, P, P, P, P, P],
     "esc_cycle_counts": [P, P, P, P, I64, I64, I64, P, P, P],
     "esc_graphlet_counts": [P, P, P, P, I64, I64, I64, P, I64, P, P],
+    "esc_edge_distance": [P, I64, P, P, P, P, I64, I64, I64, I32, I32, I32, I32, F32, P, I64, I64, P, P],
+    "esc_node_input_fwd": [P, I64, P, I64, P, P, I64, I64, I64, P, I64, P, P],
+    "esc_node_input_bwd": [P, I64, P, I64, I64, I64, P, P],
+    "esc_mse_loss": [P, P, I64, I64, F32, P, P, P],
 }
 _RET = {"esc_last_error": ctypes.c_char_p, "esc_bag_bwd_scratch": c_int64, "esc_bag_fwd_stats_block_rows": c_int64, "esc_gine_aggregate_bwd_stats_slots": c_int64, "esc_linear_stats_block_rows": c_int64, "esc_plan_csr_scratch": c_int64, "esc_embed_plan_scratch": c_int64, "esc_prof_read_all": c_int64, "esc_prof_span_read": c_int64,
         "esc_linear_bwd_weight_scratch": c_int64, "esc_bn_scratch": c_int64, "esc_linear_bwd_bn_block_rows": c_int64,

@@ -11,7 +11,7 @@ the same graphs moved with `.to(device)`, in the same order as torch's own sampl
 in the caller's loop is then a no-op).
 
 The device path is taken only for what it reproduces exactly: `Data` items that carry the ESC keys (x, edge_index,
-y, pos_enc, pos_index, pos_batch, optionally edge_attr) and nothing else, no `follow_batch`, no worker processes, the
+y, pos_enc, pos_index, pos_batch, optionally edge_attr, and QM9's pos / node_type / name) and nothing else, no `follow_batch`, no worker processes, the
 default sampler / collate.  Anything else — and `device=None` / a CPU-only box — is the host collate of the
 reference.  (The host path is the reference's loader, not a fallback of the HIP kernels: the model itself refuses CPU
 tensors.)  A dataset that is edited after the first iteration must be re-pinned with `loader.repin()`.
@@ -24,6 +24,7 @@ from .batch import Batch
 from .data import Data
 
 _STORE_KEYS = ("x", "edge_index", "y", "pos_enc", "pos_index", "pos_batch")
+_GEO_KEYS = ("pos", "node_type")
 
 
 def _merge(samples, follow_batch):
@@ -50,8 +51,18 @@ def _storable(item):
     if not isinstance(item, Data):
         return False
     keys = set(item.keys)
-    if not set(_STORE_KEYS) <= keys or not keys <= set(_STORE_KEYS + ("edge_attr",)):
+    if not set(_STORE_KEYS) <= keys or not keys <= set(_STORE_KEYS + ("edge_attr",) + _GEO_KEYS + ("name",)):
         return False
+    if keys & set(_GEO_KEYS + ("name",)):                # the QM9 keys: pos float [n, 3] and node_type int64 [n] together
+        if not set(_GEO_KEYS) <= keys or ("name" in keys and not isinstance(item.name, str)):
+            return False
+        keys = keys - {"name"}
+        if not (torch.is_tensor(item.pos) and torch.is_tensor(item.node_type) and torch.is_tensor(item.x)):
+            return False
+        n = item.x.size(0)
+        if not (item.x.dim() == 2 and item.x.dtype == torch.float32 and item.pos.dtype == torch.float32 and
+                tuple(item.pos.shape) == (n, 3) and item.node_type.dtype == torch.int64 and tuple(item.node_type.shape) == (n,)):
+            return False
     return all(torch.is_tensor(item[k]) for k in keys) and item.x.dim() >= 1 and item.x.size(0) > 0
 
 
@@ -85,7 +96,8 @@ class DataLoader(torch.utils.data.DataLoader):
                     items = [self.dataset[i] for i in range(n)]
                 except TypeError:
                     items = None                   # iterable-style dataset: host path
-                if items and all(_storable(g) for g in items):
+                if items and all(_storable(g) for g in items) and \
+                        len({frozenset(set(g.keys) & set(_GEO_KEYS + ("name",))) for g in items}) == 1:
                     from .store import DeviceGraphStore
                     store = DeviceGraphStore(items, dev)
         self.__dict__["_esc_store"] = store

@@ -275,3 +275,79 @@ def exp_split(num_graphs, split, splits=10, modulo=4, mod_thresh=1):
     val = rest[split * m:(split + 1) * m]
     train = rest[:split * m] + rest[(split + 1) * m:]
     return dict(train=train, val=val, test=test, lrn=lrn, exp=exp)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# QM9-shaped synthetic molecules (the QM9 download is absent offline): the fields run_qm9.py reads.
+# ---------------------------------------------------------------------------------------------------------
+QM9_ATOMIC_NUMBERS = (1, 6, 7, 8, 9)                       # node_type r <-> atomic number QM9_ATOMIC_NUMBERS[r]
+_QM9_MIX = np.random.RandomState(20240).uniform(-1.0, 1.0, size=(12, 8))      # fixed target mixing (12 targets x 8 descriptors)
+
+
+def _embed_molecule(n, ei, rng):
+    """pos float32 [n, 3]: node 0 at the origin, every other atom 1-1.6 away from its parent in the breadth-first tree of
+    the bond graph and at least 0.7 away from every atom placed before it (no two atoms coincide).  A ring-closing bond
+    joins two atoms the tree placed independently, so it may be longer."""
+    nbrs = [[] for _ in range(n)]
+    for a, b in ei.T:
+        nbrs[int(a)].append(int(b))
+    pos = np.zeros((n, 3), dtype=np.float64)
+    placed, order = {0}, [0]
+    for u in order:
+        for v in nbrs[u]:
+            if v in placed:
+                continue
+            for _try in range(200):
+                d = rng.randn(3)
+                cand = pos[u] + d / np.linalg.norm(d) * rng.uniform(1.0, 1.6)
+                if min(np.linalg.norm(pos[w] - cand) for w in placed) >= 0.7:
+                    break
+            pos[v] = cand
+            placed.add(v)
+            order.append(v)
+    return pos.astype(np.float32)
+
+
+def synthetic_qm9_graphs(first, count):
+    """QM9 layout (reference run_qm9.py:198-231, qm9_models.py:106-107): x float [n, 8] (column 0 the atomic number from
+    {1, 6, 7, 8, 9}, columns 1-6 binary, column 7 a small count), node_type int64 [n] in [0, 5) (the index of the atomic
+    number), pos float [n, 3], edge_attr float one-hot [E, 4], coalesced edges in both directions, y float [1, 12] (smooth
+    functions of composition and geometry, so that training has signal), name str.  7-29 atoms, seeded by graph id."""
+    out = []
+    for g in range(first, first + count):
+        n, ei, rings, rng = molecule_like_edges(70000 + g, 7, 29)
+        node_type = rng.choice(5, size=n, p=(0.45, 0.35, 0.08, 0.1, 0.02))
+        pos = _embed_molecule(n, ei, rng)
+        x = np.zeros((n, 8), dtype=np.float32)
+        x[:, 0] = np.array(QM9_ATOMIC_NUMBERS)[node_type]
+        x[:, 1:7] = rng.randint(0, 2, size=(n, 6))
+        deg = np.bincount(ei[0], minlength=n)
+        x[:, 7] = np.minimum(deg, 4)
+        bond = rng.randint(0, 4, size=ei.shape[1])
+        key = {}
+        for k in range(ei.shape[1]):                       # same bond type in both directions
+            a, b = int(ei[0, k]), int(ei[1, k])
+            bond[k] = key.setdefault((min(a, b), max(a, b)), bond[k])
+        edge_attr = np.zeros((ei.shape[1], 4), dtype=np.float32)
+        edge_attr[np.arange(ei.shape[1]), bond] = 1.0
+        centred = pos.astype(np.float64) - pos.mean(0)
+        blen = np.linalg.norm(pos[ei[1]] - pos[ei[0]], axis=1).astype(np.float64)
+        desc = np.array([np.sqrt((centred ** 2).sum(1).mean()), n / 10.0, float((node_type > 0).mean()), x[:, 0].sum() / 50.0,
+                         blen.mean(), float(rings), float((bond == 0).mean()), x[:, 1:7].mean()])
+        y = _QM9_MIX @ desc + 0.1 * np.sin(_QM9_MIX @ desc * 3.0)
+        out.append(Data(x=torch.tensor(x), edge_index=torch.tensor(ei), edge_attr=torch.tensor(edge_attr),
+                        y=torch.tensor(y.astype(np.float32)).view(1, 12), pos=torch.tensor(pos),
+                        node_type=torch.tensor(node_type, dtype=torch.int64), name="syn_qm9_%06d" % g, num_nodes=n))
+    return out
+
+
+def build_qm9_dataset(raw, h=3, target=0, **distance_flags):
+    """The dataset of run_qm9.py:198-231 for NestedGIN_eff: create_subgraphs(g, h, use_rd=True, self_loop=True) on the HIP
+    feature builder, y = y[:, target] (MyTransform), then the Distance transform (geometry.edge_distance_many; flags norm,
+    squared, relative_pos, ...) once the self loops exist — edge_attr becomes [bond one-hot | distance]."""
+    from .geometry import edge_distance_many
+    done = create_subgraphs_many(raw, h, use_rd=True, self_loop=True)
+    for d in done:
+        d.num_nodes = None
+        d.y = d.y[:, int(target)]
+    return edge_distance_many(done, **distance_flags)

@@ -383,6 +383,92 @@ def l1_loss(pred, y, denom=None):
     return _L1Loss.apply(pred, y, denom)
 
 
+class _MseLoss(Function):
+    """F.mse_loss(pred, y) (reference run_qm9.py:348): squares summed in fp64 by esc_mse_loss; `denom` overrides the mean's
+    divisor (the global graph count under graph-sharded data parallelism)."""
+
+    @staticmethod
+    def forward(ctx, pred, y, denom):
+        _dev(pred, y)
+        _on(pred.device, y)
+        ctx.shape = pred.shape
+        pred = pred.contiguous().view(-1)
+        y = y.contiguous().view(-1)
+        if pred.numel() != y.numel():
+            raise ValueError("mse_loss: %d predictions vs %d targets" % (pred.numel(), y.numel()))
+        M = pred.numel()
+        loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+        dpred = torch.empty(M, dtype=torch.float32, device=pred.device)
+        nv.call("esc_mse_loss", nv.ptr(pred), nv.ptr(y), M, int(denom or M), 1.0, nv.ptr(loss), nv.ptr(dpred), nv.stream())
+        ctx.save_for_backward(dpred)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (dpred,) = ctx.saved_tensors
+        return (dpred * g).view(ctx.shape), None, None
+
+
+def mse_loss(pred, y, denom=None):
+    return _MseLoss.apply(pred, y, denom)
+
+
+def _rows_ld(t, width):
+    """2-D [N, width] float32 view with unit inner stride (a column slice of wider rows is taken as it is) + its leading
+    dimension"""
+    if t.dim() != 2 or t.size(1) != width:
+        raise ValueError("expected a [N, %d] tensor, got shape %s" % (width, tuple(t.shape)))
+    if t.stride(1) != 1 or (t.size(0) > 1 and t.stride(0) < width):
+        t = t.contiguous()
+    return t, (t.stride(0) if t.size(0) > 1 else max(width, t.stride(0)))
+
+
+class _NodeInput(Function):
+    """cat([x, pos], 1) + table[node_type] (reference qm9_models.py:106-107) in one launch; x and pos are data (no
+    gradient), the table's gradient is the small-table segmented sum of esc_embed_bwd."""
+
+    @staticmethod
+    def forward(ctx, x, pos, node_type, table):
+        _dev(x, pos, table)
+        _on(table.device, x, pos, node_type)
+        if node_type.dtype != torch.int64:
+            raise TypeError("node_input: node_type must be int64, got %s" % node_type.dtype)
+        N, F = x.size(0), x.size(1) if x.dim() == 2 else -1
+        if F < 1 or table.dim() != 2 or table.size(1) != F + 3:
+            raise ValueError("node_input: x %s and pos %s need a table of %d columns, got %s"
+                             % (tuple(x.shape), tuple(pos.shape), F + 3, tuple(table.shape)))
+        x, ldx = _rows_ld(x, F)
+        pos, ldp = _rows_ld(pos, 3)
+        node_type = node_type.reshape(-1).contiguous()
+        if pos.size(0) != N or node_type.numel() != N:
+            raise ValueError("node_input: %d rows of x, %d of pos, %d node types" % (N, pos.size(0), node_type.numel()))
+        table = table.contiguous()
+        out = torch.empty((N, F + 3), dtype=torch.float32, device=table.device)
+        bad = torch.zeros(1, dtype=torch.int32, device=table.device)
+        nv.call("esc_node_input_fwd", nv.ptr(x), ldx, nv.ptr(pos), ldp, nv.ptr(node_type), nv.ptr(table), table.size(0), F, N,
+                nv.ptr(out), F + 3, nv.ptr(bad), nv.stream())
+        known = getattr(node_type, "_esc_known_range", None)      # a batch of the device store: the range was checked once
+        if not (known is not None and known[1] == node_type._version and known[0][0] >= 0 and known[0][1] < table.size(0)):
+            if int(bad.item()):
+                raise IndexError("node_input: node_type outside the %d-row table" % table.size(0))
+        ctx.save_for_backward(node_type)
+        ctx.rows, ctx.F = table.size(0), F
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (node_type,) = ctx.saved_tensors
+        g, ld = _rows(g)
+        dtable = torch.empty((ctx.rows, ctx.F + 3), dtype=torch.float32, device=g.device)
+        nv.call("esc_node_input_bwd", nv.ptr(g), ld, nv.ptr(node_type), node_type.numel(), ctx.rows, ctx.F, nv.ptr(dtable),
+                nv.stream())
+        return None, None, None, dtable
+
+
+def node_input(x, pos, node_type, table):
+    return _NodeInput.apply(x, pos, node_type, table)
+
+
 class _BceLogits(Function):
     """BCEWithLogitsLoss()(pred[is_labeled], y[is_labeled]), is_labeled = (y == y) (run_ogb_mol.py:65-72);
     `denom` overrides the divisor (global labeled count under graph sharding)."""

@@ -52,7 +52,21 @@ class DeviceGraphStore(object):
         self.num_graphs = G
         self.x_is_int = not data_list[0].x.is_floating_point()       # categorical node features (ZINC / OGB)
         self.x_was_1d = data_list[0].x.dim() == 1
-        self.x_all = torch.cat([d.x.reshape(d.x.size(0), -1).float() for d in data_list]).contiguous().to(dev)
+        # QM9 graphs (pos float [n, 3] + node_type int64 [n], optionally a str name): the node rows are packed as
+        # [x | pos | float(node_type)], so the collate kernels gather them like any other x; the batch exposes views
+        self.geo_dim, self.names, self.node_type_range = None, None, None
+        if data_list[0]["pos"] is not None and data_list[0]["node_type"] is not None:
+            self.geo_dim = int(data_list[0].x.reshape(data_list[0].x.size(0), -1).size(1))
+            nt = torch.cat([d.node_type.reshape(-1) for d in data_list])
+            if nt.numel() and (int(nt.min()) < -(1 << 24) or int(nt.max()) > (1 << 24)):
+                raise ValueError("DeviceGraphStore: node_type does not survive the fp32 packing")
+            self.node_type_range = (int(nt.min()), int(nt.max())) if nt.numel() else (0, 0)
+            self.x_all = torch.cat([torch.cat([d.x.reshape(d.x.size(0), -1).float(), d.pos.reshape(-1, 3).float(),
+                                               d.node_type.reshape(-1, 1).float()], dim=1) for d in data_list]).contiguous().to(dev)
+            if data_list[0]["name"] is not None:
+                self.names = [d.name for d in data_list]
+        else:
+            self.x_all = torch.cat([d.x.reshape(d.x.size(0), -1).float() for d in data_list]).contiguous().to(dev)
         ea = [d.edge_attr for d in data_list]
         self.edge_attr_all = None if any(a is None for a in ea) else torch.cat(ea, dim=0).contiguous().to(dev)
         self._compute_int_ranges()
@@ -135,7 +149,7 @@ class DeviceGraphStore(object):
 
     # ---- on-disk cache: the processed dataset, like the reference's data_*.pt (GraphCountDataset.py:119-120) ----
     _HOST = ("h_node_ptr", "h_edge_ptr", "h_nnz_ptr", "h_y_ptr")
-    _META = ("num_graphs", "x_dim", "y_dim", "y_is_vector", "x_is_int", "x_was_1d")
+    _META = ("num_graphs", "x_dim", "y_dim", "y_is_vector", "x_is_int", "x_was_1d", "geo_dim", "names", "node_type_range")
 
     def save(self, path):
         """torch.save of every tensor of the store (sorted views included) — reload with DeviceGraphStore.load."""
@@ -151,6 +165,8 @@ class DeviceGraphStore(object):
         what `Data.from_dict(data)` / the dataset's `slices` expect."""
         x = self.x_all.cpu()
         x = (x.long().view(-1) if self.x_was_1d else x.long()) if self.x_is_int else x
+        geo = getattr(self, "geo_dim", None)
+        packed, x = x, (x[:, :geo].contiguous() if geo is not None else x)
         y = self.y_all.cpu()
         data = dict(x=x, edge_index=torch.stack([self.esrc_all, self.edst_all]).cpu(),
                     y=y.view(-1) if (self.y_is_vector and self.y_dim == 1) else y,
@@ -159,6 +175,9 @@ class DeviceGraphStore(object):
                       pos_enc=self.h_nnz_ptr.clone(), pos_index=self.h_nnz_ptr.clone(), pos_batch=self.h_nnz_ptr.clone())
         if self.edge_attr_all is not None:
             data["edge_attr"], slices["edge_attr"] = self.edge_attr_all.cpu(), self.h_edge_ptr.clone()
+        if geo is not None:
+            data["pos"], slices["pos"] = packed[:, geo:geo + 3].contiguous(), self.h_node_ptr.clone()
+            data["node_type"], slices["node_type"] = packed[:, geo + 3].long(), self.h_node_ptr.clone()
         return data, slices
 
     @classmethod
@@ -168,6 +187,8 @@ class DeviceGraphStore(object):
         from .data import Data
         get = (lambda k: data[k] if k in data else None) if isinstance(data, dict) else (lambda k: getattr(data, k, None))
         keys = [k for k in ("x", "edge_index", "edge_attr", "y", "pos_enc", "pos_index", "pos_batch") if get(k) is not None]
+        if "pos" in slices and "node_type" in slices and get("pos") is not None and get("node_type") is not None:
+            keys += ["pos", "node_type"]
         for k in ("x", "edge_index", "y", "pos_enc", "pos_index", "pos_batch"):
             if k not in keys or k not in slices:
                 raise KeyError("from_data_slices: key %r missing from data / slices" % k)
@@ -190,6 +211,7 @@ class DeviceGraphStore(object):
         self = cls.__new__(cls)
         self.device = dev
         self.edge_attr_all = None                             # optional tensors are absent from the blob when None
+        self.geo_dim, self.names, self.node_type_range = None, None, None      # (absent from a cache older than the QM9 keys)
         for k, v in blob.items():
             setattr(self, k, v if (k in cls._HOST or k in cls._META) else v.to(dev))
         self._compute_int_ranges()
@@ -295,6 +317,14 @@ class DeviceGraphStore(object):
         out = Batch()
         if self.x_is_int:                                    # small categorical ids survive the fp32 round trip exactly
             x = x.view(-1) if self.x_was_1d else x
+        geo = getattr(self, "geo_dim", None)
+        if geo is not None:                                  # views of the packed rows [x | pos | float(node_type)]
+            packed, x = x, x[:, :geo]
+            out.pos = packed[:, geo:geo + 3]
+            out.node_type = packed[:, geo + 3].long()
+            out.node_type._esc_known_range = (self.node_type_range, out.node_type._version)
+            if self.names is not None:
+                out.name = [self.names[i] for i in ids_h.tolist()]
         out.x, out.edge_index = x, edge_index
         if ea_fused:
             out.edge_attr = edge_attr
@@ -331,6 +361,10 @@ class DeviceGraphStore(object):
             shifts = dict(x=zero, edge_index=node[:-1], y=zero, pos_enc=zero, pos_index=zero, pos_batch=edge[:-1])
             if has_attr:
                 slices["edge_attr"], shifts["edge_attr"] = edge, zero
+            if geo is not None:
+                slices["pos"], shifts["pos"], slices["node_type"], shifts["node_type"] = node, zero, node, zero
+                if self.names is not None:
+                    slices["name"], shifts["name"] = list(range(B + 1)), zero
             return slices, shifts
         object.__setattr__(out, "_lazy_slices", lazy_slices)
         return out

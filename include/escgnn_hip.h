@@ -769,6 +769,31 @@ int esc_graphlet_counts(const int64_t* node_ptr, const int64_t* edge_ptr, const 
                         int64_t total_nodes, int64_t total_edges, int32_t* out, int64_t ld_out, int32_t* status,
                         void* stream);
 
+/* ---- QM9 geometry (reference distance.py:25-47, qm9_models.py:106-107, run_qm9.py:348; csrc/geometry.hip) --------------
+ * esc_edge_distance: the `Distance` transform for G graphs in one launch.  Same ragged, graph-local-id layout as
+ * esc_cycle_counts; pos is float32 [total_nodes, ld_pos >= 3].  With row = src, col = dst: d = |pos[dst] - pos[src]|_2 (the
+ * sum of squares when `squared`); with `norm`, d is divided by the maximum over the edges of its own graph, or by max_value
+ * when use_max_value (a maximum of 0 gives 0/0 = NaN, as the reference does).  out[e, col] = d and, with relative_pos,
+ * out[e, col+1 .. col+3] = pos[dst] - pos[src]; the other columns of out are left untouched.  Graphs without edges are
+ * skipped.  status[G]: 0, or ESC_EINVAL for an id or a range outside the arrays (nothing of that graph is written).
+ * One workgroup per graph, no atomics. */
+int esc_edge_distance(const float* pos, int64_t ld_pos, const int64_t* src, const int64_t* dst, const int64_t* node_ptr,
+                      const int64_t* edge_ptr, int64_t G, int64_t total_nodes, int64_t total_edges, int norm, int squared,
+                      int relative_pos, int use_max_value, float max_value, float* out, int64_t ld_out, int64_t col,
+                      int32_t* status, void* stream);
+/* out[i, :F] = x[i, :] + table[t_i, :F]; out[i, F:F+3] = pos[i, :] + table[t_i, F:F+3] with t = node_type (int64 [N]), table
+ * float32 [rows, F+3] contiguous, any F >= 1.  A type outside the table contributes a zero row and sets *bad_flag (may be
+ * NULL) to 1.  Backward: dtable[r, :] = sum_{i: t_i = r} g[i, :] (esc_embed_bwd's fixed-order sum); x and pos are data. */
+int esc_node_input_fwd(const float* x, int64_t ld_x, const float* pos, int64_t ld_pos, const int64_t* node_type,
+                       const float* table, int64_t rows, int64_t F, int64_t N, float* out, int64_t ld_out, int32_t* bad_flag,
+                       void* stream);
+int esc_node_input_bwd(const float* g, int64_t ld_g, const int64_t* node_type, int64_t N, int64_t rows, int64_t F,
+                       float* dtable, void* stream);
+/* loss[0] = sum_i (pred_i - y_i)^2 / denom (differences, squares and sum in fp64, fixed order, rounded once);
+ * dpred_i = 2 (pred_i - y_i) * grad_scale / denom (dpred may be NULL).  denom = M for F.mse_loss(mean). */
+int esc_mse_loss(const float* pred, const float* y, int64_t M, int64_t denom, float grad_scale, float* loss, float* dpred,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
