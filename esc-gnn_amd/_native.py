@@ -174,6 +174,8 @@ SIGNATURES = {
     "esc_node_input_fwd": [P, I64, P, I64, P, P, I64, I64, I64, P, I64, P, P],
     "esc_node_input_bwd": [P, I64, P, I64, I64, I64, P, P],
     "esc_mse_loss": [P, P, I64, I64, F32, P, P, P],
+    "esc_act_fwd": [P, I64, I64, I64, I32, P, I64, P],
+    "esc_act_bwd": [P, I64, P, I64, I64, I64, I32, P, I64, P],
 }
 _RET = {"esc_last_error": ctypes.c_char_p, "esc_bag_bwd_scratch": c_int64, "esc_bag_fwd_stats_block_rows": c_int64, "esc_gine_aggregate_bwd_stats_slots": c_int64, "esc_linear_stats_block_rows": c_int64, "esc_plan_csr_scratch": c_int64, "esc_embed_plan_scratch": c_int64, "esc_prof_read_all": c_int64, "esc_prof_span_read": c_int64,
         "esc_linear_bwd_weight_scratch": c_int64, "esc_bn_scratch": c_int64, "esc_linear_bwd_bn_block_rows": c_int64,

@@ -351,3 +351,72 @@ def build_qm9_dataset(raw, h=3, target=0, **distance_flags):
         d.num_nodes = None
         d.y = d.y[:, int(target)]
     return edge_distance_many(done, **distance_flags)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# CSL (circular skip links): a defined graph family, generated here instead of read from the benchmark's pickle.
+# ---------------------------------------------------------------------------------------------------------
+CSL_SKIPS = (2, 3, 4, 5, 6, 9, 11, 12, 13, 16)             # class k <-> skip length CSL_SKIPS[k]
+
+
+def csl_edge_index(num_nodes, skip, perm=None):
+    """The cycle 0 - 1 - ... - (n-1) - 0 plus the skip links i - (i + skip) mod n, node i renamed perm[i]; both directions,
+    sorted by (src, dst).  4-regular for 1 < skip < n - 1, 2 * skip != n."""
+    i = np.arange(num_nodes)
+    pairs = np.concatenate([np.stack([i, (i + 1) % num_nodes], 1), np.stack([i, (i + skip) % num_nodes], 1)])
+    if perm is not None:
+        pairs = np.asarray(perm)[pairs]
+    return _both_directions_sorted(pairs.tolist())
+
+
+def csl_graphs(num_nodes=41, skips=CSL_SKIPS, copies=15, seed=0):
+    """The CSL classification set (reference run_csl.py:83 reads it as GNNBenchmarkDataset 'CSL'): len(skips) classes of
+    `copies` isomorphic graphs each, class by class.  Copy 0 of a class keeps the cycle labelling, the others are relabelled
+    by permutations drawn in order from np.random.RandomState(seed).  y = int64 [1] class index; x = ones[n, 1], which is
+    what the reference model substitutes when a graph has no x (run_csl.py:205-208)."""
+    rng = np.random.RandomState(seed)
+    out = []
+    for k, skip in enumerate(skips):
+        for c in range(copies):
+            perm = rng.permutation(num_nodes) if c else None
+            out.append(Data(x=torch.ones(num_nodes, 1), edge_index=csl_edge_index(num_nodes, int(skip), perm),
+                            y=torch.tensor([k], dtype=torch.int64), num_nodes=num_nodes))
+    return out
+
+
+def build_csl_dataset(graphs, h=4):
+    """the pre_transform of run_csl.py:78-80: create_subgraphs(g, h, node_label='hop', use_rd=True, self_loop=True) for
+    every graph, on the HIP feature builder"""
+    return build_feature_dataset(graphs, h, use_rd=True, self_loop=True)
+
+
+def csl_k_fold(labels, folds=10, seed=12345):
+    """The split protocol of the reference's kernel/train_eval.py:225-240: stratified, shuffled test folds; the validation
+    fold of split i is the test fold of split i - 1 (split 0 takes the last one); training is everything else.  Returns
+    (train, test, val): three lists of `folds` sorted int64 index arrays.
+
+    Pure numpy.  The folds have the sizes and per-class counts of scikit-learn's StratifiedKFold(folds, shuffle=True) —
+    class k gives fold i as many graphs as there are k's among sorted(labels)[i::folds], placed by one shuffle per class
+    from np.random.RandomState(seed) — but not necessarily its permutation: which graph lands in which fold is this
+    function's own."""
+    y = np.asarray(labels).reshape(-1)
+    classes, y_enc = np.unique(y, return_inverse=True)
+    if folds < 2 or np.bincount(y_enc).max() < folds:
+        raise ValueError("csl_k_fold: %d folds need at least %d graphs in some class" % (folds, folds))
+    y_sorted = np.sort(y_enc)
+    alloc = np.stack([np.bincount(y_sorted[i::folds], minlength=len(classes)) for i in range(folds)])    # [fold, class]
+    rng = np.random.RandomState(seed)
+    fold_of = np.empty(len(y), dtype=np.int64)
+    for k in range(len(classes)):
+        f = np.arange(folds).repeat(alloc[:, k])
+        rng.shuffle(f)
+        fold_of[y_enc == k] = f
+    test = [np.where(fold_of == i)[0].astype(np.int64) for i in range(folds)]
+    val = [test[i - 1] for i in range(folds)]
+    train = []
+    for i in range(folds):
+        mask = np.ones(len(y), dtype=bool)
+        mask[test[i]] = False
+        mask[val[i]] = False
+        train.append(np.where(mask)[0].astype(np.int64))
+    return train, test, val

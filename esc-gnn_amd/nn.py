@@ -71,6 +71,20 @@ class AbsorbedELU(torch.nn.ELU):
         return x
 
 
+class ELU(torch.nn.ELU):
+    """torch.nn.ELU(alpha = 1) computed by the HIP activation kernel (ops.elu) — an ELU with no BatchNorm in front of it to
+    absorb it (reference run_csl.py:152-169).  No parameters: child indices and state_dict layout are torch.nn.ELU's."""
+
+    def __init__(self, alpha=1.0, inplace=False):
+        if alpha != 1.0:
+            raise ValueError("esc_gnn_amd.nn.ELU: only alpha = 1.0 has a kernel (got %r)" % (alpha,))
+        super().__init__(alpha=alpha, inplace=False)
+
+    def forward(self, x):
+        lead = x.shape[:-1]
+        return ops.elu(x.reshape(-1, x.shape[-1])).view(*lead, x.shape[-1])
+
+
 class Embedding(torch.nn.Embedding):
     """torch.nn.Embedding whose lookup and gradient run through the ESC bag kernels (one entry of weight 1 per row)."""
 

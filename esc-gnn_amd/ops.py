@@ -469,6 +469,51 @@ def node_input(x, pos, node_type, table):
     return _NodeInput.apply(x, pos, node_type, table)
 
 
+ACT_CODES = {"relu": 1, "elu": 2}
+
+
+class _Act(Function):
+    """A bare ReLU / ELU(alpha = 1) (reference run_csl.py:152-169,219: no BatchNorm in front to fuse it behind).  Only the
+    output is saved: the backward reads d act / d v off Y."""
+
+    @staticmethod
+    def forward(ctx, x, code):
+        _dev(x)
+        x, ldx = _rows(x)
+        M, C = x.shape
+        y = torch.empty((M, C), dtype=torch.float32, device=x.device)
+        nv.call("esc_act_fwd", nv.ptr(x), ldx, M, C, code, nv.ptr(y), C, nv.stream())
+        ctx.save_for_backward(y)
+        ctx.code = code
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        _dev(dy)
+        dy, ldg = _rows(dy)
+        M, C = y.shape
+        dx = torch.empty((M, C), dtype=torch.float32, device=y.device)
+        nv.call("esc_act_bwd", nv.ptr(y), C, nv.ptr(dy), ldg, M, C, ctx.code, nv.ptr(dx), C, nv.stream())
+        return dx, None
+
+
+def act(x, kind):
+    """kind: 'relu' | 'elu' on a [M, C] tensor; a view with unit inner stride (a column slice of wider rows) is read in
+    place through its row stride, any other layout is made contiguous first"""
+    if kind not in ACT_CODES:
+        raise ValueError("act: kind must be 'relu' or 'elu', got %r" % (kind,))
+    return _Act.apply(x, ACT_CODES[kind])
+
+
+def elu(x):
+    return act(x, "elu")
+
+
+def relu(x):
+    return act(x, "relu")
+
+
 class _BceLogits(Function):
     """BCEWithLogitsLoss()(pred[is_labeled], y[is_labeled]), is_labeled = (y == y) (run_ogb_mol.py:65-72);
     `denom` overrides the divisor (global labeled count under graph sharding)."""

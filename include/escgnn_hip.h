@@ -794,6 +794,17 @@ int esc_node_input_bwd(const float* g, int64_t ld_g, const int64_t* node_type, i
 int esc_mse_loss(const float* pred, const float* y, int64_t M, int64_t denom, float grad_scale, float* loss, float* dpred,
                  void* stream);
 
+/* ---- a bare activation (reference run_csl.py:148-172,219: ELU with no BatchNorm in front; csrc/activation.hip) ----------
+ * act: the fused-activation codes of the norm kernels, 1 = ReLU, 2 = ELU(alpha = 1); anything else is ESC_EINVAL.
+ * Forward: Y[r, c] = max(X[r, c], 0)  |  X > 0 ? X : expm1(X) over float32 [M, C] with row strides ld_x, ld_y >= C.
+ * Backward, from the forward OUTPUT: dX = Y > 0 ? dY : 0  |  Y > 0 ? dY : dY * (Y + 1).
+ * Y may alias X and dX may alias dY.  Columns C .. ld-1 are neither read nor written.  M == 0 or C == 0: success, no launch.
+ * 16 bytes per lane when C and every leading dimension are multiples of 4 and every pointer is 16-byte aligned, one float
+ * per lane otherwise. */
+int esc_act_fwd(const float* X, int64_t ld_x, int64_t M, int64_t C, int act, float* Y, int64_t ld_y, void* stream);
+int esc_act_bwd(const float* Y, int64_t ld_y, const float* dY, int64_t ld_dy, int64_t M, int64_t C, int act, float* dX,
+                int64_t ld_dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
