@@ -3,6 +3,8 @@
 Public surface mirrors the reference's modules for this path:
     create_subgraphs (utils_edge_efficient.py), Batch (batch.py), DataLoader (dataloader.py),
     NestedGIN_eff (run_graphcount.py), GINEConv.
+Layers live in nn.py, what the NestedGIN model files share (Z_TABLE_ROWS, the MLP / z_embedding blocks, edge term, conv
+stack) in nested.py, what the run_*.py drivers share in harness.py.
 """
 from .data import Data  # noqa: F401
 from .batch import Batch  # noqa: F401

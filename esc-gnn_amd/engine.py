@@ -23,6 +23,7 @@ from ctypes import c_float, c_int32, c_int64, c_uint64, c_void_p
 import torch
 
 from . import _native as nv
+from .nested import Z_TABLE_ROWS
 from .plan import plan_of
 
 MAX_LAYERS = 16
@@ -360,7 +361,6 @@ def zinc_engine_ready(m, data):
     if not zinc_engine_supports(m, data):
         return False
     from .plan import graph_ptr_of
-    from .run_graphcount import Z_TABLE_ROWS
     plan = plan_of(data, Z_TABLE_ROWS)
     if getattr(m, "node_readout", False):
         return plan.num_nodes >= 2
@@ -370,7 +370,6 @@ def zinc_engine_ready(m, data):
 def _zinc_batch(model, data, need_y, y=None):
     """esc_mol_batch_t of a ZINC batch; `y`: the targets of a training step when they are not data.y itself"""
     from .plan import graph_ptr_of
-    from .run_graphcount import Z_TABLE_ROWS
     dev = model.lin1.weight.device
     if data.edge_index.device != dev:
         data.to(dev)
@@ -516,7 +515,6 @@ def _ogb_batch(model, data, need_y, seed=0):
     from .ogb_mol_gnn import ATOM_FEATURE_DIMS, BOND_FEATURE_DIMS
     from .ops import embed_plan
     from .plan import graph_ptr_of
-    from .run_graphcount import Z_TABLE_ROWS
     dev = model.graph_pred_linear.weight.device
     if data.edge_index.device != dev:
         data.to(dev)
@@ -552,7 +550,6 @@ def ogb_engine_ready(m, data):
     if not ogb_engine_supports(m, data):
         return False
     from .plan import graph_ptr_of
-    from .run_graphcount import Z_TABLE_ROWS
     return graph_ptr_of(data, plan_of(data, Z_TABLE_ROWS))[1] >= 2
 
 

@@ -12,38 +12,26 @@ model is future work ("Expressiveness runs").
 """
 import torch
 import torch.nn.functional as F
-from torch.nn import ReLU, Sequential
+from torch.nn import ReLU
 
-from . import ops
-from .nn import GINEConv, Linear, global_add_pool
+from . import nested, ops
+from .nested import Z_TABLE_ROWS
+from .nn import Linear, global_add_pool
 from .plan import plan_of
-from .run_graphcount import Z_TABLE_ROWS, _bn_relu
-
-
-def _conv(n_in, hidden):
-    return GINEConv(Sequential(Linear(n_in, hidden), ReLU(), Linear(hidden, hidden), ReLU()), train_eps=False,
-                    edge_dim=hidden)
 
 
 class NestedGIN(torch.nn.Module):
     def __init__(self, num_features, num_layers, hidden):
         super().__init__()
-        self.conv1 = _conv(num_features, hidden)
-        self.convs = torch.nn.ModuleList(_conv(hidden, hidden) for _ in range(num_layers - 1))
+        self.conv1 = nested.plain_conv(num_features, hidden, ReLU)
+        self.convs = torch.nn.ModuleList(nested.plain_conv(hidden, hidden, ReLU) for _ in range(num_layers - 1))
         self.lin1 = Linear(hidden, hidden)
         self.lin2 = Linear(hidden, hidden)
         self.z_initial = torch.nn.Embedding(Z_TABLE_ROWS, hidden)
-        self.z_embedding = Sequential(*_bn_relu(hidden), Linear(hidden, hidden), *_bn_relu(hidden))
+        self.z_embedding = nested.z_embedding(hidden)
 
     def reset_parameters(self):
-        self.conv1.reset_parameters()
-        for conv in self.convs:
-            conv.reset_parameters()
-        for layer in self.z_embedding.children():
-            if hasattr(layer, "reset_parameters"):
-                layer.reset_parameters()
-        self.lin1.reset_parameters()
-        self.lin2.reset_parameters()
+        nested.reset_parameters(self, "conv1", "convs", "z_embedding", "lin1", "lin2")
 
     def logits(self, data):
         """the head's input: everything up to lin2 (the training loop feeds it to ops.log_softmax_nll)"""
@@ -51,16 +39,9 @@ class NestedGIN(torch.nn.Module):
         data.to(dev)
         edge_index = data.edge_index
         plan = plan_of(data, Z_TABLE_ROWS)
-        if "edge_pos" in data:                       # dense layout of the slow variant (run_sr.py:186-189)
-            z = ops.linear(data.edge_pos.float(), self.z_initial.weight.t().contiguous())
-        else:
-            z = ops.esc_bag(self.z_initial.weight, plan)
-        z = self.z_embedding(z)
+        z = self.z_embedding(nested.edge_term(self.z_initial, data, plan))
         x = data.x.float() if "x" in data else torch.ones([data.num_nodes, 1], device=dev)
-        x = self.conv1(x, edge_index, z, plan)
-        for conv in self.convs:
-            x = conv(x, edge_index, z, plan)
-        x = global_add_pool(x, data.batch)
+        x = global_add_pool(nested.conv_stack(self, x, edge_index, z, plan)[-1], data.batch)
         x = F.relu(self.lin1(x))
         x = F.dropout(x, p=0.5, training=self.training)
         return self.lin2(x)

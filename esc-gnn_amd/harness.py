@@ -1,6 +1,8 @@
-"""Pieces shared by the training drivers (run_zinc / run_ogb_mol): device + process-group set-up, seeding,
-result directory bookkeeping and graph-sharded batch iteration (rank r takes a contiguous slice of
-every global batch; the only collective of a step is the weighted all-reduce of the flat gradient bucket)."""
+"""Pieces shared by the training drivers (run_*.py): the argument parser, device + process-group set-up, seeding, result
+directory bookkeeping, graph-sharded batch iteration (rank r takes a contiguous slice of every global batch;
+the only collective of a step is the weighted all-reduce of the flat gradient bucket), the epoch loop of the regression
+drivers and the passes of the classification drivers.  No driver imports from another driver."""
+import argparse
 import os
 import random
 import shutil
@@ -11,7 +13,18 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from . import ops
 from .parallel import shard_slice
+
+BATCH = 20       # graphs per batch of the expressiveness runs (reference run_sr.py:236, run_exp.py:296-300)
+
+
+def parser_from(flags, description):
+    """argparse parser of a driver's _FLAGS: (name, add_argument keywords) pairs"""
+    ap = argparse.ArgumentParser(description=description)
+    for name, kw in flags:
+        ap.add_argument(name, **kw)
+    return ap
 
 
 class Context(object):
@@ -69,8 +82,9 @@ def default_appendix(appendix):
     return appendix if appendix != "" else "_" + time.strftime("%Y%m%d%H%M%S")
 
 
-def sharded_batches(store, batch_size, ctx, shuffle, generator=None):
-    """Global batches of `batch_size` graphs in loader order; this rank collates its contiguous share."""
+def sharded_ids(store, batch_size, ctx, shuffle, generator=None):
+    """(this rank's graph ids, size of the global batch) for every global batch of `batch_size` graphs in loader order:
+    rank r takes a contiguous slice.  Only len(store) is read; nothing touches the device."""
     G = len(store)
     if shuffle and ctx.world > 1 and generator is None:
         # the global CPU RNG would give every rank the same permutation only while all ranks consume it identically;
@@ -84,10 +98,16 @@ def sharded_batches(store, batch_size, ctx, shuffle, generator=None):
             # step's collectives: training drops it (every rank alike), evaluation hands it to rank 0
             if shuffle or ctx.rank != 0:
                 continue
-            yield store.collate(ids), ids.numel()
+            yield ids, ids.numel()
             continue
         lo, hi = shard_slice(ids.numel(), ctx.rank, ctx.world)
-        yield store.collate(ids[lo:hi]), ids.numel()
+        yield ids[lo:hi], ids.numel()
+
+
+def sharded_batches(store, batch_size, ctx, shuffle, generator=None):
+    """Global batches of `batch_size` graphs in loader order; this rank collates its contiguous share."""
+    for ids, n_global in sharded_ids(store, batch_size, ctx, shuffle, generator):
+        yield store.collate(ids), n_global
 
 
 _prefetch_streams = {}
@@ -134,3 +154,95 @@ def prefetched(batches, device, warm=None):
         torch.cuda.current_stream(device).wait_event(ready)
         ahead = issue()                                    # queued BEFORE the caller enqueues step i: overlaps it
         yield item
+
+
+EPOCH_LINE = "Epoch: {:03d}, LR: {:7f}, Loss: {:.7f}, Validation MAE: {:.7f}, Test MAE: {:.7f}, Test MAE norm: {:.7f}"
+
+
+def fit_regression(ctx, args, model, optimizer, scheduler, train, test, val_store, test_store, std, cmd_input, timed=True):
+    """Epoch loop of the MAE regression drivers (reference run_zinc.py:309-339, run_graphcount.py:585-613): train, validate,
+    step the plateau scheduler, test when validation improves or at the 10th epoch since the last test, append the line to
+    log.txt, checkpoint after the last epoch and print the closing lines.  `timed`: with "Training time cost".  Returns
+    the last log line."""
+    t1 = time.time()
+    best_val_error, count, log = None, 0, ""
+    for epoch in range(1, args.epochs + 1):
+        lr = optimizer.param_groups[0]["lr"]
+        loss = train(epoch)
+        val_error = test(val_store)
+        scheduler.step(val_error)
+        count += 1
+        if best_val_error is None:
+            best_val_error = val_error
+        if val_error <= best_val_error or count == 10:
+            count = 0
+            test_error = test(test_store)
+            best_val_error = val_error
+            log = EPOCH_LINE.format(epoch, lr, loss, val_error, test_error, test_error / float(std))
+            if ctx.rank == 0:
+                print("\n" + log + "\n")
+                with open(os.path.join(args.res_dir, "log.txt"), "a") as fh:
+                    fh.write(log + "\n")
+    if ctx.rank == 0:
+        torch.save(model.state_dict(), os.path.join(args.res_dir, "model_checkpoint{}.pth".format(args.epochs)))
+        if timed:
+            print("Training time cost: {}s".format(time.time() - t1))
+        print(cmd_input[:-1])
+        print(log)
+    return log
+
+
+# ---- classification runs (run_exp / run_csl; run_sr for find_data_file and the batch size) ----------------------------
+def find_data_file(root, names):
+    """`root` itself when it is a file, else the first of root/<name>, root/raw/<name> that exists; None otherwise"""
+    if os.path.isfile(root):
+        return root
+    for name in names:
+        for p in (os.path.join(root, name), os.path.join(root, "raw", name)):
+            if os.path.isfile(p):
+                return p
+    return None
+
+
+def labels_of(data):
+    """int64 class labels of a batch.  The device store keeps y as float32; 0 / 1 survive that exactly — checked."""
+    y = data.y.view(-1)
+    if y.dtype == torch.int64:
+        return y
+    yl = y.long()
+    assert torch.equal(yl.to(y.dtype), y), "graph labels are not integers"
+    return yl
+
+
+def classify_train(model, loader, optimizer, device):
+    """one epoch of F.nll_loss(log_softmax(logits), y) / F.cross_entropy(logits, y) -> mean loss per graph"""
+    model.train()
+    loss_all = 0
+    for data in loader:
+        optimizer.zero_grad()
+        data = data.to(device)
+        loss = ops.log_softmax_nll(model.logits(data), labels_of(data))
+        loss.backward()
+        loss_all += data.num_graphs * loss.item()
+        optimizer.step()
+    return loss_all / len(loader.dataset)
+
+
+def classify_test(model, loader, device):
+    """accuracy over the loader's graphs; the correct predictions are counted by the loss launch"""
+    model.eval()
+    correct = 0
+    with torch.no_grad():
+        for data in loader:
+            data = data.to(device)
+            correct += ops.log_softmax_nll(model.logits(data), labels_of(data), return_aux=True)[2]
+    return correct / len(loader.dataset)
+
+
+def print_final_result(acc, tr_acc):
+    """mean and standard deviation over the splits of the test and the train accuracy"""
+    acc, tr_acc = torch.tensor(acc, dtype=torch.float64), torch.tensor(tr_acc, dtype=torch.float64)
+    std = (lambda t: float(t.std()) if t.numel() > 1 else float("nan"))
+    print("---------------- Final Result ----------------")
+    print("Mean: {:7f}, Std: {:7f}".format(float(acc.mean()), std(acc)))
+    print("Tr Mean: {:7f}, Std: {:7f}".format(float(tr_acc.mean()), std(tr_acc)))

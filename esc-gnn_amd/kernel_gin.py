@@ -5,12 +5,11 @@ ReLU (:368-374), graph-level readout by global_mean_pool by default, log_softmax
 Same state_dict key layout as the reference class."""
 import torch
 import torch.nn.functional as F
-from torch.nn import Dropout, Sequential
 
-from . import ops
-from .nn import AbsorbedReLU, BatchNorm1d, GINEConv, Linear, global_mean_pool
+from . import nested
+from .nested import Z_TABLE_ROWS
+from .nn import BatchNorm1d, GINEConv, Linear, global_mean_pool
 from .plan import plan_of
-from .run_graphcount import Z_TABLE_ROWS, _bn_relu, _mlp
 
 
 class NestedGIN_eff(torch.nn.Module):
@@ -22,42 +21,24 @@ class NestedGIN_eff(torch.nn.Module):
         self.use_rd, self.use_z, self.graph_pred, self.use_cycle = use_rd, True, graph_pred, use_cycle
         self.use_id, self.dropout, self.multi_layer, self.edge_nest = use_id, dropout, multi_layer, edge_nest
         self.z_initial = torch.nn.Embedding(Z_TABLE_ROWS, hidden)
-        self.z_embedding = Sequential(Dropout(dropout), *_bn_relu(hidden), Linear(hidden, hidden),
-                                      Dropout(dropout), *_bn_relu(hidden))
+        self.z_embedding = nested.z_embedding(hidden, dropout=dropout)
         input_dim = dataset.num_features
-        self.conv1 = GINEConv(_mlp(input_dim, hidden, dropout), train_eps=True, edge_dim=hidden)
+        self.conv1 = GINEConv(nested.mlp(input_dim, hidden, dropout), train_eps=True, edge_dim=hidden)
         self.convs = torch.nn.ModuleList(
-            GINEConv(_mlp(hidden, hidden, dropout), train_eps=True, edge_dim=hidden) for _ in range(num_layers - 1))
+            GINEConv(nested.mlp(hidden, hidden, dropout), train_eps=True, edge_dim=hidden) for _ in range(num_layers - 1))
         self.lin1 = Linear(num_layers * hidden, hidden)
         self.bn_lin1 = BatchNorm1d(hidden, eps=1e-5, momentum=0.1)
         self.lin2 = Linear(hidden, 1 if use_cycle else dataset.num_classes)
 
     def reset_parameters(self):
-        for layer in self.z_embedding.children():
-            if hasattr(layer, "reset_parameters"):
-                layer.reset_parameters()
-        self.conv1.reset_parameters()
-        for conv in self.convs:
-            conv.reset_parameters()
-        self.lin1.reset_parameters()
-        self.bn_lin1.reset_parameters()
-        self.lin2.reset_parameters()
+        nested.reset_parameters(self, "z_embedding", "conv1", "convs", "lin1", "bn_lin1", "lin2")
 
     def forward(self, data):
         data.to(self.lin1.weight.device)
         x, edge_index, batch = data.x, data.edge_index, data.batch
         plan = plan_of(data, Z_TABLE_ROWS)
-        if "edge_pos" in data:
-            z = ops.linear(data.edge_pos.float(), self.z_initial.weight.t().contiguous())
-        else:
-            z = ops.esc_bag(self.z_initial.weight, plan)
-        z = self.z_embedding(z)
-        h = self.conv1(x.float(), edge_index, z, plan)
-        xs = [h]
-        for conv in self.convs:
-            h = conv(h, edge_index, z, plan)
-            xs.append(h)
-        o = torch.cat(xs, dim=1)
+        z = self.z_embedding(nested.edge_term(self.z_initial, data, plan))
+        o = torch.cat(nested.conv_stack(self, x.float(), edge_index, z, plan), dim=1)
         if self.graph_pred:
             o = global_mean_pool(o, batch)
         o = self.lin1(o)

@@ -11,12 +11,12 @@ device RNG like the reference; plain elementwise adds (virtual-node / residual s
 """
 import torch
 import torch.nn.functional as F
-from torch.nn import Dropout, Sequential
+from torch.nn import Sequential
 
-from . import ops
+from . import engine, nested, ops
+from .nested import Z_TABLE_ROWS
 from .nn import AbsorbedReLU, BatchNorm1d, Embedding, Linear, global_add_pool, global_mean_pool
 from .plan import plan_of
-from .run_graphcount import Z_TABLE_ROWS, _bn_relu
 
 ATOM_FEATURE_DIMS = (119, 5, 12, 12, 10, 6, 6, 2, 2)     # ogb.utils.features.get_atom_feature_dims() @1.3.3
 BOND_FEATURE_DIMS = (5, 6, 2)                            # ogb.utils.features.get_bond_feature_dims() @1.3.3
@@ -83,10 +83,8 @@ class GNN_node_efficient(torch.nn.Module):
         self.num_layer, self.drop_ratio, self.JK, self.residual = num_layer, drop_ratio, JK, residual
         self.virtual_node, self.use_rd, self.use_rp, self.adj_dropout = virtual_node, use_rd, use_rp, adj_dropout
         self.center_pool_virtual, self.RNI, self.skip_node_encoder = center_pool_virtual, RNI, skip_node_encoder
-        dropout = drop_ratio
         self.z_initial = torch.nn.Embedding(Z_TABLE_ROWS, emb_dim)
-        self.z_embedding = Sequential(Dropout(dropout), *_bn_relu(emb_dim), Linear(emb_dim, emb_dim), Dropout(dropout),
-                                      *_bn_relu(emb_dim))
+        self.z_embedding = nested.z_embedding(emb_dim, dropout=drop_ratio)
         if not skip_node_encoder:
             if dataset.startswith("ogbg-mol"):
                 self.node_encoder = AtomEncoder(emb_dim)
@@ -119,11 +117,7 @@ class GNN_node_efficient(torch.nn.Module):
         if self.virtual_node:
             vn = self.virtualnode_embedding(torch.zeros(num_graphs, dtype=edge_index.dtype, device=edge_index.device))
         h0 = x if self.skip_node_encoder else self.node_encoder(x)
-        if "edge_pos" in batched_data:
-            z = ops.linear(batched_data.edge_pos.float(), self.z_initial.weight.t().contiguous())
-        else:
-            z = ops.esc_bag(self.z_initial.weight, plan)
-        z = self.z_embedding(z)
+        z = self.z_embedding(nested.edge_term(self.z_initial, batched_data, plan))
         h_list = [h0]
         if perturb is not None:
             h_list[0] = h_list[0] + perturb
@@ -170,17 +164,12 @@ class GNN(torch.nn.Module):
         self.step_engine = True       # training-mode forward through the whole-step engine when the batch allows it
 
     def forward(self, data, perturb=None):
-        if self.training and torch.is_grad_enabled() and self.step_engine and perturb is None:
-            from .engine import ogb_engine_forward, ogb_engine_ready
+        if self.training == torch.is_grad_enabled() and self.step_engine and perturb is None:
             if data.edge_index.device != self.graph_pred_linear.weight.device:
                 data.to(self.graph_pred_linear.weight.device)
-            if ogb_engine_ready(self, data):
-                return ogb_engine_forward(self, data)      # one autograd node (csrc/engine.hip esc_ogb_*)
-        if not self.training and not torch.is_grad_enabled() and self.step_engine and perturb is None:
-            from .engine import ogb_engine_predict, ogb_engine_ready
-            if data.edge_index.device != self.graph_pred_linear.weight.device:
-                data.to(self.graph_pred_linear.weight.device)
-            if ogb_engine_ready(self, data):
-                return ogb_engine_predict(self, data)      # eval-mode forward as one call (esc_ogb_predict)
+            if engine.ogb_engine_ready(self, data):
+                if self.training:
+                    return engine.ogb_engine_forward(self, data)      # one autograd node (csrc/engine.hip esc_ogb_*)
+                return engine.ogb_engine_predict(self, data)          # eval-mode forward as one call (esc_ogb_predict)
         x = self.gnn_node(data, perturb=perturb)
         return self.graph_pred_linear(self.pool(x, data.batch))

@@ -6,12 +6,11 @@ Same constructor and state_dict key layout as the reference class.  Per-op path 
 that are multiples of 4, and this model's are 11 and 261."""
 import torch
 import torch.nn.functional as F
-from torch.nn import Dropout, Sequential
 
-from . import ops
+from . import nested, ops
+from .nested import Z_TABLE_ROWS
 from .nn import BatchNorm1d, GINEConv, Linear, global_mean_pool
 from .plan import plan_of
-from .run_graphcount import Z_TABLE_ROWS, _bn_relu, _mlp
 
 
 class NestedGIN_eff(torch.nn.Module):
@@ -22,12 +21,11 @@ class NestedGIN_eff(torch.nn.Module):
         hidden, dropout = 256, 0.0
         self.dropout = dropout
         self.z_initial = torch.nn.Embedding(Z_TABLE_ROWS, hidden)
-        self.z_embedding = Sequential(Dropout(dropout), *_bn_relu(hidden), Linear(hidden, hidden), Dropout(dropout),
-                                      *_bn_relu(hidden))
+        self.z_embedding = nested.z_embedding(hidden, dropout=dropout)
         input_dim = dataset.num_features + 3
-        self.conv1 = GINEConv(_mlp(input_dim, hidden, dropout), train_eps=True, edge_dim=hidden + edge_attr_dim)
+        self.conv1 = GINEConv(nested.mlp(input_dim, hidden, dropout), train_eps=True, edge_dim=hidden + edge_attr_dim)
         self.convs = torch.nn.ModuleList(
-            GINEConv(_mlp(hidden, hidden, dropout), train_eps=True, edge_dim=hidden + edge_attr_dim)
+            GINEConv(nested.mlp(hidden, hidden, dropout), train_eps=True, edge_dim=hidden + edge_attr_dim)
             for _ in range(num_layers - 1))
         self.lin1 = Linear(num_layers * hidden, hidden)
         self.bn_lin1 = BatchNorm1d(hidden, eps=1e-5, momentum=0.1, fuse_relu=True)    # dropout is 0 => ReLU follows BN
@@ -35,16 +33,7 @@ class NestedGIN_eff(torch.nn.Module):
         self.node_type_embedding = torch.nn.Embedding(5, input_dim)
 
     def reset_parameters(self):
-        for layer in self.z_embedding.children():
-            if hasattr(layer, "reset_parameters"):
-                layer.reset_parameters()
-        self.conv1.reset_parameters()
-        for conv in self.convs:
-            conv.reset_parameters()
-        self.lin1.reset_parameters()
-        self.bn_lin1.reset_parameters()
-        self.lin2.reset_parameters()
-        self.node_type_embedding.reset_parameters()
+        nested.reset_parameters(self, "z_embedding", "conv1", "convs", "lin1", "bn_lin1", "lin2", "node_type_embedding")
 
     def forward(self, data):
         data.to(self.lin1.weight.device)
@@ -58,15 +47,6 @@ class NestedGIN_eff(torch.nn.Module):
         x = ops.node_input(data.x, data.pos, data.node_type, self.node_type_embedding.weight)
         edge_index = data.edge_index
         plan = plan_of(data, Z_TABLE_ROWS)
-        if "edge_pos" in data:
-            z = ops.linear(data.edge_pos.float(), self.z_initial.weight.t().contiguous())
-        else:
-            z = ops.esc_bag(self.z_initial.weight, plan)
-        z = self.z_embedding(z)
+        z = self.z_embedding(nested.edge_term(self.z_initial, data, plan))
         z = torch.cat((z, data.edge_attr), dim=-1)
-        h = self.conv1(x, edge_index, z, plan)
-        xs = [h]
-        for conv in self.convs:
-            h = conv(h, edge_index, z, plan)
-            xs.append(h)
-        return torch.cat(xs, dim=1)
+        return torch.cat(nested.conv_stack(self, x, edge_index, z, plan), dim=1)

@@ -15,7 +15,8 @@ from an HBM-resident store (DataLoader).  Nothing is written to a log file.
 import torch
 
 from . import ops
-from .run_exp import labels_of
+from .harness import (Context, classify_test, classify_train, labels_of, parser_from, print_final_result,
+                      seed_everything)
 
 _FLAGS = [  # same names, types and defaults as the reference CLI
     ("--model", dict(type=str, default="GIN")),
@@ -38,18 +39,13 @@ EPOCH_LINE = ("Epoch: {:03d}, LR: {:7f}, Train Loss: {:.7f}, Val Loss: {:.7f}, V
 
 
 def build_parser():
-    import argparse
-    ap = argparse.ArgumentParser(description="Nested GNN for CSL datasets (MI355X hot path).")
-    for name, kw in _FLAGS:
-        ap.add_argument(name, **kw)
-    return ap
+    return parser_from(_FLAGS, "Nested GNN for CSL datasets (MI355X hot path).")
 
 
 def main(argv=None):
     from .csl_models import NestedGIN
     from .dataloader import DataLoader
     from .datasets import build_csl_dataset, csl_graphs, csl_k_fold
-    from .harness import Context, seed_everything
     from .optim import FlatAdam, ReduceLROnPlateau
 
     args = build_parser().parse_args(argv)
@@ -68,19 +64,6 @@ def main(argv=None):
     device = ctx.device
     model = NestedGIN(args.layers, args.width).to(device)
 
-    def train(loader, optimizer):
-        model.train()
-        total_loss = 0
-        for data in loader:
-            optimizer.zero_grad()
-            num_graphs = data.num_graphs
-            data = data.to(device)
-            loss = ops.log_softmax_nll(model.logits(data), labels_of(data))       # F.cross_entropy(out, y)
-            loss.backward()
-            total_loss += loss.item() * num_graphs
-            optimizer.step()
-        return total_loss / len(loader.dataset)
-
     def val(loader):
         model.eval()
         total_loss = 0
@@ -90,15 +73,6 @@ def main(argv=None):
                 data = data.to(device)
                 total_loss += ops.log_softmax_nll(model.logits(data), labels_of(data)).item() * num_graphs
         return total_loss / len(loader.dataset)
-
-    def test(loader):
-        model.eval()
-        correct = 0
-        with torch.no_grad():
-            for data in loader:
-                data = data.to(device)
-                correct += ops.log_softmax_nll(model.logits(data), labels_of(data), return_aux=True)[2]
-        return correct / len(loader.dataset)
 
     acc, tr_acc = [], []
     folds = csl_k_fold([int(d.y) for d in dataset], FOLDS)
@@ -115,23 +89,19 @@ def main(argv=None):
         best_val_loss, test_acc, train_acc = 100, 0, 0
         for epoch in range(args.epochs):
             lr = optimizer.param_groups[0]["lr"]
-            train_loss = train(train_loader, optimizer)
+            train_loss = classify_train(model, train_loader, optimizer, device)     # F.cross_entropy(out, y)
             val_loss = val(val_loader)
             scheduler.step(val_loss)
             if best_val_loss >= val_loss:
                 best_val_loss = val_loss
-            train_acc = test(train_loader)
-            val_acc = test(val_loader)
+            train_acc = classify_test(model, train_loader, device)
+            val_acc = classify_test(model, val_loader, device)
             test_loss = val(test_loader)
-            test_acc = test(test_loader)
+            test_acc = classify_test(model, test_loader, device)
             print(EPOCH_LINE.format(epoch + 1, lr, train_loss, val_loss, val_acc, test_loss, test_acc, train_acc))
         acc.append(test_acc)
         tr_acc.append(train_acc)
-    acc, tr_acc = torch.tensor(acc, dtype=torch.float64), torch.tensor(tr_acc, dtype=torch.float64)
-    std = (lambda t: float(t.std()) if t.numel() > 1 else float("nan"))
-    print("---------------- Final Result ----------------")
-    print("Mean: {:7f}, Std: {:7f}".format(float(acc.mean()), std(acc)))
-    print("Tr Mean: {:7f}, Std: {:7f}".format(float(tr_acc.mean()), std(tr_acc)))
+    print_final_result(acc, tr_acc)
     ctx.close()
 
 

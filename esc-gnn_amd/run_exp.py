@@ -14,7 +14,8 @@ logits); every batch is collated on the device from an HBM-resident store (DataL
 import torch
 
 from . import ops
-from .run_sr import BATCH, find_data_file
+from .harness import (BATCH, Context, classify_test, classify_train, find_data_file, labels_of, parser_from,
+                      print_final_result, seed_everything)
 
 _FLAGS = [  # same names, types and defaults as the reference CLI
     ("--model", dict(type=str, default="GIN")),
@@ -37,28 +38,13 @@ EPOCH_LINE = ("Epoch: {:03d}, LR: {:7f}, Train Loss: {:.7f}, Val Loss: {:.7f}, T
 
 
 def build_parser():
-    import argparse
-    ap = argparse.ArgumentParser(description="Nested GNN for EXP/CEXP datasets (MI355X hot path).")
-    for name, kw in _FLAGS:
-        ap.add_argument(name, **kw)
-    return ap
-
-
-def labels_of(data):
-    """int64 class labels of a batch.  The device store keeps y as float32; 0 / 1 survive that exactly — checked."""
-    y = data.y.view(-1)
-    if y.dtype == torch.int64:
-        return y
-    yl = y.long()
-    assert torch.equal(yl.to(y.dtype), y), "graph labels are not integers"
-    return yl
+    return parser_from(_FLAGS, "Nested GNN for EXP/CEXP datasets (MI355X hot path).")
 
 
 def main(argv=None):
     from .dataloader import DataLoader
     from .datasets import build_expressive_dataset, exp_split, load_exp_txt
     from .expressive_models import NestedGIN
-    from .harness import Context, seed_everything
     from .optim import FlatAdam, ReduceLROnPlateau
 
     args = build_parser().parse_args(argv)
@@ -79,18 +65,6 @@ def main(argv=None):
     device = ctx.device
     model = NestedGIN(dataset[0].num_features, args.layers, args.width).to(device)
 
-    def train(loader, optimizer):
-        model.train()
-        loss_all = 0
-        for data in loader:
-            data = data.to(device)
-            optimizer.zero_grad()
-            loss = ops.log_softmax_nll(model.logits(data), labels_of(data))     # F.nll_loss(model(data), data.y)
-            loss.backward()
-            loss_all += data.num_graphs * loss.item()
-            optimizer.step()
-        return loss_all / len(loader.dataset)
-
     def val(loader):
         model.eval()
         loss_all = 0
@@ -99,15 +73,6 @@ def main(argv=None):
                 data = data.to(device)
                 loss_all += ops.log_softmax_nll(model.logits(data), labels_of(data), reduction="sum").item()
         return loss_all / len(loader.dataset)
-
-    def test(loader):
-        model.eval()
-        correct = 0
-        with torch.no_grad():
-            for data in loader:
-                data = data.to(device)
-                correct += ops.log_softmax_nll(model.logits(data), labels_of(data), return_aux=True)[2]
-        return correct / len(loader.dataset)
 
     acc, tr_acc = [], []
     for i in range(args.splits):
@@ -127,23 +92,19 @@ def main(argv=None):
         best_val_loss, test_acc, train_acc = 100, 0, 0
         for epoch in range(args.epochs):
             lr = optimizer.param_groups[0]["lr"]
-            train_loss = train(train_loader, optimizer)
+            train_loss = classify_train(model, train_loader, optimizer, device)     # F.nll_loss(model(data), data.y)
             val_loss = val(val_loader)
             scheduler.step(val_loss)
             if best_val_loss >= val_loss:
                 best_val_loss = val_loss
-            train_acc = test(train_loader)
-            test_acc = test(test_loader)
-            test_exp_acc = test(test_exp_loader) if sub["exp"] else float("nan")
-            test_lrn_acc = test(test_lrn_loader) if sub["lrn"] else float("nan")
+            train_acc = classify_test(model, train_loader, device)
+            test_acc = classify_test(model, test_loader, device)
+            test_exp_acc = classify_test(model, test_exp_loader, device) if sub["exp"] else float("nan")
+            test_lrn_acc = classify_test(model, test_lrn_loader, device) if sub["lrn"] else float("nan")
             print(EPOCH_LINE.format(epoch + 1, lr, train_loss, val_loss, test_acc, test_exp_acc, test_lrn_acc, train_acc))
         acc.append(test_acc)
         tr_acc.append(train_acc)
-    acc, tr_acc = torch.tensor(acc, dtype=torch.float64), torch.tensor(tr_acc, dtype=torch.float64)
-    std = (lambda t: float(t.std()) if t.numel() > 1 else float("nan"))
-    print("---------------- Final Result ----------------")
-    print("Mean: {:7f}, Std: {:7f}".format(float(acc.mean()), std(acc)))
-    print("Tr Mean: {:7f}, Std: {:7f}".format(float(tr_acc.mean()), std(tr_acc)))
+    print_final_result(acc, tr_acc)
     ctx.close()
 
 

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .harness import Context, default_appendix, open_result_dir, parser_from, prefetched, sharded_batches
 from .ogb_mol_gnn import GNN
 
 _FLAGS = [  # same names, types and defaults as the reference CLI (its `type=bool` flags included: any non-empty
@@ -67,11 +68,7 @@ TASKS = {"ogbg-molhiv": (1, 0.0), "ogbg-molpcba": (128, 0.6)}     # (num_tasks, 
 
 
 def build_parser():
-    import argparse
-    ap = argparse.ArgumentParser(description="ESC-GNN for OGB molecular graphs (MI355X hot path).")
-    for name, kw in _FLAGS:
-        ap.add_argument(name, **kw)
-    return ap
+    return parser_from(_FLAGS, "ESC-GNN for OGB molecular graphs (MI355X hot path).")
 
 
 class StepLR(object):
@@ -93,7 +90,6 @@ def main(argv=None):
     import time
 
     from .datasets import build_feature_dataset, synthetic_ogbmol_graphs
-    from .harness import Context, default_appendix, open_result_dir, prefetched, sharded_batches
     from .metrics import Evaluator
     from .optim import FlatAdam
     from .parallel import broadcast_buffers, broadcast_parameters

@@ -18,6 +18,7 @@ ignores --use_pos and --use_max_dist; they are accepted and ignored here too.
 import torch
 
 from . import ops
+from .harness import Context, default_appendix, open_result_dir, parser_from, seed_everything, sharded_batches
 from .qm9_models import NestedGIN_eff
 
 # unit conversion of the 12 regression targets (reference :24-31): PyG's QM9 units back to the original ones
@@ -59,11 +60,7 @@ REFERENCE_FLAGS = tuple(name for name, _ in _FLAGS[:-2])
 
 
 def build_parser():
-    import argparse
-    ap = argparse.ArgumentParser(description="ESC-GNN for QM9 graphs (MI355X hot path).")
-    for name, kw in _FLAGS:
-        ap.add_argument(name, **kw)
-    return ap
+    return parser_from(_FLAGS, "ESC-GNN for QM9 graphs (MI355X hot path).")
 
 
 class _Features(object):
@@ -102,7 +99,6 @@ def main(argv=None):
     import os
     import time
 
-    from .harness import Context, default_appendix, open_result_dir, seed_everything, sharded_batches
     from .optim import FlatAdam, ReduceLROnPlateau
     from .store import DeviceGraphStore
 

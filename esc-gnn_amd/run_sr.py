@@ -7,11 +7,10 @@ libescgnn_hip.so, and the pairwise distances and the below-threshold count are o
 
     python -m esc_gnn_amd.run_sr --data_root data/sr25
 """
-import os
-
 import torch
 
 from . import ops
+from .harness import BATCH, Context, find_data_file, parser_from, seed_everything
 
 _FLAGS = [  # same names, types and defaults as the reference CLI
     ("--model", dict(type=str, default="GIN")),
@@ -25,27 +24,11 @@ _FLAGS = [  # same names, types and defaults as the reference CLI
     ("--data_root", dict(type=str, default="data/sr25", help="directory that holds raw/sr251256.g6 (or the file itself)")),
     ("--seed", dict(type=int, default=None, help="seed torch before the model is built (default: unseeded, as the reference)")),
 ]
-BATCH = 20
 THRESHOLD = 1e-2
 
 
 def build_parser():
-    import argparse
-    ap = argparse.ArgumentParser(description="Nested GNN on SR25 (MI355X hot path).")
-    for name, kw in _FLAGS:
-        ap.add_argument(name, **kw)
-    return ap
-
-
-def find_data_file(root, names):
-    """`root` itself when it is a file, else the first of root/<name>, root/raw/<name> that exists; None otherwise"""
-    if os.path.isfile(root):
-        return root
-    for name in names:
-        for p in (os.path.join(root, name), os.path.join(root, "raw", name)):
-            if os.path.isfile(p):
-                return p
-    return None
+    return parser_from(_FLAGS, "Nested GNN on SR25 (MI355X hot path).")
 
 
 def predictions(model, dataset, device):
@@ -62,7 +45,6 @@ def predictions(model, dataset, device):
 def main(argv=None):
     from .datasets import build_expressive_dataset, load_sr25
     from .expressive_models import NestedGIN
-    from .harness import Context, seed_everything
 
     args = build_parser().parse_args(argv)
     if args.model != "GIN":

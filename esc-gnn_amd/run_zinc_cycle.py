@@ -18,6 +18,8 @@ prints `Test MAE` as run_zinc does.
 import torch
 
 from . import ops
+from .harness import (Context, default_appendix, fit_regression, open_result_dir, parser_from, prefetched, seed_everything,
+                      sharded_batches)
 from .zinc_cycle_models import NestedGIN_eff
 
 _FLAGS = [  # same names, types and defaults as the reference CLI
@@ -68,11 +70,7 @@ _FLAGS = [  # same names, types and defaults as the reference CLI
 
 
 def build_parser():
-    import argparse
-    ap = argparse.ArgumentParser(description="ESC-GNN for ZINC cycle counting (MI355X hot path).")
-    for name, kw in _FLAGS:
-        ap.add_argument(name, **kw)
-    return ap
+    return parser_from(_FLAGS, "ESC-GNN for ZINC cycle counting (MI355X hot path).")
 
 
 def _load_splits(args):
@@ -85,10 +83,8 @@ def _load_splits(args):
 
 
 def main(argv=None):
-    import os
     import time
 
-    from .harness import Context, default_appendix, open_result_dir, prefetched, seed_everything, sharded_batches
     from .optim import FlatAdam, ReduceLROnPlateau
     from .parallel import broadcast_buffers, broadcast_parameters
     from .store import DeviceGraphStore
@@ -186,32 +182,7 @@ def main(argv=None):
         print("Test MAE: %.7f" % test(stores[2]))         # (the reference's branch cannot run: see the module docstring)
         ctx.close()
         return
-    t1 = time.time()
-    best_val_error, count, log = None, 0, ""
-    for epoch in range(1, args.epochs + 1):
-        lr = optimizer.param_groups[0]["lr"]
-        loss = train(epoch)
-        val_error = test(stores[1])
-        scheduler.step(val_error)
-        count += 1
-        if best_val_error is None:
-            best_val_error = val_error
-        if val_error <= best_val_error or count == 10:    # reference :318-321
-            count = 0
-            test_error = test(stores[2])
-            best_val_error = val_error
-            log = ("Epoch: {:03d}, LR: {:7f}, Loss: {:.7f}, Validation MAE: {:.7f}, "
-                   "Test MAE: {:.7f}, Test MAE norm: {:.7f}").format(epoch, lr, loss, val_error, test_error,
-                                                                     test_error / float(std))
-            if ctx.rank == 0:
-                print("\n" + log + "\n")
-                with open(os.path.join(args.res_dir, "log.txt"), "a") as fh:
-                    fh.write(log + "\n")
-    if ctx.rank == 0:
-        torch.save(model.state_dict(), os.path.join(args.res_dir, "model_checkpoint{}.pth".format(args.epochs)))
-        print("Training time cost: {}s".format(time.time() - t1))
-        print(cmd_input[:-1])
-        print(log)
+    fit_regression(ctx, args, model, optimizer, scheduler, train, test, stores[1], stores[2], std, cmd_input)
     ctx.close()
 
 

@@ -3,7 +3,6 @@ zinc_models.NestedGIN_eff.  The two class bodies differ in one line: the cycle m
 cat(xs) row by row, bn_lin1 normalises over the nodes and lin2 predicts one value per node (the 3..6-cycles through it,
 run_zinc_cycle.py).  Same constructor, parameters and state_dict keys as zinc_models.NestedGIN_eff; the training and eval
 forwards run through the ZINC step engine with node_readout = 1 (csrc/engine.hip esc_zinc_*)."""
-import torch
 import torch.nn.functional as F
 
 from . import zinc_models
@@ -12,16 +11,7 @@ from . import zinc_models
 class NestedGIN_eff(zinc_models.NestedGIN_eff):
     node_readout = True            # esc_zinc_gin_t.node_readout: pred / y / loss per node
 
-    def forward(self, data):
-        data.to(self.lin1.weight.device)
-        if self.training and torch.is_grad_enabled() and self.step_engine:
-            from .engine import zinc_engine_forward, zinc_engine_ready
-            if zinc_engine_ready(self, data):
-                return zinc_engine_forward(self, data)     # the whole step as one autograd node (csrc/engine.hip esc_zinc_*)
-        if not self.training and not torch.is_grad_enabled() and self.step_engine:
-            from .engine import zinc_engine_predict, zinc_engine_ready
-            if zinc_engine_ready(self, data):
-                return zinc_engine_predict(self, data)     # eval-mode forward as one call (esc_zinc_predict)
-        o = self.lin1(self._node_states(data))             # reference :601-602: no pooling
+    def _readout(self, states, data):
+        o = self.lin1(states)                              # reference :601-602: no pooling
         o = self.bn_lin1(o) if o.size(0) > 1 else F.elu(o)  # :603-607 (dropout p = 0; ELU fused into the BatchNorm)
         return self.lin2(o)

@@ -4,20 +4,11 @@ the ESC bag kernels), edge term = [z_emb | edge_type_embedding] (edge_dim = 256 
 readout (HIP segment-pool), dropout 0.  Same constructor and state_dict key layout as the reference class."""
 import torch
 import torch.nn.functional as F
-from torch.nn import Dropout, Sequential
 
-from . import ops
-from .nn import AbsorbedELU, BatchNorm1d, Embedding, GINEConv, Linear, global_add_pool
+from . import engine, nested
+from .nested import Z_TABLE_ROWS
+from .nn import BatchNorm1d, Embedding, GINEConv, Linear, global_add_pool
 from .plan import plan_of
-from .run_graphcount import Z_TABLE_ROWS
-
-
-def _bn_elu(hidden):
-    return BatchNorm1d(hidden, fuse_relu="elu"), AbsorbedELU()
-
-
-def _mlp_elu(n_in, hidden, p):
-    return Sequential(Linear(n_in, hidden), Dropout(p), *_bn_elu(hidden), Linear(hidden, hidden), Dropout(p), *_bn_elu(hidden))
 
 
 class NestedGIN_eff(torch.nn.Module):
@@ -28,12 +19,11 @@ class NestedGIN_eff(torch.nn.Module):
         hidden, dropout = 256, 0.0
         self.dropout = dropout
         self.z_initial = torch.nn.Embedding(Z_TABLE_ROWS, hidden)
-        self.z_embedding = Sequential(Dropout(dropout), *_bn_elu(hidden), Linear(hidden, hidden), Dropout(dropout),
-                                      *_bn_elu(hidden))
+        self.z_embedding = nested.z_embedding(hidden, "elu", dropout)
         input_dim, edge_attr_dim = 32, 32
-        self.conv1 = GINEConv(_mlp_elu(input_dim, hidden, dropout), train_eps=True, edge_dim=hidden + edge_attr_dim)
+        self.conv1 = GINEConv(nested.mlp(input_dim, hidden, dropout, "elu"), train_eps=True, edge_dim=hidden + edge_attr_dim)
         self.convs = torch.nn.ModuleList(
-            GINEConv(_mlp_elu(hidden, hidden, dropout), train_eps=True, edge_dim=hidden + edge_attr_dim)
+            GINEConv(nested.mlp(hidden, hidden, dropout, "elu"), train_eps=True, edge_dim=hidden + edge_attr_dim)
             for _ in range(num_layers - 1))
         self.lin1 = Linear(num_layers * hidden, hidden)
         self.bn_lin1 = BatchNorm1d(hidden, eps=1e-5, momentum=0.1, fuse_relu="elu")   # dropout is 0 => ELU follows BN
@@ -42,30 +32,20 @@ class NestedGIN_eff(torch.nn.Module):
         self.edge_type_embedding = Embedding(100, 32)
 
     def reset_parameters(self):
-        for layer in self.z_embedding.children():
-            if hasattr(layer, "reset_parameters"):
-                layer.reset_parameters()
-        self.conv1.reset_parameters()
-        for conv in self.convs:
-            conv.reset_parameters()
-        self.lin1.reset_parameters()
-        self.bn_lin1.reset_parameters()
-        self.lin2.reset_parameters()
-        self.node_type_embedding.reset_parameters()
-        self.edge_type_embedding.reset_parameters()
+        nested.reset_parameters(self, "z_embedding", "conv1", "convs", "lin1", "bn_lin1", "lin2", "node_type_embedding",
+                                "edge_type_embedding")
 
     def forward(self, data):
         data.to(self.lin1.weight.device)
-        if self.training and torch.is_grad_enabled() and self.step_engine:
-            from .engine import zinc_engine_forward, zinc_engine_ready
-            if zinc_engine_ready(self, data):
-                return zinc_engine_forward(self, data)     # the whole step as one autograd node (csrc/engine.hip esc_zinc_*)
-        if not self.training and not torch.is_grad_enabled() and self.step_engine:
-            from .engine import zinc_engine_predict, zinc_engine_ready
-            if zinc_engine_ready(self, data):
-                return zinc_engine_predict(self, data)     # eval-mode forward as one call (esc_zinc_predict)
-        o = global_add_pool(self._node_states(data), data.batch)
-        o = self.lin1(o)
+        if self.step_engine and self.training == torch.is_grad_enabled() and engine.zinc_engine_ready(self, data):
+            if self.training:
+                return engine.zinc_engine_forward(self, data)     # the whole step as one autograd node (esc_zinc_*)
+            return engine.zinc_engine_predict(self, data)         # eval-mode forward as one call (esc_zinc_predict)
+        return self._readout(self._node_states(data), data)
+
+    def _readout(self, states, data):
+        """what follows the engine dispatch (reference :600-610); zinc_cycle_models overrides it"""
+        o = self.lin1(global_add_pool(states, data.batch))
         o = self.bn_lin1(o) if o.size(0) > 1 else F.elu(o)      # reference :606-609 (dropout p = 0)
         return self.lin2(o)
 
@@ -73,15 +53,6 @@ class NestedGIN_eff(torch.nn.Module):
         """cat(xs) of the per-op path (reference :581-598): the embeddings, the edge term and the GINE layers"""
         x, edge_index = self.node_type_embedding(data.x.view(-1)), data.edge_index
         plan = plan_of(data, Z_TABLE_ROWS)
-        if "edge_pos" in data:
-            z = ops.linear(data.edge_pos.float(), self.z_initial.weight.t().contiguous())
-        else:
-            z = ops.esc_bag(self.z_initial.weight, plan)
-        z = self.z_embedding(z)
+        z = self.z_embedding(nested.edge_term(self.z_initial, data, plan))
         z = torch.cat((z, self.edge_type_embedding(data.edge_attr.view(-1))), dim=-1)
-        h = self.conv1(x, edge_index, z, plan)
-        xs = [h]
-        for conv in self.convs:
-            h = conv(h, edge_index, z, plan)
-            xs.append(h)
-        return torch.cat(xs, dim=1)
+        return torch.cat(nested.conv_stack(self, x, edge_index, z, plan), dim=1)
