@@ -13,6 +13,9 @@
 namespace esc {
 
 constexpr int NORM_ROWBLOCKS = 512;          // scratch sizing: most row blocks (= workgroups per column block) ever used
+// the fused-activation codes (0 none, 1 ReLU, 2 ELU): any other value would be ELU in the float4 kernels and the identity in the
+// scalar ones, so the entry points refuse it
+static inline bool act_code_ok(int act) { return act >= 0 && act <= 2; }
 
 // fused activation after the affine: 0 none, 1 ReLU, 2 ELU(alpha=1) (zinc_models.py:513-522 uses ELU)
 __device__ __forceinline__ float act_fwd(float v, int act) {
@@ -34,6 +37,13 @@ __device__ __forceinline__ float act_grad_from_out(float y, int act) {
 __device__ __forceinline__ float pre_act_fwd(float x, float mu, float is, float ga, float be) {
   const float sc = ga * is;
   return fmaf(x, sc, be - mu * sc);
+}
+// The pre-activation the backward differentiates when the output was never materialised.  ReLU: the forward's own expression
+// (above), its mask must be the forward's.  ELU has no mask to agree with, but its derivative exp(v) carries the ABSOLUTE
+// error of v, and the fused form loses |mean * scale| * 2^-24 of it to cancellation (|mean| / sigma = 1e3: 20 times the 1e-5
+// parity bar in dgamma / dbeta) — the centred form gamma * xhat + beta does not.
+__device__ __forceinline__ float pre_act_bwd(float x, float xh, float mu, float is, float ga, float be, int act) {
+  return act == 2 ? fmaf(xh, ga, be) : pre_act_fwd(x, mu, is, ga, be);
 }
 // ... or through the pre-activation v when the output was never materialised
 __device__ __forceinline__ float act_grad_from_pre(float v, int act) {
@@ -150,8 +160,8 @@ __device__ __forceinline__ void bn_bwd_partial_body(const float* __restrict__ X,
           g.x *= act_grad_from_out(y.x, relu); g.y *= act_grad_from_out(y.y, relu);
           g.z *= act_grad_from_out(y.z, relu); g.w *= act_grad_from_out(y.w, relu);
         } else {
-          g.x *= act_grad_from_pre(pre_act_fwd(x.x, mu.x, is.x, ga.x, be.x), relu); g.y *= act_grad_from_pre(pre_act_fwd(x.y, mu.y, is.y, ga.y, be.y), relu);
-          g.z *= act_grad_from_pre(pre_act_fwd(x.z, mu.z, is.z, ga.z, be.z), relu); g.w *= act_grad_from_pre(pre_act_fwd(x.w, mu.w, is.w, ga.w, be.w), relu);
+          g.x *= act_grad_from_pre(pre_act_bwd(x.x, xh.x, mu.x, is.x, ga.x, be.x, relu), relu); g.y *= act_grad_from_pre(pre_act_bwd(x.y, xh.y, mu.y, is.y, ga.y, be.y, relu), relu);
+          g.z *= act_grad_from_pre(pre_act_bwd(x.z, xh.z, mu.z, is.z, ga.z, be.z, relu), relu); g.w *= act_grad_from_pre(pre_act_bwd(x.w, xh.w, mu.w, is.w, ga.w, be.w, relu), relu);
         }
       }
       s1.x += g.x; s1.y += g.y; s1.z += g.z; s1.w += g.w;
@@ -316,7 +326,7 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __rest
     const float xv = X[(size_t)r * ldx + c];
     const float xh = (xv - mu) * is;
     if (relu) {   // activation derivative from the forward output (if kept) or from the recomputed pre-activation
-      g *= Y ? act_grad_from_out(Y[(size_t)r * ldy + c], relu) : act_grad_from_pre(pre_act_fwd(xv, mu, is, ga, be), relu);
+      g *= Y ? act_grad_from_out(Y[(size_t)r * ldy + c], relu) : act_grad_from_pre(pre_act_bwd(xv, xh, mu, is, ga, be, relu), relu);
     }
     s1 += g;
     s2 = fmaf(g, xh, s2);
@@ -347,6 +357,11 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float2* __re
   }
 }
 
+// dX MAY BE dY (include/escgnn_hip.h promises it, engine.hip relies on it) although both are __restrict__: every thread loads
+// the dY elements of an iteration before it stores the dX elements at the SAME addresses, and no other thread touches them.
+// Keep it so — no load of dY (a prefetch of the next row, say) may be moved behind a store to dX of an earlier iteration
+// unless the two are different rows.  The same holds for bn_bwd_apply_rows_body and bn_bwd_node_kernel below;
+// tests/test_hip_norm_dispatch.py compares in-place with out-of-place results bit for bit on every path.
 template <int VEC, int ACT, bool HAS_Y>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ X, int64_t ldx,
                                                            const float* __restrict__ Y, int64_t ldy,
@@ -386,7 +401,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
       float g = gv[t];
       if constexpr (ACT != 0) {
         if constexpr (HAS_Y) g *= act_grad_from_out(yv[t], relu);
-        else g *= act_grad_from_pre(pre_act_fwd(xv[t], mean[c + t], is, gamma ? gamma[c + t] : 1.f, beta ? beta[c + t] : 0.f), relu);
+        else g *= act_grad_from_pre(pre_act_bwd(xv[t], xh, mean[c + t], is, gamma ? gamma[c + t] : 1.f, beta ? beta[c + t] : 0.f, relu), relu);
       }
       const float2 k = coef[c + t];
       ov[t] = (gamma ? gamma[c + t] : 1.f) * is * (g - k.x - xh * k.y);
@@ -408,6 +423,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
 // costs more than 64 extra loads per lane.
 // DROP_IN: as in the partial kernel (g = dY * keep / (1-p)); DROP_OUT: X itself was dropout(input), so the result is
 // multiplied by ITS keep mask / (1-p) on the way out (z_embedding's Dropout -> BatchNorm order, ogb_mol_gnn.py:638-645)
+// (dX may be dY: see bn_bwd_apply_kernel — a row's dY is loaded before its dX is stored, by the same lane)
 template <int ACT, bool HAS_Y, bool FOLD, bool DROP_IN, bool DROP_OUT>
 __device__ __forceinline__ void bn_bwd_apply_rows_body(const float* __restrict__ X, int64_t ldx,
                                                          const float* __restrict__ Y, int64_t ldy,
@@ -464,8 +480,8 @@ __device__ __forceinline__ void bn_bwd_apply_rows_body(const float* __restrict__
         g.x *= act_grad_from_out(y.x, relu); g.y *= act_grad_from_out(y.y, relu);
         g.z *= act_grad_from_out(y.z, relu); g.w *= act_grad_from_out(y.w, relu);
       } else {
-        g.x *= act_grad_from_pre(pre_act_fwd(x.x, mu.x, is.x, ga.x, be.x), relu); g.y *= act_grad_from_pre(pre_act_fwd(x.y, mu.y, is.y, ga.y, be.y), relu);
-        g.z *= act_grad_from_pre(pre_act_fwd(x.z, mu.z, is.z, ga.z, be.z), relu); g.w *= act_grad_from_pre(pre_act_fwd(x.w, mu.w, is.w, ga.w, be.w), relu);
+        g.x *= act_grad_from_pre(pre_act_bwd(x.x, xh.x, mu.x, is.x, ga.x, be.x, relu), relu); g.y *= act_grad_from_pre(pre_act_bwd(x.y, xh.y, mu.y, is.y, ga.y, be.y, relu), relu);
+        g.z *= act_grad_from_pre(pre_act_bwd(x.z, xh.z, mu.z, is.z, ga.z, be.z, relu), relu); g.w *= act_grad_from_pre(pre_act_bwd(x.w, xh.w, mu.w, is.w, ga.w, be.w, relu), relu);
       }
     }
     // same expression as bn_bwd_apply_kernel: gamma * invstd * (g - k.x - xhat * k.y)
@@ -683,8 +699,8 @@ __global__ __launch_bounds__(256) void bn_bwd_node_kernel(const float* __restric
             g.x *= act_grad_from_out(y.x, relu); g.y *= act_grad_from_out(y.y, relu);
             g.z *= act_grad_from_out(y.z, relu); g.w *= act_grad_from_out(y.w, relu);
           } else {
-            g.x *= act_grad_from_pre(pre_act_fwd(x.x, mu.x, is.x, ga.x, be.x), relu); g.y *= act_grad_from_pre(pre_act_fwd(x.y, mu.y, is.y, ga.y, be.y), relu);
-            g.z *= act_grad_from_pre(pre_act_fwd(x.z, mu.z, is.z, ga.z, be.z), relu); g.w *= act_grad_from_pre(pre_act_fwd(x.w, mu.w, is.w, ga.w, be.w), relu);
+            g.x *= act_grad_from_pre(pre_act_bwd(x.x, xh.x, mu.x, is.x, ga.x, be.x, relu), relu); g.y *= act_grad_from_pre(pre_act_bwd(x.y, xh.y, mu.y, is.y, ga.y, be.y, relu), relu);
+            g.z *= act_grad_from_pre(pre_act_bwd(x.z, xh.z, mu.z, is.z, ga.z, be.z, relu), relu); g.w *= act_grad_from_pre(pre_act_bwd(x.w, xh.w, mu.w, is.w, ga.w, be.w, relu), relu);
           }
         }
         s1.x += g.x; s1.y += g.y; s1.z += g.z; s1.w += g.w;
@@ -835,6 +851,7 @@ int esc_affine_act_fold(const float* X, int64_t ld_x, int64_t M, int64_t C, cons
   ESC_REQUIRE(M > 1 && M < (1LL << 31) && C > 0 && C % 4 == 0 && bn->C == C && bn->rows > 1 && bn->block_rows > 0 && ld_x >= C && ld_y >= C &&
               ld_x % 4 == 0 && ld_y % 4 == 0 && aligned16(X) && aligned16(Y), "esc_affine_act_fold: bad sizes / alignment");
   ESC_REQUIRE((bn->scale == nullptr) == (bn->shift == nullptr), "esc_affine_act_fold: scale/shift must come together");
+  ESC_REQUIRE(act_code_ok(relu), "esc_affine_act_fold: relu must be 0 (none), 1 (ReLU) or 2 (ELU), got %d", relu);
   BnFoldDev f{reinterpret_cast<const float2*>(bn->partials), (int)cdiv(bn->rows, bn->block_rows), (int)bn->block_rows, (int)bn->rows,
               (int)bn->C, bn->eps, bn->momentum, bn->gamma, bn->beta, bn->mean, bn->invstd, bn->scale, bn->shift,
               bn->running_mean, bn->running_var};
@@ -852,6 +869,7 @@ int esc_bn_apply(const float* X, int64_t ld_x, int64_t M, int64_t C, const float
                  int64_t ld_y, void* stream) {
   ESC_REQUIRE(X && Y && mean && invstd, "esc_bn_apply: null pointer");
   ESC_REQUIRE(M >= 0 && C > 0 && ld_x >= C && ld_y >= C, "esc_bn_apply: bad sizes");
+  ESC_REQUIRE(act_code_ok(relu), "esc_bn_apply: relu must be 0 (none), 1 (ReLU) or 2 (ELU), got %d", relu);
   if (M == 0) return ESC_OK;
   hipStream_t s = (hipStream_t)stream;
   const bool vec = (C % 4 == 0) && (ld_x % 4 == 0) && (ld_y % 4 == 0) && aligned16(X) && aligned16(Y);
@@ -867,6 +885,7 @@ int esc_affine_act(const float* X, int64_t ld_x, int64_t M, int64_t C, const flo
                    int relu, float* Y, int64_t ld_y, void* stream) {
   ESC_REQUIRE(X && Y && scale && shift, "esc_affine_act: null pointer");
   ESC_REQUIRE(M >= 0 && C > 0 && ld_x >= C && ld_y >= C, "esc_affine_act: bad sizes");
+  ESC_REQUIRE(act_code_ok(relu), "esc_affine_act: relu must be 0 (none), 1 (ReLU) or 2 (ELU), got %d", relu);
   if (M == 0) return ESC_OK;
   hipStream_t s = (hipStream_t)stream;
   const bool vec = (C % 4 == 0) && (ld_x % 4 == 0) && (ld_y % 4 == 0) && aligned16(X) && aligned16(Y) &&
@@ -992,6 +1011,7 @@ int esc_bn_bwd(const float* X, int64_t ld_x, const float* Y, int64_t ld_y, const
                float* dbeta, float* scratch, void* stream) {
   ESC_REQUIRE(X && dY && dX && mean && invstd && scratch, "esc_bn_bwd: null pointer");
   ESC_REQUIRE(M > 0 && C > 0 && ld_x >= C && ld_dy >= C && ld_dx >= C && (!Y || ld_y >= C) && M < (1LL << 31), "esc_bn_bwd: bad sizes");
+  ESC_REQUIRE(act_code_ok(relu), "esc_bn_bwd: relu must be 0 (none), 1 (ReLU) or 2 (ELU), got %d", relu);
   hipStream_t s = (hipStream_t)stream;
   float2* partial = (float2*)scratch;
   float2* coef = partial + (size_t)NORM_ROWBLOCKS * 4 * C;
@@ -1088,6 +1108,7 @@ int esc_bn_bwd_sums(const float* X, int64_t ld_x, const float* Y, int64_t ld_y, 
                     float* dbeta, float* scratch, void* stream) {
   ESC_REQUIRE(X && dY && sums && mean && invstd && scratch, "esc_bn_bwd_sums: null pointer");
   ESC_REQUIRE(M > 0 && C > 0 && ld_x >= C && ld_dy >= C && (!Y || ld_y >= C) && M < (1LL << 31), "esc_bn_bwd_sums: bad sizes");
+  ESC_REQUIRE(act_code_ok(relu), "esc_bn_bwd_sums: relu must be 0 (none), 1 (ReLU) or 2 (ELU), got %d", relu);
   return bn_bwd_reduce(X, ld_x, Y, ld_y, dY, ld_dy, M, C, mean, invstd, gamma, beta, relu, 1, false, dgamma, dbeta,
                        (float2*)scratch, (float2*)sums, (hipStream_t)stream);
 }
@@ -1097,6 +1118,7 @@ int esc_bn_bwd_coef(const float* X, int64_t ld_x, const float* Y, int64_t ld_y, 
                     float* coef, float* dgamma, float* dbeta, float* scratch, void* stream) {
   ESC_REQUIRE(X && dY && coef && mean && invstd && scratch, "esc_bn_bwd_coef: null pointer");
   ESC_REQUIRE(M > 0 && C > 0 && ld_x >= C && ld_dy >= C && (!Y || ld_y >= C) && M < (1LL << 31), "esc_bn_bwd_coef: bad sizes");
+  ESC_REQUIRE(act_code_ok(relu), "esc_bn_bwd_coef: relu must be 0 (none), 1 (ReLU) or 2 (ELU), got %d", relu);
   return bn_bwd_reduce(X, ld_x, Y, ld_y, dY, ld_dy, M, C, mean, invstd, gamma, beta, relu, M, true, dgamma, dbeta,
                        (float2*)scratch, (float2*)coef, (hipStream_t)stream);
 }
@@ -1116,6 +1138,7 @@ int esc_bn_bwd_apply(const float* X, int64_t ld_x, const float* Y, int64_t ld_y,
                      int64_t ld_dx, void* stream) {
   ESC_REQUIRE(X && dY && dX && mean && invstd && coef, "esc_bn_bwd_apply: null pointer");
   ESC_REQUIRE(M > 0 && C > 0 && ld_x >= C && ld_dy >= C && ld_dx >= C && (!Y || ld_y >= C) && M < (1LL << 31), "esc_bn_bwd_apply: bad sizes");
+  ESC_REQUIRE(act_code_ok(relu), "esc_bn_bwd_apply: relu must be 0 (none), 1 (ReLU) or 2 (ELU), got %d", relu);
   return bn_bwd_apply_impl(X, ld_x, Y, ld_y, dY, ld_dy, M, C, mean, invstd, gamma, beta, relu, (const float2*)coef, dX,
                            ld_dx, (hipStream_t)stream);
 }

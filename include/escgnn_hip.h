@@ -347,6 +347,7 @@ int esc_bn_bwd_coef_from_partials(const float* partial, int64_t slots, int64_t M
 /* ---- BatchNorm1d (training statistics) + ReLU, torch.nn.BatchNorm1d call sites
  * run_graphcount.py:55-60,66-72,80-87,115 --------------------------------------------------
  * `relu` arguments below select the fused activation: 0 none, 1 ReLU, 2 ELU(alpha=1) (zinc_models.py:513-522).
+ * Any other code is refused (ESC_EINVAL) before a launch.
  * stats: mean[C], invstd[C] of X[M,C] (biased variance, eps), optional running-stat update
  * (momentum, unbiased variance) exactly as torch does; then Y = relu?(gamma*(X-mean)*invstd+beta). */
 int64_t esc_bn_scratch(int64_t C);      /* floats of scratch the three calls below need */
@@ -365,7 +366,7 @@ int esc_bn_stats_from_partials_rows(const float* partials, int64_t M, int64_t C,
                                     float momentum, float* mean, float* invstd, float* running_mean,
                                     float* running_var, const float* gamma, const float* beta, float* scale,
                                     float* shift, void* stream);
-/* Y = act(BN(X)) with the BatchNorm still in partial form (bn->C == C <= 1024, C % 4 == 0, 16-byte aligned rows) */
+/* Y = act(BN(X)) with the BatchNorm still in partial form (bn->C == C, C % 4 == 0, 16-byte aligned rows) */
 int esc_affine_act_fold(const float* X, int64_t ld_x, int64_t M, int64_t C, const esc_bn_fold* bn, int relu, float* Y,
                         int64_t ld_y, void* stream);
 int esc_bn_apply(const float* X, int64_t ld_x, int64_t M, int64_t C, const float* mean,

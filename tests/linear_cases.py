@@ -229,6 +229,27 @@ class Buf(object):
         return self.view(self.dev.cpu())
 
 
+class ByteBuf(object):
+    """A dense [rows, width] uint8 operand (a dropout keep mask) with `guard` bytes of `outside` in front and behind; its first
+    byte is 16-byte aligned + offset_bytes"""
+
+    def __init__(self, live, guard, device, outside=0xA5, offset_bytes=0):
+        front = cdiv(guard, 16) * 16
+        self.base, self.n = front + offset_bytes, live.numel()
+        self.host = torch.full((self.base + self.n + guard,), outside, dtype=torch.uint8)
+        self.host[self.base:self.base + self.n] = live.reshape(-1)
+        raw = torch.empty(self.host.numel() + 16, dtype=torch.uint8, device=device)
+        skew = (-raw.data_ptr()) % 16
+        self.dev = raw[skew:skew + self.host.numel()]
+        self.dev.copy_(self.host)
+
+    def ptr(self):
+        return self.dev.data_ptr() + self.base
+
+    def untouched(self):
+        return torch.equal(self.dev.cpu(), self.host)
+
+
 def _uniform(rows, width, seed):
     g = torch.Generator().manual_seed(seed)
     return torch.rand(rows, width, generator=g) * 2 - 1
