@@ -140,6 +140,7 @@ bool bn_bwd_fold();                    // node-sized BatchNorm backward: the app
 void set_bn_bwd_fold(int on);
 bool last_block_finalize();
 void set_last_block_finalize(int on);
+void set_linear_knob(int knob, int value);      // the Linear dispatch's knobs 0..7 and 11 (linear_mfma.hip owns the state, linear_plan.h reads it)
 
 // Partials that the last workgroup will read are written with agent-scope (write-through, `sc1`) stores: they
 // become visible device-wide when the store is acknowledged, so the publishing workgroups need NO L2 write-back /

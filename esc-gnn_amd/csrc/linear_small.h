@@ -9,14 +9,12 @@
 // (the N <= 16 forward rides on a 64x32 tile of gemm_dma.h, the K-wide dX of an N <= 16 layer is linear_narrow_dx).
 #pragma once
 #include "common.h"
+#include "linear_plan.h"
 
 namespace esc {
 namespace small {
 
-constexpr int SMALL_MAX = 16;
-constexpr int ROWS_FWD = 32;          // rows per workgroup = rows per BatchNorm partial (the GEMM epilogue's contract)
-constexpr int SMALLN_DX_MAX_N = ((160 * 1024 / 4) / (32 + SMALL_MAX) - 4) & ~3;      // 848: smalln_dx keeps [32 + SMALL_MAX][N + 4] floats in the 160 KiB LDS
-constexpr int ROWS_WGRAD = 32;        // reduction rows per slab (a slab is N*K <= 16*1280 floats: hundreds of them are cheap to sum)
+// SMALL_MAX, ROWS_FWD, SMALLN_DX_MAX_N, ROWS_WGRAD: linear_plan.h (the dispatch reads them too)
 
 // thread = output column n; the K weights of its column live in registers; X rows are workgroup-uniform scalars
 template <int KMAX>

@@ -1,5 +1,6 @@
 // runtime.hip — error reporting + HIP-event kernel-family profiler of libescgnn_hip.so
 #include "common.h"
+#include "linear_plan.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -112,6 +113,23 @@ unsigned* tickets(int n) {
 }  // namespace esc
 
 extern "C" {
+
+// tuning knobs, one numbering for the whole library:
+//   0..7  the Linear dispatch: forward tile edge-sized / node-sized, dX tile edge-sized / node-sized, dW tile, dW workgroups wanted,
+//         dW least rows per split, node-sized dual-launch tile (plan::PlanKnobs in linear_plan.h; tile ids: plan::R01_TILE)
+//   8     BatchNorm finalize in the GEMM's last workgroup       9   workgroups per column block of the BatchNorm reductions
+//   10    dynamic-LDS floor of the edge stream's GEMMs          11  kernel-family mask of the Linear dispatch (plan::PlanKnobs::use_dma)
+//   12    BatchNorm backward: the apply kernel folds the partials     13  BatchNorm backward in one launch
+int esc_tune_set(int knob, int value) {
+  if (knob == 8) { esc::set_last_block_finalize(value); return ESC_OK; }
+  if (knob == 9) { esc::set_norm_rowblock_cap(value); return ESC_OK; }
+  if (knob == 12) { esc::set_bn_bwd_fold(value); return ESC_OK; }
+  if (knob == 13) { esc::set_bn_bwd_one_launch(value); return ESC_OK; }
+  if (knob == 10) { esc::set_edge_lds_floor(value); return ESC_OK; }
+  ESC_REQUIRE(knob == 11 || (knob >= 0 && knob < esc::plan::KNOB_COUNT), "esc_tune_set: unknown knob %d", knob);
+  esc::set_linear_knob(knob, value);
+  return ESC_OK;
+}
 
 int esc_abi_version(void) { return 8; }   // 8: esc_edge_distance, esc_node_input_fwd / _bwd, esc_mse_loss; 7: esc_engine_set_gemm_stats, esc_engine_set_materialise_edge_act, esc_linear_bwd_set_wgrad_stream removed; 6: esc_collate_args rebuilt on the staged block + int32 store views, esc_collate_cols lost col_ptr, esc_nested_gin_t.counters; 5: esc_graphlet_counts; 4: esc_zinc_gin_t.node_readout, esc_cycle_counts; 2: esc_features_* take sum_nodes_sq; esc_zinc_*, esc_embed_*; 3: esc_collate_args grew (edge_attr, x_long, graph_ptr), esc_embed_plan
 const char* esc_last_error(void) { return esc::g_err; }

@@ -16,8 +16,10 @@ A case is Case(name, entry, M, N, K, layout, prologue, bias, accumulate, family,
   family      the kernel family the case is MEANT to reach (family_of documents why)
   dx          bwd_both only: False passes dX == NULL
 
-family_of() transcribes the dispatchers' predicates.  It is documentation of intent, not the oracle: the GPU test
-anchors it to the library through esc_linear_stats_block_rows, and every result is compared with fp64.
+family_of(), stats_block_rows() and scratch_needed() transcribe the dispatch plan of csrc/linear_plan.h.  The transcription
+is checked: tests/test_linear_plan_cpu.py compiles that header into a host program and compares its family, row-block
+height and slab count with these functions for every record of the table under every family mask.  The GPU test anchors
+it to the built library through esc_linear_stats_block_rows, and every result is compared with fp64.
 """
 import collections
 
@@ -34,7 +36,7 @@ FAMILIES = {
 }
 OPERANDS = {"fwd": ("X", "W", "Y"), "bwd_input": ("Y", "W", "dX"), "bwd_weight": ("Y", "X", "dW"),
             "bwd_both": ("Y", "X", "W", "dX", "dW")}
-# the constants of the dispatchers (csrc/linear_mfma.hip, linear_small.h)
+# the constants of the dispatchers (csrc/linear_plan.h)
 SMALL_MAX, NARROW_N, NARROW_K, NARROW_ROWS, ROWS_WGRAD, PRO_MAX_K = 16, 4, 256, 32, 32, 1280
 SMALLN_DX_MAX_N = 848                                  # smalln_dx keeps [32 + 16][N + 4] floats in the 160 KiB LDS
 KNOB_DEFAULTS = (1, 4, 1, 4, 4, 512, 128, 2)           # knobs 0..7
@@ -136,7 +138,7 @@ def stats_block_rows(case, use_dma=USE_DMA_DEFAULT):
     return stats_block_rows_of(family_of("fwd", case._replace(prologue=False), use_dma))
 
 
-# ---- the scratch plans, transcribed (csrc/linear_mfma.hip: dma_wgrad_plan, wgrad_plan_tile, both_impl, weight_impl) -------------
+# ---- the scratch plans, transcribed (csrc/linear_plan.h: dma_wgrad_splits, r01_wgrad_splits, plan_both, plan_dw) -------------
 def _dma_wgrad_splits(M, N, K, bm, bn):
     sp = max(1, min(cdiv(256, cdiv(N, bm) * cdiv(K, bn)), cdiv(M, 128)))
     per = max(128, cdiv(cdiv(M, sp), 32) * 32)
