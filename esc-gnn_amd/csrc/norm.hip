@@ -6,13 +6,16 @@
 // (lane = column), rows are strided over waves.  Statistics are accumulated per wave around a shift
 // (first row of the wave's stripe) and merged with Chan's formula in fp64, so fp32 cancellation in
 // E[x^2]-E[x]^2 never shows up at the 1e-5 parity bar.
+//
+// Which kernel serves a call, on which grid, is decided in norm_plan.h (host-only, checked on the CPU by
+// tests/test_norm_plan_cpu.py); every entry below validates its arguments, takes its plan and switches on it.
 #include "common.h"
+#include "norm_plan.h"
 
-#include <cstdlib>
+#include <type_traits>
 
 namespace esc {
 
-constexpr int NORM_ROWBLOCKS = 512;          // scratch sizing: most row blocks (= workgroups per column block) ever used
 // the fused-activation codes (0 none, 1 ReLU, 2 ELU): any other value would be ELU in the float4 kernels and the identity in the
 // scalar ones, so the entry points refuse it
 static inline bool act_code_ok(int act) { return act >= 0 && act <= 2; }
@@ -50,7 +53,20 @@ __device__ __forceinline__ float act_grad_from_pre(float v, int act) {
   if (act == 1) return v > 0.f ? 1.f : 0.f;
   if (act == 2) return v > 0.f ? 1.f : expf(v);
   return 1.f;
-}          // grid.y; x4 waves => 256 row slots
+}
+// g *= act'(.) of a column quad, from the forward output ...
+template <int ACT>
+__device__ __forceinline__ void act_grad_mul_out(float4& g, const float4& y) {
+  g.x *= act_grad_from_out(y.x, ACT); g.y *= act_grad_from_out(y.y, ACT);
+  g.z *= act_grad_from_out(y.z, ACT); g.w *= act_grad_from_out(y.w, ACT);
+}
+// ... or from the recomputed pre-activation
+template <int ACT>
+__device__ __forceinline__ void act_grad_mul_pre(float4& g, const float4& x, const float4& xh, const float4& mu, const float4& is,
+                                                 const float4& ga, const float4& be) {
+  g.x *= act_grad_from_pre(pre_act_bwd(x.x, xh.x, mu.x, is.x, ga.x, be.x, ACT), ACT); g.y *= act_grad_from_pre(pre_act_bwd(x.y, xh.y, mu.y, is.y, ga.y, be.y, ACT), ACT);
+  g.z *= act_grad_from_pre(pre_act_bwd(x.z, xh.z, mu.z, is.z, ga.z, be.z, ACT), ACT); g.w *= act_grad_from_pre(pre_act_bwd(x.w, xh.w, mu.w, is.w, ga.w, be.w, ACT), ACT);
+}
 
 // slot p owns rows p, p+P, p+2P, ...   partial[(p*C + c)] = {mean, M2}
 __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict__ X, int64_t ld, int M, int C,
@@ -133,7 +149,6 @@ __device__ __forceinline__ void bn_bwd_partial_body(const float* __restrict__ X,
                                                                 float2* __restrict__ coef,
                                                                 const unsigned char* __restrict__ dmask, float dscale) {
   ESC_PRIO();
-  constexpr int relu = ACT;
   __shared__ float4 sh[3][2][64];
   const int lane = lane_id(), wave = threadIdx.x >> 6;
   const int c = (blockIdx.x * 64 + lane) * 4;
@@ -155,14 +170,8 @@ __device__ __forceinline__ void bn_bwd_partial_body(const float* __restrict__ X,
       const float4 x = *reinterpret_cast<const float4*>(X + (size_t)r * ldx + c);
       const float4 xh = make_float4((x.x - mu.x) * is.x, (x.y - mu.y) * is.y, (x.z - mu.z) * is.z, (x.w - mu.w) * is.w);
       if constexpr (ACT != 0) {
-        if constexpr (HAS_Y) {
-          const float4 y = *reinterpret_cast<const float4*>(Y + (size_t)r * ldy + c);
-          g.x *= act_grad_from_out(y.x, relu); g.y *= act_grad_from_out(y.y, relu);
-          g.z *= act_grad_from_out(y.z, relu); g.w *= act_grad_from_out(y.w, relu);
-        } else {
-          g.x *= act_grad_from_pre(pre_act_bwd(x.x, xh.x, mu.x, is.x, ga.x, be.x, relu), relu); g.y *= act_grad_from_pre(pre_act_bwd(x.y, xh.y, mu.y, is.y, ga.y, be.y, relu), relu);
-          g.z *= act_grad_from_pre(pre_act_bwd(x.z, xh.z, mu.z, is.z, ga.z, be.z, relu), relu); g.w *= act_grad_from_pre(pre_act_bwd(x.w, xh.w, mu.w, is.w, ga.w, be.w, relu), relu);
-        }
+        if constexpr (HAS_Y) act_grad_mul_out<ACT>(g, *reinterpret_cast<const float4*>(Y + (size_t)r * ldy + c));
+        else act_grad_mul_pre<ACT>(g, x, xh, mu, is, ga, be);
       }
       s1.x += g.x; s1.y += g.y; s1.z += g.z; s1.w += g.w;
       s2.x = fmaf(g.x, xh.x, s2.x); s2.y = fmaf(g.y, xh.y, s2.y); s2.z = fmaf(g.z, xh.z, s2.z); s2.w = fmaf(g.w, xh.w, s2.w);
@@ -437,7 +446,6 @@ __device__ __forceinline__ void bn_bwd_apply_rows_body(const float* __restrict__
                                                          float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                          const unsigned char* __restrict__ dmask, float dscale) {
   ESC_PRIO();
-  constexpr int relu = ACT;
   const int c = (blockIdx.x * 64 + lane_id()) * 4;
   if (c >= C) return;
   const int slot = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -475,14 +483,8 @@ __device__ __forceinline__ void bn_bwd_apply_rows_body(const float* __restrict__
     }
     const float4 xh = make_float4((x.x - mu.x) * is.x, (x.y - mu.y) * is.y, (x.z - mu.z) * is.z, (x.w - mu.w) * is.w);
     if constexpr (ACT != 0) {
-      if constexpr (HAS_Y) {
-        const float4 y = *reinterpret_cast<const float4*>(Y + (size_t)r * ldy + c);
-        g.x *= act_grad_from_out(y.x, relu); g.y *= act_grad_from_out(y.y, relu);
-        g.z *= act_grad_from_out(y.z, relu); g.w *= act_grad_from_out(y.w, relu);
-      } else {
-        g.x *= act_grad_from_pre(pre_act_bwd(x.x, xh.x, mu.x, is.x, ga.x, be.x, relu), relu); g.y *= act_grad_from_pre(pre_act_bwd(x.y, xh.y, mu.y, is.y, ga.y, be.y, relu), relu);
-        g.z *= act_grad_from_pre(pre_act_bwd(x.z, xh.z, mu.z, is.z, ga.z, be.z, relu), relu); g.w *= act_grad_from_pre(pre_act_bwd(x.w, xh.w, mu.w, is.w, ga.w, be.w, relu), relu);
-      }
+      if constexpr (HAS_Y) act_grad_mul_out<ACT>(g, *reinterpret_cast<const float4*>(Y + (size_t)r * ldy + c));
+      else act_grad_mul_pre<ACT>(g, x, xh, mu, is, ga, be);
     }
     // same expression as bn_bwd_apply_kernel: gamma * invstd * (g - k.x - xhat * k.y)
     float4 o = make_float4(a.x * (g.x - k01.x - xh.x * k01.y), a.y * (g.y - k01.z - xh.y * k01.w),
@@ -649,8 +651,6 @@ __global__ __launch_bounds__(256) void bn_sync_coef_kernel(float2* __restrict__ 
   coef[c] = make_float2(v.x * inv, v.y * inv);
 }
 
-// >= 4 rows per wave slot (scalar kernels keep the old 64-block cap: their finalize cost grows with the slot count)
-// forward statistics: 64 (their finalize merges 4 slots per block with Chan's formula, its cost grows with the count);
 // ---- node-sized BatchNorm backward in ONE launch ---------------------------------------------------------------------------
 // partial sums -> grid barrier -> every workgroup adds the slots of its 256 columns -> dX from the rows it still holds in
 // registers.  Replaces partial + finalize + apply (three dependent launches at the ~4.5 us floor each, 13 times per training
@@ -669,7 +669,6 @@ __global__ __launch_bounds__(256) void bn_bwd_node_kernel(const float* __restric
                                                           float* __restrict__ dbeta, float* __restrict__ dX, int64_t ldd,
                                                           int* err) {
   ESC_PRIO();
-  constexpr int relu = ACT;
   constexpr int RPW = 4;
   __shared__ float4 sh[3][2][64];
   __shared__ float2 coef_s[256];
@@ -694,14 +693,8 @@ __global__ __launch_bounds__(256) void bn_bwd_node_kernel(const float* __restric
         const float4 x = *reinterpret_cast<const float4*>(X + (size_t)r * ldx + c);
         xh = make_float4((x.x - mu.x) * is.x, (x.y - mu.y) * is.y, (x.z - mu.z) * is.z, (x.w - mu.w) * is.w);
         if constexpr (ACT != 0) {
-          if constexpr (HAS_Y) {
-            const float4 y = *reinterpret_cast<const float4*>(Y + (size_t)r * ldy + c);
-            g.x *= act_grad_from_out(y.x, relu); g.y *= act_grad_from_out(y.y, relu);
-            g.z *= act_grad_from_out(y.z, relu); g.w *= act_grad_from_out(y.w, relu);
-          } else {
-            g.x *= act_grad_from_pre(pre_act_bwd(x.x, xh.x, mu.x, is.x, ga.x, be.x, relu), relu); g.y *= act_grad_from_pre(pre_act_bwd(x.y, xh.y, mu.y, is.y, ga.y, be.y, relu), relu);
-            g.z *= act_grad_from_pre(pre_act_bwd(x.z, xh.z, mu.z, is.z, ga.z, be.z, relu), relu); g.w *= act_grad_from_pre(pre_act_bwd(x.w, xh.w, mu.w, is.w, ga.w, be.w, relu), relu);
-          }
+          if constexpr (HAS_Y) act_grad_mul_out<ACT>(g, *reinterpret_cast<const float4*>(Y + (size_t)r * ldy + c));
+          else act_grad_mul_pre<ACT>(g, x, xh, mu, is, ga, be);
         }
         s1.x += g.x; s1.y += g.y; s1.z += g.z; s1.w += g.w;
         s2.x = fmaf(g.x, xh.x, s2.x); s2.y = fmaf(g.y, xh.y, s2.y); s2.z = fmaf(g.z, xh.z, s2.z); s2.w = fmaf(g.w, xh.w, s2.w);
@@ -784,12 +777,58 @@ __global__ __launch_bounds__(256) void bn_bwd_node_kernel(const float* __restric
   }
 }
 
-// backward sums: norm_rowblock_cap() = 256 (one slot per block, plain sums) — swept on MI355X: 35 -> 28 us edge-sized
-static inline int rowblocks(int64_t M, bool wide, bool backward = false) {
-  // (forward statistics of edge-sized inputs on 256 instead of 64 row blocks: measured no gain inside the step, r03)
-  const int64_t cap = (wide && backward) ? norm_rowblock_cap() : 64;
-  const int64_t want = cdiv(M, 16);
-  return (int)(want < 1 ? 1 : (want > cap ? cap : want));
+// ---- host side: validate, plan (norm_plan.h), launch ----------------------------------------------------------------------
+using norm::Grid;
+static inline dim3 dim(Grid g) { return dim3(g.x, g.y); }
+static norm::NormKnobs knobs() { return norm::NormKnobs{last_block_finalize(), norm_rowblock_cap(), bn_bwd_fold(), bn_bwd_one_launch()}; }
+
+// the operands the backward entries share
+struct BwdArgs {
+  const float* X; int64_t ld_x; const float* Y; int64_t ld_y; const float* dY; int64_t ld_dy; int64_t M, C;
+  const float *mean, *invstd, *gamma, *beta; int relu;
+};
+static norm::BwdOps ops_of(const BwdArgs& a, const float* dX, int64_t ld_dx, const void* partial, const void* coef, const float* dgamma,
+                           const float* dbeta) {
+  return norm::BwdOps{norm::mat(a.X, a.ld_x), norm::mat(a.Y, a.ld_y), norm::mat(a.dY, a.ld_dy), norm::mat(dX, ld_dx),
+                      a.mean, a.invstd, a.gamma, a.beta, partial, coef, dgamma, dbeta};
+}
+
+// (relu, Y given) -> the compile-time <ACT, HAS_Y> of the backward kernels, handed to a generic lambda f(act, has_y) as
+// integral constants.  Without an activation Y is never read: ACT == 0 is instantiated with HAS_Y == false only.
+template <int V> using int_c = std::integral_constant<int, V>;
+template <typename F>
+static void with_act(int relu, bool has_y, F&& f) {
+  if (relu == 0)      f(int_c<0>{}, std::false_type{});
+  else if (relu == 1) { if (has_y) f(int_c<1>{}, std::true_type{}); else f(int_c<1>{}, std::false_type{}); }
+  else                { if (has_y) f(int_c<2>{}, std::true_type{}); else f(int_c<2>{}, std::false_type{}); }
+}
+
+// the float4 column sums; tk: the last workgroup folds the slots into dgamma / dbeta / coef, else a finalize launch (or a folding apply) follows
+static void launch_bwd_partial_v4(const BwdArgs& a, Grid g, float2* partial, unsigned* tk, float* dgamma, float* dbeta, float2* coef, hipStream_t s) {
+  with_act(a.relu, a.Y != nullptr, [&](auto act, auto has_y) {
+    esc::launch(ESC_K_NORM, bn_bwd_partial_kernel_v4<decltype(act)::value, decltype(has_y)::value>, dim(g), dim3(256), 0, s, a.X, a.ld_x, a.Y, a.ld_y,
+                a.dY, a.ld_dy, (int)a.M, (int)a.C, a.mean, a.invstd, a.gamma, a.beta, partial, tk, dgamma, dbeta, coef);
+  });
+}
+// the rows-form apply; fold: coef is the [fold_slots][C] partial array and the kernel writes dgamma / dbeta
+static void launch_bwd_rows(const BwdArgs& a, Grid g, bool fold, const float2* coef, float* dX, int64_t ld_dx, int fold_slots, float* dgamma,
+                            float* dbeta, hipStream_t s) {
+  with_act(a.relu, a.Y != nullptr, [&](auto act, auto has_y) {
+    constexpr int A = decltype(act)::value;
+    constexpr bool H = decltype(has_y)::value;
+    esc::launch(ESC_K_NORM, fold ? bn_bwd_apply_rows<A, H, true> : bn_bwd_apply_rows<A, H, false>, dim(g), dim3(256), 0, s, a.X, a.ld_x, a.Y, a.ld_y,
+                a.dY, a.ld_dy, (int)a.M, (int)a.C, a.mean, a.invstd, a.gamma, a.beta, coef, dX, ld_dx, fold_slots, dgamma, dbeta);
+  });
+}
+static void launch_bwd_finalize(const float2* partial, int64_t divisor, int64_t C, int64_t slots, float* dgamma, float* dbeta, float2* coef, hipStream_t s) {
+  esc::launch(ESC_K_NORM, bn_bwd_finalize_kernel, dim(norm::column_grid(C, 4)), dim3(256), 0, s, partial, (int)divisor, (int)C, (int)slots, dgamma, dbeta, coef);
+}
+// the forward finalize over P partials; block_rows == 0: slot p owns rows p, p+P, ...
+static void launch_finalize(const float* partials, int64_t M, int64_t C, int64_t P, int64_t block_rows, float eps, float momentum, float* mean,
+                            float* invstd, float* running_mean, float* running_var, const float* gamma, const float* beta, float* scale,
+                            float* shift, void* stream) {
+  esc::launch(ESC_K_NORM, bn_finalize_kernel, dim(norm::column_grid(C, 4)), dim3(256), 0, (hipStream_t)stream, (const float2*)partials, (int)M, (int)C,
+              (int)P, (int)block_rows, eps, momentum, mean, invstd, running_mean, running_var, gamma, beta, scale, shift);
 }
 
 }  // namespace esc
@@ -798,7 +837,7 @@ using namespace esc;
 
 extern "C" {
 
-int64_t esc_bn_scratch(int64_t C) { return (int64_t)NORM_ROWBLOCKS * 4 * C * 2 + 2 * C; }
+int64_t esc_bn_scratch(int64_t C) { return norm::scratch_floats(C); }
 
 int esc_bn_stats(const float* X, int64_t ld_x, int64_t M, int64_t C, float eps, float momentum,
                  float* mean, float* invstd, float* running_mean, float* running_var,
@@ -808,12 +847,11 @@ int esc_bn_stats(const float* X, int64_t ld_x, int64_t M, int64_t C, float eps, 
   ESC_REQUIRE(X && mean && invstd && scratch, "esc_bn_stats: null pointer");
   ESC_REQUIRE(M > 1 && C > 0 && ld_x >= C && M < (1LL << 31), "esc_bn_stats: need more than 1 row per channel (M=%ld, C=%ld)", (long)M, (long)C);
   hipStream_t s = (hipStream_t)stream;
-  const bool wide = (C % 4 == 0) && (ld_x % 4 == 0) && aligned16(X) && aligned16(scratch);
-  const int rb = rowblocks(M, wide);
-  if (wide) esc::launch(ESC_K_NORM, bn_partial_kernel_v4, dim3((unsigned)cdiv(C, 256), rb), dim3(256), 0, s, X, ld_x, (int)M, (int)C, (float2*)scratch);
-  else      esc::launch(ESC_K_NORM, bn_partial_kernel, dim3((unsigned)cdiv(C, 64), rb), dim3(256), 0, s, X, ld_x, (int)M, (int)C, (float2*)scratch);
+  const norm::Plan p = norm::plan_stats(plan::Op{X, ld_x}, scratch, M, C);
+  if (p.reduce == norm::R_V4) esc::launch(ESC_K_NORM, bn_partial_kernel_v4, dim(p.grid[0]), dim3(256), 0, s, X, ld_x, (int)M, (int)C, (float2*)scratch);
+  else                        esc::launch(ESC_K_NORM, bn_partial_kernel, dim(p.grid[0]), dim3(256), 0, s, X, ld_x, (int)M, (int)C, (float2*)scratch);
   ESC_CHECK_LAUNCH("esc_bn_stats.partial");
-  esc::launch(ESC_K_NORM, bn_finalize_kernel, dim3((unsigned)cdiv(C, 4)), dim3(256), 0, s, (const float2*)scratch, (int)M, (int)C, rb * 4, 0, eps, momentum, mean, invstd, running_mean, running_var, gamma, beta, scale, shift);
+  launch_finalize(scratch, M, C, p.slots, 0, eps, momentum, mean, invstd, running_mean, running_var, gamma, beta, scale, shift, stream);
   ESC_CHECK_LAUNCH("esc_bn_stats.finalize");
   return ESC_OK;
 }
@@ -824,9 +862,7 @@ int esc_bn_stats_from_partials(const float* partials, int64_t M, int64_t C, floa
   ESC_REQUIRE(partials && mean && invstd, "esc_bn_stats_from_partials: null pointer");
   ESC_REQUIRE(M > 1 && C > 0 && M < (1LL << 31), "esc_bn_stats_from_partials: need more than 1 row per channel");
   ESC_REQUIRE((scale == nullptr) == (shift == nullptr), "esc_bn_stats_from_partials: scale/shift must come together");
-  esc::launch(ESC_K_NORM, bn_finalize_kernel, dim3((unsigned)cdiv(C, 4)), dim3(256), 0, (hipStream_t)stream,
-              (const float2*)partials, (int)M, (int)C, (int)cdiv(M, 32), 32, eps, momentum, mean, invstd, running_mean,
-              running_var, gamma, beta, scale, shift);
+  launch_finalize(partials, M, C, cdiv(M, 32), 32, eps, momentum, mean, invstd, running_mean, running_var, gamma, beta, scale, shift, stream);
   ESC_CHECK_LAUNCH("esc_bn_stats_from_partials");
   return ESC_OK;
 }
@@ -838,9 +874,7 @@ int esc_bn_stats_from_partials_rows(const float* partials, int64_t M, int64_t C,
   ESC_REQUIRE(partials && mean && invstd, "esc_bn_stats_from_partials_rows: null pointer");
   ESC_REQUIRE(M > 1 && C > 0 && M < (1LL << 31) && block_rows > 0, "esc_bn_stats_from_partials_rows: need more than 1 row per channel");
   ESC_REQUIRE((scale == nullptr) == (shift == nullptr), "esc_bn_stats_from_partials_rows: scale/shift must come together");
-  esc::launch(ESC_K_NORM, bn_finalize_kernel, dim3((unsigned)cdiv(C, 4)), dim3(256), 0, (hipStream_t)stream,
-              (const float2*)partials, (int)M, (int)C, (int)cdiv(M, block_rows), (int)block_rows, eps, momentum, mean, invstd,
-              running_mean, running_var, gamma, beta, scale, shift);
+  launch_finalize(partials, M, C, cdiv(M, block_rows), block_rows, eps, momentum, mean, invstd, running_mean, running_var, gamma, beta, scale, shift, stream);
   ESC_CHECK_LAUNCH("esc_bn_stats_from_partials_rows");
   return ESC_OK;
 }
@@ -848,17 +882,14 @@ int esc_bn_stats_from_partials_rows(const float* partials, int64_t M, int64_t C,
 int esc_affine_act_fold(const float* X, int64_t ld_x, int64_t M, int64_t C, const esc_bn_fold* bn, int relu, float* Y,
                         int64_t ld_y, void* stream) {
   ESC_REQUIRE(X && Y && bn && bn->partials && bn->mean && bn->invstd, "esc_affine_act_fold: null pointer");
-  ESC_REQUIRE(M > 1 && M < (1LL << 31) && C > 0 && C % 4 == 0 && bn->C == C && bn->rows > 1 && bn->block_rows > 0 && ld_x >= C && ld_y >= C &&
-              ld_x % 4 == 0 && ld_y % 4 == 0 && aligned16(X) && aligned16(Y), "esc_affine_act_fold: bad sizes / alignment");
+  ESC_REQUIRE(M > 1 && M < (1LL << 31) && C > 0 && bn->C == C && bn->rows > 1 && bn->block_rows > 0 && ld_x >= C && ld_y >= C &&
+              norm::mats_vec(C, {plan::Op{X, ld_x}, plan::Op{Y, ld_y}}), "esc_affine_act_fold: bad sizes / alignment");
   ESC_REQUIRE((bn->scale == nullptr) == (bn->shift == nullptr), "esc_affine_act_fold: scale/shift must come together");
   ESC_REQUIRE(act_code_ok(relu), "esc_affine_act_fold: relu must be 0 (none), 1 (ReLU) or 2 (ELU), got %d", relu);
   BnFoldDev f{reinterpret_cast<const float2*>(bn->partials), (int)cdiv(bn->rows, bn->block_rows), (int)bn->block_rows, (int)bn->rows,
               (int)bn->C, bn->eps, bn->momentum, bn->gamma, bn->beta, bn->mean, bn->invstd, bn->scale, bn->shift,
               bn->running_mean, bn->running_var};
-  // 32 rows per workgroup: every workgroup re-reads the partials (77 KB for 2 400 rows of 256 columns), so fewer and
-  // fatter workgroups than the plain affine pass
-  const unsigned rb = (unsigned)(cdiv(M, 32) < 1024 ? cdiv(M, 32) : 1024);
-  esc::launch(ESC_K_NORM, affine_act_fold_rows, dim3((unsigned)cdiv(C, 256), rb), dim3(256), 0, (hipStream_t)stream, X, ld_x,
+  esc::launch(ESC_K_NORM, affine_act_fold_rows, dim(norm::plan_affine_fold(M, C).grid[0]), dim3(256), 0, (hipStream_t)stream, X, ld_x,
               (int)M, (int)C, f, relu, Y, ld_y);
   ESC_CHECK_LAUNCH("esc_affine_act_fold");
   return ESC_OK;
@@ -872,11 +903,9 @@ int esc_bn_apply(const float* X, int64_t ld_x, int64_t M, int64_t C, const float
   ESC_REQUIRE(act_code_ok(relu), "esc_bn_apply: relu must be 0 (none), 1 (ReLU) or 2 (ELU), got %d", relu);
   if (M == 0) return ESC_OK;
   hipStream_t s = (hipStream_t)stream;
-  const bool vec = (C % 4 == 0) && (ld_x % 4 == 0) && (ld_y % 4 == 0) && aligned16(X) && aligned16(Y);
-  const int64_t work = M * (vec ? C / 4 : C);
-  const unsigned blocks = (unsigned)(cdiv(work, 256) < 4096 ? cdiv(work, 256) : 4096);
-  if (vec) esc::launch(ESC_K_NORM, bn_apply_kernel<4>, dim3(blocks), dim3(256), 0, s, X, ld_x, M, (int)C, mean, invstd, gamma, beta, relu, Y, ld_y);
-  else     esc::launch(ESC_K_NORM, bn_apply_kernel<1>, dim3(blocks), dim3(256), 0, s, X, ld_x, M, (int)C, mean, invstd, gamma, beta, relu, Y, ld_y);
+  const norm::Plan p = norm::plan_apply(plan::Op{X, ld_x}, plan::Op{Y, ld_y}, M, C);
+  esc::launch(ESC_K_NORM, p.apply == norm::A_FLAT4 ? bn_apply_kernel<4> : bn_apply_kernel<1>, dim(p.grid[0]), dim3(256), 0, s, X, ld_x, M, (int)C, mean,
+              invstd, gamma, beta, relu, Y, ld_y);
   ESC_CHECK_LAUNCH("esc_bn_apply");
   return ESC_OK;
 }
@@ -888,16 +917,12 @@ int esc_affine_act(const float* X, int64_t ld_x, int64_t M, int64_t C, const flo
   ESC_REQUIRE(act_code_ok(relu), "esc_affine_act: relu must be 0 (none), 1 (ReLU) or 2 (ELU), got %d", relu);
   if (M == 0) return ESC_OK;
   hipStream_t s = (hipStream_t)stream;
-  const bool vec = (C % 4 == 0) && (ld_x % 4 == 0) && (ld_y % 4 == 0) && aligned16(X) && aligned16(Y) &&
-                   aligned16(scale) && aligned16(shift);
-  const int64_t work = M * (vec ? C / 4 : C);
-  const unsigned blocks = (unsigned)(cdiv(work, 256) < 4096 ? cdiv(work, 256) : 4096);
-  if (vec && M < (1LL << 31)) {
-    const unsigned rb = (unsigned)(cdiv(M, 16) < 2048 ? cdiv(M, 16) : 2048);        // 4 rows per wave and pass
-    esc::launch(ESC_K_NORM, affine_act_rows, dim3((unsigned)cdiv(C, 256), rb), dim3(256), 0, s, X, ld_x, (int)M, (int)C, scale, shift, relu, Y, ld_y);
-  }
-  else if (vec) esc::launch(ESC_K_NORM, affine_act_kernel<4>, dim3(blocks), dim3(256), 0, s, X, ld_x, M, (int)C, scale, shift, relu, Y, ld_y);
-  else          esc::launch(ESC_K_NORM, affine_act_kernel<1>, dim3(blocks), dim3(256), 0, s, X, ld_x, M, (int)C, scale, shift, relu, Y, ld_y);
+  const norm::Plan p = norm::plan_affine(plan::Op{X, ld_x}, plan::Op{Y, ld_y}, scale, shift, M, C);
+  if (p.apply == norm::A_ROWS)
+    esc::launch(ESC_K_NORM, affine_act_rows, dim(p.grid[0]), dim3(256), 0, s, X, ld_x, (int)M, (int)C, scale, shift, relu, Y, ld_y);
+  else
+    esc::launch(ESC_K_NORM, p.apply == norm::A_FLAT4 ? affine_act_kernel<4> : affine_act_kernel<1>, dim(p.grid[0]), dim3(256), 0, s, X, ld_x, M, (int)C,
+                scale, shift, relu, Y, ld_y);
   ESC_CHECK_LAUNCH("esc_affine_act");
   return ESC_OK;
 }
@@ -941,66 +966,34 @@ int esc_bn_eval_coef(const float* running_mean, const float* running_var, const 
 
 // column sums of the BatchNorm backward: coef[c] = (sum g, sum g*xhat) / divisor, dgamma = sum g*xhat, dbeta = sum g
 // (g = dY * act'(.)).  divisor = M for the local BatchNorm; 1 when the sums are still to be all-reduced (SyncBN).
-static int bn_bwd_reduce(const float* X, int64_t ld_x, const float* Y, int64_t ld_y, const float* dY, int64_t ld_dy,
-                         int64_t M, int64_t C, const float* mean, const float* invstd, const float* gamma,
-                         const float* beta, int relu, int64_t divisor, bool allow_fuse, float* dgamma, float* dbeta,
-                         float2* partial, float2* coef, hipStream_t s) {
-  const bool wide = (C % 4 == 0) && (ld_x % 4 == 0) && (ld_dy % 4 == 0) && (!Y || ld_y % 4 == 0) && aligned16(X) &&
-                    aligned16(dY) && (!Y || aligned16(Y)) && aligned16(mean) && aligned16(invstd) &&
-                    (!gamma || aligned16(gamma)) && (!beta || aligned16(beta)) && aligned16(partial);
-  // node-sized inputs: few fat workgroups (>= 32 rows each) whose last one folds the <= 64 slots itself (knob 8);
-  // edge-sized: many workgroups + a wide finalize launch (one workgroup cannot pull hundreds of slots quickly)
-  const bool fuse = allow_fuse && wide && M <= 4096 && divisor == M && last_block_finalize();
-  const int rb = fuse ? (int)(cdiv(M, 32) < 64 ? cdiv(M, 32) : 64) : rowblocks(M, wide, true);
-  if (wide) {
-    const dim3 grid((unsigned)cdiv(C, 256), rb);
-    unsigned* tk = fuse ? tickets((int)grid.x) : nullptr;
-    ESC_REQUIRE(!fuse || tk != nullptr, "esc_bn_bwd: no ticket counters");
-#define ESC_BWD_PARTIAL(A, H) esc::launch(ESC_K_NORM, bn_bwd_partial_kernel_v4<A, H>, grid, dim3(256), 0, s, X, ld_x, Y, ld_y, dY, ld_dy, (int)M, (int)C, mean, invstd, gamma, beta, partial, tk, dgamma, dbeta, coef)
-    if (relu == 0)      ESC_BWD_PARTIAL(0, false);
-    else if (relu == 1) { if (Y) ESC_BWD_PARTIAL(1, true); else ESC_BWD_PARTIAL(1, false); }
-    else                { if (Y) ESC_BWD_PARTIAL(2, true); else ESC_BWD_PARTIAL(2, false); }
-#undef ESC_BWD_PARTIAL
-    if (!fuse) {
-      ESC_CHECK_LAUNCH("esc_bn_bwd.partial");
-      esc::launch(ESC_K_NORM, bn_bwd_finalize_kernel, dim3((unsigned)cdiv(C, 4)), dim3(256), 0, s, partial, (int)divisor, (int)C, rb, dgamma, dbeta, coef);
-    }
+static int bn_bwd_reduce(const BwdArgs& a, const norm::Plan& p, int64_t divisor, float* dgamma, float* dbeta, float2* partial, float2* coef,
+                         hipStream_t s) {
+  const bool fused = p.reduce == norm::R_FUSED;
+  if (p.reduce == norm::R_SCALAR) {
+    esc::launch(ESC_K_NORM, bn_bwd_partial_kernel, dim(p.grid[0]), dim3(256), 0, s, a.X, a.ld_x, a.Y, a.ld_y, a.dY, a.ld_dy, (int)a.M, (int)a.C, a.mean,
+                a.invstd, a.relu, a.gamma, a.beta, partial);
+  } else {
+    unsigned* tk = fused ? tickets((int)p.grid[0].x) : nullptr;
+    ESC_REQUIRE(!fused || tk != nullptr, "esc_bn_bwd: no ticket counters");
+    launch_bwd_partial_v4(a, p.grid[0], partial, tk, dgamma, dbeta, coef, s);
   }
-  else {
-    esc::launch(ESC_K_NORM, bn_bwd_partial_kernel, dim3((unsigned)cdiv(C, 64), rb), dim3(256), 0, s, X, ld_x, Y, ld_y, dY, ld_dy, (int)M, (int)C, mean, invstd, relu, gamma, beta, partial);
+  if (!fused) {
     ESC_CHECK_LAUNCH("esc_bn_bwd.partial");
-    esc::launch(ESC_K_NORM, bn_bwd_finalize_kernel, dim3((unsigned)cdiv(C, 4)), dim3(256), 0, s, partial, (int)divisor, (int)C, rb * 4, dgamma, dbeta, coef);
+    launch_bwd_finalize(partial, divisor, a.C, p.slots, dgamma, dbeta, coef, s);
   }
   ESC_CHECK_LAUNCH("esc_bn_bwd.finalize");
   return ESC_OK;
 }
 
 // dX = gamma * invstd * (g - coef.x - xhat * coef.y)
-static int bn_bwd_apply_impl(const float* X, int64_t ld_x, const float* Y, int64_t ld_y, const float* dY, int64_t ld_dy,
-                             int64_t M, int64_t C, const float* mean, const float* invstd, const float* gamma,
-                             const float* beta, int relu, const float2* coef, float* dX, int64_t ld_dx, hipStream_t s) {
-  const bool vec = (C % 4 == 0) && (ld_x % 4 == 0) && (ld_dy % 4 == 0) && (ld_dx % 4 == 0) && (!Y || ld_y % 4 == 0) &&
-                   aligned16(X) && aligned16(dY) && aligned16(dX) && (!Y || aligned16(Y)) &&
-                   (!gamma || aligned16(gamma));
-  const int64_t work = M * (vec ? C / 4 : C);
-  const unsigned blocks = (unsigned)(cdiv(work, 256) < 4096 ? cdiv(work, 256) : 4096);
-#define ESC_BWD_APPLY(V, A, H) esc::launch(ESC_K_NORM, bn_bwd_apply_kernel<V, A, H>, dim3(blocks), dim3(256), 0, s, X, ld_x, Y, ld_y, dY, ld_dy, M, (int)C, mean, invstd, gamma, beta, coef, dX, ld_dx)
-#define ESC_BWD_APPLY_V(V)                                                                 \
-  if (relu == 0)      ESC_BWD_APPLY(V, 0, false);                                           \
-  else if (relu == 1) { if (Y) ESC_BWD_APPLY(V, 1, true); else ESC_BWD_APPLY(V, 1, false); } \
-  else                { if (Y) ESC_BWD_APPLY(V, 2, true); else ESC_BWD_APPLY(V, 2, false); }
-  const bool rows_form = vec && aligned16(mean) && aligned16(invstd) && (!beta || aligned16(beta)) && aligned16(coef);
-  if (rows_form) {
-    const dim3 grid((unsigned)cdiv(C, 256), (unsigned)(cdiv(M, 16) < 2048 ? cdiv(M, 16) : 2048));
-#define ESC_BWD_ROWS(A, H) esc::launch(ESC_K_NORM, bn_bwd_apply_rows<A, H, false>, grid, dim3(256), 0, s, X, ld_x, Y, ld_y, dY, ld_dy, (int)M, (int)C, mean, invstd, gamma, beta, coef, dX, ld_dx, 0, (float*)nullptr, (float*)nullptr)
-    if (relu == 0)      ESC_BWD_ROWS(0, false);
-    else if (relu == 1) { if (Y) ESC_BWD_ROWS(1, true); else ESC_BWD_ROWS(1, false); }
-    else                { if (Y) ESC_BWD_ROWS(2, true); else ESC_BWD_ROWS(2, false); }
-#undef ESC_BWD_ROWS
-  }
-  else if (vec) { ESC_BWD_APPLY_V(4) } else { ESC_BWD_APPLY_V(1) }
-#undef ESC_BWD_APPLY_V
-#undef ESC_BWD_APPLY
+static int bn_bwd_apply_impl(const BwdArgs& a, norm::Apply form, Grid g, const float2* coef, float* dX, int64_t ld_dx, hipStream_t s) {
+  if (form == norm::A_ROWS) launch_bwd_rows(a, g, false, coef, dX, ld_dx, 0, nullptr, nullptr, s);
+  else with_act(a.relu, a.Y != nullptr, [&](auto act, auto has_y) {
+    constexpr int A = decltype(act)::value;
+    constexpr bool H = decltype(has_y)::value;
+    esc::launch(ESC_K_NORM, form == norm::A_FLAT4 ? bn_bwd_apply_kernel<4, A, H> : bn_bwd_apply_kernel<1, A, H>, dim(g), dim3(256), 0, s, a.X, a.ld_x,
+                a.Y, a.ld_y, a.dY, a.ld_dy, a.M, (int)a.C, a.mean, a.invstd, a.gamma, a.beta, coef, dX, ld_dx);
+  });
   ESC_CHECK_LAUNCH("esc_bn_bwd.apply");
   return ESC_OK;
 }
@@ -1013,53 +1006,37 @@ int esc_bn_bwd(const float* X, int64_t ld_x, const float* Y, int64_t ld_y, const
   ESC_REQUIRE(M > 0 && C > 0 && ld_x >= C && ld_dy >= C && ld_dx >= C && (!Y || ld_y >= C) && M < (1LL << 31), "esc_bn_bwd: bad sizes");
   ESC_REQUIRE(act_code_ok(relu), "esc_bn_bwd: relu must be 0 (none), 1 (ReLU) or 2 (ELU), got %d", relu);
   hipStream_t s = (hipStream_t)stream;
+  const BwdArgs a{X, ld_x, Y, ld_y, dY, ld_dy, M, C, mean, invstd, gamma, beta, relu};
   float2* partial = (float2*)scratch;
-  float2* coef = partial + (size_t)NORM_ROWBLOCKS * 4 * C;
-  // node-sized: 32 fat row blocks leave 32 partial slots and the apply kernel adds them itself — no finalize launch
-  const bool all16 = aligned16(X) && aligned16(dY) && aligned16(dX) && (!Y || aligned16(Y)) && aligned16(mean) && aligned16(invstd) &&
-                     (!gamma || aligned16(gamma)) && (!beta || aligned16(beta)) && aligned16(partial) &&
-                     (!dgamma || aligned16(dgamma)) && (!dbeta || aligned16(dbeta));
-  if (bn_bwd_one_launch() && M >= 64 && M <= 4096 && C % 4 == 0 && ld_x % 4 == 0 && ld_dy % 4 == 0 && ld_dx % 4 == 0 && (!Y || ld_y % 4 == 0) && all16) {
-    const dim3 grid((unsigned)cdiv(C, 256), (unsigned)cdiv(M, 16));
-    unsigned* bar = tickets(2 * (int)grid.x);
-    ESC_REQUIRE(bar != nullptr, "esc_bn_bwd: no barrier counters");
-    int* noerr = nullptr;
-#define ESC_BWD_NODE(A, H) esc::launch(ESC_K_NORM, bn_bwd_node_kernel<A, H>, grid, dim3(256), 0, s, X, ld_x, Y, ld_y, dY, ld_dy, (int)M, (int)C, mean, invstd, gamma, beta, partial, bar, dgamma, dbeta, dX, ld_dx, noerr)
-    if (relu == 0)      ESC_BWD_NODE(0, false);
-    else if (relu == 1) { if (Y) ESC_BWD_NODE(1, true); else ESC_BWD_NODE(1, false); }
-    else                { if (Y) ESC_BWD_NODE(2, true); else ESC_BWD_NODE(2, false); }
-#undef ESC_BWD_NODE
-    ESC_CHECK_LAUNCH("esc_bn_bwd.node");
-    return ESC_OK;
+  float2* coef = (float2*)(scratch + norm::coef_offset(C));
+  const norm::Plan p = norm::plan_bwd(knobs(), ops_of(a, dX, ld_dx, partial, nullptr, dgamma, dbeta), M, C);
+  switch (p.family) {
+    case norm::F_BWD_NODE: {
+      unsigned* bar = tickets(2 * (int)p.grid[0].x);
+      ESC_REQUIRE(bar != nullptr, "esc_bn_bwd: no barrier counters");
+      int* noerr = nullptr;
+      with_act(relu, Y != nullptr, [&](auto act, auto has_y) {
+        esc::launch(ESC_K_NORM, bn_bwd_node_kernel<decltype(act)::value, decltype(has_y)::value>, dim(p.grid[0]), dim3(256), 0, s, X, ld_x, Y, ld_y, dY,
+                    ld_dy, (int)M, (int)C, mean, invstd, gamma, beta, partial, bar, dgamma, dbeta, dX, ld_dx, noerr);
+      });
+      ESC_CHECK_LAUNCH("esc_bn_bwd.node");
+      return ESC_OK;
+    }
+    case norm::F_BWD_FOLD:
+      launch_bwd_partial_v4(a, p.grid[0], partial, nullptr, nullptr, nullptr, nullptr, s);
+      ESC_CHECK_LAUNCH("esc_bn_bwd.partial");
+      launch_bwd_rows(a, p.grid[1], true, partial, dX, ld_dx, p.slots, dgamma, dbeta, s);
+      ESC_CHECK_LAUNCH("esc_bn_bwd.apply_fold");
+      return ESC_OK;
+    default: {
+      const int rc = bn_bwd_reduce(a, p, M, dgamma, dbeta, partial, coef, s);
+      return rc != ESC_OK ? rc : bn_bwd_apply_impl(a, p.apply, p.grid[p.launches - 1], coef, dX, ld_dx, s);
+    }
   }
-  if (bn_bwd_fold() && M >= 64 && M <= 4096 && C % 4 == 0 && ld_x % 4 == 0 && ld_dy % 4 == 0 && ld_dx % 4 == 0 && (!Y || ld_y % 4 == 0) && all16 &&
-      !last_block_finalize()) {
-    const int rb = (int)(cdiv(M, 32) < 32 ? cdiv(M, 32) : 32);
-    const dim3 grid((unsigned)cdiv(C, 256), rb);
-    float* nof = nullptr; float2* noc = nullptr; unsigned* tk = nullptr;
-#define ESC_BWD_PARTIAL(A, H) esc::launch(ESC_K_NORM, bn_bwd_partial_kernel_v4<A, H>, grid, dim3(256), 0, s, X, ld_x, Y, ld_y, dY, ld_dy, (int)M, (int)C, mean, invstd, gamma, beta, partial, tk, nof, nof, noc)
-    if (relu == 0)      ESC_BWD_PARTIAL(0, false);
-    else if (relu == 1) { if (Y) ESC_BWD_PARTIAL(1, true); else ESC_BWD_PARTIAL(1, false); }
-    else                { if (Y) ESC_BWD_PARTIAL(2, true); else ESC_BWD_PARTIAL(2, false); }
-#undef ESC_BWD_PARTIAL
-    ESC_CHECK_LAUNCH("esc_bn_bwd.partial");
-    const dim3 agrid((unsigned)cdiv(C, 256), (unsigned)(cdiv(M, 16) < 2048 ? cdiv(M, 16) : 2048));
-    const float2* cpart = partial;
-#define ESC_BWD_ROWS(A, H) esc::launch(ESC_K_NORM, bn_bwd_apply_rows<A, H, true>, agrid, dim3(256), 0, s, X, ld_x, Y, ld_y, dY, ld_dy, (int)M, (int)C, mean, invstd, gamma, beta, cpart, dX, ld_dx, rb, dgamma, dbeta)
-    if (relu == 0)      ESC_BWD_ROWS(0, false);
-    else if (relu == 1) { if (Y) ESC_BWD_ROWS(1, true); else ESC_BWD_ROWS(1, false); }
-    else                { if (Y) ESC_BWD_ROWS(2, true); else ESC_BWD_ROWS(2, false); }
-#undef ESC_BWD_ROWS
-    ESC_CHECK_LAUNCH("esc_bn_bwd.apply_fold");
-    return ESC_OK;
-  }
-  int rc = bn_bwd_reduce(X, ld_x, Y, ld_y, dY, ld_dy, M, C, mean, invstd, gamma, beta, relu, M, true, dgamma, dbeta, partial, coef, s);
-  if (rc != ESC_OK) return rc;
-  return bn_bwd_apply_impl(X, ld_x, Y, ld_y, dY, ld_dy, M, C, mean, invstd, gamma, beta, relu, coef, dX, ld_dx, s);
 }
 
 int esc_bn_bwd_dropout_ok(int64_t C, int64_t ld_x, int64_t ld_dy, int64_t ld_dx) {
-  return C % 4 == 0 && ld_x % 4 == 0 && ld_dy % 4 == 0 && ld_dx % 4 == 0;
+  return norm::mats_vec(C, {plan::Op{nullptr, ld_x}, plan::Op{nullptr, ld_dy}, plan::Op{nullptr, ld_dx}});
 }
 
 int esc_bn_bwd_dropout(const float* X, int64_t ld_x, const float* dY, int64_t ld_dy, int64_t M, int64_t C, const float* mean,
@@ -1068,38 +1045,31 @@ int esc_bn_bwd_dropout(const float* X, int64_t ld_x, const float* dY, int64_t ld
   ESC_REQUIRE(X && dY && dX && mean && invstd && scratch && mask, "esc_bn_bwd_dropout: null pointer");
   ESC_REQUIRE(M > 0 && C > 0 && ld_x >= C && ld_dy >= C && ld_dx >= C && M < (1LL << 31) && p > 0.f && p < 1.f && (relu == 0 || relu == 1),
               "esc_bn_bwd_dropout: bad arguments");
+  const BwdArgs a{X, ld_x, nullptr, 0, dY, ld_dy, M, C, mean, invstd, gamma, beta, relu};
   float2* partial = (float2*)scratch;
-  float2* coef = partial + (size_t)NORM_ROWBLOCKS * 4 * C;
-  ESC_REQUIRE(esc_bn_bwd_dropout_ok(C, ld_x, ld_dy, ld_dx) && aligned16(X) && aligned16(dY) && aligned16(dX) && aligned16(mean) &&
-              aligned16(invstd) && (!gamma || aligned16(gamma)) && (!beta || aligned16(beta)) && aligned16(partial) && aligned16(coef) &&
-              (reinterpret_cast<uintptr_t>(mask) & 3) == 0, "esc_bn_bwd_dropout: operands must be 16-byte aligned with widths a multiple of 4");
+  float2* coef = (float2*)(scratch + norm::coef_offset(C));
+  const norm::Plan pl = norm::plan_bwd_dropout(knobs(), ops_of(a, dX, ld_dx, partial, nullptr, nullptr, nullptr), M, C, mask_on_output != 0);
+  ESC_REQUIRE(pl.family != norm::F_NONE && (reinterpret_cast<uintptr_t>(mask) & 3) == 0,
+              "esc_bn_bwd_dropout: operands must be 16-byte aligned with widths a multiple of 4");
   hipStream_t s = (hipStream_t)stream;
   const float dscale = (float)(1.0 / (1.0 - (double)p));
-  const int rb = rowblocks(M, true, true);
-  const dim3 grid((unsigned)cdiv(C, 256), rb);
   const unsigned char* mk = (const unsigned char*)mask;
-  if (mask_on_output) {        // the sums are those of the plain BatchNorm backward
-    const float* noy = nullptr; unsigned* tk = nullptr; float* nof = nullptr; float2* noc = nullptr;
-    if (relu) esc::launch(ESC_K_NORM, bn_bwd_partial_kernel_v4<1, false>, grid, dim3(256), 0, s, X, ld_x, noy, (int64_t)0, dY, ld_dy, (int)M, (int)C, mean, invstd, gamma, beta, partial, tk, nof, nof, noc);
-    else      esc::launch(ESC_K_NORM, bn_bwd_partial_kernel_v4<0, false>, grid, dim3(256), 0, s, X, ld_x, noy, (int64_t)0, dY, ld_dy, (int)M, (int)C, mean, invstd, gamma, beta, partial, tk, nof, nof, noc);
-  } else {
-    if (relu) esc::launch(ESC_K_NORM, bn_bwd_partial_drop_kernel<1>, grid, dim3(256), 0, s, X, ld_x, dY, ld_dy, (int)M, (int)C, mean, invstd, gamma, beta, partial, mk, dscale);
-    else      esc::launch(ESC_K_NORM, bn_bwd_partial_drop_kernel<0>, grid, dim3(256), 0, s, X, ld_x, dY, ld_dy, (int)M, (int)C, mean, invstd, gamma, beta, partial, mk, dscale);
-  }
-  ESC_CHECK_LAUNCH("esc_bn_bwd_dropout.partial");
-  esc::launch(ESC_K_NORM, bn_bwd_finalize_kernel, dim3((unsigned)cdiv(C, 4)), dim3(256), 0, s, (const float2*)partial, (int)M, (int)C, rb, dgamma, dbeta, coef);
-  ESC_CHECK_LAUNCH("esc_bn_bwd_dropout.finalize");
-  const dim3 agrid((unsigned)cdiv(C, 256), (unsigned)(cdiv(M, 16) < 2048 ? cdiv(M, 16) : 2048));
-  const float2* kc = coef;
-  if (mask_on_output) {
-    if (relu) esc::launch(ESC_K_NORM, bn_bwd_apply_rows_drop<1, false, true>, agrid, dim3(256), 0, s, X, ld_x, dY, ld_dy, (int)M, (int)C, mean, invstd, gamma, beta, kc, dX, ld_dx, mk, dscale);
-    else      esc::launch(ESC_K_NORM, bn_bwd_apply_rows_drop<0, false, true>, agrid, dim3(256), 0, s, X, ld_x, dY, ld_dy, (int)M, (int)C, mean, invstd, gamma, beta, kc, dX, ld_dx, mk, dscale);
-  } else {
-    if (relu) esc::launch(ESC_K_NORM, bn_bwd_apply_rows_drop<1, true, false>, agrid, dim3(256), 0, s, X, ld_x, dY, ld_dy, (int)M, (int)C, mean, invstd, gamma, beta, kc, dX, ld_dx, mk, dscale);
-    else      esc::launch(ESC_K_NORM, bn_bwd_apply_rows_drop<0, true, false>, agrid, dim3(256), 0, s, X, ld_x, dY, ld_dy, (int)M, (int)C, mean, invstd, gamma, beta, kc, dX, ld_dx, mk, dscale);
-  }
-  ESC_CHECK_LAUNCH("esc_bn_bwd_dropout.apply");
-  return ESC_OK;
+  auto run = [&](auto act) -> int {
+    constexpr int A = decltype(act)::value;
+    if (mask_on_output)          // the sums are those of the plain BatchNorm backward
+      launch_bwd_partial_v4(a, pl.grid[0], partial, nullptr, nullptr, nullptr, nullptr, s);
+    else
+      esc::launch(ESC_K_NORM, bn_bwd_partial_drop_kernel<A>, dim(pl.grid[0]), dim3(256), 0, s, X, ld_x, dY, ld_dy, (int)M, (int)C, mean, invstd, gamma,
+                  beta, partial, mk, dscale);
+    ESC_CHECK_LAUNCH("esc_bn_bwd_dropout.partial");
+    launch_bwd_finalize(partial, M, C, pl.slots, dgamma, dbeta, coef, s);
+    ESC_CHECK_LAUNCH("esc_bn_bwd_dropout.finalize");
+    esc::launch(ESC_K_NORM, mask_on_output ? bn_bwd_apply_rows_drop<A, false, true> : bn_bwd_apply_rows_drop<A, true, false>, dim(pl.grid[2]), dim3(256),
+                0, s, X, ld_x, dY, ld_dy, (int)M, (int)C, mean, invstd, gamma, beta, coef, dX, ld_dx, mk, dscale);
+    ESC_CHECK_LAUNCH("esc_bn_bwd_dropout.apply");
+    return ESC_OK;
+  };
+  return relu ? run(int_c<1>{}) : run(int_c<0>{});
 }
 
 int esc_bn_bwd_sums(const float* X, int64_t ld_x, const float* Y, int64_t ld_y, const float* dY,
@@ -1109,8 +1079,9 @@ int esc_bn_bwd_sums(const float* X, int64_t ld_x, const float* Y, int64_t ld_y, 
   ESC_REQUIRE(X && dY && sums && mean && invstd && scratch, "esc_bn_bwd_sums: null pointer");
   ESC_REQUIRE(M > 0 && C > 0 && ld_x >= C && ld_dy >= C && (!Y || ld_y >= C) && M < (1LL << 31), "esc_bn_bwd_sums: bad sizes");
   ESC_REQUIRE(act_code_ok(relu), "esc_bn_bwd_sums: relu must be 0 (none), 1 (ReLU) or 2 (ELU), got %d", relu);
-  return bn_bwd_reduce(X, ld_x, Y, ld_y, dY, ld_dy, M, C, mean, invstd, gamma, beta, relu, 1, false, dgamma, dbeta,
-                       (float2*)scratch, (float2*)sums, (hipStream_t)stream);
+  const BwdArgs a{X, ld_x, Y, ld_y, dY, ld_dy, M, C, mean, invstd, gamma, beta, relu};
+  const norm::Plan p = norm::plan_bwd_reduce(knobs(), ops_of(a, nullptr, 0, scratch, nullptr, nullptr, nullptr), M, C, false, false);
+  return bn_bwd_reduce(a, p, 1, dgamma, dbeta, (float2*)scratch, (float2*)sums, (hipStream_t)stream);
 }
 
 int esc_bn_bwd_coef(const float* X, int64_t ld_x, const float* Y, int64_t ld_y, const float* dY, int64_t ld_dy, int64_t M,
@@ -1119,15 +1090,15 @@ int esc_bn_bwd_coef(const float* X, int64_t ld_x, const float* Y, int64_t ld_y, 
   ESC_REQUIRE(X && dY && coef && mean && invstd && scratch, "esc_bn_bwd_coef: null pointer");
   ESC_REQUIRE(M > 0 && C > 0 && ld_x >= C && ld_dy >= C && (!Y || ld_y >= C) && M < (1LL << 31), "esc_bn_bwd_coef: bad sizes");
   ESC_REQUIRE(act_code_ok(relu), "esc_bn_bwd_coef: relu must be 0 (none), 1 (ReLU) or 2 (ELU), got %d", relu);
-  return bn_bwd_reduce(X, ld_x, Y, ld_y, dY, ld_dy, M, C, mean, invstd, gamma, beta, relu, M, true, dgamma, dbeta,
-                       (float2*)scratch, (float2*)coef, (hipStream_t)stream);
+  const BwdArgs a{X, ld_x, Y, ld_y, dY, ld_dy, M, C, mean, invstd, gamma, beta, relu};
+  const norm::Plan p = norm::plan_bwd_reduce(knobs(), ops_of(a, nullptr, 0, scratch, nullptr, nullptr, nullptr), M, C, true, true);
+  return bn_bwd_reduce(a, p, M, dgamma, dbeta, (float2*)scratch, (float2*)coef, (hipStream_t)stream);
 }
 
 int esc_bn_bwd_coef_from_partials(const float* partial, int64_t slots, int64_t M, int64_t C, float* coef, float* dgamma,
                                   float* dbeta, void* stream) {
   ESC_REQUIRE(partial && coef && slots > 0 && M > 0 && C > 0 && M < (1LL << 31) && slots < (1LL << 31), "esc_bn_bwd_coef_from_partials: bad arguments");
-  esc::launch(ESC_K_NORM, bn_bwd_finalize_kernel, dim3((unsigned)cdiv(C, 4)), dim3(256), 0, (hipStream_t)stream,
-              reinterpret_cast<const float2*>(partial), (int)M, (int)C, (int)slots, dgamma, dbeta, reinterpret_cast<float2*>(coef));
+  launch_bwd_finalize(reinterpret_cast<const float2*>(partial), M, C, slots, dgamma, dbeta, reinterpret_cast<float2*>(coef), (hipStream_t)stream);
   ESC_CHECK_LAUNCH("esc_bn_bwd_coef_from_partials");
   return ESC_OK;
 }
@@ -1139,8 +1110,9 @@ int esc_bn_bwd_apply(const float* X, int64_t ld_x, const float* Y, int64_t ld_y,
   ESC_REQUIRE(X && dY && dX && mean && invstd && coef, "esc_bn_bwd_apply: null pointer");
   ESC_REQUIRE(M > 0 && C > 0 && ld_x >= C && ld_dy >= C && ld_dx >= C && (!Y || ld_y >= C) && M < (1LL << 31), "esc_bn_bwd_apply: bad sizes");
   ESC_REQUIRE(act_code_ok(relu), "esc_bn_bwd_apply: relu must be 0 (none), 1 (ReLU) or 2 (ELU), got %d", relu);
-  return bn_bwd_apply_impl(X, ld_x, Y, ld_y, dY, ld_dy, M, C, mean, invstd, gamma, beta, relu, (const float2*)coef, dX,
-                           ld_dx, (hipStream_t)stream);
+  const BwdArgs a{X, ld_x, Y, ld_y, dY, ld_dy, M, C, mean, invstd, gamma, beta, relu};
+  const norm::Plan p = norm::plan_bwd_apply(ops_of(a, dX, ld_dx, nullptr, coef, nullptr, nullptr), M, C);
+  return bn_bwd_apply_impl(a, p.apply, p.grid[0], (const float2*)coef, dX, ld_dx, (hipStream_t)stream);
 }
 
 }  // extern "C"

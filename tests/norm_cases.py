@@ -1,7 +1,8 @@
 """The BatchNorm case table: one record per (entry point, shape, operand layout, argument combination, knob setting, data
-regime) chosen so that every branch of the host predicates in csrc/norm.hip (and bn_fold_column in common.h) is reached by
+regime) chosen so that every branch of the host predicates in csrc/norm_plan.h (and bn_fold_column in common.h) is reached by
 name.  No GPU is needed to import or check this module (tests/test_norm_cases_cpu.py); tests/test_hip_norm_dispatch.py runs
-the table against the library.  The guarded buffers are those of tests/linear_cases.py.
+the table against the library, and tests/test_norm_plan_cpu.py holds the header the library decides with to family_of, which
+stays an independent transcription.  The guarded buffers are those of tests/linear_cases.py.
 
 A case is Case(name, entry, M, C, layout, act, has_Y, affine, running, fused, in_place, knobs, regime, extra, family):
   entry     stats | stats_partials | stats_partials_rows | affine_fold | apply | affine | eval_coef | bwd | bwd_sums | bwd_coef |
