@@ -131,7 +131,7 @@ int esc_tune_set(int knob, int value) {
   return ESC_OK;
 }
 
-int esc_abi_version(void) { return 8; }   // 8: esc_edge_distance, esc_node_input_fwd / _bwd, esc_mse_loss; 7: esc_engine_set_gemm_stats, esc_engine_set_materialise_edge_act, esc_linear_bwd_set_wgrad_stream removed; 6: esc_collate_args rebuilt on the staged block + int32 store views, esc_collate_cols lost col_ptr, esc_nested_gin_t.counters; 5: esc_graphlet_counts; 4: esc_zinc_gin_t.node_readout, esc_cycle_counts; 2: esc_features_* take sum_nodes_sq; esc_zinc_*, esc_embed_*; 3: esc_collate_args grew (edge_attr, x_long, graph_ptr), esc_embed_plan
+int esc_abi_version(void) { return ESC_ABI_VERSION; }   // 8: esc_edge_distance, esc_node_input_fwd / _bwd, esc_mse_loss; 7: esc_engine_set_gemm_stats, esc_engine_set_materialise_edge_act, esc_linear_bwd_set_wgrad_stream removed; 6: esc_collate_args rebuilt on the staged block + int32 store views, esc_collate_cols lost col_ptr, esc_nested_gin_t.counters; 5: esc_graphlet_counts; 4: esc_zinc_gin_t.node_readout, esc_cycle_counts; 2: esc_features_* take sum_nodes_sq; esc_zinc_*, esc_embed_*; 3: esc_collate_args grew (edge_attr, x_long, graph_ptr), esc_embed_plan
 const char* esc_last_error(void) { return esc::g_err; }
 
 int esc_prof_enable(int kind, int on) {

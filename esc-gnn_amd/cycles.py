@@ -8,7 +8,7 @@ import torch
 
 from . import _native as nv
 
-ESC_ERANGE = -3
+ESC_ERANGE = nv.ESC_ERANGE
 MAX_NODES = 64
 
 

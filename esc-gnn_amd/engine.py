@@ -18,7 +18,7 @@ A further family is a descriptor builder, a batch builder and one more record.
 import collections
 import ctypes
 import functools
-from ctypes import c_float, c_int32, c_int64, c_uint64, c_void_p
+from ctypes import c_void_p
 
 import torch
 
@@ -26,12 +26,23 @@ from . import _native as nv
 from .nested import Z_TABLE_ROWS
 from .plan import plan_of
 
-MAX_LAYERS = 16
-MAX_BN_COUNTERS = 2 * MAX_LAYERS + 8
-# the index arrays of a batch plan (plan.py): the tail of every family's batch struct
-_PLAN_FIELDS = ("in_ptr", "in_edge", "in_src", "out_ptr", "out_edge", "out_dst", "row_ptr", "bag_idx", "bag_val",
-                "col_ptr", "col_row", "col_val", "col_col")
-_PLAN_POINTERS = [(n, c_void_p) for n in _PLAN_FIELDS]
+MAX_LAYERS, MAX_BN_COUNTERS, MAX_TABLES = (nv.const(n) for n in ("ESC_MAX_LAYERS", "ESC_MAX_BN_COUNTERS", "ESC_MAX_TABLES"))
+
+# The descriptor and batch structs of the three families, as the header declares them (derived: _abi.py)
+_Linear, _BN, _MLP, _Conv = (nv.struct(n) for n in ("esc_linear_t", "esc_bn_t", "esc_mlp_t", "esc_conv_t"))
+_Model, _Batch = nv.struct("esc_nested_gin_t"), nv.struct("esc_batch_t")
+_Embed, _ZincModel, _MolBatch = nv.struct("esc_embed_t"), nv.struct("esc_zinc_gin_t"), nv.struct("esc_mol_batch_t")
+_TableList, _OgbLayer, _OgbModel = nv.struct("esc_table_list"), nv.struct("esc_ogb_layer_t"), nv.struct("esc_ogb_gnn_t")
+_BagPlan, _OgbBatch = nv.struct("esc_bag_plan_t"), nv.struct("esc_ogb_batch_t")
+
+
+def _names(cls):
+    return [m[0] for m in nv.members(cls)]
+
+
+# the index arrays of a batch plan (plan.py): the members from in_ptr to col_col, which every family's batch struct holds
+_PLAN_FIELDS = tuple(_names(_Batch)[_names(_Batch).index("in_ptr"):])
+assert all(set(_PLAN_FIELDS) <= set(_names(b)) for b in (_MolBatch, _OgbBatch)), "batch structs without the plan's index arrays"
 
 
 def _bind_plan(b, plan):
@@ -42,53 +53,6 @@ def _bind_plan(b, plan):
 def _f32c(t):
     """`t` as contiguous float32 (itself when it already is)"""
     return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
-
-
-class _Linear(ctypes.Structure):
-    _fields_ = [("w", c_void_p), ("b", c_void_p), ("dw", c_void_p), ("db", c_void_p),
-                ("in_dim", c_int64), ("out_dim", c_int64)]
-
-
-class _BN(ctypes.Structure):
-    _fields_ = [("gamma", c_void_p), ("beta", c_void_p), ("dgamma", c_void_p), ("dbeta", c_void_p),
-                ("running_mean", c_void_p), ("running_var", c_void_p), ("eps", c_float), ("momentum", c_float)]
-
-
-class _MLP(ctypes.Structure):
-    _fields_ = [("lin0", _Linear), ("bn0", _BN), ("lin1", _Linear), ("bn1", _BN)]
-
-
-class _Conv(ctypes.Structure):
-    _fields_ = [("eps", c_void_p), ("deps", c_void_p), ("nn", _MLP), ("lin", _Linear)]
-
-
-class _Model(ctypes.Structure):
-    _fields_ = [("num_layers", c_int64), ("hidden", c_int64), ("in_dim", c_int64), ("z_rows", c_int64),
-                ("z_table", c_void_p), ("dz_table", c_void_p),
-                ("zbn0", _BN), ("zlin", _Linear), ("zbn1", _BN), ("xemb", _MLP),
-                ("conv", _Conv * MAX_LAYERS), ("lin1", _Linear), ("bn_lin1", _BN), ("lin2", _Linear),
-                ("n_counters", c_int64), ("counters", c_void_p * MAX_BN_COUNTERS)]
-
-
-class _Batch(ctypes.Structure):
-    _fields_ = [("N", c_int64), ("E", c_int64), ("Z", c_int64), ("x", c_void_p), ("y", c_void_p)] + _PLAN_POINTERS
-
-
-class _Embed(ctypes.Structure):
-    _fields_ = [("w", c_void_p), ("dw", c_void_p), ("rows", c_int64), ("dim", c_int64)]
-
-
-class _ZincModel(ctypes.Structure):
-    _fields_ = [("num_layers", c_int64), ("hidden", c_int64), ("z_rows", c_int64),
-                ("z_table", c_void_p), ("dz_table", c_void_p),
-                ("zbn0", _BN), ("zlin", _Linear), ("zbn1", _BN), ("node_emb", _Embed), ("edge_emb", _Embed),
-                ("conv", _Conv * MAX_LAYERS), ("lin1", _Linear), ("bn_lin1", _BN), ("lin2", _Linear),
-                ("node_readout", c_int32), ("pad_", c_int32)]
-
-
-class _MolBatch(ctypes.Structure):
-    _fields_ = ([("N", c_int64), ("E", c_int64), ("Z", c_int64), ("G", c_int64), ("node_type", c_void_p),
-                 ("edge_type", c_void_p), ("y", c_void_p), ("graph_ptr", c_void_p)] + _PLAN_POINTERS)
 
 
 def _grad_ptr(p):
@@ -208,7 +172,7 @@ def _arm_collective(model, device, cache=None):
         install_collective(width, device, groups[0])
 
 
-_ALLREDUCE_T = ctypes.CFUNCTYPE(ctypes.c_int, c_void_p, c_int64, c_void_p, c_void_p)
+_ALLREDUCE_T = nv.callback("esc_allreduce_fn")
 _collective = {}            # the installed provider: keeps the callback object, the exchange buffers and the group alive
 
 
@@ -411,35 +375,6 @@ def _zinc_batch(model, data, need_y, y=None):
 
 
 # ---- OGB molecule variant (ogb_mol_gnn.GNN(gnn_type="gin_eff"); csrc/engine.hip esc_ogb_*) -----------------------------
-MAX_TABLES = 64
-
-
-class _TableList(ctypes.Structure):
-    _fields_ = [("count", c_int32), ("rows", c_int32 * MAX_TABLES), ("w", c_void_p * MAX_TABLES), ("dw", c_void_p * MAX_TABLES)]
-
-
-class _OgbLayer(ctypes.Structure):
-    _fields_ = [("eps", c_void_p), ("deps", c_void_p), ("pos", _Linear), ("lin0", _Linear), ("bn0", _BN), ("lin1", _Linear),
-                ("bn", _BN), ("vlin0", _Linear), ("vbn0", _BN), ("vlin1", _Linear), ("vbn1", _BN), ("bond_row0", c_int64)]
-
-
-class _OgbModel(ctypes.Structure):
-    _fields_ = [("num_layers", c_int64), ("hidden", c_int64), ("z_rows", c_int64), ("num_tasks", c_int64),
-                ("residual", c_int32), ("mean_pool", c_int32), ("drop_ratio", c_float), ("pad_", c_int32),
-                ("z_table", c_void_p), ("dz_table", c_void_p), ("zbn0", _BN), ("zlin", _Linear), ("zbn1", _BN),
-                ("tables", _TableList), ("atom_rows", c_int64), ("bond_rows", c_int64), ("vn_w", c_void_p), ("vn_dw", c_void_p),
-                ("layer", _OgbLayer * MAX_LAYERS), ("head", _Linear)]
-
-
-class _BagPlan(ctypes.Structure):
-    _fields_ = [("n_entries", c_int64)] + [(n, c_void_p) for n in ("row_ptr", "idx", "ones", "col_ptr", "c_row", "c_col")]
-
-
-class _OgbBatch(ctypes.Structure):
-    _fields_ = ([("N", c_int64), ("E", c_int64), ("Z", c_int64), ("G", c_int64), ("atoms", _BagPlan), ("bonds", _BagPlan),
-                 ("y", c_void_p), ("graph_ptr", c_void_p), ("zero_idx", c_void_p)] + _PLAN_POINTERS + [("seed", c_uint64)])
-
-
 def ogb_engine_supports(m, data=None):
     """what esc_ogb_* covers: the run_ogb_mol `--gnn gin_eff` configuration — ogbg-mol* encoders, virtual node, JK last,
     sum / mean pooling, BatchNorm statistics per rank or over ONE process group (nn.BatchNorm1d.convert_sync); sparse ESC bag;

@@ -11,7 +11,7 @@ import torch
 
 from . import _native as nv
 
-ESC_ERANGE = -3
+ESC_ERANGE = nv.ESC_ERANGE
 MAX_NODES = 64
 NUM_ORBITS = 11
 GRAPHLET_NAMES = ("tailed_triangle", "chordal_cycle", "4_clique", "4_path", "triangle_rectangle")

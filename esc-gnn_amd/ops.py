@@ -648,8 +648,8 @@ def embed_plan(index, dims, known_range=None):
         raise RuntimeError("esc_gnn_amd: embedding plans are built on the GPU (got a %s tensor)" % index.device.type)
     n, k = index.shape
     dev = index.device
-    if k != len(dims) or k > 16:
-        raise ValueError("embed_plan: index has %d columns for %d tables (at most 16)" % (k, len(dims)))
+    if k != len(dims) or k > nv.const("ESC_MAX_EMBED_COLS"):
+        raise ValueError("embed_plan: index has %d columns for %d tables (at most %d)" % (k, len(dims), nv.const("ESC_MAX_EMBED_COLS")))
     if known_range is None:                              # the device store leaves the dataset-wide range on the tensors it collates
         tag = getattr(index, "_esc_known_range", None)
         if tag is not None and tag[1] == index._version:

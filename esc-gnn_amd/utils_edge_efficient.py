@@ -12,7 +12,7 @@ import torch
 from . import _native as nv
 from .data import Data
 
-ESC_ERANGE = -3
+ESC_ERANGE = nv.ESC_ERANGE
 
 
 def _device():

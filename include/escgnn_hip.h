@@ -13,6 +13,17 @@
  * the reference call site (file:line under /root/reference) whose device work it replaces.
  * Index arrays are int32 ("compact") unless stated; user-visible int64 tensors are produced
  * only by esc_collate_* / esc_features_fill so they stay bit-identical to the reference's.
+ *
+ * Python reads THIS FILE: esc-gnn_amd/_abi.py derives the whole ctypes binding from it at import (*The
+ * binding is derived from the header*), and refuses, quoting the text, whatever is not one of these forms:
+ *   #define ESC_NAME <integer expression>     literals, + - * ( ) and ESC_ constants defined above it; other # lines are skipped
+ *   enum { ESC_NAME [= <integer expression>], ... };
+ *   typedef struct NAME { <member>; ... } NAME;      member = [const] TYPE [*]name[[dim]] {, [*]name[[dim]]}
+ *   typedef TYPE (*NAME)(<parameters>);              a callback type
+ *   TYPE NAME(<parameters>);                         parameter = [const] TYPE [*]name, or `void` alone; may span lines
+ * TYPE is int64_t, int32_t, int, uint64_t, float, double, or behind a `*` also void, char, uint8_t and any struct defined above;
+ * a member (not a parameter) may hold an earlier struct by value; `const char*` is the one pointer a function may return.  No
+ * bit-fields, unions, nested or anonymous structs, pointers to pointers, `* const`, function-like macros or #if'd-out declarations.
  */
 #ifndef ESCGNN_HIP_H
 #define ESCGNN_HIP_H
@@ -28,7 +39,8 @@ extern "C" {
 #define ESC_ELAUNCH (-2)  /* HIP runtime error at launch */
 #define ESC_ERANGE (-3)   /* input outside the encodable range (degree>=200, rd bin>=100, h>4, n too large) */
 
-int esc_abi_version(void);                /* bumps when a signature changes */
+#define ESC_ABI_VERSION 8                 /* bump when a signature or a struct changes; the library returns it, Python compares */
+int esc_abi_version(void);                /* ESC_ABI_VERSION of the header the library was built from */
 const char* esc_last_error(void);         /* message of the last failing call on this thread */
 
 /* ---- profiling hook: HIP-event timing of one kernel family on its own launch stream ------ */

@@ -3,13 +3,9 @@ import os
 sys.path[:0] = [os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))]      # the repo root
 import esc_gnn_amd as E
 from esc_gnn_amd import _native as nv
-from ctypes import c_void_p, c_int64, c_int32
-class Job(ctypes.Structure):
-    _fields_ = [("slabs", c_void_p), ("n", c_int64), ("splits", c_int32), ("cols", c_int64), ("dw", c_void_p), ("ld_dw", c_int64),
-                ("db_part", c_void_p), ("rows", c_int64), ("db", c_void_p)]
+Job = nv.ReduceJob
 dev = 'cuda:0'
 lib = nv.lib()
-lib.esc_slab_reduce_jobs.argtypes = [c_void_p, ctypes.c_int, c_void_p]
 def bench(name, specs, reps=30, sets=6):
     # specs: list of (rows N_out, cols K_in, splits); `sets` rotating copies so the slabs are not cache-resident
     all_jobs, keep = [], []
