@@ -63,8 +63,10 @@ __global__ __launch_bounds__(1024) void bce_logits_kernel(const float* __restric
   }
 }
 
-// torch.optim.Adam single-tensor arithmetic, in torch's operation order:
+// torch.optim.Adam single-tensor arithmetic, in torch's operation order up to FMA contraction:
 //   m.lerp_(g, 1-b1); v.mul_(b2).addcmul_(g, g, 1-b2); denom = sqrt(v)/sqrt(bc2) + eps; p += -(lr/bc1) * m/denom
+// This file is not built with -ffp-contract=off, so each a * b + c below may round once instead of twice: the results are
+// within rounding of torch's fp32 Adam, not its bits (tests/loss_cases.py bounds both forms against fp64).
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                    float one_minus_b1, float b2, float one_minus_b2,

@@ -362,6 +362,7 @@ class _L1Loss(Function):
     def forward(ctx, pred, y, denom):
         _dev(pred, y)
         _on(pred.device, y)
+        ctx.shape = pred.shape
         pred = pred.contiguous().view(-1)
         y = y.contiguous().view(-1)
         if pred.numel() != y.numel():
@@ -376,7 +377,7 @@ class _L1Loss(Function):
     @staticmethod
     def backward(ctx, g):
         (dpred,) = ctx.saved_tensors
-        return (dpred * g).view(-1, 1), None, None
+        return (dpred * g).view(ctx.shape), None, None
 
 
 def l1_loss(pred, y, denom=None):
