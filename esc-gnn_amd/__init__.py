@@ -24,7 +24,7 @@ __all__ = ["create_subgraphs", "create_subgraphs_many", "Data", "Batch", "DataLo
 def install_dropin():
     """Register this package's modules under the reference's top-level module names, so that an unmodified
     `from utils_edge_efficient import create_subgraphs`, `from batch import Batch`,
-    `from dataloader import DataLoader`, `from kernel.gin import NestedGIN_eff`, `from zinc_models import *`,
+    `from utils import create_subgraphs`, `from dataloader import DataLoader`, `from kernel.gin import NestedGIN_eff`, `from zinc_models import *`,
     `from zinc_cycle_models import *`, `from qm9_models import *`, `from distance import Distance`,
     `from ogb_mol_gnn import GNN` or `from modules.gine_operations import GINEPLUS` resolves here."""
     import sys
@@ -33,6 +33,8 @@ def install_dropin():
                    utils_edge_efficient as _uee, zinc_cycle_models as _zinc_cycle, zinc_models as _zinc)
     from .modules import gine_operations as _gine_ops
     sys.modules.setdefault("utils_edge_efficient", _uee)
+    from . import utils as _utils                       # the node-rooted create_subgraphs (run_zinc --model NGNN)
+    sys.modules.setdefault("utils", _utils)
     sys.modules.setdefault("zinc_models", _zinc)
     sys.modules.setdefault("zinc_cycle_models", _zinc_cycle)
     from . import geometry as _geometry, qm9_models as _qm9

@@ -44,6 +44,14 @@ ABI_VERSION = const("ESC_ABI_VERSION")
 ESC_ERANGE = const("ESC_ERANGE")            # the status of an input outside the encodable range (cycles, graphlets, features)
 SIGNATURES = {name: args for name, (args, _) in _ABI.functions.items()}     # name -> argtypes
 _RET = {name: ret for name, (_, ret) in _ABI.functions.items()}
+# the entry points of the extension header (escgnn_subgraphs.h: the NGNN baseline), derived the same way and bound beside them
+EXTENSION_HEADER = os.path.join(os.path.dirname(_abi.HEADER), "escgnn_subgraphs.h")
+try:
+    _EXT = _abi.load(EXTENSION_HEADER)
+except OSError as exc:
+    raise NativeLibraryError("esc_gnn_amd: cannot read the C header %s the binding is derived from (%s)" % (EXTENSION_HEADER, exc)) from exc
+EXTENSION_SIGNATURES = {name: args for name, (args, _) in _EXT.functions.items()}
+_RET.update({name: ret for name, (_, ret) in _EXT.functions.items()})
 KIND = {name[len("ESC_K_"):].lower(): v for name, v in _ABI.enum.items() if name != "ESC_K_COUNT"}
 
 CollateArgs = struct("esc_collate_args")
@@ -67,7 +75,7 @@ def lib():
             "esc_gnn_amd: %s not found. The HIP hot path has no fallback — build it with "
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C esc-gnn_amd/csrc`." % LIB_PATH)
     h = ctypes.CDLL(LIB_PATH)
-    for name, args in SIGNATURES.items():
+    for name, args in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()):
         try:
             fn = getattr(h, name)
         except AttributeError as exc:

@@ -35,6 +35,7 @@
 //                computed once, in the count pass, and kept in `work` for the fill pass.
 // Integer work bound by LDS/L2 latency, not HBM.
 #include "common.h"
+#include "jacobi_pinv.h"
 
 namespace esc {
 
@@ -282,88 +283,7 @@ __global__ __launch_bounds__(64) void feat_class_mark_kernel(ClassArgs a) {
   }
 }
 
-// ---- one-sided Jacobi SVD based pseudo-inverse probe, NT threads, column-major matrices (LDS or global) -----
-// On entry Gm = L (m x m), Vm = I.  On exit Gm = L*V with mutually orthogonal columns.
-// Returns the squared-norm threshold below which a column counts as numerically null:
-// 4 (m eps)^2 ||L||_F^2, i.e. scipy.linalg.pinv's default cutoff max(M,N)*eps*sigma_max with a
-// small margin (||L||_F >= sigma_max).  Null columns are neither rotated nor inverted.
-template <int NT>
-__device__ double jacobi_orthogonalise(double* __restrict__ Gm, double* __restrict__ Vm, int m, int ld, double* red) {
-  const int tid = threadIdx.x;
-  double fro2 = 0.0;
-  for (int idx = tid; idx < m * m; idx += NT) {
-    const double v = Gm[(size_t)(idx / m) * ld + (idx % m)];
-    fro2 += v * v;
-  }
-  fro2 = wave_sum(fro2);
-  if (NT > 64) {                                  // fixed order over the waves: the threshold is the same in every thread
-    __syncthreads();
-    if ((tid & 63) == 0) red[tid >> 6] = fro2;
-    __syncthreads();
-    fro2 = 0.0;
-    for (int w = 0; w < NT / 64; ++w) fro2 += red[w];
-    __syncthreads();
-  }
-  const double meps = (double)m * 2.220446049250313e-16;
-  const double null2 = 4.0 * meps * meps * fro2;
-  if (m < 2 || fro2 == 0.0) return null2;
-  const int M = (m + 1) & ~1;                  // round-robin needs an even player count (last = dummy)
-  const int npairs = M / 2;
-  int S = 1;                                   // sub-lanes per pair (power of two, inside one wave)
-  while (S < 64 && npairs * S * 2 <= NT) S *= 2;
-  if (NT > 64 && S < 8) S = 8;                 // global-memory matrices: 8 consecutive rows per pair = one 64-B segment
-  const int pairs_per_pass = NT / S;
-  for (int sweep = 0; sweep < 40; ++sweep) {
-    int rotated = 0;
-    for (int r = 0; r < M - 1; ++r) {
-      for (int p0 = 0; p0 < npairs; p0 += pairs_per_pass) {
-        const int pi = p0 + tid / S, sub = tid % S;
-        int p = -1, q = -1;
-        if (pi < npairs) {
-          const int a = pi, b = M - 1 - pi;
-          p = (a == 0) ? 0 : 1 + ((a - 1 + r) % (M - 1));
-          q = 1 + ((b - 1 + r) % (M - 1));
-          if (p > q) { const int t = p; p = q; q = t; }
-          if (q >= m) p = -1;                  // paired with the dummy player
-        }
-        double al = 0.0, be = 0.0, ga = 0.0;
-        if (p >= 0) {
-          const double* gp = Gm + (size_t)p * ld;
-          const double* gq = Gm + (size_t)q * ld;
-          for (int i = sub; i < m; i += S) {
-            const double x = gp[i], y = gq[i];
-            al += x * x; be += y * y; ga += x * y;
-          }
-        }
-        for (int o = 1; o < S; o <<= 1) {
-          al += __shfl_xor(al, o, 64); be += __shfl_xor(be, o, 64); ga += __shfl_xor(ga, o, 64);
-        }
-        bool rot = false;
-        double c = 1.0, s = 0.0;
-        if (p >= 0 && al > null2 && be > null2 && fabs(ga) > 1e-15 * sqrt(al * be)) {
-          const double zeta = (be - al) / (2.0 * ga);
-          const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-          c = 1.0 / sqrt(1.0 + t * t);
-          s = c * t;
-          rot = true;
-        }
-        if (rot) {
-          double* gp = Gm + (size_t)p * ld; double* gq = Gm + (size_t)q * ld;
-          double* vp = Vm + (size_t)p * ld; double* vq = Vm + (size_t)q * ld;
-          for (int i = sub; i < m; i += S) {
-            const double x = gp[i], y = gq[i];
-            gp[i] = c * x - s * y; gq[i] = s * x + c * y;
-            const double u = vp[i], w = vq[i];
-            vp[i] = c * u - s * w; vq[i] = s * u + c * w;
-          }
-        }
-        rotated |= __syncthreads_or(rot ? 1 : 0);
-      }
-    }
-    if (!rotated) break;
-  }
-  return null2;
-}
+// (jacobi_orthogonalise, the one-sided Jacobi SVD behind the pseudo-inverse, lives in jacobi_pinv.h: subgraphs.hip shares it)
 
 // ---- one pseudo-inverse per class, then the rd row of every member edge ----------------------------------
 // HUGE = false: one wave, matrices in LDS with leading dimension a.ld; HUGE = true: 256 threads, matrices on this

@@ -1,0 +1,414 @@
+// subgraphs.hip — node-rooted h-hop subgraph expansion of a collated batch (the NGNN baseline's pre_transform) on the GPU.
+//
+// Replaces create_subgraphs / k_hop_subgraph of the reference's utils.py:18-132,135-229: a python loop over every node with
+// a tensor-mask BFS, a relabel and a scipy pinv per root, run once per dataset on the host.  Here the expansion runs per
+// batch on the device, so there is no pre-processed dataset and no host collate of subgraphs.
+//
+// Semantics restated:
+//   * S_r = nodes within h hops of r walking target -> source (`col, row = edge_index`, :145), as feat_bfs_kernel does
+//   * sub-edges = ALL edges with both endpoints in S_r, in their original order; self loops and repeats kept (:218-222)
+//   * hop label z = hop + 1 (:154,:167)
+//   * the label LIST of a node gets one entry per frontier edge that reaches it in its level (:163-167 test `visited`, which
+//     only grows after the level), so a node with two or more such edges carries the label twice: `paths` counts them
+//     (0 for the root) and the python layer forms the reference's spd / drnl columns from (z, paths)
+//   * rd[i] = P[0,0] + P[i,i] - P[0,i] - P[i,0], P = pinv(D_in - A) over the non-loop sub-edges, fp64 -> fp32 (:59-74)
+//
+// Canonical order (the contract): the sub-nodes of r are the root, then ascending (hop, node id).  The reference's
+// order inside a level is the iteration order of a CPython set; the model does not depend on it.
+//
+// One wave per root, twice: the count pass sizes the output, the fill pass repeats the BFS (cheaper than keeping n^2 hop
+// tables between the passes) and writes with stable ballot-prefix compaction.  Integer work bound by LDS / L2 latency.
+#include "common.h"
+#include "jacobi_pinv.h"
+#include "../../include/escgnn_subgraphs.h"
+
+namespace esc {
+
+constexpr unsigned char SUB_INF = 255;
+constexpr int SUB_RD_MAX = 96;          // largest subgraph whose two m x m fp64 matrices fit LDS (147 KB); LDS_SUBGRAPH of features.hip
+
+// last g with ptr[g] <= i
+__device__ __forceinline__ int sub_find_segment(const int64_t* __restrict__ ptr, int G, int64_t i) {
+  int lo = 0, hi = G;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (ptr[mid] <= i) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// ---- per-graph validation (one wave per graph): ids inside the graph, graph inside the LDS tables -----------------
+__global__ __launch_bounds__(64) void sub_validate_kernel(const int64_t* __restrict__ node_ptr,
+                                                          const int64_t* __restrict__ edge_ptr,
+                                                          const int64_t* __restrict__ src, const int64_t* __restrict__ dst,
+                                                          int G, int64_t total_nodes, int64_t total_edges, int64_t max_nodes,
+                                                          int* __restrict__ status) {
+  const int g = blockIdx.x;
+  if (g >= G) return;
+  const int lane = threadIdx.x;
+  const int64_t n0 = node_ptr[g], n1 = node_ptr[g + 1], e0 = edge_ptr[g], e1 = edge_ptr[g + 1];
+  int bad = 0;
+  // per graph: ordered and inside the arrays; the first and the last also pin the ends, so that together the ranges tile
+  // [0, total) and every root falls inside the graph find_segment gives it (a root of a refused graph is skipped)
+  const bool ends = (g > 0 || (n0 == 0 && e0 == 0)) && (g < G - 1 || (n1 == total_nodes && e1 == total_edges));
+  if (!ends || n0 < 0 || n1 < n0 || n1 > total_nodes || n1 - n0 > max_nodes || e0 < 0 || e1 < e0 || e1 > total_edges) {
+    bad = 1;
+  } else {
+    for (int64_t j = e0 + lane; j < e1; j += 64) {
+      const int64_t s = src[j], d = dst[j];
+      if (s < n0 || s >= n1 || d < n0 || d >= n1) bad = 1;
+    }
+  }
+  bad = __any(bad) ? 1 : 0;
+  if (lane == 0) status[g] = bad ? ESC_ERANGE : 0;
+}
+
+// what one root's wave knows about its graph
+struct SubRoot {
+  int g, n, r;
+  int64_t n0, e0;
+  int Eg;
+};
+
+__device__ __forceinline__ SubRoot sub_locate(const int64_t* __restrict__ node_ptr, const int64_t* __restrict__ edge_ptr, int G,
+                                              int64_t r_glob) {
+  SubRoot q;
+  q.g = sub_find_segment(node_ptr, G, r_glob);
+  q.n0 = node_ptr[q.g];
+  q.n = (int)(node_ptr[q.g + 1] - q.n0);
+  q.r = (int)(r_glob - q.n0);
+  q.e0 = edge_ptr[q.g];
+  q.Eg = (int)(edge_ptr[q.g + 1] - q.e0);
+  return q;
+}
+
+// level-synchronous BFS from q.r over the graph's edge list (global ids, L2 resident); hop[x] = d(r, x) or SUB_INF beyond h.
+// Every lane that reaches a node in level d writes the same d: the race is benign.
+__device__ __forceinline__ void sub_bfs(const SubRoot& q, const int64_t* __restrict__ src, const int64_t* __restrict__ dst, int h,
+                                        unsigned char* hop) {
+  const int lane = threadIdx.x;
+  for (int x = lane; x < q.n; x += 64) hop[x] = SUB_INF;
+  __syncthreads();
+  if (lane == 0) hop[q.r] = 0;
+  __syncthreads();
+  for (int d = 1; d <= h; ++d) {
+    int grew = 0;
+    for (int j = lane; j < q.Eg; j += 64) {
+      const int s = (int)(src[q.e0 + j] - q.n0), t = (int)(dst[q.e0 + j] - q.n0);
+      if (hop[t] == d - 1 && hop[s] == SUB_INF) { hop[s] = (unsigned char)d; grew = 1; }
+    }
+    __syncthreads();
+    if (!__any(grew)) break;
+  }
+}
+
+// ---- count pass: |S_r| and the number of sub-edges of every root, left in the pointer arrays for the scan ----------
+__global__ __launch_bounds__(64) void sub_count_kernel(const int64_t* __restrict__ node_ptr, const int64_t* __restrict__ edge_ptr,
+                                                       const int64_t* __restrict__ src, const int64_t* __restrict__ dst, int G,
+                                                       int64_t total_nodes, int h, const int* __restrict__ status,
+                                                       int64_t* __restrict__ cnt_nodes, int64_t* __restrict__ cnt_edges) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int lane = threadIdx.x;
+  const int64_t r_glob = blockIdx.x;
+  if (r_glob >= total_nodes) return;
+  const SubRoot q = sub_locate(node_ptr, edge_ptr, G, r_glob);
+  if (status[q.g] != 0) {
+    if (lane == 0) { cnt_nodes[r_glob] = 0; cnt_edges[r_glob] = 0; }
+    return;
+  }
+  unsigned char* hop = smem;
+  sub_bfs(q, src, dst, h, hop);
+  int nn = 0, ne = 0;
+  for (int x0 = 0; x0 < q.n; x0 += 64) {
+    const int x = x0 + lane;
+    nn += __popcll(__ballot(x < q.n && hop[x] != SUB_INF));
+  }
+  for (int j0 = 0; j0 < q.Eg; j0 += 64) {
+    const int j = j0 + lane;
+    bool keep = false;
+    if (j < q.Eg) keep = hop[src[q.e0 + j] - q.n0] != SUB_INF && hop[dst[q.e0 + j] - q.n0] != SUB_INF;
+    ne += __popcll(__ballot(keep));
+  }
+  if (lane == 0) { cnt_nodes[r_glob] = nn; cnt_edges[r_glob] = ne; }
+}
+
+// ---- in-place exclusive scan of int64 counts (scan_counts_kernel's scheme: one workgroup, 1024-wide chunks with a carry);
+// blockIdx.x picks the array ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void sub_scan_kernel(int64_t* __restrict__ a0, int64_t* __restrict__ a1, int64_t n) {
+  __shared__ int64_t wsum[16];
+  __shared__ int64_t carry_s;
+  int64_t* __restrict__ buf = blockIdx.x == 0 ? a0 : a1;
+  if (threadIdx.x == 0) carry_s = 0;
+  __syncthreads();
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (int64_t base = 0; base < n; base += 1024) {
+    const int64_t i = base + threadIdx.x;
+    const int64_t v = (i < n) ? buf[i] : 0;
+    int64_t incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int64_t t = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += t;
+    }
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    int64_t woff = 0;
+    for (int k = 0; k < w; ++k) woff += wsum[k];
+    const int64_t carry = carry_s;
+    if (i < n) buf[i] = carry + woff + incl - v;
+    __syncthreads();
+    if (threadIdx.x == 1023) carry_s = carry + woff + incl;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) buf[n] = carry_s;
+}
+
+// ---- fill pass ------------------------------------------------------------------------------------------------------
+struct SubFillArgs {
+  const int64_t* node_ptr; const int64_t* edge_ptr; const int64_t* src; const int64_t* dst;
+  const int64_t* sub_node_ptr; const int64_t* sub_edge_ptr;
+  int64_t* orig_node; int64_t* hop_label; int64_t* hop_paths; int64_t* node_to_subgraph; int64_t* node_to_graph;
+  int64_t* sub_src; int64_t* sub_dst; int64_t* orig_edge;
+  float* rd;
+  int* status;
+  int64_t total_nodes, total_sub_nodes, total_sub_edges;
+  int G, h, n_cap, ld;
+};
+
+// LDS: hop[n_cap] bytes | loc[n_cap] shorts | paths[n_cap] ints; (RD) Gm[ld*ld] Vm[ld*ld] inv_s2[ld] vrow[ld] red[8] doubles
+// start where `paths` did — it is dead once the node rows are written (4096-node graphs with ld = 96: 158 KB of the 160)
+template <bool RD>
+__global__ __launch_bounds__(64) void sub_fill_kernel(SubFillArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int lane = threadIdx.x;
+  const int64_t r_glob = blockIdx.x;
+  if (r_glob >= a.total_nodes) return;
+  const SubRoot q = sub_locate(a.node_ptr, a.edge_ptr, a.G, r_glob);
+  // a graph the count pass refused has zero-length ranges (a valid root holds at least itself).  `status` is not read here:
+  // another root of this graph may be setting it for an rd overflow, which must not silence this one
+  if (a.sub_node_ptr[r_glob + 1] == a.sub_node_ptr[r_glob]) return;
+  if (a.sub_node_ptr[r_glob + 1] > a.total_sub_nodes || a.sub_edge_ptr[r_glob + 1] > a.total_sub_edges) {
+    if (threadIdx.x == 0) a.status[q.g] = ESC_ERANGE;       // the caller's totals are not those of the count pass: write nothing
+    return;
+  }
+  unsigned char* hop = smem;                                // [n_cap]
+  short* loc = reinterpret_cast<short*>(hop + a.n_cap);     // [n_cap]
+  int* paths = reinterpret_cast<int*>(loc + a.n_cap);       // [n_cap]
+  sub_bfs(q, a.src, a.dst, a.h, hop);
+  // canonical positions: level by level, ascending node id inside a level (the root is the only node of level 0)
+  int m = 0;
+  for (int d = 0; d <= a.h; ++d) {
+    const int before = m;
+    for (int x0 = 0; x0 < q.n; x0 += 64) {
+      const int x = x0 + lane;
+      const bool mine = x < q.n && hop[x] == d;
+      const unsigned long long msk = __ballot(mine);
+      if (mine) loc[x] = (short)(m + __popcll(msk & ((1ull << lane) - 1ull)));
+      m += __popcll(msk);
+    }
+    if (m == before) break;                                 // an empty level ends the BFS
+  }
+  for (int x = lane; x < q.n; x += 64) { paths[x] = 0; if (hop[x] == SUB_INF) loc[x] = -1; }
+  __syncthreads();
+  const int64_t sn0 = a.sub_node_ptr[r_glob], se0 = a.sub_edge_ptr[r_glob];
+  // sub-edges in their original order, relabelled to global sub-node ids; and the frontier edges into every node
+  int base = 0;
+  for (int j0 = 0; j0 < q.Eg; j0 += 64) {
+    const int j = j0 + lane;
+    bool keep = false;
+    int s = 0, t = 0;
+    if (j < q.Eg) {
+      s = (int)(a.src[q.e0 + j] - q.n0); t = (int)(a.dst[q.e0 + j] - q.n0);
+      keep = hop[s] != SUB_INF && hop[t] != SUB_INF;
+    }
+    const unsigned long long msk = __ballot(keep);
+    if (keep) {
+      const int64_t p = se0 + base + __popcll(msk & ((1ull << lane) - 1ull));
+      a.sub_src[p] = sn0 + loc[s]; a.sub_dst[p] = sn0 + loc[t]; a.orig_edge[p] = q.e0 + j;
+      if ((int)hop[t] + 1 == (int)hop[s]) atomicAdd(&paths[s], 1);
+    }
+    base += __popcll(msk);
+  }
+  __syncthreads();
+  for (int x = lane; x < q.n; x += 64) {
+    if (hop[x] == SUB_INF) continue;
+    const int64_t p = sn0 + loc[x];
+    a.orig_node[p] = q.n0 + x; a.hop_label[p] = (int64_t)hop[x] + 1; a.hop_paths[p] = paths[x];
+    a.node_to_subgraph[p] = r_glob; a.node_to_graph[p] = q.g;
+  }
+  if (!RD) return;
+  if (m > SUB_RD_MAX || m > a.ld) {                          // wave-uniform
+    if (lane == 0) a.status[q.g] = ESC_ERANGE;
+    return;
+  }
+  const int ld = a.ld;
+  __syncthreads();                                          // `paths` has been read: the matrices take its place
+  const size_t off = ((size_t)a.n_cap * 3 + 15) & ~(size_t)15;
+  double* Gm = reinterpret_cast<double*>(smem + off);
+  double* Vm = Gm + (size_t)ld * ld;
+  double* inv_s2 = Vm + (size_t)ld * ld;
+  double* vrow = inv_s2 + ld;
+  double* red = vrow + ld;
+  for (int idx = lane; idx < m * m; idx += 64) {
+    const int cc = idx / m, rr = idx % m;
+    Gm[(size_t)cc * ld + rr] = 0.0;
+    Vm[(size_t)cc * ld + rr] = (cc == rr) ? 1.0 : 0.0;
+  }
+  __syncthreads();
+  // L = D_in - A over the non-loop sub-edges (scipy csgraph.laplacian), column-major
+  for (int j = lane; j < q.Eg; j += 64) {
+    const int s = (int)(a.src[q.e0 + j] - q.n0), t = (int)(a.dst[q.e0 + j] - q.n0);
+    if (s == t || hop[s] == SUB_INF || hop[t] == SUB_INF) continue;
+    const int ls = loc[s], lt = loc[t];
+    atomicAdd(&Gm[(size_t)lt * ld + ls], -1.0);             // L[s][t] -= 1   ([col t][row s]); integer values: order free
+    atomicAdd(&Gm[(size_t)lt * ld + lt], 1.0);              // L[t][t] += 1   (in-degree, loops excluded)
+  }
+  __syncthreads();
+  const double null2 = jacobi_orthogonalise<64>(Gm, Vm, m, ld, red);
+  __syncthreads();
+  pinv_from_jacobi<64>(Gm, Vm, m, ld, null2, inv_s2, vrow);
+  const double* __restrict__ P = Vm;                        // P[i][j] at P[j*ld + i]; the root is local node 0
+  const double p00 = P[0];
+  for (int i = lane; i < m; i += 64) {
+    const double rd64 = ((p00 + P[(size_t)i * ld + i]) - P[(size_t)i * ld]) - P[i];   // lxx + lyy - lxy - lyx (:73): 0 at the root
+    a.rd[sn0 + i] = (float)rd64;
+  }
+}
+
+// ---- subgraph_pooling = 'center': the first row of every segment ---------------------------------------------------------
+__global__ __launch_bounds__(256) void segment_first_fwd_kernel(const float* __restrict__ x, int64_t ld_x,
+                                                                const int64_t* __restrict__ ptr, int64_t S, int64_t C,
+                                                                float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= S * C) return;
+  const int64_t s = i / C, c = i - s * C;
+  const int64_t first = ptr[s];
+  out[i] = first < ptr[s + 1] ? x[first * ld_x + c] : 0.f;  // (an empty segment has no first row)
+}
+
+// every row of dx is written: the gradient on a segment's first row, zero elsewhere — no memset, no atomics
+__global__ __launch_bounds__(256) void segment_first_bwd_kernel(const float* __restrict__ dout, int64_t ld_dout,
+                                                                const int64_t* __restrict__ ptr,
+                                                                const int64_t* __restrict__ node_to_segment, int64_t N,
+                                                                int64_t C, float* __restrict__ dx) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= N * C) return;
+  const int64_t row = i / C, c = i - row * C;
+  const int64_t s = node_to_segment[row];
+  dx[i] = ptr[s] == row ? dout[s * ld_dout + c] : 0.f;
+}
+
+static size_t sub_fill_lds(int n_cap, int ld, bool rd) {
+  const size_t plain = ((size_t)n_cap * 7 + 15) & ~(size_t)15;
+  if (!rd) return plain;
+  const size_t with_rd = (((size_t)n_cap * 3 + 15) & ~(size_t)15) + ((size_t)2 * ld * ld + 2 * (size_t)ld + 8) * 8;
+  return with_rd > plain ? with_rd : plain;
+}
+
+static int sub_check(const char* fn, const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* src, const int64_t* dst,
+                     int64_t G, int64_t total_nodes, int64_t total_edges, int64_t max_nodes, int h) {
+  ESC_REQUIRE(node_ptr && edge_ptr, "%s: null pointer", fn);
+  ESC_REQUIRE((src && dst) || total_edges == 0, "%s: null edge arrays", fn);
+  ESC_REQUIRE(G > 0 && G < (1LL << 31), "%s: bad graph count %ld", fn, (long)G);
+  if (h < 1 || h > 98) {
+    set_error("%s: h=%d outside 1..98 (the model's z tables have 100 rows and z = hop + 1)", fn, h);
+    return ESC_ERANGE;
+  }
+  if (max_nodes < 1 || max_nodes > 4096) {
+    set_error("%s: max_nodes=%ld outside 1..4096", fn, (long)max_nodes);
+    return ESC_ERANGE;
+  }
+  if (total_nodes < 0 || total_edges < 0 || total_nodes >= (1LL << 31) - 1 || total_edges >= (1LL << 31) - 1) {
+    set_error("%s: %ld nodes / %ld edges: totals must stay below 2^31", fn, (long)total_nodes, (long)total_edges);
+    return ESC_ERANGE;
+  }
+  return ESC_OK;
+}
+
+}  // namespace esc
+
+using namespace esc;
+
+extern "C" {
+
+int esc_subgraph_count(const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* src, const int64_t* dst, int64_t G,
+                       int64_t total_nodes, int64_t total_edges, int64_t max_nodes, int h, int64_t* sub_node_ptr,
+                       int64_t* sub_edge_ptr, int32_t* status, void* stream) {
+  const int rc = sub_check("esc_subgraph_count", node_ptr, edge_ptr, src, dst, G, total_nodes, total_edges, max_nodes, h);
+  if (rc) return rc;
+  ESC_REQUIRE(sub_node_ptr && sub_edge_ptr && status, "esc_subgraph_count: null output");
+  hipStream_t s = (hipStream_t)stream;
+  esc::launch(ESC_K_FEATURES, sub_validate_kernel, dim3((unsigned)G), dim3(64), 0, s, node_ptr, edge_ptr, src, dst, (int)G,
+              total_nodes, total_edges, max_nodes, status);
+  ESC_CHECK_LAUNCH("esc_subgraph_count.validate");
+  if (total_nodes > 0) {
+    const int n_cap = (int)((max_nodes + 3) & ~3LL);
+    esc::launch(ESC_K_FEATURES, sub_count_kernel, dim3((unsigned)total_nodes), dim3(64), (size_t)n_cap, s, node_ptr, edge_ptr,
+                src, dst, (int)G, total_nodes, h, (const int*)status, sub_node_ptr, sub_edge_ptr);
+    ESC_CHECK_LAUNCH("esc_subgraph_count.count");
+  }
+  esc::launch(ESC_K_FEATURES, sub_scan_kernel, dim3(2), dim3(1024), 0, s, sub_node_ptr, sub_edge_ptr, total_nodes);
+  ESC_CHECK_LAUNCH("esc_subgraph_count.scan");
+  return ESC_OK;
+}
+
+int esc_subgraph_fill(const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* src, const int64_t* dst, int64_t G,
+                      int64_t total_nodes, int64_t total_edges, int64_t max_nodes, int h, const int64_t* sub_node_ptr,
+                      const int64_t* sub_edge_ptr, int64_t total_sub_nodes, int64_t total_sub_edges, int use_rd,
+                      int64_t* orig_node, int64_t* hop_label, int64_t* hop_paths, int64_t* node_to_subgraph,
+                      int64_t* node_to_graph, int64_t* sub_src, int64_t* sub_dst, int64_t* orig_edge, float* rd,
+                      int32_t* status, void* stream) {
+  const int rc = sub_check("esc_subgraph_fill", node_ptr, edge_ptr, src, dst, G, total_nodes, total_edges, max_nodes, h);
+  if (rc) return rc;
+  ESC_REQUIRE(sub_node_ptr && sub_edge_ptr && status, "esc_subgraph_fill: null pointer");
+  if (total_sub_nodes < 0 || total_sub_edges < 0 || total_sub_nodes >= (1LL << 31) - 1 || total_sub_edges >= (1LL << 31) - 1) {
+    set_error("esc_subgraph_fill: %ld sub-nodes / %ld sub-edges: totals must stay below 2^31", (long)total_sub_nodes,
+              (long)total_sub_edges);
+    return ESC_ERANGE;
+  }
+  if (total_nodes == 0 || total_sub_nodes == 0) return ESC_OK;
+  ESC_REQUIRE(orig_node && hop_label && hop_paths && node_to_subgraph && node_to_graph, "esc_subgraph_fill: null node output");
+  ESC_REQUIRE((sub_src && sub_dst && orig_edge) || total_sub_edges == 0, "esc_subgraph_fill: null edge output");
+  ESC_REQUIRE(!use_rd || rd, "esc_subgraph_fill: use_rd without an rd output");
+  hipStream_t s = (hipStream_t)stream;
+  SubFillArgs a{};
+  a.node_ptr = node_ptr; a.edge_ptr = edge_ptr; a.src = src; a.dst = dst; a.sub_node_ptr = sub_node_ptr; a.sub_edge_ptr = sub_edge_ptr;
+  a.orig_node = orig_node; a.hop_label = hop_label; a.hop_paths = hop_paths; a.node_to_subgraph = node_to_subgraph;
+  a.node_to_graph = node_to_graph; a.sub_src = sub_src; a.sub_dst = sub_dst; a.orig_edge = orig_edge; a.rd = rd; a.status = status;
+  a.total_nodes = total_nodes; a.total_sub_nodes = total_sub_nodes; a.total_sub_edges = total_sub_edges; a.G = (int)G; a.h = h; a.n_cap = (int)((max_nodes + 3) & ~3LL);
+  const int m_even = (int)((max_nodes + 1) & ~1LL);
+  a.ld = m_even < SUB_RD_MAX ? m_even : SUB_RD_MAX;
+  if (use_rd) {
+    const size_t lds = sub_fill_lds(a.n_cap, a.ld, true);
+    ESC_REQUIRE(lds <= 160 * 1024, "esc_subgraph_fill: rd working set %zu B exceeds LDS", lds);
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)sub_fill_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    esc::launch(ESC_K_FEATURES, sub_fill_kernel<true>, dim3((unsigned)total_nodes), dim3(64), lds, s, a);
+  } else {
+    esc::launch(ESC_K_FEATURES, sub_fill_kernel<false>, dim3((unsigned)total_nodes), dim3(64), sub_fill_lds(a.n_cap, a.ld, false), s, a);
+  }
+  ESC_CHECK_LAUNCH("esc_subgraph_fill.fill");
+  return ESC_OK;
+}
+
+int esc_segment_first_fwd(const float* x, int64_t ld_x, const int64_t* ptr, int64_t S, int64_t C, float* out, void* stream) {
+  ESC_REQUIRE(S >= 0 && C >= 0 && ld_x >= C && S * C < (1LL << 40), "esc_segment_first_fwd: bad shape");
+  if (S * C == 0) return ESC_OK;
+  ESC_REQUIRE(x && ptr && out, "esc_segment_first_fwd: null pointer");
+  esc::launch(ESC_K_FEATURES, segment_first_fwd_kernel, dim3((unsigned)cdiv(S * C, 256)), dim3(256), 0, (hipStream_t)stream, x, ld_x,
+              ptr, S, C, out);
+  ESC_CHECK_LAUNCH("esc_segment_first_fwd");
+  return ESC_OK;
+}
+
+int esc_segment_first_bwd(const float* dout, int64_t ld_dout, const int64_t* ptr, const int64_t* node_to_segment, int64_t N,
+                          int64_t C, float* dx, void* stream) {
+  ESC_REQUIRE(N >= 0 && C >= 0 && ld_dout >= C && N * C < (1LL << 40), "esc_segment_first_bwd: bad shape");
+  if (N * C == 0) return ESC_OK;
+  ESC_REQUIRE(dout && ptr && node_to_segment && dx, "esc_segment_first_bwd: null pointer");
+  esc::launch(ESC_K_FEATURES, segment_first_bwd_kernel, dim3((unsigned)cdiv(N * C, 256)), dim3(256), 0, (hipStream_t)stream, dout,
+              ld_dout, ptr, node_to_segment, N, C, dx);
+  ESC_CHECK_LAUNCH("esc_segment_first_bwd");
+  return ESC_OK;
+}
+
+}  // extern "C"

@@ -311,6 +311,9 @@ def zinc_engine_supports(m, data=None):
     """what esc_zinc_* covers: the run_zinc configuration (dropout 0; BatchNorm statistics per rank or, after
     nn.BatchNorm1d.convert_sync, over ONE process group through the collective provider), sparse ESC bag, at least two graphs
     in the batch (the reference skips bn_lin1 for one, zinc_models.py:603-604)"""
+    from .zinc_models import NestedGIN_eff
+    if not isinstance(m, NestedGIN_eff):                    # (the NGNN baseline trains through the per-op path)
+        return False
     if m.dropout != 0 or m.lin1.weight.device.type != "cuda" or m.lin2.out_features != 1 or not _one_sync_group(m):
         return False
     if data is not None:

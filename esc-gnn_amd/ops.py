@@ -955,3 +955,37 @@ def pdist(x, threshold=None):
     nv.call("esc_pdist", nv.ptr(x), ldx, M, C, nv.ptr(out), float(threshold if threshold is not None else 0.0),
             nv.ptr(below), nv.stream())
     return out if threshold is None else (out, int(below.item()))
+
+
+class _SegmentFirst(Function):
+    """x[first row of every segment]: the reference's `x[center_indices]` (zinc_models.py:388-392, the root is the first node
+    of its subgraph) without the host round trip of np.unique; the gradient writes every row once (no memset, no atomics)."""
+
+    @staticmethod
+    def forward(ctx, x, ptr, node_to_segment):
+        _dev(x)
+        _on(x.device, ptr, node_to_segment)
+        if ptr.dtype != torch.int64 or node_to_segment.dtype != torch.int64:
+            raise TypeError("segment_first: ptr and node_to_segment must be int64")
+        x, ldx = _rows(x)
+        ptr, node_to_segment = ptr.contiguous(), node_to_segment.contiguous()
+        S, C = ptr.numel() - 1, x.size(1)
+        if node_to_segment.numel() != x.size(0):
+            raise ValueError("segment_first: %d rows but %d segment ids" % (x.size(0), node_to_segment.numel()))
+        out = torch.empty((S, C), dtype=torch.float32, device=x.device)
+        nv.call("esc_segment_first_fwd", nv.ptr(x), ldx, nv.ptr(ptr), S, C, nv.ptr(out), nv.stream())
+        ctx.ptr, ctx.seg, ctx.n = ptr, node_to_segment, x.size(0)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        g, ldg = _rows(g)
+        C = g.size(1)
+        dx = torch.empty((ctx.n, C), dtype=torch.float32, device=g.device)
+        nv.call("esc_segment_first_bwd", nv.ptr(g), ldg, nv.ptr(ctx.ptr), nv.ptr(ctx.seg), ctx.n, C, nv.ptr(dx), nv.stream())
+        return dx, None, None
+
+
+def segment_first(x, ptr, node_to_segment):
+    """out[s] = x[ptr[s]]; ptr: int64 [S+1] segment pointers, node_to_segment: int64 [N] (non-decreasing)."""
+    return _SegmentFirst.apply(x, ptr, node_to_segment)

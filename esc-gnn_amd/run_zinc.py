@@ -1,5 +1,6 @@
 """ZINC driver on the ESC hot path — the MI355X-native twin of /root/reference/run_zinc.py for
-`--model NestedGIN_eff` (BASELINE config 4): flags (:21-86), processed-name / feature settings (:161-176,
+`--model NestedGIN_eff` (BASELINE config 4) and the node-rooted baseline `--model NGNN`: flags (:21-86), processed-name /
+feature settings (:161-176,
 `create_subgraphs_eff(g, h, use_rd, self_loop)` :141-146), target normalisation (:211-217), L1 training loop and
 "test when validation improves or every 10 epochs" logging (:279-339).
 
@@ -7,20 +8,25 @@ data/zinc/raw/ZINC.pkl is absent (.MISSING_LARGE_BLOBS) and is a DGL pickle, so 
 ZINC-shaped molecules (datasets.synthetic_zinc_graphs).  The whole dataset lives in HBM (DeviceGraphStore); forward,
 loss, backward and Adam run through libescgnn_hip.so; under torchrun the global batch is sharded by graph.
 
+`--model NGNN` (reference :159-161, zinc_models.py:306-405) trains the subgraph GNN ESC-GNN is measured against on the same
+molecules: the split holds the plain graphs, and every step expands the batch into its rooted subgraphs on the device
+(subgraphs.expand_subgraphs, csrc/subgraphs.hip) before the per-op forward / L1 / backward / Adam.
+
     python -m esc_gnn_amd.run_zinc --model NestedGIN_eff --h 3 --layers 6 --epochs 1000
+    python -m esc_gnn_amd.run_zinc --model NGNN --h 3 --layers 5 --epochs 1000
 """
 import torch
 
 from . import ops
 from .harness import (Context, default_appendix, fit_regression, open_result_dir, parser_from, prefetched, seed_everything,
                       sharded_batches)
-from .zinc_models import NestedGIN_eff
+from .zinc_models import NGNN, NestedGIN_eff
 
 _FLAGS = [  # same names, types and defaults as the reference CLI
     ("--target", dict(default=0, type=int)),
     ("--filter", dict(action="store_true", default=False)),
     ("--convert", dict(type=str, default="post")),
-    ("--model", dict(type=str, default="NestedGIN_eff", help="NestedGIN_eff (GNN / NGNN / I2GNN baselines: out of scope)")),
+    ("--model", dict(type=str, default="NestedGIN_eff", help="NestedGIN_eff | NGNN (GNN / I2GNN baselines: out of scope)")),
     ("--layers", dict(type=int, default=6)),
     ("--h", dict(type=int, default=3)),
     ("--max_nodes_per_hop", dict(type=int, default=None)),
@@ -71,7 +77,10 @@ def _load_splits(args):
     from .datasets import build_feature_dataset, synthetic_zinc_graphs
     G = args.synthetic_graphs
     raw = synthetic_zinc_graphs(0, G)
-    done = build_feature_dataset(raw, args.h, use_rd=args.use_rd, self_loop=args.self_loop)     # reference :141-146
+    if args.model == "NGNN":                              # plain molecules: the rooted subgraphs are expanded per batch
+        done = raw
+    else:
+        done = build_feature_dataset(raw, args.h, use_rd=args.use_rd, self_loop=args.self_loop)     # reference :141-146
     n_tr, n_va = (G * 10) // 12, G // 12
     return done[:n_tr], done[n_tr:n_tr + n_va], done[n_tr + n_va:]
 
@@ -84,7 +93,7 @@ def main(argv=None):
     from .store import DeviceGraphStore
 
     args = build_parser().parse_args(argv)
-    if args.model != "NestedGIN_eff":
+    if args.model not in ("NestedGIN_eff", "NGNN"):
         print("Error: no such model!")                    # reference :173-175 (baselines are not on the ESC path)
         raise SystemExit(1)
     if args.max_nodes_per_hop is not None:
@@ -104,11 +113,23 @@ def main(argv=None):
         for d in part:
             d.y = (d.y - mean) / std
     ctx.say("Mean = %.3f, Std = %.3f" % (float(mean), float(std)))
-    stores = [DeviceGraphStore(part, ctx.device) for part in (tr, va, te)]
+    ngnn = args.model == "NGNN"
+    if ngnn:                                               # per-graph subgraph sizes: one count pass per split
+        from .subgraphs import PlainGraphStore
+        stores = [PlainGraphStore(part, args.h, ctx.device) for part in (tr, va, te)]
+    else:
+        stores = [DeviceGraphStore(part, ctx.device) for part in (tr, va, te)]
     n_train = len(tr)
 
-    model = NestedGIN_eff(None, num_layers=args.layers, use_rd=args.use_rd, RNI=args.RNI, drop_ratio=args.drop_ratio,
-                          edge_attr_dim=5, use_pos=args.use_pos, use_max_dist=args.use_max_dist)
+    kwargs = dict(num_layers=args.layers, subgraph_pooling=args.subgraph_pooling, subgraph2_pooling=args.subgraph2_pooling,
+                  use_pos=args.use_pos, edge_attr_dim=5, use_max_dist=args.use_max_dist, use_rd=args.use_rd, RNI=args.RNI,
+                  drop_ratio=args.drop_ratio, use_pooling_nn=args.use_pooling_nn, use_virtual_node=args.virtual_node,
+                  double_pooling=args.double_pooling, gate=args.gate)               # reference :241-255
+    if ngnn:
+        model = NGNN(None, **kwargs)
+    else:
+        model = NestedGIN_eff(None, num_layers=args.layers, use_rd=args.use_rd, RNI=args.RNI, drop_ratio=args.drop_ratio,
+                              edge_attr_dim=5, use_pos=args.use_pos, use_max_dist=args.use_max_dist)
     if args.load_model is not None:
         model.load_state_dict(torch.load(args.load_model, map_location="cpu"))
     ctx.say("Using " + model.__class__.__name__ + " model")
@@ -125,12 +146,19 @@ def main(argv=None):
     from .engine import ZincStepEngine, zinc_engine_ready, zinc_engine_supports
     engine = ZincStepEngine(model) if zinc_engine_supports(model) else None     # forward + L1 + backward in ONE call
 
+    def expanded(store, batches):
+        """NGNN: every plain batch becomes the disconnected graph of its rooted subgraphs, on the device"""
+        for data, n_global in batches:
+            yield store.expand(data, args.node_label, args.use_rd), n_global
+
     def train(epoch):
         model.train()
         loss_all = torch.zeros((), device=ctx.device)
         batches = sharded_batches(stores[0], args.batch_size, ctx, True, gen)
         if args.prefetch:         # the next batch is collated on a side stream while this one trains
             batches = prefetched(batches, ctx.device)
+        if ngnn:
+            batches = expanded(stores[0], batches)
         for data, n_global in batches:
             if engine is not None and zinc_engine_ready(model, data):           # (a 1-graph tail batch takes the per-op path)
                 n_loc = data.y.numel()
@@ -162,7 +190,8 @@ def main(argv=None):
         model.eval()
         tot = torch.zeros(2, device=ctx.device)
         with torch.no_grad():
-            for data, _ in sharded_batches(store, args.batch_size, ctx, False):
+            batches = sharded_batches(store, args.batch_size, ctx, False)
+            for data, _ in (expanded(store, batches) if ngnn else batches):
                 y_hat = model(data)[:, 0]
                 tot[0] += torch.sum(torch.abs(y_hat - data.y.view(-1)))
                 tot[1] += y_hat.numel()

@@ -763,6 +763,8 @@ int esc_features_fill(const int64_t* node_ptr, const int64_t* edge_ptr, int64_t 
                       int64_t* out_src, int64_t* out_dst, int64_t* in_edge_of_out, int64_t* pos_enc,
                       int64_t* pos_index, int64_t* pos_batch, int32_t* status, void* work, void* stream);
 
+/* (the node-rooted subgraph expansion of the NGNN baseline and its first-row pooling are declared in escgnn_subgraphs.h) */
+
 /* ---- cycle-counting labels (reference dataset_zinc_cycle.py:45-61; csrc/cycles.hip) ------------------------------------
  * Same ragged, graph-local-id layout as esc_features_count (node_ptr / edge_ptr [G+1], src / dst [total_edges]).  Self loops
  * are dropped and the edges symmetrised and de-duplicated; out[v][k-3] (float32 [total_nodes, 4], 16-byte aligned) is the
