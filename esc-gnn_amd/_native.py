@@ -52,6 +52,14 @@ except OSError as exc:
     raise NativeLibraryError("esc_gnn_amd: cannot read the C header %s the binding is derived from (%s)" % (EXTENSION_HEADER, exc)) from exc
 EXTENSION_SIGNATURES = {name: args for name, (args, _) in _EXT.functions.items()}
 _RET.update({name: ret for name, (_, ret) in _EXT.functions.items()})
+# the second extension header (escgnn_i2gnn.h: the I2GNN baseline's expansion, pooling and gate), under names of its own
+I2GNN_HEADER = os.path.join(os.path.dirname(_abi.HEADER), "escgnn_i2gnn.h")
+try:
+    _I2 = _abi.load(I2GNN_HEADER)
+except OSError as exc:
+    raise NativeLibraryError("esc_gnn_amd: cannot read the C header %s the binding is derived from (%s)" % (I2GNN_HEADER, exc)) from exc
+I2GNN_SIGNATURES = {name: args for name, (args, _) in _I2.functions.items()}
+_RET.update({name: ret for name, (_, ret) in _I2.functions.items()})
 KIND = {name[len("ESC_K_"):].lower(): v for name, v in _ABI.enum.items() if name != "ESC_K_COUNT"}
 
 CollateArgs = struct("esc_collate_args")
@@ -75,7 +83,7 @@ def lib():
             "esc_gnn_amd: %s not found. The HIP hot path has no fallback — build it with "
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C esc-gnn_amd/csrc`." % LIB_PATH)
     h = ctypes.CDLL(LIB_PATH)
-    for name, args in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()):
+    for name, args in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()) + list(I2GNN_SIGNATURES.items()):
         try:
             fn = getattr(h, name)
         except AttributeError as exc:

@@ -18,9 +18,13 @@
 //
 // One wave per root, twice: the count pass sizes the output, the fill pass repeats the BFS (cheaper than keeping n^2 hop
 // tables between the passes) and writes with stable ballot-prefix compaction.  Integer work bound by LDS / L2 latency.
+//
+// The second half of the file is the I2GNN baseline's expansion (esc_subgraph2_count / _fill, include/escgnn_i2gnn.h): the same
+// subgraphs, once per neighbour of their root, labelled with the distances to both.  It reuses the helpers above unchanged.
 #include "common.h"
 #include "jacobi_pinv.h"
 #include "../../include/escgnn_subgraphs.h"
+#include "../../include/escgnn_i2gnn.h"
 
 namespace esc {
 
@@ -325,6 +329,263 @@ static int sub_check(const char* fn, const int64_t* node_ptr, const int64_t* edg
   return ESC_OK;
 }
 
+// ===== the I2GNN baseline: every rooted subgraph once per neighbour of its root (reference utils_edge_I2.py:132-256, 726-813;
+// DESIGN.md 6i).  S_r is the subgraph above; the neighbours of r are the targets of the sub-edges whose source is r, in
+// sub-edge order (repeats and a self loop kept); copy c labels every node with its distances to r and to the c-th
+// neighbour j.  The distances to j come from an unbounded BFS inside S_r (find_all_spd :475-561).  A root with no
+// neighbour has one copy whose second label pair and second rd column repeat the first.
+constexpr int SUB2_MAX_NODES = 1536;    // 9 B of LDS tables per node beside the two 96 x 96 fp64 matrices (see sub2_fill_lds)
+constexpr int SUB2_H_MAX = 47;          // the largest label is 2h + 5 and the model's z tables have 100 rows
+
+__global__ __launch_bounds__(64) void sub2_count_kernel(const int64_t* __restrict__ node_ptr, const int64_t* __restrict__ edge_ptr,
+                                                        const int64_t* __restrict__ src, const int64_t* __restrict__ dst, int G,
+                                                        int64_t total_nodes, int h, const int* __restrict__ status,
+                                                        int64_t* __restrict__ cnt_nodes, int64_t* __restrict__ cnt_edges,
+                                                        int64_t* __restrict__ cnt_s2) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int lane = threadIdx.x;
+  const int64_t r_glob = blockIdx.x;
+  if (r_glob >= total_nodes) return;
+  const SubRoot q = sub_locate(node_ptr, edge_ptr, G, r_glob);
+  if (status[q.g] != 0) {
+    if (lane == 0) { cnt_nodes[r_glob] = 0; cnt_edges[r_glob] = 0; cnt_s2[r_glob] = 0; }
+    return;
+  }
+  unsigned char* hop = smem;
+  sub_bfs(q, src, dst, h, hop);
+  int nn = 0, ne = 0, nk = 0;
+  for (int x0 = 0; x0 < q.n; x0 += 64) {
+    const int x = x0 + lane;
+    nn += __popcll(__ballot(x < q.n && hop[x] != SUB_INF));
+  }
+  for (int j0 = 0; j0 < q.Eg; j0 += 64) {
+    const int j = j0 + lane;
+    bool keep = false, nb = false;
+    if (j < q.Eg) {
+      const int s = (int)(src[q.e0 + j] - q.n0);
+      keep = hop[s] != SUB_INF && hop[dst[q.e0 + j] - q.n0] != SUB_INF;
+      nb = keep && s == q.r;
+    }
+    ne += __popcll(__ballot(keep));
+    nk += __popcll(__ballot(nb));
+  }
+  const int64_t mult = nk > 0 ? nk : 1;
+  if (lane == 0) { cnt_nodes[r_glob] = mult * nn; cnt_edges[r_glob] = mult * ne; cnt_s2[r_glob] = mult; }
+}
+
+struct Sub2FillArgs {
+  const int64_t* node_ptr; const int64_t* edge_ptr; const int64_t* src; const int64_t* dst;
+  const int64_t* sub_node_ptr; const int64_t* sub_edge_ptr; const int64_t* sub2_ptr;
+  int64_t* orig_node; int64_t* z; int64_t* node_to_subgraph2; int64_t* node_to_graph;
+  int64_t* sub_src; int64_t* sub_dst; int64_t* orig_edge;
+  int64_t* subgraph2_to_subgraph; int64_t* center_idx; int64_t* s2_node_ptr;
+  float* rd;
+  int* status;
+  int64_t total_nodes, total_sub_nodes, total_sub_edges, total_s2;
+  int G, h, n_cap, ld;
+};
+
+// LDS: hop[n_cap] two[n_cap] hopj[n_cap] bytes | loc[n_cap] shorts | cnt[n_cap] ints; (RD) Gm[ld*ld] Vm[ld*ld] inv_s2[ld] vrow[ld]
+// red[8] doubles behind them: the pseudo-inverse stays alive for every copy, so nothing is overlaid
+template <bool RD>
+__global__ __launch_bounds__(64) void sub2_fill_kernel(Sub2FillArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ int jsel;
+  const int lane = threadIdx.x;
+  const int64_t r_glob = blockIdx.x;
+  if (r_glob >= a.total_nodes) return;
+  if (r_glob == 0 && lane == 0) a.s2_node_ptr[0] = 0;       // every other entry is the end of a copy, written by its root
+  const SubRoot q = sub_locate(a.node_ptr, a.edge_ptr, a.G, r_glob);
+  const int64_t sn0 = a.sub_node_ptr[r_glob], se0 = a.sub_edge_ptr[r_glob], s20 = a.sub2_ptr[r_glob];
+  if (a.sub_node_ptr[r_glob + 1] == sn0) return;            // a graph the count pass refused (see sub_fill_kernel)
+  if (a.sub_node_ptr[r_glob + 1] > a.total_sub_nodes || a.sub_edge_ptr[r_glob + 1] > a.total_sub_edges ||
+      a.sub2_ptr[r_glob + 1] > a.total_s2) {
+    if (lane == 0) a.status[q.g] = ESC_ERANGE;              // the caller's totals are not those of the count pass: write nothing
+    return;
+  }
+  unsigned char* hop = smem;                                // [n_cap] distance to the root
+  unsigned char* two = hop + a.n_cap;                       // [n_cap] two or more frontier edges into the node (root's BFS)
+  unsigned char* hopj = two + a.n_cap;                      // [n_cap] distance to the neighbour, inside S_r
+  short* loc = reinterpret_cast<short*>(hopj + a.n_cap);    // [n_cap]
+  int* cnt = reinterpret_cast<int*>(loc + a.n_cap);         // [n_cap] frontier edges into the node, of the BFS at hand
+  sub_bfs(q, a.src, a.dst, a.h, hop);
+  int m = 0;
+  for (int d = 0; d <= a.h; ++d) {
+    const int before = m;
+    for (int x0 = 0; x0 < q.n; x0 += 64) {
+      const int x = x0 + lane;
+      const bool mine = x < q.n && hop[x] == d;
+      const unsigned long long msk = __ballot(mine);
+      if (mine) loc[x] = (short)(m + __popcll(msk & ((1ull << lane) - 1ull)));
+      m += __popcll(msk);
+    }
+    if (m == before) break;
+  }
+  for (int x = lane; x < q.n; x += 64) { cnt[x] = 0; if (hop[x] == SUB_INF) loc[x] = -1; }
+  __syncthreads();
+  int e = 0, K = 0;
+  for (int j0 = 0; j0 < q.Eg; j0 += 64) {
+    const int j = j0 + lane;
+    bool keep = false, nb = false;
+    if (j < q.Eg) {
+      const int s = (int)(a.src[q.e0 + j] - q.n0), t = (int)(a.dst[q.e0 + j] - q.n0);
+      keep = hop[s] != SUB_INF && hop[t] != SUB_INF;
+      nb = keep && s == q.r;
+      if (keep && (int)hop[t] + 1 == (int)hop[s]) atomicAdd(&cnt[s], 1);
+    }
+    e += __popcll(__ballot(keep));
+    K += __popcll(__ballot(nb));
+  }
+  __syncthreads();
+  for (int x = lane; x < q.n; x += 64) two[x] = cnt[x] >= 2 ? 1 : 0;
+  const int mult = K > 0 ? K : 1;
+  if ((int64_t)mult * m != a.sub_node_ptr[r_glob + 1] - sn0 || (int64_t)mult * e != a.sub_edge_ptr[r_glob + 1] - se0 ||
+      (int64_t)mult != a.sub2_ptr[r_glob + 1] - s20) {      // wave-uniform: pointers that the count pass did not make
+    if (lane == 0) a.status[q.g] = ESC_ERANGE;
+    return;
+  }
+  bool rd_ok = RD;
+  const int ld = a.ld;
+  const double* P = nullptr;                                // P[i][j] at P[j*ld + i]; the root is local node 0
+  if (RD) {
+    if (m > SUB_RD_MAX || m > ld) {                         // wave-uniform; the rd rows of this root stay unwritten
+      if (lane == 0) a.status[q.g] = ESC_ERANGE;
+      rd_ok = false;
+    } else {
+      const size_t off = ((size_t)a.n_cap * 9 + 15) & ~(size_t)15;
+      double* Gm = reinterpret_cast<double*>(smem + off);
+      double* Vm = Gm + (size_t)ld * ld;
+      double* inv_s2 = Vm + (size_t)ld * ld;
+      double* vrow = inv_s2 + ld;
+      double* red = vrow + ld;
+      for (int idx = lane; idx < m * m; idx += 64) {
+        const int cc = idx / m, rr = idx % m;
+        Gm[(size_t)cc * ld + rr] = 0.0;
+        Vm[(size_t)cc * ld + rr] = (cc == rr) ? 1.0 : 0.0;
+      }
+      __syncthreads();
+      for (int j = lane; j < q.Eg; j += 64) {               // L = D_in - A over the non-loop sub-edges, as sub_fill_kernel
+        const int s = (int)(a.src[q.e0 + j] - q.n0), t = (int)(a.dst[q.e0 + j] - q.n0);
+        if (s == t || hop[s] == SUB_INF || hop[t] == SUB_INF) continue;
+        const int ls = loc[s], lt = loc[t];
+        atomicAdd(&Gm[(size_t)lt * ld + ls], -1.0);
+        atomicAdd(&Gm[(size_t)lt * ld + lt], 1.0);
+      }
+      __syncthreads();
+      const double null2 = jacobi_orthogonalise<64>(Gm, Vm, m, ld, red);
+      __syncthreads();
+      pinv_from_jacobi<64>(Gm, Vm, m, ld, null2, inv_s2, vrow);
+      P = Vm;
+    }
+  }
+  __syncthreads();
+  for (int c = 0; c < mult; ++c) {
+    const int64_t n_at = sn0 + (int64_t)c * m, e_at = se0 + (int64_t)c * e;
+    int jx = q.r;
+    if (K > 0) {
+      // the c-th neighbour: target of the c-th sub-edge that leaves the root
+      int base = 0;
+      for (int j0 = 0; j0 < q.Eg && base <= c; j0 += 64) {
+        const int j = j0 + lane;
+        bool nb = false;
+        int t = 0;
+        if (j < q.Eg) {
+          t = (int)(a.dst[q.e0 + j] - q.n0);
+          nb = (int)(a.src[q.e0 + j] - q.n0) == q.r && hop[t] != SUB_INF;
+        }
+        const unsigned long long msk = __ballot(nb);
+        if (nb && base + __popcll(msk & ((1ull << lane) - 1ull)) == c) jsel = t;
+        base += __popcll(msk);
+      }
+      for (int x = lane; x < q.n; x += 64) { hopj[x] = SUB_INF; cnt[x] = 0; }
+      __syncthreads();
+      jx = jsel;
+      if (lane == 0) hopj[jx] = 0;
+      __syncthreads();
+      // the reference's unbounded BFS from the neighbour over the sub-edges only, target -> source.  It ends within h + 1
+      // levels on any graph: the sub-edge r -> j puts r at distance 1 of j, and every node of S_r reaches r inside S_r in
+      // hop <= h steps, so d_j <= h + 1, every node of S_r is reached and the largest label is (h + 2) + (h + 3) <= 99
+      for (int d = 1; d <= a.h + 1; ++d) {
+        int grew = 0;
+        for (int j = lane; j < q.Eg; j += 64) {
+          const int s = (int)(a.src[q.e0 + j] - q.n0), t = (int)(a.dst[q.e0 + j] - q.n0);
+          if (hop[s] != SUB_INF && hopj[t] == d - 1 && hopj[s] == SUB_INF) { hopj[s] = (unsigned char)d; grew = 1; }
+        }
+        __syncthreads();
+        if (!__any(grew)) break;
+      }
+      for (int j = lane; j < q.Eg; j += 64) {
+        const int s = (int)(a.src[q.e0 + j] - q.n0), t = (int)(a.dst[q.e0 + j] - q.n0);
+        if (hop[s] != SUB_INF && hopj[t] != SUB_INF && (int)hopj[t] + 1 == (int)hopj[s]) atomicAdd(&cnt[s], 1);
+      }
+      __syncthreads();
+    }
+    const int lj = loc[jx];
+    const int64_t shift = a.h + 3;
+    for (int x = lane; x < q.n; x += 64) {
+      if (hop[x] == SUB_INF) continue;
+      const int k = loc[x];
+      const int64_t p = n_at + k;
+      const int64_t z0 = (int64_t)hop[x] + 1, z1 = two[x] ? z0 : 0;
+      int64_t z2 = z0, z3 = z1;                             // no neighbour: the root's pair tiled twice
+      if (K > 0) {
+        const int64_t dj = hopj[x] == SUB_INF ? 0 : (int64_t)hopj[x] + 1;
+        z2 = dj + shift; z3 = (cnt[x] >= 2 ? dj : 0) + shift;
+      }
+      a.orig_node[p] = q.n0 + x;
+      a.z[4 * p] = z0; a.z[4 * p + 1] = z1; a.z[4 * p + 2] = z2; a.z[4 * p + 3] = z3;
+      a.node_to_subgraph2[p] = s20 + c; a.node_to_graph[p] = q.g;
+      if (RD && rd_ok) {
+        const double pkk = P[(size_t)k * ld + k];
+        const double r0 = ((P[0] + pkk) - P[(size_t)k * ld]) - P[k];                          // l_00 + l_kk - L[0,k] - L[k,0]
+        const double rj = ((P[(size_t)lj * ld + lj] + pkk) - P[(size_t)k * ld + lj]) - P[(size_t)lj * ld + k];
+        a.rd[2 * p] = (float)r0; a.rd[2 * p + 1] = (float)rj;
+      }
+    }
+    int base = 0;
+    for (int j0 = 0; j0 < q.Eg; j0 += 64) {
+      const int j = j0 + lane;
+      bool keep = false;
+      int s = 0, t = 0;
+      if (j < q.Eg) {
+        s = (int)(a.src[q.e0 + j] - q.n0); t = (int)(a.dst[q.e0 + j] - q.n0);
+        keep = hop[s] != SUB_INF && hop[t] != SUB_INF;
+      }
+      const unsigned long long msk = __ballot(keep);
+      if (keep) {
+        const int64_t p = e_at + base + __popcll(msk & ((1ull << lane) - 1ull));
+        a.sub_src[p] = n_at + loc[s]; a.sub_dst[p] = n_at + loc[t]; a.orig_edge[p] = q.e0 + j;
+      }
+      base += __popcll(msk);
+    }
+    if (lane == 0) {
+      a.subgraph2_to_subgraph[s20 + c] = r_glob;
+      a.center_idx[2 * (s20 + c)] = n_at; a.center_idx[2 * (s20 + c) + 1] = n_at + lj;
+      a.s2_node_ptr[s20 + c + 1] = n_at + m;
+    }
+    __syncthreads();                                        // hopj / cnt / jsel are rewritten by the next copy
+  }
+}
+
+static size_t sub2_fill_lds(int n_cap, int ld, bool rd) {
+  const size_t tables = ((size_t)n_cap * 9 + 15) & ~(size_t)15;
+  return rd ? tables + ((size_t)2 * ld * ld + 2 * (size_t)ld + 8) * 8 : tables;
+}
+
+static int sub2_check(const char* fn, const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* src, const int64_t* dst,
+                      int64_t G, int64_t total_nodes, int64_t total_edges, int64_t max_nodes, int h) {
+  if (h < 1 || h > SUB2_H_MAX) {
+    set_error("%s: h=%d outside 1..%d (the model's z tables have 100 rows and the second root's labels reach 2h + 5)", fn, h,
+              SUB2_H_MAX);
+    return ESC_ERANGE;
+  }
+  if (max_nodes < 1 || max_nodes > SUB2_MAX_NODES) {
+    set_error("%s: max_nodes=%ld outside 1..%d", fn, (long)max_nodes, SUB2_MAX_NODES);
+    return ESC_ERANGE;
+  }
+  return sub_check(fn, node_ptr, edge_ptr, src, dst, G, total_nodes, total_edges, max_nodes, h);
+}
+
 }  // namespace esc
 
 using namespace esc;
@@ -387,6 +648,72 @@ int esc_subgraph_fill(const int64_t* node_ptr, const int64_t* edge_ptr, const in
     esc::launch(ESC_K_FEATURES, sub_fill_kernel<false>, dim3((unsigned)total_nodes), dim3(64), sub_fill_lds(a.n_cap, a.ld, false), s, a);
   }
   ESC_CHECK_LAUNCH("esc_subgraph_fill.fill");
+  return ESC_OK;
+}
+
+int esc_subgraph2_count(const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* src, const int64_t* dst, int64_t G,
+                        int64_t total_nodes, int64_t total_edges, int64_t max_nodes, int h, int64_t* sub_node_ptr,
+                        int64_t* sub_edge_ptr, int64_t* sub2_ptr, int32_t* status, void* stream) {
+  const int rc = sub2_check("esc_subgraph2_count", node_ptr, edge_ptr, src, dst, G, total_nodes, total_edges, max_nodes, h);
+  if (rc) return rc;
+  ESC_REQUIRE(sub_node_ptr && sub_edge_ptr && sub2_ptr && status, "esc_subgraph2_count: null output");
+  hipStream_t s = (hipStream_t)stream;
+  esc::launch(ESC_K_FEATURES, sub_validate_kernel, dim3((unsigned)G), dim3(64), 0, s, node_ptr, edge_ptr, src, dst, (int)G,
+              total_nodes, total_edges, max_nodes, status);
+  ESC_CHECK_LAUNCH("esc_subgraph2_count.validate");
+  if (total_nodes > 0) {
+    const int n_cap = (int)((max_nodes + 3) & ~3LL);
+    esc::launch(ESC_K_FEATURES, sub2_count_kernel, dim3((unsigned)total_nodes), dim3(64), (size_t)n_cap, s, node_ptr, edge_ptr,
+                src, dst, (int)G, total_nodes, h, (const int*)status, sub_node_ptr, sub_edge_ptr, sub2_ptr);
+    ESC_CHECK_LAUNCH("esc_subgraph2_count.count");
+  }
+  esc::launch(ESC_K_FEATURES, sub_scan_kernel, dim3(2), dim3(1024), 0, s, sub_node_ptr, sub_edge_ptr, total_nodes);
+  esc::launch(ESC_K_FEATURES, sub_scan_kernel, dim3(1), dim3(1024), 0, s, sub2_ptr, sub2_ptr, total_nodes);
+  ESC_CHECK_LAUNCH("esc_subgraph2_count.scan");
+  return ESC_OK;
+}
+
+int esc_subgraph2_fill(const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* src, const int64_t* dst, int64_t G,
+                       int64_t total_nodes, int64_t total_edges, int64_t max_nodes, int h, const int64_t* sub_node_ptr,
+                       const int64_t* sub_edge_ptr, const int64_t* sub2_ptr, int64_t total_sub_nodes, int64_t total_sub_edges,
+                       int64_t total_subgraphs2, int use_rd, int64_t* orig_node, int64_t* z, int64_t* node_to_subgraph2,
+                       int64_t* node_to_graph, int64_t* sub_src, int64_t* sub_dst, int64_t* orig_edge,
+                       int64_t* subgraph2_to_subgraph, int64_t* center_idx, int64_t* s2_node_ptr, float* rd, int32_t* status,
+                       void* stream) {
+  const int rc = sub2_check("esc_subgraph2_fill", node_ptr, edge_ptr, src, dst, G, total_nodes, total_edges, max_nodes, h);
+  if (rc) return rc;
+  ESC_REQUIRE(sub_node_ptr && sub_edge_ptr && sub2_ptr && status && s2_node_ptr, "esc_subgraph2_fill: null pointer");
+  if (total_sub_nodes < 0 || total_sub_edges < 0 || total_subgraphs2 < 0 || total_sub_nodes >= (1LL << 31) - 1 ||
+      total_sub_edges >= (1LL << 31) - 1 || total_subgraphs2 > total_sub_nodes) {
+    set_error("esc_subgraph2_fill: %ld sub-nodes / %ld sub-edges / %ld subgraph2s: totals must stay below 2^31",
+              (long)total_sub_nodes, (long)total_sub_edges, (long)total_subgraphs2);
+    return ESC_ERANGE;
+  }
+  if (total_nodes == 0 || total_sub_nodes == 0) return ESC_OK;
+  ESC_REQUIRE(orig_node && z && node_to_subgraph2 && node_to_graph && subgraph2_to_subgraph && center_idx,
+              "esc_subgraph2_fill: null node output");
+  ESC_REQUIRE((sub_src && sub_dst && orig_edge) || total_sub_edges == 0, "esc_subgraph2_fill: null edge output");
+  ESC_REQUIRE(!use_rd || rd, "esc_subgraph2_fill: use_rd without an rd output");
+  hipStream_t s = (hipStream_t)stream;
+  Sub2FillArgs a{};
+  a.node_ptr = node_ptr; a.edge_ptr = edge_ptr; a.src = src; a.dst = dst;
+  a.sub_node_ptr = sub_node_ptr; a.sub_edge_ptr = sub_edge_ptr; a.sub2_ptr = sub2_ptr;
+  a.orig_node = orig_node; a.z = z; a.node_to_subgraph2 = node_to_subgraph2; a.node_to_graph = node_to_graph;
+  a.sub_src = sub_src; a.sub_dst = sub_dst; a.orig_edge = orig_edge; a.subgraph2_to_subgraph = subgraph2_to_subgraph;
+  a.center_idx = center_idx; a.s2_node_ptr = s2_node_ptr; a.rd = rd; a.status = status;
+  a.total_nodes = total_nodes; a.total_sub_nodes = total_sub_nodes; a.total_sub_edges = total_sub_edges; a.total_s2 = total_subgraphs2;
+  a.G = (int)G; a.h = h; a.n_cap = (int)((max_nodes + 3) & ~3LL);
+  const int m_even = (int)((max_nodes + 1) & ~1LL);
+  a.ld = m_even < SUB_RD_MAX ? m_even : SUB_RD_MAX;
+  const size_t lds = sub2_fill_lds(a.n_cap, a.ld, use_rd != 0);
+  ESC_REQUIRE(lds + 16 <= 160 * 1024, "esc_subgraph2_fill: working set %zu B exceeds LDS", lds);
+  if (use_rd) {
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)sub2_fill_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    esc::launch(ESC_K_FEATURES, sub2_fill_kernel<true>, dim3((unsigned)total_nodes), dim3(64), lds, s, a);
+  } else {
+    esc::launch(ESC_K_FEATURES, sub2_fill_kernel<false>, dim3((unsigned)total_nodes), dim3(64), lds, s, a);
+  }
+  ESC_CHECK_LAUNCH("esc_subgraph2_fill.fill");
   return ESC_OK;
 }
 

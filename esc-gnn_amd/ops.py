@@ -989,3 +989,150 @@ class _SegmentFirst(Function):
 def segment_first(x, ptr, node_to_segment):
     """out[s] = x[ptr[s]]; ptr: int64 [S+1] segment pointers, node_to_segment: int64 [N] (non-decreasing)."""
     return _SegmentFirst.apply(x, ptr, node_to_segment)
+
+
+class _PoolMeanCenterSide(Function):
+    """cat([global_mean_pool(x, node_to_subgraph2), x[center_idx[:, 0]], x[center_idx[:, 1]]], -1) of the reference's I2GNN
+    (zinc_cycle_models.py:218-222) in one pass over x (csrc/i2pool.hip); the gradient writes every row once — a centre that is
+    also the side row (a root without neighbours, a self loop) receives both terms."""
+
+    @staticmethod
+    def forward(ctx, x, ptr, center_idx, node_to_segment):
+        _dev(x)
+        _on(x.device, ptr, center_idx, node_to_segment)
+        if ptr.dtype != torch.int64 or center_idx.dtype != torch.int64 or node_to_segment.dtype != torch.int64:
+            raise TypeError("pool_mean_center_side: ptr, center_idx and node_to_segment must be int64")
+        x, ldx = _rows(x)
+        ptr, center_idx, node_to_segment = ptr.contiguous(), center_idx.contiguous(), node_to_segment.contiguous()
+        S, C = ptr.numel() - 1, x.size(1)
+        if center_idx.shape != (S, 2):
+            raise ValueError("pool_mean_center_side: center_idx %s for %d segments" % (tuple(center_idx.shape), S))
+        if node_to_segment.numel() != x.size(0):
+            raise ValueError("pool_mean_center_side: %d rows but %d segment ids" % (x.size(0), node_to_segment.numel()))
+        out = torch.empty((S, 3 * C), dtype=torch.float32, device=x.device)
+        nv.call("esc_pool_mean_center_side_fwd", nv.ptr(x), ldx, nv.ptr(ptr), center_idx.data_ptr(), center_idx.data_ptr() + 8, 2,
+                S, C, nv.ptr(out), 3 * C, nv.stream())
+        ctx.ptr, ctx.ci, ctx.seg, ctx.n = ptr, center_idx, node_to_segment, x.size(0)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        g, ldg = _rows(g)
+        C = g.size(1) // 3
+        dx = torch.empty((ctx.n, C), dtype=torch.float32, device=g.device)
+        nv.call("esc_pool_mean_center_side_bwd", nv.ptr(g), ldg, nv.ptr(ctx.ptr), ctx.ci.data_ptr(), ctx.ci.data_ptr() + 8, 2,
+                nv.ptr(ctx.seg), ctx.n, C, nv.ptr(dx), C, nv.stream())
+        return dx, None, None, None
+
+
+def pool_mean_center_side(x, ptr, center_idx, node_to_segment):
+    """out[s] = [mean of x[ptr[s]:ptr[s+1]] | x[center_idx[s, 0]] | x[center_idx[s, 1]]]; ptr: int64 [S+1], center_idx: int64
+    [S, 2] (rows inside segment s), node_to_segment: int64 [N] (non-decreasing)."""
+    return _PoolMeanCenterSide.apply(x, ptr, center_idx, node_to_segment)
+
+
+class _SigmoidMul(Function):
+    """sigmoid(a) * x: the gate `subgraph_gate[layer](z_emb) * x` of the reference's I2GNN (zinc_cycle_models.py:205-206,
+    219-220; the Sigmoid of the Sequential moves into this kernel), finite for every finite a."""
+
+    @staticmethod
+    def forward(ctx, a, x):
+        _dev(a, x)
+        _on(a.device, x)
+        a, lda = _rows(a)
+        x, ldx = _rows(x)
+        if a.shape != x.shape:
+            raise ValueError("sigmoid_mul: shapes %s and %s differ" % (tuple(a.shape), tuple(x.shape)))
+        M, C = a.shape
+        y = torch.empty((M, C), dtype=torch.float32, device=a.device)
+        nv.call("esc_sigmoid_mul_fwd", nv.ptr(a), lda, nv.ptr(x), ldx, M, C, nv.ptr(y), C, nv.stream())
+        ctx.save_for_backward(a, x)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        a, x = ctx.saved_tensors
+        g, ldg = _rows(g)
+        M, C = a.shape
+        da = torch.empty((M, C), dtype=torch.float32, device=g.device) if ctx.needs_input_grad[0] else None
+        dx = torch.empty((M, C), dtype=torch.float32, device=g.device) if ctx.needs_input_grad[1] else None
+        if da is not None or dx is not None:
+            nv.call("esc_sigmoid_mul_bwd", nv.ptr(a), a.stride(0) if M > 1 else C, nv.ptr(x), x.stride(0) if M > 1 else C,
+                    nv.ptr(g), ldg, M, C, nv.ptr(da), nv.ptr(dx), nv.stream())
+        return da, dx
+
+
+def sigmoid_mul(a, x):
+    return _SigmoidMul.apply(a, x)
+
+
+def group_plan(index, n_keys):
+    """The stable grouping of the positions of an UNSORTED index vector by key (esc_plan_csr), with what the two transposed
+    bag launches below need: built once per index tensor and cached on it, shared by every layer and both directions (I2GNN's
+    node_to_original_node: the context mean and the gather back).  No read-back: the keys come from the expansion kernel, and a
+    key outside [0, n_keys) only sets `bad`."""
+    from .plan import _csr
+    cache = getattr(index, "_esc_group", None)
+    key = (index._version, int(n_keys))
+    if cache is not None and cache[0] == key:
+        return cache[1]
+    dev, n = index.device, index.numel()
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    col_ptr, c_row = _csr(index, int(n_keys), bad=bad)
+    counts = (col_ptr[1:] - col_ptr[:-1]).clamp(min=1).to(torch.float32)
+    plan = dict(n=n, n_keys=int(n_keys), idx32=index.to(torch.int32), row_ptr=torch.arange(n + 1, dtype=torch.int32, device=dev),
+                ones=torch.ones(n, dtype=torch.int32, device=dev), col_ptr=col_ptr, c_row=c_row, bad=bad,
+                inv_count=(1.0 / counts).view(-1, 1))
+    index._esc_group = (key, plan)
+    return plan
+
+
+def _bag_rows(table, row_ptr, idx32, ones, n_out):
+    table = table.contiguous()
+    H = table.size(1)
+    out = torch.empty((n_out, H), dtype=torch.float32, device=table.device)
+    nv.call("esc_bag_fwd", nv.ptr(table), H, nv.ptr(row_ptr), nv.ptr(idx32), nv.ptr(ones), n_out, nv.ptr(out), H, nv.stream())
+    return out
+
+
+class _GatherRows(Function):
+    """table[index] for an unsorted index with repeats (`...[data.node_to_original_node]`, zinc_cycle_models.py:276): the bag
+    kernel with one unit entry per row; its gradient is the group sum below — each the transpose of the other, both
+    deterministic (entry order) and without atomics."""
+
+    @staticmethod
+    def forward(ctx, table, plan):
+        _dev(table)
+        ctx.plan = plan
+        return _bag_rows(table, plan["row_ptr"], plan["idx32"], plan["ones"], plan["n"])
+
+    @staticmethod
+    def backward(ctx, g):
+        p = ctx.plan
+        return _bag_rows(g, p["col_ptr"], p["c_row"], p["ones"], p["n_keys"]), None
+
+
+class _GroupSum(Function):
+    """out[k] = sum of the rows whose key is k, in position order (scatter-add over an unsorted index); gradient = gather."""
+
+    @staticmethod
+    def forward(ctx, x, plan):
+        _dev(x)
+        ctx.plan = plan
+        return _bag_rows(x, plan["col_ptr"], plan["c_row"], plan["ones"], plan["n_keys"])
+
+    @staticmethod
+    def backward(ctx, g):
+        p = ctx.plan
+        return _bag_rows(g, p["row_ptr"], p["idx32"], p["ones"], p["n"]), None
+
+
+def gather_rows(table, plan):
+    return _GatherRows.apply(table, plan)
+
+
+def group_mean(x, plan):
+    """global_mean_pool(x, index) for the unsorted index the plan was built from"""
+    if x.size(0) != plan["n"]:
+        raise ValueError("group_mean: %d rows for a plan of %d" % (x.size(0), plan["n"]))
+    return _GroupSum.apply(x, plan) * plan["inv_count"]

@@ -1,5 +1,5 @@
 """ZINC cycle counting on the ESC hot path — the MI355X-native twin of the reference's run_zinc_cycle.py for
-`--model NestedGIN_eff`: flags (:20-85), feature settings (`create_subgraphs_eff(g, h, use_rd, self_loop)` :140-146),
+`--model NestedGIN_eff` and the subgraph baseline `--model I2GNN`: flags (:20-85), feature settings (`create_subgraphs_eff(g, h, use_rd, self_loop)` :140-146),
 targets y = data.y[:, target] without normalisation (:205-215: the normalising lines are commented out there, the
 Mean / Std are printed and Std scales the reported MAE), L1 over the NODES, and "test when validation improves or every 10
 epochs" logging (:282-325).  test() returns sum |y_hat - y| over the nodes / the number of GRAPHS * std (:292-306).
@@ -13,20 +13,26 @@ sharded by graph and every loss / gradient denominator is the global NODE count.
 Deviation: the reference's `--eval` branch unpacks six values from a test() that returns one, so it cannot run; here it
 prints `Test MAE` as run_zinc does.
 
+`--model I2GNN` (reference :159-161, zinc_cycle_models.py:116-307, the reference's default model) trains the subgraph GNN
+that counts cycles on the same molecules and labels: the split holds the plain graphs (subgraphs2.I2GraphStore), and every
+step expands the batch into one copy of every rooted subgraph per neighbour of its root on the device
+(subgraphs2.expand_subgraphs2, csrc/subgraphs.hip) before the per-op forward / L1 / backward / Adam.
+
     python -m esc_gnn_amd.run_zinc_cycle --model NestedGIN_eff --h 3 --target 0
+    python -m esc_gnn_amd.run_zinc_cycle --model I2GNN --h 3 --target 0
 """
 import torch
 
 from . import ops
 from .harness import (Context, default_appendix, fit_regression, open_result_dir, parser_from, prefetched, seed_everything,
                       sharded_batches)
-from .zinc_cycle_models import NestedGIN_eff
+from .zinc_cycle_models import I2GNN, NestedGIN_eff
 
 _FLAGS = [  # same names, types and defaults as the reference CLI
     ("--target", dict(default=0, type=int, help="cycle length - 3: column of the [n, 4] node labels")),
     ("--filter", dict(action="store_true", default=False)),
     ("--convert", dict(type=str, default="post")),
-    ("--model", dict(type=str, default="NestedGIN_eff", help="NestedGIN_eff (GNN / NGNN / I2GNN baselines: out of scope)")),
+    ("--model", dict(type=str, default="NestedGIN_eff", help="NestedGIN_eff | I2GNN (GNN / NGNN baselines: out of scope)")),
     ("--layers", dict(type=int, default=6)),
     ("--h", dict(type=int, default=3)),
     ("--max_nodes_per_hop", dict(type=int, default=None)),
@@ -77,7 +83,10 @@ def _load_splits(args):
     from .datasets import build_feature_dataset, synthetic_zinc_cycle_graphs
     G = args.synthetic_graphs
     raw = synthetic_zinc_cycle_graphs(0, G)
-    done = build_feature_dataset(raw, args.h, use_rd=args.use_rd, self_loop=args.self_loop)     # reference :140-146
+    if args.model == "I2GNN":                             # plain molecules: the subgraph2s are expanded per batch
+        done = raw
+    else:
+        done = build_feature_dataset(raw, args.h, use_rd=args.use_rd, self_loop=args.self_loop)     # reference :140-146
     n_tr, n_va = (G * 10) // 12, G // 12
     return done[:n_tr], done[n_tr:n_tr + n_va], done[n_tr + n_va:]
 
@@ -90,9 +99,13 @@ def main(argv=None):
     from .store import DeviceGraphStore
 
     args = build_parser().parse_args(argv)
-    if args.model != "NestedGIN_eff":
-        print("Error: no such model!")                    # reference :166-168 (GNN / NGNN / I2GNN: out of scope)
+    if args.model not in ("NestedGIN_eff", "I2GNN"):
+        print("Error: no such model!")                    # reference :166-168 (GNN / NGNN: out of scope)
         raise SystemExit(1)
+    i2gnn = args.model == "I2GNN"
+    if i2gnn:                                             # what the expansion has no path for: refused before anything is built
+        from .subgraphs2 import _check
+        _check(args.h, args.node_label, args.max_nodes_per_hop, None, args.self_loop)
     if args.max_nodes_per_hop is not None:
         raise NotImplementedError("max_nodes_per_hop: random neighbour sampling is outside the ESC hot path")
     if not 0 <= args.target < 4:
@@ -110,11 +123,22 @@ def main(argv=None):
     y_train_val = torch.cat([d.y[:, target] for d in tr + va], dim=0)       # reference :209-215 (not applied)
     mean, std = y_train_val.mean(dim=0), y_train_val.std(dim=0)
     ctx.say("Mean = %.3f, Std = %.3f" % (float(mean), float(std)))
-    stores = [DeviceGraphStore(part, ctx.device) for part in (tr, va, te)]
+    if i2gnn:                                             # per-graph sizes and both limits: one count pass per split
+        from .subgraphs2 import I2GraphStore
+        stores = [I2GraphStore(part, args.h, args.use_rd, ctx.device) for part in (tr, va, te)]
+    else:
+        stores = [DeviceGraphStore(part, ctx.device) for part in (tr, va, te)]
     n_train = len(tr)
 
-    model = NestedGIN_eff(None, num_layers=args.layers, use_rd=args.use_rd, RNI=args.RNI, drop_ratio=args.drop_ratio,
-                          edge_attr_dim=5, use_pos=args.use_pos, use_max_dist=args.use_max_dist)
+    if i2gnn:
+        model = I2GNN(None, num_layers=args.layers, subgraph_pooling=args.subgraph_pooling,
+                      subgraph2_pooling=args.subgraph2_pooling, use_pos=args.use_pos, edge_attr_dim=5,
+                      use_max_dist=args.use_max_dist, use_rd=args.use_rd, RNI=args.RNI, drop_ratio=args.drop_ratio,
+                      use_pooling_nn=args.use_pooling_nn, use_virtual_node=args.virtual_node,
+                      double_pooling=args.double_pooling, gate=args.gate)               # reference :241-255
+    else:
+        model = NestedGIN_eff(None, num_layers=args.layers, use_rd=args.use_rd, RNI=args.RNI, drop_ratio=args.drop_ratio,
+                              edge_attr_dim=5, use_pos=args.use_pos, use_max_dist=args.use_max_dist)
     if args.load_model is not None:
         model.load_state_dict(torch.load(args.load_model, map_location="cpu"))
     ctx.say("Using " + model.__class__.__name__ + " model")
@@ -131,6 +155,11 @@ def main(argv=None):
     from .engine import ZincStepEngine, zinc_engine_ready, zinc_engine_supports
     engine = ZincStepEngine(model) if zinc_engine_supports(model) else None     # forward + L1 + backward in ONE call
 
+    def expanded(store, batches):
+        """I2GNN: every plain batch becomes the disconnected graph of its subgraph2s, on the device"""
+        for data, n_global in batches:
+            yield store.expand(data), n_global
+
     def train(epoch):
         # loss_all: sum over batches of (node-mean L1) * (graphs in the global batch), reference :272-284
         model.train()
@@ -138,6 +167,8 @@ def main(argv=None):
         batches = sharded_batches(stores[0], args.batch_size, ctx, True, gen)
         if args.prefetch:         # the next batch is collated on a side stream while this one trains
             batches = prefetched(batches, ctx.device)
+        if i2gnn:
+            batches = expanded(stores[0], batches)
         for data, n_graphs in batches:
             y = data.y[:, target].contiguous()
             n_loc = y.numel()
@@ -172,7 +203,8 @@ def main(argv=None):
         model.eval()
         err = torch.zeros(1, device=ctx.device)
         with torch.no_grad():
-            for data, _ in sharded_batches(store, args.batch_size, ctx, False):
+            batches = sharded_batches(store, args.batch_size, ctx, False)
+            for data, _ in (expanded(store, batches) if i2gnn else batches):
                 y_hat = model(data)[:, 0]
                 err += torch.sum(torch.abs(y_hat - data.y[:, target]))
         ctx.all_reduce(err)
