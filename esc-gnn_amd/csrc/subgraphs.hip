@@ -23,23 +23,14 @@
 // subgraphs, once per neighbour of their root, labelled with the distances to both.  It reuses the helpers above unchanged.
 #include "common.h"
 #include "jacobi_pinv.h"
+#include "subgraph_bfs.h"
 #include "../../include/escgnn_subgraphs.h"
 #include "../../include/escgnn_i2gnn.h"
 
 namespace esc {
 
-constexpr unsigned char SUB_INF = 255;
 constexpr int SUB_RD_MAX = 96;          // largest subgraph whose two m x m fp64 matrices fit LDS (147 KB); LDS_SUBGRAPH of features.hip
-
-// last g with ptr[g] <= i
-__device__ __forceinline__ int sub_find_segment(const int64_t* __restrict__ ptr, int G, int64_t i) {
-  int lo = 0, hi = G;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (ptr[mid] <= i) lo = mid; else hi = mid;
-  }
-  return lo;
-}
+// (SUB_INF, sub_find_segment, SubRoot, sub_locate and sub_bfs: subgraph_bfs.h, shared with multihop.hip)
 
 // ---- per-graph validation (one wave per graph): ids inside the graph, graph inside the LDS tables -----------------
 __global__ __launch_bounds__(64) void sub_validate_kernel(const int64_t* __restrict__ node_ptr,
@@ -65,45 +56,6 @@ __global__ __launch_bounds__(64) void sub_validate_kernel(const int64_t* __restr
   }
   bad = __any(bad) ? 1 : 0;
   if (lane == 0) status[g] = bad ? ESC_ERANGE : 0;
-}
-
-// what one root's wave knows about its graph
-struct SubRoot {
-  int g, n, r;
-  int64_t n0, e0;
-  int Eg;
-};
-
-__device__ __forceinline__ SubRoot sub_locate(const int64_t* __restrict__ node_ptr, const int64_t* __restrict__ edge_ptr, int G,
-                                              int64_t r_glob) {
-  SubRoot q;
-  q.g = sub_find_segment(node_ptr, G, r_glob);
-  q.n0 = node_ptr[q.g];
-  q.n = (int)(node_ptr[q.g + 1] - q.n0);
-  q.r = (int)(r_glob - q.n0);
-  q.e0 = edge_ptr[q.g];
-  q.Eg = (int)(edge_ptr[q.g + 1] - q.e0);
-  return q;
-}
-
-// level-synchronous BFS from q.r over the graph's edge list (global ids, L2 resident); hop[x] = d(r, x) or SUB_INF beyond h.
-// Every lane that reaches a node in level d writes the same d: the race is benign.
-__device__ __forceinline__ void sub_bfs(const SubRoot& q, const int64_t* __restrict__ src, const int64_t* __restrict__ dst, int h,
-                                        unsigned char* hop) {
-  const int lane = threadIdx.x;
-  for (int x = lane; x < q.n; x += 64) hop[x] = SUB_INF;
-  __syncthreads();
-  if (lane == 0) hop[q.r] = 0;
-  __syncthreads();
-  for (int d = 1; d <= h; ++d) {
-    int grew = 0;
-    for (int j = lane; j < q.Eg; j += 64) {
-      const int s = (int)(src[q.e0 + j] - q.n0), t = (int)(dst[q.e0 + j] - q.n0);
-      if (hop[t] == d - 1 && hop[s] == SUB_INF) { hop[s] = (unsigned char)d; grew = 1; }
-    }
-    __syncthreads();
-    if (!__any(grew)) break;
-  }
 }
 
 // ---- count pass: |S_r| and the number of sub-edges of every root, left in the pointer arrays for the scan ----------
@@ -327,6 +279,16 @@ static int sub_check(const char* fn, const int64_t* node_ptr, const int64_t* edg
     return ESC_ERANGE;
   }
   return ESC_OK;
+}
+
+// the two kernels above that multihop.hip launches as well (subgraph_bfs.h)
+void sub_launch_validate(const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* src, const int64_t* dst, int64_t G,
+                         int64_t total_nodes, int64_t total_edges, int64_t max_nodes, int* status, hipStream_t s) {
+  esc::launch(ESC_K_FEATURES, sub_validate_kernel, dim3((unsigned)G), dim3(64), 0, s, node_ptr, edge_ptr, src, dst, (int)G, total_nodes,
+              total_edges, max_nodes, status);
+}
+void sub_launch_scan(int64_t* a0, int64_t* a1, int64_t n, hipStream_t s) {
+  esc::launch(ESC_K_FEATURES, sub_scan_kernel, dim3(2), dim3(1024), 0, s, a0, a1, n);
 }
 
 // ===== the I2GNN baseline: every rooted subgraph once per neighbour of its root (reference utils_edge_I2.py:132-256, 726-813;

@@ -768,6 +768,72 @@ def neighbour_sum(x, e, plan):
     return _NeighbourSum.apply(x, e, plan)
 
 
+class _GinePlusAggregate(Function):
+    """(1+eps[0]) x_0 + sum_{d=1..k} (1+eps[d]) sum_{j: d(j->i)=d} relu(x_{d-1}[j] + [d=1] e) — everything GINEPLUS /
+    NAIVEGINEPLUS compute before self.nn (modules/gine_operations.py:306-362) in one launch per direction over the two
+    groupings of a MultihopPlan (csrc/gineplus.hip), k <= 4."""
+
+    @staticmethod
+    def forward(ctx, plan, e, eps, *xs):
+        k = len(xs)
+        _dev(e, eps, *xs)
+        dev = xs[0].device
+        _on(dev, e, eps, plan.in_ptr, plan.in_meta, plan.out_ptr, plan.meta, *xs)
+        rows = [_rows(x) for x in xs]
+        N, C = rows[0][0].shape
+        for x, _ in rows:
+            if tuple(x.shape) != (N, C):
+                raise ValueError("gineplus_aggregate: rows of %s and %s" % (tuple(x.shape), (N, C)))
+        if N != plan.num_nodes:
+            raise ValueError("gineplus_aggregate: %d rows for a plan of %d nodes" % (N, plan.num_nodes))
+        eps = eps.contiguous()
+        if tuple(eps.shape) != (k + 1, C):
+            raise ValueError("gineplus_aggregate: eps %s, expected %s" % (tuple(eps.shape), (k + 1, C)))
+        M1 = plan.num_d1
+        e, lde = _rows(e)
+        if tuple(e.shape) != (M1, C):
+            raise ValueError("gineplus_aggregate: edge term %s does not match %d distance-1 pairs x %d" % (tuple(e.shape), M1, C))
+        out = torch.empty((N, C), dtype=torch.float32, device=dev)
+        xa = []
+        for t in range(4):
+            x, ld = rows[t] if t < k else (None, 0)
+            xa += [nv.ptr(x), ld]
+        nv.call("esc_gineplus_aggregate_fwd", *xa, nv.ptr(e) if M1 else None, lde, nv.ptr(plan.in_ptr),
+                nv.ptr(plan.in_meta) if plan.num_pairs else None, nv.ptr(eps), N, C, k, M1, nv.ptr(out), C, nv.stream())
+        ctx.save_for_backward(e, eps, *[x for x, _ in rows])
+        ctx.plan, ctx.k, ctx.xa, ctx.lde = plan, k, xa, lde
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        e, eps = ctx.saved_tensors[:2]
+        xs = ctx.saved_tensors[2:]
+        plan, k = ctx.plan, ctx.k
+        g, ldg = _rows(g)
+        N, C = xs[0].shape
+        M1, dev = e.size(0), g.device
+        need_e, need_eps = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        dx = torch.empty((k, N, C), dtype=torch.float32, device=dev)
+        d_e = torch.empty((M1, C), dtype=torch.float32, device=dev) if need_e else None
+        part = d_eps = None
+        if need_eps:
+            part = torch.empty((int(nv.lib().esc_gineplus_bwd_blocks(N)), (k + 1) * C), dtype=torch.float32, device=dev)
+            d_eps = torch.empty((k + 1, C), dtype=torch.float32, device=dev)
+        nv.call("esc_gineplus_aggregate_bwd", *ctx.xa, nv.ptr(e) if M1 else None, ctx.lde, nv.ptr(g), ldg, nv.ptr(plan.out_ptr),
+                nv.ptr(plan.meta) if plan.num_pairs else None, nv.ptr(eps), N, C, k, M1, nv.ptr(dx), nv.ptr(d_e) if M1 else None,
+                nv.ptr(part), nv.ptr(d_eps), nv.stream())
+        return (None, d_e, d_eps) + tuple(dx[t] for t in range(k))
+
+
+def gineplus_aggregate(xs, e, eps, plan):
+    """xs: the k rows X_0..X_{k-1} (GINEPLUS: the k latest layer outputs; NAIVEGINEPLUS: k times the same tensor), e [M1, C]
+    the edge term of the distance-1 pairs in (row, col) order, eps [k+1, C], plan a multihop.MultihopPlan."""
+    xs = list(xs)
+    if not 1 <= len(xs) <= 4:
+        raise ValueError("gineplus_aggregate: k=%d outside 1..4 (larger k takes the per-distance path)" % len(xs))
+    return _GinePlusAggregate.apply(plan, e, eps, *xs)
+
+
 class _SegmentBroadcast(Function):
     """rows[batch] for a sorted batch vector (virtual-node embedding -> nodes, ogb_mol_gnn.py:744): the transpose of
     global_add_pool, run by the segment-pool kernels."""

@@ -9,7 +9,12 @@ molecule-shaped graphs with the ogbg-mol feature layout (datasets.synthetic_ogbm
 tasks with NaN labels) and `metrics.Evaluator` stands in for ogb's.  Dataset resident in HBM; forward, loss,
 backward and Adam through libescgnn_hip.so; graph-sharded under torchrun.
 
+`--gnn gine+` (reference :419-427, modules/gine_operations.py) trains the multi-hop GINE+ baseline on the same molecules, loop,
+evaluator and checkpoints: the splits hold the raw graphs (no feature build), and every batch gets its multi-hop edges on the
+device (multihop.MultihopGraphStore, csrc/multihop.hip) before the per-op forward / masked BCE / backward / Adam.
+
     python -m esc_gnn_amd.run_ogb_mol --h 4 --gnn gin_eff --edge_nest True --efficient True --self_loop True
+    python -m esc_gnn_amd.run_ogb_mol --gnn gine+
 """
 import numpy as np
 import torch
@@ -96,7 +101,10 @@ def main(argv=None):
     from .store import DeviceGraphStore
 
     args = build_parser().parse_args(argv)
-    if args.gnn != "gin_eff" or not (args.edge_nest and args.efficient) or args.h is None:
+    gineplus = args.gnn == "gine+"
+    if gineplus and args.h is not None:
+        raise NotImplementedError("`--gnn gine+` with --h (GINE+ on rooted subgraphs, h=%d) is out of scope: leave --h unset" % args.h)
+    if not gineplus and (args.gnn != "gin_eff" or not (args.edge_nest and args.efficient) or args.h is None):
         raise NotImplementedError("only `--gnn gin_eff --edge_nest True --efficient True --h H` is the ESC hot path; "
                                   "the other --gnn types are the reference's baselines")
     if args.use_rp is not None or args.use_deg or args.use_id is not None or args.RNI:
@@ -118,12 +126,25 @@ def main(argv=None):
     num_tasks, nan_ratio = TASKS.get(args.dataset, (1, 0.0))
     t1 = time.time()
     raw = synthetic_ogbmol_graphs(0, args.synthetic_graphs, num_tasks, nan_ratio)
-    done = build_feature_dataset(raw, args.h, use_rd=args.use_rd, self_loop=args.self_loop)     # reference :321-326
+    GINEPLUS_K = 3                                          # reference :421
+    if gineplus:                                            # raw molecules: the multi-hop edges are built per batch on the device
+        done = raw
+    else:
+        done = build_feature_dataset(raw, args.h, use_rd=args.use_rd, self_loop=args.self_loop)     # reference :321-326
     t2 = time.time()
     G = len(done)
     n_tr, n_va = (G * 8) // 10, G // 10
     parts = (done[:n_tr], done[n_tr:n_tr + n_va], done[n_tr + n_va:])
-    stores = [DeviceGraphStore(p, ctx.device) for p in parts]
+    if gineplus:                                            # per-graph pair counts: one count pass per split, no read-back per step
+        from .multihop import MultihopGraphStore
+        stores = [MultihopGraphStore(p, GINEPLUS_K, ctx.device) for p in parts]
+    else:
+        stores = [DeviceGraphStore(p, ctx.device) for p in parts]
+
+    def expanded(store, batches):
+        """gine+: every plain batch gets multihop_edge_index / distance and the aggregate's plan, on the device"""
+        for data, n_global in batches:
+            yield store.expand(data), n_global
     evaluator = Evaluator(args.dataset)
     eval_metric = evaluator.eval_metric
     kwargs = dict(num_layer=args.num_layer, residual=args.residual, use_rd=args.use_rd, use_rp=args.use_rp,
@@ -133,7 +154,7 @@ def main(argv=None):
         from .engine import OgbStepEngine, ogb_engine_ready, ogb_engine_supports
         model.train()
         engine = model.__dict__.get("_esc_step_engine")
-        if engine is None and ogb_engine_supports(model):
+        if engine is None and not gineplus and ogb_engine_supports(model):      # (gine+ has no whole-step engine: per-op branch)
             engine = model.__dict__["_esc_step_engine"] = OgbStepEngine(model)    # forward + masked BCE + backward in ONE call
         if engine is not None:
             engine.refresh()                                # (the optimiser owns the gradient buffers: re-read the addresses)
@@ -142,6 +163,8 @@ def main(argv=None):
         batches = sharded_batches(stores[0], args.batch_size, ctx, True, gen)
         if args.prefetch:         # the next batch is collated (and its embedding plans built) on a side stream while this one trains
             batches = prefetched(batches, ctx.device, warm)
+        if gineplus:
+            batches = expanded(stores[0], batches)
         for data, _ in batches:
             y = data.y.view(-1, num_tasks)
             if engine is not None and ogb_engine_ready(model, data):
@@ -175,7 +198,8 @@ def main(argv=None):
             if ckpt:
                 model.load_state_dict(torch.load(ckpt, map_location=ctx.device))
             y_true, y_pred = [], []
-            for data, _ in sharded_batches(store, args.batch_size, ctx, False):
+            batches = sharded_batches(store, args.batch_size, ctx, False)
+            for data, _ in (expanded(store, batches) if gineplus else batches):
                 pred = model(data)
                 y_true.append(data.y.view(pred.shape))
                 y_pred.append(pred)
@@ -197,8 +221,13 @@ def main(argv=None):
     for run in range(start_run, start_run + args.runs - args.run_from + 1):
         torch.manual_seed(run)                             # the reference leaves runs unseeded; seeded here for replay
         gen = torch.Generator().manual_seed(run)           # the shuffle order every rank shards identically
-        model = GNN(args.dataset, num_tasks, gnn_type="gin_eff", emb_dim=args.emb_dim, drop_ratio=args.drop_ratio,
-                    virtual_node=args.virtual_node, RNI=args.RNI, deg_graph=None, deg_sub=None, **kwargs).to(ctx.device)
+        if gineplus:                                       # reference :419-427
+            from .modules.gine_operations import ClassifierNetwork
+            model = ClassifierNetwork(hidden=args.emb_dim, out_dim=num_tasks, layers=args.num_layer, dropout=args.drop_ratio,
+                                      virtual_node=args.virtual_node, k=GINEPLUS_K, conv_type="gin+", nested=False).to(ctx.device)
+        else:
+            model = GNN(args.dataset, num_tasks, gnn_type="gin_eff", emb_dim=args.emb_dim, drop_ratio=args.drop_ratio,
+                        virtual_node=args.virtual_node, RNI=args.RNI, deg_graph=None, deg_sub=None, **kwargs).to(ctx.device)
         broadcast_parameters(model, 0)
         optimizer = FlatAdam(model.parameters(), lr=args.lr)
         scheduler = StepLR(optimizer, 20, args.lr_decay_factor) if args.scheduler else None
