@@ -114,6 +114,16 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
+// counter-based uniform in [0,1): two rounds of a 64-bit mix of (seed, element index) — stateless, so the backward
+// could regenerate the mask; it is stored instead (one byte per element) to keep the two passes independent
+__device__ __forceinline__ float uniform01(unsigned long long seed, unsigned long long i) {
+  unsigned long long z = seed + i * 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return (float)(z >> 40) * (1.0f / 16777216.0f);
+}
+
 // ---- "last workgroup finishes the reduction" ------------------------------------------------------------------
 // A per-device pool of zeroed ticket counters (runtime.hip).  A kernel whose workgroups each publish a partial
 // result takes a ticket after an agent-scope release fence; the workgroup drawing the last ticket sees every

@@ -184,16 +184,6 @@ __global__ __launch_bounds__(256) void embed_bwd_one_row_kernel(const float* __r
   if (q == 0 && c < C) dtable[c] = ((part[threadIdx.x] + part[threadIdx.x + 64]) + part[threadIdx.x + 128]) + part[threadIdx.x + 192];
 }
 
-// counter-based uniform in [0,1): two rounds of a 64-bit mix of (seed, element index) — stateless, so the backward
-// could regenerate the mask; it is stored instead (one byte per element) to keep the two passes independent
-__device__ __forceinline__ float uniform01(unsigned long long seed, unsigned long long i) {
-  unsigned long long z = seed + i * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return (float)(z >> 40) * (1.0f / 16777216.0f);
-}
-
 // y = dropout_p(x) + res:  keep with probability 1-p, multiply by scale = 1/(1-p) (torch.nn.functional.dropout); p == 0: y = x + res
 __global__ __launch_bounds__(256) void dropout_fwd_kernel(const float* __restrict__ x, int64_t ld_x, int64_t M, int C, float p,
                                                           float scale, unsigned long long seed, const float* __restrict__ res, int64_t ld_r,

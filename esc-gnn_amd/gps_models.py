@@ -1,0 +1,127 @@
+"""ESC-GNN inside a graph transformer — the MI355X twin of the reference's GraphGPS fork for what configs/GPS/zinc-GPS.yaml
+selects: GPSLayer (GraphGPS/graphgps/layer/gps_layer.py) with `GINE+Transformer`, batch_norm True, layer_norm False, and
+GPSModel (graphgps/network/gps_model.py) with the TypeDictNode / TypeDictEdge encoders, head `san_graph` and add pooling.
+Same state_dict key layout as the reference classes, so a reference checkpoint loads.
+
+Every GPSLayer first adds the ESC edge term to the edge attributes — z_embedding(bag over its own z_initial table), the
+primitive this library is built around — and the reference adds it IN PLACE (gps_layer.py:188): layer l therefore sees the
+terms of layers 0..l.  Here the sum is carried from layer to layer as a value, which is the same arithmetic.  It then runs a
+GINE layer and full self-attention over each graph's nodes side by side, adds the two and applies a feed-forward block.
+
+All arithmetic runs through the ops of this package (bag, GINE aggregate, Linear, BatchNorm, ReLU / ELU, embeddings, ragged
+attention, sum pooling); residual adds and the model-level Dropout stay torch ops as in the other models.  Per-op path only.
+
+`edge_attn_emb` and `edge_attn_linear` exist in the reference's state_dict although nothing uses them with `Transformer` (they
+feed the attn_bias of `BiasedTransformer`, which the reference's own collate leaves None); they are created here so that
+checkpoints load, and take no part in the forward.
+
+Out of scope: LapPE (the yaml's node encoder is TypeDictNode+LapPE; here TypeDictNode at full width — LapPE needs Laplacian
+eigenvectors with random sign flips, a follow-up), BiasedTransformer / attn_bias, Performer and BigBird, the other local GNN
+types, layer_norm, graphgym's config system and wandb, a whole-step engine, data parallelism."""
+import torch
+from torch.nn import Dropout, ModuleList, Sequential
+
+from . import nested
+from .nested import Z_TABLE_ROWS
+from .nn import BatchNorm1d, Embedding, GINEConv, GraphMultiheadAttention, Linear, ReLU, global_add_pool
+from .plan import graph_ptr_of, plan_of
+
+
+class GPSLayer(torch.nn.Module):
+    """Local GINE + full graph attention + feed-forward (gps_layer.py:19-302 for local_gnn_type 'GINE', global_model_type
+    'Transformer', act 'relu', batch_norm)."""
+
+    def __init__(self, dim_h, num_heads, dropout=0.0, attn_dropout=0.0):
+        super().__init__()
+        self.dim_h, self.num_heads = dim_h, num_heads
+        self.local_model = GINEConv(Sequential(Linear(dim_h, dim_h), ReLU(), Linear(dim_h, dim_h)))     # constant eps = 0, no edge Linear
+        self.edge_attn_emb = torch.nn.Embedding(101, num_heads, padding_idx=100)                         # unused: see the module docstring
+        self.edge_attn_linear = Sequential(torch.nn.Linear(num_heads, num_heads), torch.nn.ReLU(),
+                                           torch.nn.Linear(num_heads, num_heads), torch.nn.ReLU(),
+                                           torch.nn.Linear(num_heads, num_heads))
+        self.self_attn = GraphMultiheadAttention(dim_h, num_heads, dropout=attn_dropout)
+        self.norm1_local = BatchNorm1d(dim_h)
+        self.norm1_attn = BatchNorm1d(dim_h)
+        self.dropout_local = Dropout(dropout)
+        self.dropout_attn = Dropout(dropout)
+        self.ff_linear1 = Linear(dim_h, dim_h * 2)
+        self.ff_linear2 = Linear(dim_h * 2, dim_h)
+        self.act_fn_ff = ReLU()
+        self.norm2 = BatchNorm1d(dim_h)
+        self.ff_dropout1 = Dropout(dropout)
+        self.ff_dropout2 = Dropout(dropout)
+        self.z_initial = torch.nn.Embedding(Z_TABLE_ROWS, dim_h)
+        self.z_embedding = nested.z_embedding(dim_h, "elu", dropout)
+
+    def forward(self, h, edge_attr, data, plan, graph_ptr, max_nodes):
+        """(node states, edge attributes) -> the same after this layer; the edge attributes carry this layer's ESC term on"""
+        if "pos_index" in data:
+            edge_attr = edge_attr + self.z_embedding(nested.edge_term(self.z_initial, data, plan))
+        h_local = self.dropout_local(self.local_model(h, data.edge_index, edge_attr, plan))
+        h_local = self.norm1_local(h + h_local)
+        h_attn = self.dropout_attn(self.self_attn(h, graph_ptr, max_nodes))
+        h_attn = self.norm1_attn(h + h_attn)
+        h = h_local + h_attn
+        ff = self.ff_dropout1(self.act_fn_ff(self.ff_linear1(h)))
+        h = h + self.ff_dropout2(self.ff_linear2(ff))
+        return self.norm2(h), edge_attr
+
+
+class _TypeDict(torch.nn.Module):
+    """TypeDictNodeEncoder / TypeDictEdgeEncoder (graphgps/encoder/type_dict_encoder.py:81-116): one embedding table"""
+
+    def __init__(self, num_types, emb_dim):
+        super().__init__()
+        self.encoder = Embedding(num_types, emb_dim)
+
+    def forward(self, index):
+        return self.encoder(index)
+
+
+class FeatureEncoder(torch.nn.Module):
+    """gps_model.py:12-51 with node_encoder TypeDictNode, edge_encoder TypeDictEdge and no encoder BatchNorm"""
+
+    def __init__(self, dim_inner, node_types, edge_types):
+        super().__init__()
+        self.node_encoder = _TypeDict(node_types, dim_inner)
+        self.edge_encoder = _TypeDict(edge_types, dim_inner)
+
+
+class SANGraphHead(torch.nn.Module):
+    """graphgps/head/san_graph.py: pooling, then Linear(H, H/2), ReLU, Linear(H/2, H/4), ReLU, Linear(H/4, dim_out)"""
+
+    def __init__(self, dim_in, dim_out, L=2):
+        super().__init__()
+        self.FC_layers = ModuleList([Linear(dim_in // 2 ** l, dim_in // 2 ** (l + 1)) for l in range(L)]
+                                    + [Linear(dim_in // 2 ** L, dim_out)])
+        self.L = L
+        self.activation = ReLU()
+
+    def forward(self, h, batch, num_graphs):
+        g = global_add_pool(h, batch, num_graphs)
+        for l in range(self.L):
+            g = self.activation(self.FC_layers[l](g))
+        return self.FC_layers[self.L](g)
+
+
+class GPSModel(torch.nn.Module):
+    """gps_model.py:54-108 under zinc-GPS.yaml; defaults = that file's values.  forward(data) -> [G, dim_out] predictions.
+    The largest graph of the batch is read off `data._esc_max_nodes` when the loader left it there (the device store knows it
+    on the host); otherwise the attention op reads it back once per batch."""
+
+    def __init__(self, layers=10, dim_hidden=64, n_heads=4, dropout=0.0, attn_dropout=0.5, node_types=28, edge_types=4, dim_out=1):
+        super().__init__()
+        self.encoder = FeatureEncoder(dim_hidden, node_types, edge_types)
+        self.layers = Sequential(*[GPSLayer(dim_hidden, n_heads, dropout, attn_dropout) for _ in range(layers)])
+        self.post_mp = SANGraphHead(dim_hidden, dim_out)
+
+    def forward(self, data):
+        data.to(self.post_mp.FC_layers[0].weight.device)
+        plan = plan_of(data, Z_TABLE_ROWS)
+        graph_ptr, num_graphs = graph_ptr_of(data, plan)
+        max_nodes = getattr(data, "_esc_max_nodes", None)
+        h = self.encoder.node_encoder(data.x.view(data.x.size(0), -1)[:, 0])          # type_dict_encoder.py:96: the first column
+        edge_attr = self.encoder.edge_encoder(data.edge_attr.view(-1))
+        for layer in self.layers:
+            h, edge_attr = layer(h, edge_attr, data, plan, graph_ptr, max_nodes)
+        return self.post_mp(h, data.batch, num_graphs)

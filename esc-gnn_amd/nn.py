@@ -85,6 +85,18 @@ class ELU(torch.nn.ELU):
         return ops.elu(x.reshape(-1, x.shape[-1])).view(*lead, x.shape[-1])
 
 
+class ReLU(torch.nn.ReLU):
+    """torch.nn.ReLU computed by the HIP activation kernel (ops.relu) — a ReLU with no BatchNorm in front of it to absorb it
+    (the GINE MLP, the feed-forward block and the head of the reference's graph transformer)."""
+
+    def __init__(self, inplace=False):
+        super().__init__(inplace=False)
+
+    def forward(self, x):
+        lead = x.shape[:-1]
+        return ops.relu(x.reshape(-1, x.shape[-1])).view(*lead, x.shape[-1])
+
+
 class Embedding(torch.nn.Embedding):
     """torch.nn.Embedding whose lookup and gradient run through the ESC bag kernels (one entry of weight 1 per row)."""
 
@@ -137,3 +149,31 @@ def global_add_pool(x, batch, size=None):
 def global_mean_pool(x, batch, size=None):
     """PyG global_mean_pool: segment sum / max(count, 1)."""
     return ops.segment_pool(x, batch, size, mean=True)
+
+
+class GraphMultiheadAttention(torch.nn.Module):
+    """torch.nn.MultiheadAttention(embed_dim, num_heads, dropout, batch_first=True) as self-attention inside every graph of a
+    ragged batch: the same parameters, initialisation and state_dict keys (in_proj_weight, in_proj_bias, out_proj.weight,
+    out_proj.bias - a reference checkpoint's attention block loads unchanged), computed as ops.linear -> ops.graph_attention ->
+    ops.linear off graph_ptr instead of to_dense_batch + key_padding_mask + gather."""
+
+    def __init__(self, embed_dim, num_heads, dropout=0.0):
+        super().__init__()
+        if embed_dim % num_heads:
+            raise ValueError("embed_dim must be divisible by num_heads")
+        self.embed_dim, self.num_heads, self.dropout = embed_dim, num_heads, dropout
+        self.in_proj_weight = torch.nn.Parameter(torch.empty(3 * embed_dim, embed_dim))
+        self.in_proj_bias = torch.nn.Parameter(torch.empty(3 * embed_dim))
+        self.out_proj = Linear(embed_dim, embed_dim)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        """torch.nn.MultiheadAttention._reset_parameters"""
+        torch.nn.init.xavier_uniform_(self.in_proj_weight)
+        torch.nn.init.constant_(self.in_proj_bias, 0.0)
+        torch.nn.init.constant_(self.out_proj.bias, 0.0)
+
+    def forward(self, x, graph_ptr, max_nodes=None):
+        qkv = ops.linear(x, self.in_proj_weight, self.in_proj_bias)
+        h = ops.graph_attention(qkv, graph_ptr, self.num_heads, p=self.dropout, training=self.training, max_nodes=max_nodes)
+        return self.out_proj(h)

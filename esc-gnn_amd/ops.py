@@ -1202,3 +1202,100 @@ def group_mean(x, plan):
     if x.size(0) != plan["n"]:
         raise ValueError("group_mean: %d rows for a plan of %d" % (x.size(0), plan["n"]))
     return _GroupSum.apply(x, plan) * plan["inv_count"]
+
+
+# ---- graph transformer (csrc/attention.hip, include/escgnn_gps.h) -----------------------------------------------------------
+def _pair_ptr(graph_ptr):
+    """int64 [G+1] exclusive scan of n_g^2 on the device (torch plumbing, no read-back), cached on the graph_ptr tensor the way
+    _seg_ptr caches segment pointers: the ten attention layers of a step share it"""
+    cache = getattr(graph_ptr, "_esc_pairs", None)
+    if cache is not None and cache[0] == graph_ptr._version:
+        return cache[1]
+    n = (graph_ptr[1:] - graph_ptr[:-1]).to(torch.int64)
+    pair_ptr = torch.zeros(graph_ptr.numel(), dtype=torch.int64, device=graph_ptr.device)
+    torch.cumsum(n * n, 0, out=pair_ptr[1:])
+    graph_ptr._esc_pairs = (graph_ptr._version, pair_ptr)
+    return pair_ptr
+
+
+def attention_max_nodes(head_dim):
+    """the largest graph esc_graph_attention_* take at this head_dim (0: no kernel for that head_dim)"""
+    return int(nv.lib().esc_graph_attention_max_nodes(int(head_dim)))
+
+
+class _GraphAttention(Function):
+    """softmax(Q K^T / sqrt(d)) V per head over the nodes of each graph, with dropout on the attention weights: the reference's
+    to_dense_batch -> torch.nn.MultiheadAttention(key_padding_mask) -> [mask] between the two projections
+    (GraphGPS/graphgps/layer/gps_layer.py:234-236), one launch per direction off graph_ptr.  Saves qkv, the row log-sum-exp and
+    the keep mask; the probabilities are recomputed by the backward."""
+
+    @staticmethod
+    def forward(ctx, qkv, graph_ptr, pair_ptr, heads, head_dim, p, seed, max_nodes):
+        qkv, ld = _rows(qkv)
+        N, H = qkv.size(0), heads * head_dim
+        G, dev = graph_ptr.numel() - 1, qkv.device
+        out = torch.empty((N, H), dtype=torch.float32, device=dev)
+        lse = torch.empty((heads, N), dtype=torch.float32, device=dev)
+        mask_pairs = N * max_nodes if p > 0.0 else 0           # >= sum n_g^2, known without reading graph_ptr back
+        mask = torch.empty(heads * mask_pairs, dtype=torch.uint8, device=dev) if p > 0.0 else None
+        nv.call("esc_graph_attention_fwd", nv.ptr(qkv), ld, nv.ptr(graph_ptr), nv.ptr(pair_ptr), G, N, mask_pairs, max_nodes,
+                heads, head_dim, float(p), int(seed), nv.ptr(out), H, nv.ptr(lse), nv.ptr(mask), nv.stream())
+        ctx.save_for_backward(qkv, lse, mask)
+        ctx.args = (graph_ptr, pair_ptr, G, N, mask_pairs, max_nodes, heads, head_dim, float(p))
+        ctx.mark_non_differentiable(lse)
+        ctx.set_materialize_grads(False)                       # no zero-filled gradients of lse and mask: two launches per backward
+        return (out, lse) if mask is None else (out, lse, mask)
+
+    @staticmethod
+    def backward(ctx, d_out, *unused):
+        if d_out is None:
+            return (None,) * 8
+        qkv, lse, mask = ctx.saved_tensors
+        graph_ptr, pair_ptr, G, N, mask_pairs, max_nodes, heads, head_dim, p = ctx.args
+        _dev(d_out)
+        d_out, ldg = _rows(d_out)
+        d_qkv = torch.empty((N, 3 * heads * head_dim), dtype=torch.float32, device=qkv.device)
+        nv.call("esc_graph_attention_bwd", nv.ptr(qkv), qkv.stride(0) if N > 1 else qkv.size(1), nv.ptr(d_out), ldg, nv.ptr(lse),
+                nv.ptr(mask), nv.ptr(graph_ptr), nv.ptr(pair_ptr), G, N, mask_pairs, max_nodes, heads, head_dim, p, nv.ptr(d_qkv),
+                nv.stream())
+        return d_qkv, None, None, None, None, None, None, None
+
+
+def graph_attention(qkv, graph_ptr, heads, p=0.0, training=False, max_nodes=None, seed=None, return_aux=False):
+    """Multi-head self-attention inside every graph of a ragged batch.  qkv: [N, 3H] rows [q | k | v] (a column slice of wider
+    rows is read in place), graph_ptr: int32 [G+1] node ranges on the device, H = heads * head_dim.  Dropout with rate p on the
+    attention weights when `training` (counter-based masks: `seed`, drawn from torch's generator when None).
+    max_nodes: the largest graph of the batch as the HOST knows it (the device store's h_node_ptr) - given, nothing is read back;
+    None costs one read-back of graph_ptr, cached on it.  Limits: head_dim a multiple of 4 and at most 64, max_nodes at most
+    attention_max_nodes(head_dim); beyond them RuntimeError, raised before anything is launched.
+    return_aux: also (lse [heads, N], keep mask bytes or None; the mask's layout: include/escgnn_gps.h)."""
+    _dev(qkv)
+    _on(qkv.device, graph_ptr)
+    if graph_ptr.dtype != torch.int32 or graph_ptr.dim() != 1 or graph_ptr.numel() < 1:
+        raise TypeError("graph_attention: graph_ptr must be a 1-D int32 tensor of G+1 node offsets")
+    heads = int(heads)
+    if qkv.dim() != 2 or heads < 1 or qkv.size(1) % (3 * heads):
+        raise RuntimeError("graph_attention: qkv %s is not [N, 3 * H] with heads * head_dim == H for %d heads"
+                           % (tuple(qkv.shape), heads))
+    head_dim = qkv.size(1) // (3 * heads)
+    limit = attention_max_nodes(head_dim)
+    if limit == 0:
+        raise RuntimeError("graph_attention: head_dim %d must be a multiple of 4 and at most 64" % head_dim)
+    graph_ptr = graph_ptr.contiguous()
+    if max_nodes is None:
+        cache = getattr(graph_ptr, "_esc_max_nodes", None)
+        if cache is None or cache[0] != graph_ptr._version:
+            widest = int((graph_ptr[1:] - graph_ptr[:-1]).max()) if graph_ptr.numel() > 1 else 0
+            cache = graph_ptr._esc_max_nodes = (graph_ptr._version, widest)
+        max_nodes = cache[1]
+    max_nodes = int(max_nodes)
+    if max_nodes > limit:
+        raise RuntimeError("graph_attention: a graph of %d nodes exceeds the limit of %d nodes per graph at head_dim %d"
+                           % (max_nodes, limit, head_dim))
+    p = float(p) if training else 0.0
+    if not 0.0 <= p < 1.0:
+        raise ValueError("graph_attention: dropout rate %g outside [0, 1)" % p)
+    if p > 0.0 and seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())      # host generator: seeded runs repeat, nothing waits for the device
+    res = _GraphAttention.apply(qkv, graph_ptr, _pair_ptr(graph_ptr), heads, head_dim, p, seed or 0, max_nodes)
+    return (res[0], res[1], res[2] if len(res) > 2 else None) if return_aux else res[0]

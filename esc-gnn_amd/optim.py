@@ -3,6 +3,8 @@ fp32 buffer, so the optimiser step is one esc_adam_step launch and the data-para
 exchange is one RCCL all-reduce of `flat_grad`.  Arithmetic = torch.optim.Adam
 (reference run_graphcount.py:478: Adam(model.parameters(), lr), defaults betas=(0.9,0.999), eps=1e-8).
 """
+import math
+
 import torch
 
 from . import _native as nv
@@ -10,7 +12,9 @@ from .parallel import FlatBucket
 
 
 class FlatAdam(FlatBucket):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, late=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, late=None, weight_decay=0.0):
+        """weight_decay: decoupled (torch.optim.AdamW: p *= 1 - lr * weight_decay before the update), as one scaling of the flat
+        parameter buffer; 0.0 adds no launch and changes no bit."""
         params = [p for p in params]
         if params and params[0].device.type != "cuda":
             raise RuntimeError("FlatAdam runs on the HIP device only; there is no CPU fallback")
@@ -18,6 +22,8 @@ class FlatAdam(FlatBucket):
         self.exp_avg = torch.zeros_like(self.flat_param)
         self.exp_avg_sq = torch.zeros_like(self.flat_param)
         self.param_groups = [dict(lr=lr, betas=betas, eps=eps, params=self.params)]
+        if weight_decay:                                  # (the key exists only then: checkpoints without decay keep their layout)
+            self.param_groups[0]["weight_decay"] = weight_decay
         self.step_count = 0
 
     def step(self, grad_denom=None):
@@ -25,9 +31,18 @@ class FlatAdam(FlatBucket):
         target count returned by `all_reduce_sum`)."""
         g = self.param_groups[0]
         self.step_count += 1
+        if g.get("weight_decay"):
+            self.flat_param.mul_(1.0 - float(g["lr"]) * float(g["weight_decay"]))
         nv.call("esc_adam_step_scaled", nv.ptr(self.flat_param), nv.ptr(self.flat_grad), nv.ptr(self.exp_avg),
                 nv.ptr(self.exp_avg_sq), self.flat_param.numel(), float(g["lr"]), float(g["betas"][0]),
                 float(g["betas"][1]), float(g["eps"]), self.step_count, nv.ptr(grad_denom), nv.stream())
+
+    def clip_scale(self, max_norm):
+        """device scalar max((|g|_2 + 1e-6) / max_norm, 1) over the flat gradient buffer: dividing the gradients by it is
+        torch.nn.utils.clip_grad_norm_(params, max_norm).  Hand it to step(grad_denom=...): the division rides on the Adam
+        launch, and nothing is read back."""
+        norm = torch.linalg.vector_norm(self.flat_grad)
+        return ((norm + 1e-6) / float(max_norm)).clamp_(min=1.0).reshape(1)
 
     def state_dict(self):
         return dict(step=self.step_count, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq,
@@ -63,3 +78,28 @@ class ReduceLROnPlateau(object):
                 if g["lr"] - new > 1e-8:
                     g["lr"] = new
             self.num_bad = 0
+
+
+class CosineWithWarmup(object):
+    """The `cosine_with_warmup` schedule of the reference's graph transformer (GraphGPS/graphgps/optimizer/extra_optimizers.py,
+    get_cosine_schedule_with_warmup with num_cycles = 0.5, stepped once per epoch through torch's LambdaLR): lr = base_lr *
+    factor(epoch), factor linear from 1e-6 up to 1 over the warm-up epochs, then half a cosine down to 0 at max_epoch.  Works on
+    any object with `param_groups`, like ReduceLROnPlateau above; step() takes and ignores a metric so that
+    harness.fit_regression can drive it."""
+
+    def __init__(self, optimizer, num_warmup_epochs, max_epoch):
+        self.optimizer, self.num_warmup_epochs, self.max_epoch = optimizer, int(num_warmup_epochs), int(max_epoch)
+        self.base_lrs = [g["lr"] for g in optimizer.param_groups]
+        self.last_epoch = -1
+        self.step()                                        # LambdaLR applies factor(0) on construction
+
+    def factor(self, epoch):
+        if epoch < self.num_warmup_epochs:
+            return max(1e-6, float(epoch) / float(max(1, self.num_warmup_epochs)))
+        progress = float(epoch - self.num_warmup_epochs) / float(max(1, self.max_epoch - self.num_warmup_epochs))
+        return max(0.0, 0.5 * (1.0 + math.cos(math.pi * 0.5 * 2.0 * progress)))
+
+    def step(self, metric=None):
+        self.last_epoch += 1
+        for g, base in zip(self.optimizer.param_groups, self.base_lrs):
+            g["lr"] = base * self.factor(self.last_epoch)

@@ -1,0 +1,136 @@
+"""ZINC driver of ESC-GNN inside a graph transformer — the MI355X-native twin of the reference's GraphGPS fork run with
+GraphGPS/configs/GPS/zinc-GPS.yaml: GPSModel (gps_models.py) with ten `GINE+Transformer` layers of width 64 and 4 heads, AdamW
+with weight decay 1e-5, gradient-norm clipping at 1.0 (graphgps/config/optimizers_config.py), the cosine schedule with 50
+warm-up epochs, L1 loss on the raw targets (GraphGPS does not normalise y), batch 32.  Every flag's default is that file's value.
+
+Data are what run_zinc uses: seeded ZINC-shaped molecules (datasets.synthetic_zinc_graphs; data/zinc/raw/ZINC.pkl is absent),
+then the ESC features of create_subgraphs_eff(h, use_rd=True, self_loop=True) (GraphGPS/graphgps/loader/master_loader.py:32-33),
+the whole dataset resident in HBM (DeviceGraphStore).  The loop is run_zinc's per-op branch: forward, ops.l1_loss, backward, one
+flat AdamW launch whose gradient divisor is the clipping scale (no read-back), driven by harness.fit_regression.
+The attention of every layer runs straight off the batch's graph_ptr (csrc/attention.hip); the largest graph of the store is
+known on the host and travels on the batch, so nothing is read back for it.
+
+Out of scope: LapPE (the yaml's node encoder is TypeDictNode+LapPE; here TypeDictNode at full width), BiasedTransformer /
+attn_bias, Performer and BigBird, the other local GNN types, layer_norm, graphgym's config system and wandb, a whole-step
+engine, and data parallelism (WORLD_SIZE > 1 is refused).
+
+    python -m esc_gnn_amd.run_zinc_gps --h 3 --epochs 2000
+"""
+import os
+
+import torch
+
+from . import ops
+from .gps_models import GPSModel
+from .harness import Context, default_appendix, fit_regression, open_result_dir, parser_from, seed_everything, sharded_batches
+
+_FLAGS = [  # defaults: GraphGPS/configs/GPS/zinc-GPS.yaml (gt.*, train.batch_size, optim.*, dataset.*_num_types)
+    ("--layers", dict(type=int, default=10)),
+    ("--n_heads", dict(type=int, default=4)),
+    ("--dim_hidden", dict(type=int, default=64)),
+    ("--dropout", dict(type=float, default=0.0)),
+    ("--attn_dropout", dict(type=float, default=0.5)),
+    ("--batch_size", dict(type=int, default=32)),
+    ("--lr", dict(type=float, default=1e-3)),
+    ("--weight_decay", dict(type=float, default=1e-5)),
+    ("--epochs", dict(type=int, default=2000)),
+    ("--num_warmup_epochs", dict(type=int, default=50)),
+    ("--clip_grad_norm", dict(type=int, default=1, help="1: clip the gradient norm (optim.clip_grad_norm: True), 0: do not")),
+    ("--clip_grad_norm_value", dict(type=float, default=1.0, help="the largest norm (graphgps/config/optimizers_config.py)")),
+    ("--node_encoder_num_types", dict(type=int, default=28)),
+    ("--edge_encoder_num_types", dict(type=int, default=4)),
+    ("--h", dict(type=int, default=3)),
+    ("--seed", dict(type=int, default=0)),
+    ("--save_appendix", dict(default="")),
+    ("--load_model", dict(default=None)),
+    ("--eval", dict(default=0, type=int)),
+    ("--synthetic_graphs", dict(type=int, default=12000, help="train+val+test molecules (10:1:1 like ZINC-12k)")),
+]
+
+
+def build_parser():
+    return parser_from(_FLAGS, "ESC-GNN inside a GraphGPS transformer for ZINC graphs (MI355X hot path).")
+
+
+def _load_splits(args):
+    from .datasets import build_feature_dataset, synthetic_zinc_graphs
+    G = args.synthetic_graphs
+    done = build_feature_dataset(synthetic_zinc_graphs(0, G), args.h, use_rd=True, self_loop=True)     # master_loader.py:32-33
+    n_tr, n_va = (G * 10) // 12, G // 12
+    return done[:n_tr], done[n_tr:n_tr + n_va], done[n_tr + n_va:]
+
+
+def main(argv=None):
+    import time
+
+    from .optim import CosineWithWarmup, FlatAdam
+    from .store import DeviceGraphStore
+
+    args = build_parser().parse_args(argv)
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("run_zinc_gps: data parallelism is out of scope for the graph transformer (WORLD_SIZE must be 1)")
+    ctx = Context()
+    seed_everything(args.seed)
+    args.save_appendix = default_appendix(args.save_appendix)
+    args.res_dir = "results/zinc_GPS" + args.save_appendix
+    cmd_input = open_result_dir(ctx, args.res_dir, ("run_zinc_gps.py", "gps_models.py"))
+
+    t11 = time.time()
+    tr, va, te = _load_splits(args)
+    ctx.say("Preprocessing time cost: {}s,".format(time.time() - t11))
+    stores = [DeviceGraphStore(part, ctx.device) for part in (tr, va, te)]
+    widest = [int((s.h_node_ptr[1:] - s.h_node_ptr[:-1]).max()) for s in stores]      # the largest graph of each store: host data
+    n_train = len(tr)
+
+    model = GPSModel(layers=args.layers, dim_hidden=args.dim_hidden, n_heads=args.n_heads, dropout=args.dropout,
+                     attn_dropout=args.attn_dropout, node_types=args.node_encoder_num_types, edge_types=args.edge_encoder_num_types)
+    limit = ops.attention_max_nodes(args.dim_hidden // args.n_heads)
+    if max(widest) > limit:
+        raise SystemExit("run_zinc_gps: the largest graph has %d nodes, the attention kernels take at most %d at head_dim %d"
+                         % (max(widest), limit, args.dim_hidden // args.n_heads))
+    if args.load_model is not None:
+        model.load_state_dict(torch.load(args.load_model, map_location="cpu"))
+    ctx.say("Using " + model.__class__.__name__ + " model")
+    model = model.to(ctx.device)
+    optimizer = FlatAdam(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
+    scheduler = CosineWithWarmup(optimizer, args.num_warmup_epochs, args.epochs)
+    gen = torch.Generator().manual_seed(args.seed)
+
+    def batches(which, shuffle):
+        for data, _ in sharded_batches(stores[which], args.batch_size, ctx, shuffle, gen if shuffle else None):
+            data._esc_max_nodes = widest[which]            # an upper bound of this batch's largest graph, known without a read-back
+            yield data
+
+    def train(epoch):
+        model.train()
+        loss_all = torch.zeros((), device=ctx.device)
+        for data in batches(0, True):
+            optimizer.zero_grad()
+            y = data.y.view(-1, 1)
+            loss = ops.l1_loss(model(data), y)             # graphgps/loss/l1.py
+            loss.backward()
+            loss_all += loss.detach() * y.size(0)
+            optimizer.step(grad_denom=optimizer.clip_scale(args.clip_grad_norm_value) if args.clip_grad_norm else None)
+        return float(loss_all) / n_train
+
+    def test(store):
+        which = next(i for i, s in enumerate(stores) if s is store)
+        model.eval()
+        tot = torch.zeros(2, device=ctx.device)
+        with torch.no_grad():
+            for data in batches(which, False):
+                y_hat = model(data)[:, 0]
+                tot[0] += torch.sum(torch.abs(y_hat - data.y.view(-1)))
+                tot[1] += y_hat.numel()
+        return float(tot[0] / tot[1])
+
+    if args.eval:
+        print("Test MAE: %.7f" % test(stores[2]))
+        ctx.close()
+        return
+    fit_regression(ctx, args, model, optimizer, scheduler, train, test, stores[1], stores[2], 1.0, cmd_input)
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
