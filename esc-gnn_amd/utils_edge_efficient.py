@@ -21,6 +21,15 @@ def _device():
     return torch.device("cuda", torch.cuda.current_device())
 
 
+def _raise_if_refused(status):
+    st = status.cpu()
+    if bool((st != 0).any()):
+        g = int(torch.nonzero(st)[0])
+        raise RuntimeError("create_subgraphs: graph %d cannot be encoded (status %d): a sub-degree >= 200, a "
+                           "resistance-distance bin outside [0,100), an edge code >= 1300 or a node id out of "
+                           "range" % (g, int(st[g])))
+
+
 def encode_edge_lists(node_counts, edge_lists, h, use_rd, self_loop):
     """Low-level batched call.  node_counts: list[int]; edge_lists: list of int64 [2, m_g] tensors with
     graph-local ids.  Returns per-graph tuples (edge_index', in_edge_of_out, pos_enc, pos_index, pos_batch)
@@ -50,6 +59,9 @@ def encode_edge_lists(node_counts, edge_lists, h, use_rd, self_loop):
             int(h), int(bool(use_rd)), int(bool(self_loop)), nv.ptr(out_edge_ptr), nv.ptr(nnz_ptr), nv.ptr(status),
             nv.ptr(work), s)
     oep = out_edge_ptr.cpu()
+    # the count pass already knows every refusal; a refused edge counts no entry, so a batch of refused graphs alone would
+    # reach the fill pass with output edges and zero-length pos_* buffers
+    _raise_if_refused(status)
     Eout = int(oep[-1])
     Z = int(nnz_ptr[Eout]) if cap else 0
     out_src = torch.empty(Eout, dtype=torch.int64, device=dev)
@@ -62,12 +74,7 @@ def encode_edge_lists(node_counts, edge_lists, h, use_rd, self_loop):
             int(bool(use_rd)), int(bool(self_loop)), nv.ptr(out_edge_ptr), nv.ptr(nnz_ptr), Eout, nv.ptr(out_src),
             nv.ptr(out_dst), nv.ptr(in_of_out), nv.ptr(pos_enc), nv.ptr(pos_index), nv.ptr(pos_batch),
             nv.ptr(status), nv.ptr(work), s)
-    st = status.cpu()
-    if bool((st != 0).any()):
-        g = int(torch.nonzero(st)[0])
-        raise RuntimeError("create_subgraphs: graph %d cannot be encoded (status %d): a sub-degree >= 200, a "
-                           "resistance-distance bin outside [0,100), an edge code >= 1300 or a node id out of "
-                           "range" % (g, int(st[g])))
+    _raise_if_refused(status)
     nnz_c = nnz_ptr[:Eout + 1].cpu()
     out_src, out_dst, in_of_out = out_src.cpu(), out_dst.cpu(), in_of_out.cpu()
     pos_enc, pos_index, pos_batch = pos_enc.cpu(), pos_index.cpu(), pos_batch.cpu()

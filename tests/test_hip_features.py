@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN, require_gpu
+from feature_cases import hub_ring as _hub_ring, regular_like as _regular_like
 import graph_sources as gs
 import ref_features as orc
 
@@ -94,27 +95,6 @@ def test_larger_graph_and_errors(E):
         encode_edge_lists([2], [torch.tensor([[0], [1]])], 5, False, False)            # h > 4
     with pytest.raises(NotImplementedError):
         E.create_subgraphs(E.Data(x=torch.ones(2, 1), edge_index=torch.tensor([[0], [1]])), 1, max_nodes_per_hop=3)
-
-
-def _hub_ring(n):
-    """node 0 joined to everyone, the others on a ring: every 2-hop ego-net is the whole graph"""
-    pairs = [(0, i) for i in range(1, n)] + [(i, i + 1) for i in range(1, n - 1)] + [(n - 1, 1)]
-    s = np.array([a for a, b in pairs] + [b for a, b in pairs], np.int64)
-    t = np.array([b for a, b in pairs] + [a for a, b in pairs], np.int64)
-    return n, s, t
-
-
-def _regular_like(n, seed):
-    """ring + two random perfect matchings (degree <= 4): 3-hop ego-nets of 50..100 nodes, many distinct ones"""
-    rng = np.random.default_rng(seed)
-    pairs = {(i, (i + 1) % n) for i in range(n)}
-    for _ in range(2):
-        p = rng.permutation(n)
-        pairs |= {(int(min(a, b)), int(max(a, b))) for a, b in zip(p[0::2], p[1::2]) if a != b}
-    pairs = sorted((min(a, b), max(a, b)) for a, b in pairs)
-    s = np.array([a for a, b in pairs] + [b for a, b in pairs], np.int64)
-    t = np.array([b for a, b in pairs] + [a for a, b in pairs], np.int64)
-    return n, s, t
 
 
 @pytest.mark.parametrize("case", ["hub130", "regular104_h3", "regular104_h4", "mol150", "mixed_batch"])
