@@ -15,15 +15,19 @@ attention, sum pooling); residual adds and the model-level Dropout stay torch op
 feed the attn_bias of `BiasedTransformer`, which the reference's own collate leaves None); they are created here so that
 checkpoints load, and take no part in the forward.
 
-Out of scope: LapPE (the yaml's node encoder is TypeDictNode+LapPE; here TypeDictNode at full width — LapPE needs Laplacian
-eigenvectors with random sign flips, a follow-up), BiasedTransformer / attn_bias, Performer and BigBird, the other local GNN
-types, layer_norm, graphgym's config system and wandb, a whole-step engine, data parallelism."""
+The yaml's node encoder is TypeDictNode+LapPE.  GPSModel(lap_pe=True) builds it as the reference's Concat2NodeEncoder does:
+encoder1 = the type embedding at width dim_hidden - dim_pe, encoder2 = nn.LapPENodeEncoder over the batch's EigVals / EigVecs
+(lappe.py computes them on the device), the node state their concatenation.  The default, lap_pe=False, is TypeDictNode at full
+width with the state_dict that has.
+
+Out of scope: BiasedTransformer / attn_bias, Performer and BigBird, the other local GNN types, layer_norm, the other positional
+encodings and LapPE's Transformer model, graphgym's config system and wandb, a whole-step engine, data parallelism."""
 import torch
 from torch.nn import Dropout, ModuleList, Sequential
 
 from . import nested
 from .nested import Z_TABLE_ROWS
-from .nn import BatchNorm1d, Embedding, GINEConv, GraphMultiheadAttention, Linear, ReLU, global_add_pool
+from .nn import BatchNorm1d, Embedding, GINEConv, GraphMultiheadAttention, LapPENodeEncoder, Linear, ReLU, global_add_pool
 from .plan import graph_ptr_of, plan_of
 
 
@@ -78,12 +82,28 @@ class _TypeDict(torch.nn.Module):
         return self.encoder(index)
 
 
-class FeatureEncoder(torch.nn.Module):
-    """gps_model.py:12-51 with node_encoder TypeDictNode, edge_encoder TypeDictEdge and no encoder BatchNorm"""
+class _Concat2(torch.nn.Module):
+    """Concat2NodeEncoder for TypeDictNode+LapPE (graphgps/encoder/composed_encoders.py:35-58): the type embedding at width
+    dim_emb - dim_pe, then the LapPE encoder (expand_x False), concatenated"""
 
-    def __init__(self, dim_inner, node_types, edge_types):
+    def __init__(self, num_types, dim_emb, dim_pe, max_freqs):
         super().__init__()
-        self.node_encoder = _TypeDict(node_types, dim_inner)
+        if not 0 < dim_pe < dim_emb:
+            raise ValueError("LapPE size %d is too large for desired embedding size of %d." % (dim_pe, dim_emb))
+        self.encoder1 = _TypeDict(num_types, dim_emb - dim_pe)
+        self.encoder2 = LapPENodeEncoder(dim_pe, max_freqs)
+
+    def forward(self, index, data):
+        return torch.cat([self.encoder1(index), self.encoder2(data)], 1)
+
+
+class FeatureEncoder(torch.nn.Module):
+    """gps_model.py:12-51 with node_encoder TypeDictNode (lap_pe: TypeDictNode+LapPE), edge_encoder TypeDictEdge and no encoder
+    BatchNorm"""
+
+    def __init__(self, dim_inner, node_types, edge_types, lap_pe=False, dim_pe=8, max_freqs=8):
+        super().__init__()
+        self.node_encoder = _Concat2(node_types, dim_inner, dim_pe, max_freqs) if lap_pe else _TypeDict(node_types, dim_inner)
         self.edge_encoder = _TypeDict(edge_types, dim_inner)
 
 
@@ -107,11 +127,14 @@ class SANGraphHead(torch.nn.Module):
 class GPSModel(torch.nn.Module):
     """gps_model.py:54-108 under zinc-GPS.yaml; defaults = that file's values.  forward(data) -> [G, dim_out] predictions.
     The largest graph of the batch is read off `data._esc_max_nodes` when the loader left it there (the device store knows it
-    on the host); otherwise the attention op reads it back once per batch."""
+    on the host); otherwise the attention op reads it back once per batch.  lap_pe=True: the batch must carry EigVals / EigVecs
+    (lappe.add_lap_pe, lappe.LapPETable.attach)."""
 
-    def __init__(self, layers=10, dim_hidden=64, n_heads=4, dropout=0.0, attn_dropout=0.5, node_types=28, edge_types=4, dim_out=1):
+    def __init__(self, layers=10, dim_hidden=64, n_heads=4, dropout=0.0, attn_dropout=0.5, node_types=28, edge_types=4, dim_out=1,
+                 lap_pe=False, dim_pe=8, max_freqs=8):
         super().__init__()
-        self.encoder = FeatureEncoder(dim_hidden, node_types, edge_types)
+        self.lap_pe = bool(lap_pe)
+        self.encoder = FeatureEncoder(dim_hidden, node_types, edge_types, self.lap_pe, dim_pe, max_freqs)
         self.layers = Sequential(*[GPSLayer(dim_hidden, n_heads, dropout, attn_dropout) for _ in range(layers)])
         self.post_mp = SANGraphHead(dim_hidden, dim_out)
 
@@ -120,7 +143,8 @@ class GPSModel(torch.nn.Module):
         plan = plan_of(data, Z_TABLE_ROWS)
         graph_ptr, num_graphs = graph_ptr_of(data, plan)
         max_nodes = getattr(data, "_esc_max_nodes", None)
-        h = self.encoder.node_encoder(data.x.view(data.x.size(0), -1)[:, 0])          # type_dict_encoder.py:96: the first column
+        types = data.x.view(data.x.size(0), -1)[:, 0]                                 # type_dict_encoder.py:96: the first column
+        h = self.encoder.node_encoder(types, data) if self.lap_pe else self.encoder.node_encoder(types)
         edge_attr = self.encoder.edge_encoder(data.edge_attr.view(-1))
         for layer in self.layers:
             h, edge_attr = layer(h, edge_attr, data, plan, graph_ptr, max_nodes)

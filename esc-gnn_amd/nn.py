@@ -177,3 +177,37 @@ class GraphMultiheadAttention(torch.nn.Module):
         qkv = ops.linear(x, self.in_proj_weight, self.in_proj_bias)
         h = ops.graph_attention(qkv, graph_ptr, self.num_heads, p=self.dropout, training=self.training, max_nodes=max_nodes)
         return self.out_proj(h)
+
+
+class LapPENodeEncoder(torch.nn.Module):
+    """The reference's LapPENodeEncoder (GraphGPS/graphgps/encoder/laplace_pos_encoder.py) as zinc-GPS.yaml configures it and as
+    Concat2NodeEncoder builds it (expand_x False): model DeepSet, `layers` 2, post_layers 0, raw_norm_type none.  The same
+    parameters, names and initial values - linear_A.{weight,bias} [2 dim_pe, 2] and pe_encoder.1.{weight,bias}
+    [dim_pe, 2 dim_pe] in Sequential(ReLU, Linear, ReLU) - computed by ops.lappe_encode: one launch forward, two backward.
+    forward(batch) -> [N, dim_pe], the rows the reference concatenates to batch.x.  In training one vector of random signs is
+    drawn per call (torch.rand(K) >= 0.5 -> +-1, on the batch's device as the reference does); `signs_override` (a [K] tensor
+    of +-1, default None) replaces the draw."""
+
+    def __init__(self, dim_pe=8, max_freqs=8, layers=2, model="DeepSet", post_layers=0, raw_norm_type="none"):
+        super().__init__()
+        if model != "DeepSet" or layers != 2 or post_layers != 0 or str(raw_norm_type).lower() != "none":
+            raise ValueError("LapPENodeEncoder: supported are model 'DeepSet' (not %r), layers 2 (not %r), post_layers 0 (not %r) and "
+                             "raw_norm_type 'none' (not %r)" % (model, layers, post_layers, raw_norm_type))
+        self.dim_pe, self.max_freqs = dim_pe, max_freqs
+        self.linear_A = torch.nn.Linear(2, dim_pe)               # laplace_pos_encoder.py:47 - replaced at once (line 67), but it
+        self.linear_A = torch.nn.Linear(2, 2 * dim_pe)           # has consumed the generator: equal seeds give equal weights
+        self.pe_encoder = torch.nn.Sequential(torch.nn.ReLU(), torch.nn.Linear(2 * dim_pe, dim_pe), torch.nn.ReLU())
+        self.signs_override = None
+
+    def forward(self, batch):
+        if not (hasattr(batch, "EigVals") and hasattr(batch, "EigVecs")):
+            raise ValueError("Precomputed eigen values and vectors are required for %s; set config 'posenc_LapPE.enable' to True"
+                             % self.__class__.__name__)
+        vecs, vals = batch.EigVecs, batch.EigVals
+        signs = None
+        if self.signs_override is not None:
+            signs = self.signs_override.to(device=vecs.device, dtype=torch.float32)
+        elif self.training:
+            signs = torch.where(torch.rand(vecs.size(1), device=vecs.device) >= 0.5, 1.0, -1.0)
+        lin = self.pe_encoder[1]
+        return ops.lappe_encode(vecs, vals, signs, self.linear_A.weight, self.linear_A.bias, lin.weight, lin.bias)

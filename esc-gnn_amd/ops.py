@@ -1299,3 +1299,161 @@ def graph_attention(qkv, graph_ptr, heads, p=0.0, training=False, max_nodes=None
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())      # host generator: seeded runs repeat, nothing waits for the device
     res = _GraphAttention.apply(qkv, graph_ptr, _pair_ptr(graph_ptr), heads, head_dim, p, seed or 0, max_nodes)
     return (res[0], res[1], res[2] if len(res) > 2 else None) if return_aux else res[0]
+
+
+# ---- Laplacian positional encoding (csrc/lappe.hip, include/escgnn_lappe.h) -------------------------------------------------
+def laplacian_eig_limits():
+    """(largest graph esc_laplacian_eig takes, largest graph whose matrices stay in LDS)"""
+    h = nv.lib()
+    return int(h.esc_laplacian_eig_max_nodes()), int(h.esc_laplacian_eig_lds_nodes())
+
+
+def _index_vector(t, what, dtype):
+    if not torch.is_tensor(t) or t.dtype != dtype or t.dim() != 1 or t.numel() < 1:
+        raise TypeError("%s must be a 1-D %s tensor" % (what, str(dtype).replace("torch.", "")))
+    return t.contiguous()
+
+
+def laplacian_eig(edge_index, graph_ptr, edge_ptr, max_freqs, max_nodes=None, edges_local=False, num_nodes=None):
+    """The max_freqs smallest eigenpairs of L = D - A of every graph of a ragged set, one workgroup per graph, one launch: the
+    reference's compute_posenc_stats for pe_types ['LapPE'] with laplacian_norm none and eigvec_norm L2
+    (GraphGPS/graphgps/transform/posenc_stats.py:40-73,149-182).  edge_index int64 [2, E] on the device; graph_ptr, edge_ptr
+    [G+1] node and edge range of every graph (int32 or int64; edges contiguous per graph); edges_local: the edge ends are
+    graph-local ids (a store's flat arrays) instead of batch rows.  Returns (EigVals [N, K, 1], EigVecs [N, K]) fp32, NaN in the
+    columns j >= n of a graph with n < K nodes.
+    max_nodes: the largest graph as the HOST knows it, num_nodes: N likewise; None costs one read-back of graph_ptr each.
+    Limits: laplacian_eig_limits()[0] = 256 nodes per graph, max_freqs <= 32; beyond them RuntimeError, raised before anything
+    is launched."""
+    if not torch.is_tensor(edge_index) or edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.size(0) != 2:
+        raise TypeError("laplacian_eig: edge_index must be an int64 [2, E] tensor")
+    if not edge_index.is_cuda:
+        raise RuntimeError("esc_gnn_amd: the hot path runs on the HIP device only (got a %s tensor); there is no CPU fallback"
+                           % edge_index.device)
+    dev = edge_index.device
+    for name, t in (("graph_ptr", graph_ptr), ("edge_ptr", edge_ptr)):
+        if not torch.is_tensor(t) or t.dtype not in (torch.int32, torch.int64) or t.dim() != 1 or t.numel() < 1:
+            raise TypeError("laplacian_eig: %s must be a 1-D int32 or int64 tensor of G+1 offsets" % name)
+    _on(dev, graph_ptr, edge_ptr)
+    if graph_ptr.numel() != edge_ptr.numel():
+        raise ValueError("laplacian_eig: graph_ptr has %d entries, edge_ptr %d" % (graph_ptr.numel(), edge_ptr.numel()))
+    K = int(max_freqs)
+    if not 1 <= K <= 32:
+        raise RuntimeError("laplacian_eig: max_freqs %d outside 1..32" % K)
+    limit = laplacian_eig_limits()[0]
+    G = graph_ptr.numel() - 1
+    if max_nodes is None:
+        max_nodes = int((graph_ptr[1:] - graph_ptr[:-1]).max()) if G else 0
+    max_nodes = int(max_nodes)
+    if max_nodes > limit:
+        raise RuntimeError("laplacian_eig: a graph of %d nodes exceeds the limit of %d nodes per graph" % (max_nodes, limit))
+    if num_nodes is None:
+        num_nodes = int(graph_ptr[-1])
+    return _laplacian_eig(edge_index, graph_ptr.to(torch.int64).contiguous(), edge_ptr.to(torch.int64).contiguous(), G, int(num_nodes), K,
+                          max_nodes, edges_local)
+
+
+def _laplacian_eig(edge_index, node_ptr, edge_ptr, G, N, K, max_nodes, edges_local):
+    """the launch itself: int64 pointers, every size known on the host"""
+    dev = edge_index.device
+    src, dst = edge_index[0].contiguous(), edge_index[1].contiguous()
+    vecs = torch.empty((N, K), dtype=torch.float32, device=dev)
+    vals = torch.empty((N, K), dtype=torch.float32, device=dev)
+    need = int(nv.lib().esc_laplacian_eig_scratch_bytes(N, max_nodes))
+    scratch = torch.empty(need // 8, dtype=torch.float64, device=dev) if need else None
+    nv.call("esc_laplacian_eig", nv.ptr(src), nv.ptr(dst), src.numel(), nv.ptr(node_ptr), nv.ptr(edge_ptr), G, N, int(bool(edges_local)), K,
+            max_nodes, nv.ptr(scratch), need, nv.ptr(vecs), nv.ptr(vals), nv.stream())
+    return vals.view(N, K, 1), vecs
+
+
+def lappe_gather(vecs_all, vals_all, node_ptr_all, graph_ids, graph_ptr, num_nodes):
+    """The batch's rows of a split's resident PE tables (what the reference's collate does to the EigVecs / EigVals keys), one
+    launch.  vecs_all, vals_all [N_all, K] fp32; node_ptr_all int64 [G_all+1] (device); graph_ids: the batch's graphs in batch
+    order, a HOST int64 tensor or list - checked here, an id out of range raises IndexError before anything is launched;
+    graph_ptr int32 [B+1]: the batch's node ranges; num_nodes: the batch's N.  Returns (vals [N, K, 1], vecs [N, K])."""
+    _dev(vecs_all, vals_all)
+    dev = vecs_all.device
+    if vecs_all.dim() != 2 or vals_all.shape != vecs_all.shape or not (vecs_all.is_contiguous() and vals_all.is_contiguous()):
+        raise ValueError("lappe_gather: the two tables must be contiguous [N_all, K] tensors of one shape")
+    node_ptr_all = _index_vector(node_ptr_all, "lappe_gather: node_ptr_all", torch.int64)
+    graph_ptr = _index_vector(graph_ptr, "lappe_gather: graph_ptr", torch.int32)
+    _on(dev, node_ptr_all, graph_ptr)
+    G_all, B = node_ptr_all.numel() - 1, graph_ptr.numel() - 1
+    if torch.is_tensor(graph_ids) and graph_ids.is_cuda:
+        raise RuntimeError("lappe_gather: graph_ids must live on the host (they are checked there, without a read-back)")
+    ids_h = torch.as_tensor(graph_ids, dtype=torch.int64).reshape(-1)
+    if ids_h.numel() != B:
+        raise ValueError("lappe_gather: %d graph ids for a batch of %d graphs" % (ids_h.numel(), B))
+    if B and (int(ids_h.min()) < 0 or int(ids_h.max()) >= G_all):
+        raise IndexError("lappe_gather: graph id out of range (the table holds %d graphs)" % G_all)
+    N, K = int(num_nodes), vecs_all.size(1)
+    ids_d = ids_h.to(dev, non_blocking=True)
+    vecs = torch.empty((N, K), dtype=torch.float32, device=dev)
+    vals = torch.empty((N, K), dtype=torch.float32, device=dev)
+    nv.call("esc_lappe_gather", nv.ptr(vecs_all), nv.ptr(vals_all), nv.ptr(node_ptr_all), G_all, vecs_all.size(0), nv.ptr(ids_d),
+            nv.ptr(graph_ptr), B, N, K, nv.ptr(vecs), nv.ptr(vals), nv.stream())
+    return vals.view(N, K, 1), vecs
+
+
+def lappe_encode_block_rows():
+    """rows per workgroup of esc_lappe_encode_bwd: its fixed row partition"""
+    return int(nv.lib().esc_lappe_encode_block_rows())
+
+
+class _LapPEEncode(Function):
+    """sum_j ReLU(W1 ReLU(WA [v_ij s_j, l_ij] + bA) + b1) over the frequencies whose eigenvector entry is not NaN: the reference's
+    LapPENodeEncoder.forward for the DeepSet model with 2 layers (graphgps/encoder/laplace_pos_encoder.py:94-132: cat, isnan
+    mask, linear_A, pe_encoder, masked_fill_, sum), one launch forward and two backward.  Saves only its inputs."""
+
+    @staticmethod
+    def forward(ctx, eigvecs, eigvals, signs, wA, bA, w1, b1):
+        N, K = eigvecs.shape
+        P = w1.size(0)
+        out = torch.empty((N, P), dtype=torch.float32, device=eigvecs.device)
+        nv.call("esc_lappe_encode_fwd", nv.ptr(eigvecs), nv.ptr(eigvals), nv.ptr(signs), nv.ptr(wA), nv.ptr(bA), nv.ptr(w1), nv.ptr(b1),
+                N, K, P, nv.ptr(out), P, nv.stream())
+        ctx.save_for_backward(eigvecs, eigvals, signs, wA, bA, w1, b1)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        eigvecs, eigvals, signs, wA, bA, w1, b1 = ctx.saved_tensors
+        N, K = eigvecs.shape
+        P = w1.size(0)
+        _dev(d_out)
+        d_out, ldg = _rows(d_out)
+        need = int(nv.lib().esc_lappe_encode_scratch_floats(N, P))
+        scratch = torch.empty(max(need, 1), dtype=torch.float32, device=eigvecs.device)
+        flat = torch.empty(2 * P * P + 7 * P, dtype=torch.float32, device=eigvecs.device)
+        d_wA, d_bA, d_w1, d_b1 = flat[:4 * P].view(2 * P, 2), flat[4 * P:6 * P], flat[6 * P:6 * P + 2 * P * P].view(P, 2 * P), flat[6 * P + 2 * P * P:]
+        nv.call("esc_lappe_encode_bwd", nv.ptr(eigvecs), nv.ptr(eigvals), nv.ptr(signs), nv.ptr(wA), nv.ptr(bA), nv.ptr(w1), nv.ptr(b1),
+                nv.ptr(d_out), ldg, N, K, P, nv.ptr(scratch), need, nv.ptr(d_wA), nv.ptr(d_bA), nv.ptr(d_w1), nv.ptr(d_b1), nv.stream())
+        return None, None, None, d_wA, d_bA, d_w1, d_b1
+
+
+def lappe_encode(eigvecs, eigvals, signs, wA, bA, w1, b1):
+    """The DeepSet LapPE encoder.  eigvecs [N, K], eigvals [N, K] or [N, K, 1] (NaN-padded, not differentiable), signs [K] of +-1
+    or None, wA [2P, 2], bA [2P], w1 [P, 2P], b1 [P] -> [N, P] (the C entry point also writes a column slice of a wider buffer:
+    ld_out).  Limits: P a multiple of 4 and at most 32, K <= 32; beyond them RuntimeError before any launch."""
+    _dev(eigvecs, eigvals, signs, wA, bA, w1, b1)
+    dev = eigvecs.device
+    _on(dev, eigvals, signs, wA, bA, w1, b1)
+    if eigvecs.dim() != 2:
+        raise ValueError("lappe_encode: eigvecs must be [N, K], got %s" % (tuple(eigvecs.shape),))
+    N, K = eigvecs.shape
+    if eigvals.dim() == 3 and eigvals.size(2) == 1:
+        eigvals = eigvals.view(eigvals.size(0), eigvals.size(1))
+    if eigvals.shape != eigvecs.shape:
+        raise ValueError("lappe_encode: eigvals %s does not match eigvecs %s" % (tuple(eigvals.shape), tuple(eigvecs.shape)))
+    if w1.dim() != 2:
+        raise ValueError("lappe_encode: w1 must be [P, 2P]")
+    P = w1.size(0)
+    if P % 4 or not 0 < P <= 32:
+        raise RuntimeError("lappe_encode: dim_pe %d must be a multiple of 4 and at most 32" % P)
+    if not 1 <= K <= 32:
+        raise RuntimeError("lappe_encode: max_freqs %d outside 1..32" % K)
+    if tuple(wA.shape) != (2 * P, 2) or tuple(bA.shape) != (2 * P,) or tuple(w1.shape) != (P, 2 * P) or tuple(b1.shape) != (P,):
+        raise ValueError("lappe_encode: expected wA [%d, 2], bA [%d], w1 [%d, %d], b1 [%d]" % (2 * P, 2 * P, P, 2 * P, P))
+    if signs is not None and tuple(signs.shape) != (K,):
+        raise ValueError("lappe_encode: signs must be [%d]" % K)
+    cont = [t.contiguous() for t in (eigvecs.detach(), eigvals.detach(), wA, bA, w1, b1)]
+    return _LapPEEncode.apply(cont[0], cont[1], None if signs is None else signs.detach().contiguous(), cont[2], cont[3], cont[4], cont[5])

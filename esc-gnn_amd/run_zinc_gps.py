@@ -10,11 +10,15 @@ flat AdamW launch whose gradient divisor is the clipping scale (no read-back), d
 The attention of every layer runs straight off the batch's graph_ptr (csrc/attention.hip); the largest graph of the store is
 known on the host and travels on the batch, so nothing is read back for it.
 
-Out of scope: LapPE (the yaml's node encoder is TypeDictNode+LapPE; here TypeDictNode at full width), BiasedTransformer /
-attn_bias, Performer and BigBird, the other local GNN types, layer_norm, graphgym's config system and wandb, a whole-step
-engine, and data parallelism (WORLD_SIZE > 1 is refused).
+--posenc_LapPE 1 selects the yaml's node encoder, TypeDictNode+LapPE (posenc_LapPE: laplacian_norm none, eigvec_norm L2,
+max_freqs 8, DeepSet, dim_pe 8, 2 layers): one lappe.LapPETable per split is computed on the device after the stores (one launch
+each), every batch gets its rows with one gather launch, and checkpoints carry the reference's key layout
+(encoder.node_encoder.encoder1.* / encoder2.*).  The default, 0, is TypeDictNode at full width.
 
-    python -m esc_gnn_amd.run_zinc_gps --h 3 --epochs 2000
+Out of scope: BiasedTransformer / attn_bias, Performer and BigBird, the other local GNN types, layer_norm, the other positional
+encodings, graphgym's config system and wandb, a whole-step engine, and data parallelism (WORLD_SIZE > 1 is refused).
+
+    python -m esc_gnn_amd.run_zinc_gps --h 3 --epochs 2000 --posenc_LapPE 1
 """
 import os
 
@@ -22,7 +26,7 @@ import torch
 
 from . import ops
 from .gps_models import GPSModel
-from .harness import Context, default_appendix, fit_regression, open_result_dir, parser_from, seed_everything, sharded_batches
+from .harness import Context, default_appendix, fit_regression, open_result_dir, parser_from, seed_everything, sharded_batches, sharded_ids
 
 _FLAGS = [  # defaults: GraphGPS/configs/GPS/zinc-GPS.yaml (gt.*, train.batch_size, optim.*, dataset.*_num_types)
     ("--layers", dict(type=int, default=10)),
@@ -45,6 +49,9 @@ _FLAGS = [  # defaults: GraphGPS/configs/GPS/zinc-GPS.yaml (gt.*, train.batch_si
     ("--load_model", dict(default=None)),
     ("--eval", dict(default=0, type=int)),
     ("--synthetic_graphs", dict(type=int, default=12000, help="train+val+test molecules (10:1:1 like ZINC-12k)")),
+    ("--posenc_LapPE", dict(type=int, default=0, help="1: node encoder TypeDictNode+LapPE (the reference yaml), 0: TypeDictNode")),
+    ("--posenc_LapPE_max_freqs", dict(type=int, default=8, help="posenc_LapPE.eigen.max_freqs")),
+    ("--posenc_LapPE_dim_pe", dict(type=int, default=8, help="posenc_LapPE.dim_pe (model DeepSet, layers 2)")),
 ]
 
 
@@ -81,9 +88,20 @@ def main(argv=None):
     stores = [DeviceGraphStore(part, ctx.device) for part in (tr, va, te)]
     widest = [int((s.h_node_ptr[1:] - s.h_node_ptr[:-1]).max()) for s in stores]      # the largest graph of each store: host data
     n_train = len(tr)
+    tables = None
+    if args.posenc_LapPE:
+        from .lappe import LapPETable
+        limit = ops.laplacian_eig_limits()[0]
+        if max(widest) > limit:
+            raise SystemExit("run_zinc_gps: the largest graph has %d nodes, the Laplacian eigen-solver takes at most %d" % (max(widest), limit))
+        t12 = time.time()
+        tables = [LapPETable(s, args.posenc_LapPE_max_freqs) for s in stores]
+        torch.cuda.synchronize()
+        ctx.say("LapPE table build time cost: {}s,".format(time.time() - t12))
 
     model = GPSModel(layers=args.layers, dim_hidden=args.dim_hidden, n_heads=args.n_heads, dropout=args.dropout,
-                     attn_dropout=args.attn_dropout, node_types=args.node_encoder_num_types, edge_types=args.edge_encoder_num_types)
+                     attn_dropout=args.attn_dropout, node_types=args.node_encoder_num_types, edge_types=args.edge_encoder_num_types,
+                     lap_pe=bool(args.posenc_LapPE), dim_pe=args.posenc_LapPE_dim_pe, max_freqs=args.posenc_LapPE_max_freqs)
     limit = ops.attention_max_nodes(args.dim_hidden // args.n_heads)
     if max(widest) > limit:
         raise SystemExit("run_zinc_gps: the largest graph has %d nodes, the attention kernels take at most %d at head_dim %d"
@@ -97,8 +115,14 @@ def main(argv=None):
     gen = torch.Generator().manual_seed(args.seed)
 
     def batches(which, shuffle):
-        for data, _ in sharded_batches(stores[which], args.batch_size, ctx, shuffle, gen if shuffle else None):
-            data._esc_max_nodes = widest[which]            # an upper bound of this batch's largest graph, known without a read-back
+        if tables is None:
+            for data, _ in sharded_batches(stores[which], args.batch_size, ctx, shuffle, gen if shuffle else None):
+                data._esc_max_nodes = widest[which]        # an upper bound of this batch's largest graph, known without a read-back
+                yield data
+            return
+        for ids, _ in sharded_ids(stores[which], args.batch_size, ctx, shuffle, gen if shuffle else None):
+            data = tables[which].attach(stores[which].collate(ids), ids)      # sharded_batches' collate, plus the batch's PE rows
+            data._esc_max_nodes = widest[which]
             yield data
 
     def train(epoch):
