@@ -59,6 +59,19 @@ __device__ __forceinline__ void axpy(float (&acc)[DP], float w, const float* row
     acc[c + 3] = fmaf(w, r.w, acc[c + 3]);
   }
 }
+// acc[c] += w * (row[c] - row0[c])
+template <int DP>
+__device__ __forceinline__ void axpy_diff(float (&acc)[DP], float w, const float* row, const float* row0) {
+#pragma unroll
+  for (int c = 0; c < DP; c += 4) {
+    const float4 r = *reinterpret_cast<const float4*>(row + c);
+    const float4 z = *reinterpret_cast<const float4*>(row0 + c);
+    acc[c] = fmaf(w, r.x - z.x, acc[c]);
+    acc[c + 1] = fmaf(w, r.y - z.y, acc[c + 1]);
+    acc[c + 2] = fmaf(w, r.z - z.z, acc[c + 2]);
+    acc[c + 3] = fmaf(w, r.w - z.w, acc[c + 3]);
+  }
+}
 // d columns (a multiple of 4) of a global row into DP registers (zero beyond d), times `mul`
 template <int DP>
 __device__ __forceinline__ void load_row(float (&reg)[DP], const float* src, int d, float mul) {
@@ -171,7 +184,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
   float* drows = d_qkv + (int64_t)n0 * 3 * H + a * d;
   const bool drop = z.p > 0.f;
 
-  // ---- phase A: thread = query i; delta_i = sum_j P_ij dPd_ij, then dQ_i = scale * sum_j P_ij (dPd_ij - delta_i) K_j
+  // ---- phase A: thread = query i; delta_i = sum_j P_ij dPd_ij, then dQ_i = scale * sum_j P_ij (dPd_ij - delta_i) (K_j - K_0)
   stage_pair<DP>(T0, T1, rows + H, ld, rows + 2 * H, ld, n, d, 1.f);
   __syncthreads();
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
@@ -196,7 +209,9 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
       const float P = expf(dot<DP>(q, T0 + j * DP) - L);
       float dp = dot<DP>(g, T1 + j * DP);
       if (drop) dp = mrow[j] ? dp * z.inv_keep : 0.f;
-      axpy<DP>(dq, P * (dp - delta), T0 + j * DP);
+      // sum_j P_ij (dPd_ij - delta_i) is 0 by the definition of delta, so any one row may be taken off every K_j: with K_0, a
+      // graph whose keys are all equal (one node included) gets d_q = 0 exactly instead of a rounding residue times K
+      axpy_diff<DP>(dq, P * (dp - delta), T0 + j * DP, T0);
     }
     store_row<DP>(drows + (int64_t)i * 3 * H, dq, d, z.scale);
     Ls[i] = L;
