@@ -63,6 +63,12 @@ bool trace_launch();
 // still armed — non-NULL after the call means no launch consumed it.  Not used while the stream is being captured.
 void arm_launch_event(hipEvent_t ev);
 hipEvent_t take_launch_event();
+// The same for a call that launches SEVERAL kernels and whose LAST one is the dependency: the event waits aside (no launch takes
+// it) until the callee announces its last launch with next_launch_is_last(), which arms it.  take_last_launch_event() returns (and
+// clears) what neither step consumed — non-NULL means the caller records the event itself.
+void arm_last_launch_event(hipEvent_t ev);
+void next_launch_is_last();
+hipEvent_t take_last_launch_event();
 
 template <typename... KArgs, typename... Args>
 inline void launch(int kind, void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t s,
@@ -150,7 +156,15 @@ bool bn_bwd_fold();                    // node-sized BatchNorm backward: the app
 void set_bn_bwd_fold(int on);
 bool last_block_finalize();
 void set_last_block_finalize(int on);
-void set_linear_knob(int knob, int value);      // the Linear dispatch's knobs 0..7 and 11 (linear_mfma.hip owns the state, linear_plan.h reads it)
+void set_linear_knob(int knob, int value);      // the Linear dispatch's knobs 0..7, 11 and 14 (linear_mfma.hip owns the state, linear_plan.h reads it)
+// plan::PlanKnobs::dual_split for the NEXT esc_linear_bwd_both_bn call of the calling thread (the step engine, around the readout
+// Linear's edge-stream block; esc_tune_set(14, v) is the process-wide form without events): the dX tiles and the dW tiles go out
+// as two launches on the call's stream, the dX launch asking for at least dx_lds bytes of LDS, and dx_done / dw_done become the
+// stop events of those launches (arm_launch_event; recorded behind them where that is not possible).  take_dual_split() clears
+// the request; true: no call consumed it, no event was touched, the caller signals them itself.
+struct DualSplit { hipEvent_t dx_done = nullptr, dw_done = nullptr; int dx_lds = 0; };
+void request_dual_split(const DualSplit& r);
+bool take_dual_split();
 
 // Partials that the last workgroup will read are written with agent-scope (write-through, `sc1`) stores: they
 // become visible device-wide when the store is acknowledged, so the publishing workgroups need NO L2 write-back /

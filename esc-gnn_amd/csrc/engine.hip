@@ -146,6 +146,14 @@ struct LdsFloorGuard {            // occupancy cap for the GEMMs launched while 
 // step 0.995 -> 0.980 ms; bench 1.048 -> 1.031 ms); 60 000 bytes (still co-resident) changes nothing, 82 000 (one node workgroup per
 // CU) costs 50 us, and in the forward (152-workgroup launches) the same request costs 8 us: the backward only.
 static constexpr int kNodeLdsFloorBwd = 66 * 1024;      // bytes
+// The readout Linear's edge-stream block (backward(), lin1's columns [0, L*H)) goes out as two launches, the dX tiles first, and
+// the node chain waits for those only.  The dX launch asks for kReadoutDxLds: one workgroup per CU, and beside it the
+// kNodeLdsFloorBwd of a node tile still fits — two of its 54-KB workgroups on a CU shut the node chain's launches out of that CU
+// and the chain waited for slots (DESIGN.md *Step engine, readout backward*).  Bit 7 of esc_engine_set_side_stream (and bit 6,
+// the schedule of event records) keeps the block one launch with a record behind it: A/B runs.
+static constexpr int kReadoutDxLds = 84 * 1024;         // bytes: 2 x 84 > 160, 84 + 66 <= 160
+static_assert(2 * kReadoutDxLds > 160 * 1024 && kReadoutDxLds + kNodeLdsFloorBwd <= 160 * 1024, "one readout dX tile and one node tile per CU");
+static int g_readout_one_launch = 0;
 struct NodeFloorGuard {
   explicit NodeFloorGuard(int bytes) : on_(bytes > 0) { if (on_) set_node_lds_floor(bytes); }
   ~NodeFloorGuard() { if (on_) set_node_lds_floor(0); }
@@ -198,7 +206,7 @@ static int linear_backward_bn(const Ctx& c, const float* dOut, int64_t ld_dout, 
 // (152 workgroups on 256 CUs) leave idle.  One event per dependency, no host synchronisation.
 struct EdgeStream {
   hipStream_t stream = nullptr;
-  hipEvent_t z_ready = nullptr, joined = nullptr, lin1_fork = nullptr, lin1_rest = nullptr, e_ready[ESC_MAX_LAYERS] = {}, de_ready[ESC_MAX_LAYERS] = {},
+  hipEvent_t z_ready = nullptr, joined = nullptr, lin1_fork = nullptr, lin1_rest = nullptr, lin1_dw = nullptr, e_ready[ESC_MAX_LAYERS] = {}, de_ready[ESC_MAX_LAYERS] = {},
              agg_done[ESC_MAX_LAYERS] = {};
   bool ok = false;
 };
@@ -222,6 +230,7 @@ static EdgeStream& edge_stream() {
     good = good && hipEventCreateWithFlags(&es.joined, hipEventDisableTiming) == hipSuccess;
     good = good && hipEventCreateWithFlags(&es.lin1_fork, hipEventDisableTiming) == hipSuccess;
     good = good && hipEventCreateWithFlags(&es.lin1_rest, hipEventDisableTiming) == hipSuccess;
+    good = good && hipEventCreateWithFlags(&es.lin1_dw, hipEventDisableTiming) == hipSuccess;
     for (int l = 0; l < ESC_MAX_LAYERS; ++l) {
       good = good && hipEventCreateWithFlags(&es.e_ready[l], hipEventDisableTiming) == hipSuccess;
       good = good && hipEventCreateWithFlags(&es.de_ready[l], hipEventDisableTiming) == hipSuccess;
@@ -258,6 +267,13 @@ static int g_plain_events = 0;
 struct ArmedEvent {
   ArmedEvent(hipEvent_t ev, bool on) : on_(on && !g_plain_events) { if (on_) arm_launch_event(ev); }
   ~ArmedEvent() { if (on_) (void)take_launch_event(); }
+  bool on_;
+};
+// ... and on the LAST kernel of a call that launches several (arm_last_launch_event, common.h: the callee announces its last launch)
+struct ArmedLastEvent {
+  ArmedLastEvent(hipEvent_t ev, bool on) : on_(on && !g_plain_events) { if (on_) arm_last_launch_event(ev); }
+  ~ArmedLastEvent() { if (on_) (void)take_last_launch_event(); }
+  bool bound() const { return on_ && take_last_launch_event() == nullptr; }      // once, behind the call
   bool on_;
 };
 static int chain_armed(hipEvent_t ev, const ArmedEvent& arm, hipStream_t src, hipStream_t waiter) {
@@ -661,10 +677,14 @@ static int backward(const Ctx& c, Pending* defer) {
   const bool fuse_l = kBnBwdApplyInGemm && c.act == 1 && !sync_on(c) && y.bst_part != nullptr &&
                       (split_lin1 ? (lin1_ok(0, L * H, nullptr) && lin1_ok(L * H, H, nullptr)) : lin1_ok(0, W, nullptr));
   int64_t last_slots = 0;          // > 0: slots of bst_part that hold the last layer's BatchNorm-backward sums
-  if (fuse_l)
+  bool k0_split = false;           // the edge stream's lin1 block went out as two launches: its dW slabs are ready behind lin1_dw
+  bool fork_bound = false;         // lin1_fork is the stop event of the coefficient call's last launch: no record in front of the H block
+  if (fuse_l) {
+    const ArmedLastEvent arm(es.lin1_fork, split_lin1);
     ESC_TRY(esc_bn_bwd_coef(y.Yl, H, nullptr, 0, y.dAl, H, N, H, y.bl.mean, y.bl.invstd, m->bn_lin1.gamma, m->bn_lin1.beta, 1, y.bl.coef,
                             m->bn_lin1.dgamma, m->bn_lin1.dbeta, y.bn_scratch, c.s));
-  else
+    fork_bound = arm.bound();
+  } else
     ESC_TRY(bn_backward(c, y.Yl, H, nullptr, 0, y.dAl, H, N, y.bl, m->bn_lin1, y.dAl, H, y.bn_scratch));
   // lin1 backward.  The node chain needs d(cat)[:, L*H:] (the last layer's output gradient) at once and the other
   // slices only when the first aggregate backward accumulates into them ~60 us later: with an edge stream the last
@@ -682,12 +702,21 @@ static int backward(const Ctx& c, Pending* defer) {
       return esc_linear_bwd_both_deferred(y.dAl, H, y.cat + col0, W, fa ? y.cat_scale + col0 : nullptr, fa ? y.cat_shift + col0 : nullptr, m->lin1.w + col0, W, N, H, ncols,
                                           y.dcat + col0, W, 0, m->lin1.dw + col0, W, db, slabs, &c.jobs->back(), stream);
     };
-    ESC_TRY(chain(es.lin1_fork, (hipStream_t)c.s, es.stream));
+    if ((!fork_bound && hipEventRecord(es.lin1_fork, (hipStream_t)c.s) != hipSuccess) || hipStreamWaitEvent(es.stream, es.lin1_fork, 0) != hipSuccess) {
+      set_error("esc_engine: stream event failed");
+      return ESC_ELAUNCH;
+    }
+    // the node chain needs this block's dX (lin1_rest, in front of the last layer's aggregate backward) long before anyone needs
+    // its dW slabs (lin1_dw, in front of the node-side slab reduce): two launches, the chain waits for the first only
     {
       const LdsFloorGuard cap(true);
-      ESC_TRY(part(es.stream, 0, K0, nullptr, nullptr));
+      const bool ask = fuse_l && !g_readout_one_launch && !g_plain_events;
+      if (ask) request_dual_split(DualSplit{es.lin1_rest, es.lin1_dw, kReadoutDxLds});
+      const int rc = part(es.stream, 0, K0, nullptr, nullptr);
+      k0_split = !take_dual_split() && ask;                                    // (a pending request: the call did not split)
+      ESC_TRY(rc);
     }
-    if (hipEventRecord(es.lin1_rest, es.stream) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
+    if (!k0_split && hipEventRecord(es.lin1_rest, es.stream) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
     // (the last layer's MLP backward follows at once: does it take the fused form, and can this block leave its sums?)
     const bool leave = fuse_l && fa_l && kBnBwdSumsFromDx && lin1_ok(K0, H, &nl) &&
                        mlp_backward_fused(c, m->conv[L - 1].nn, y.conv[L - 1], y.agg[L - 1], L == 1 ? y.C0 : H, N, y.cat + L * H, W, y.dcat + L * H, W,
@@ -776,6 +805,7 @@ static int backward(const Ctx& c, Pending* defer) {
   mark(PH_EDGE_BWD_DONE, ce.s);
   // node-side reductions first (with an edge stream they overlap its tail), then join, then the edge-side ones
   if (!eps_jobs.empty()) ESC_TRY(esc_reduce_sum_jobs(eps_jobs.data(), (int)eps_jobs.size(), c.s));
+  if (k0_split && hipStreamWaitEvent((hipStream_t)c.s, es.lin1_dw, 0) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
   if (c.jobs && !c.jobs->empty()) ESC_TRY(esc_slab_reduce_jobs(c.jobs->data(), (int)c.jobs->size(), c.s));
   if (es.ok) {
     if (hipEventRecord(es.joined, es.stream) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
@@ -1365,11 +1395,13 @@ int esc_engine_set_two_stream_min_edges(int64_t edges) {
   return ESC_OK;
 }
 
-/* bit 1: the edge pipeline on a second stream; bit 6: every cross-stream dependency an event record (see ArmedEvent).  The other
- * bits selected schedules that have been retired (DESIGN.md *Retired step-engine switches*) and are ignored. */
+/* bit 1: the edge pipeline on a second stream; bit 6: every cross-stream dependency an event record (see ArmedEvent) and the readout
+ * block one launch; bit 7: the readout Linear's edge-stream block one launch (see kReadoutDxLds).  The other bits selected schedules
+ * that have been retired (DESIGN.md *Retired step-engine switches*) and are ignored. */
 int esc_engine_set_side_stream(int on) {
   g_use_edge_stream = (on & 2) != 0;
   g_plain_events = (on & 64) != 0;
+  g_readout_one_launch = (on & 128) != 0;
   return ESC_OK;
 }
 

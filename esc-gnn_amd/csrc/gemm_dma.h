@@ -810,10 +810,23 @@ inline hipError_t launch_gemm(GArgs g, size_t lds_floor, hipStream_t s, int kind
   return hipSuccess;
 }
 
+// split: the dX tiles and the dW tiles as two launches on s, the dX tiles first — a consumer of dX alone waits for half the work.
+// dx_done / dw_done (each may be null) become the stop events of their launches (arm_launch_event), or are recorded behind them
+// where a launch could not take one (a stream being captured).  dx_lds: least dynamic LDS of the dX launch (bytes; an occupancy
+// cap for that launch alone, see PlanKnobs::dual_split).
+struct DualEvents { bool split = false; hipEvent_t dx_done = nullptr, dw_done = nullptr; size_t dx_lds = 0; };
+// one launch of `kern` whose completion signals ev (may be null)
+template <typename K>
+inline hipError_t launch_signalling(hipEvent_t ev, int kind, K kern, unsigned nwg, unsigned nthr, size_t lds, hipStream_t s, const DualArgs& a) {
+  if (ev != nullptr) arm_launch_event(ev);
+  esc::launch(kind, kern, dim3(nwg), dim3(nthr), lds, s, a);
+  return (ev != nullptr && take_launch_event() != nullptr) ? hipEventRecord(ev, s) : hipSuccess;      // (not taken: recorded behind the launch)
+}
 // s_dw: nullptr / s = one launch; another stream = the dX tiles on s and the dW tiles on s_dw (the caller has ordered s_dw
 // behind the operands' producers and keeps the operands untouched until s_dw has drained)
 template <int BM, int BN, int BK, int WM, int WN, int STAGES, int LW, bool PRO, bool BNB = false, bool BSTAT = false>
-inline hipError_t launch_dual(DualArgs a, size_t lds_floor, hipStream_t s, int kind = ESC_K_LINEAR, hipStream_t s_dw = nullptr) {
+inline hipError_t launch_dual(DualArgs a, size_t lds_floor, hipStream_t s, int kind = ESC_K_LINEAR, hipStream_t s_dw = nullptr,
+                              DualEvents ev = DualEvents{}) {
   using CX = Cfg<BM, BN, BK, WM, WN, STAGES, LW, false, true, (BNB ? 4 : 0) | (BSTAT ? 8 : 0), false, false>;
   using CW = Cfg<BM, BN, BK, WM, WN, STAGES, LW, true, true, (PRO ? 2 : 0) | (BNB ? 4 : 0), false, true>;
   auto kern = gemm_dual_kernel<BM, BN, BK, WM, WN, STAGES, LW, PRO, BNB, BSTAT>;
@@ -836,8 +849,19 @@ inline hipError_t launch_dual(DualArgs a, size_t lds_floor, hipStream_t s, int k
     esc::launch(k, kern, dim3(n_dw), dim3(CX::NTHR), lds, s_dw, a);
     return hipSuccess;
   }
-  esc::launch(k, kern, dim3((unsigned)a.n_dx + n_dw), dim3(CX::NTHR), lds, s, a);
-  return hipSuccess;
+  if (ev.split && a.n_dx > 0 && n_dw > 0) {
+    const size_t lds_dx = ev.dx_lds > lds ? ev.dx_lds : lds;
+    e = raise_lds(kern, lds_dx, raised_to);
+    if (e != hipSuccess) return e;
+    e = launch_signalling(ev.dx_done, k, kern, (unsigned)a.n_dx, CX::NTHR, lds_dx, s, a);
+    if (e != hipSuccess) return e;
+    a.b0 = a.n_dx;
+    return launch_signalling(ev.dw_done, k, kern, n_dw, CX::NTHR, lds, s, a);
+  }
+  // (one kind of tile only, or no split: one launch; both events, if any, behind it)
+  e = launch_signalling(ev.dw_done, k, kern, (unsigned)a.n_dx + n_dw, CX::NTHR, lds, s, a);
+  if (e != hipSuccess || ev.dx_done == nullptr) return e;
+  return hipEventRecord(ev.dx_done, s);
 }
 
 }  // namespace dma

@@ -32,8 +32,15 @@ using plan::Plan;
 static plan::PlanKnobs g_plan;
 void set_linear_knob(int knob, int value) {
   if (knob == 11) g_plan.use_dma = value;
+  else if (knob == 14) g_plan.dual_split = value;
   else g_plan.knob[knob] = value;
 }
+// the step engine's request for the calling thread's NEXT esc_linear_bwd_both_bn call (common.h): PlanKnobs::dual_split for that
+// call only, with the events that its two launches signal
+static thread_local DualSplit t_dual_split;
+static thread_local bool t_dual_split_on = false;
+void request_dual_split(const DualSplit& r) { t_dual_split = r; t_dual_split_on = true; }
+bool take_dual_split() { const bool pending = t_dual_split_on; t_dual_split_on = false; t_dual_split = DualSplit{}; return pending; }
 static const plan::PlanKnobs& knobs() {
   static const bool env_read = [] {
     if (getenv("ESC_BIG_MIN_WGS")) g_plan.big_min_wgs = atoll(getenv("ESC_BIG_MIN_WGS"));
@@ -577,7 +584,9 @@ static Plan plan_both_bn(const float* dOut, int64_t ld_dout, const esc_bn_bwd_fu
   plan::NextOps no{};
   if (b) bo = plan::BnOps{b->x, b->ld_x, b->mean, b->invstd, b->scale, b->shift, b->coef, b->relu};
   if (n) no = plan::NextOps{n->partial, n->x, n->ld_x, n->mean, n->invstd, n->scale, n->shift, n->relu};
-  return plan::plan_both_bn(knobs(), Op{dOut, ld_dout}, b ? &bo : nullptr, Op{X, ld_x}, Op{W, ld_w}, Op{dX, ld_dx}, slabs, n ? &no : nullptr,
+  plan::PlanKnobs k = knobs();
+  if (t_dual_split_on) k.dual_split = t_dual_split.dx_lds > 1 ? t_dual_split.dx_lds : 1;
+  return plan::plan_both_bn(k, Op{dOut, ld_dout}, b ? &bo : nullptr, Op{X, ld_x}, Op{W, ld_w}, Op{dX, ld_dx}, slabs, n ? &no : nullptr,
                             M, N, K);
 }
 
@@ -615,6 +624,11 @@ int esc_linear_bwd_both_bn(const float* dOut, int64_t ld_dout, const esc_bn_bwd_
   dma_fill_dx(a.dx, dOut, ld_dout, W, ld_w, M, N, K, dX, ld_dx, accumulate);
   dma_fill_dw(a.dw, dOut, ld_dout, X, ld_x, in_scale, in_shift, M, N, K, slabs, p);
   a.dx.bnb = bd; a.dw.bnb = bd;
+  // two launches (plan::PlanKnobs::dual_split): the engine's request, consumed here, names the events they signal
+  dma::DualEvents ev{};
+  ev.split = p.launches == 2;
+  ev.dx_lds = (size_t)p.dx_lds;
+  if (ev.split && t_dual_split_on) { ev.dx_done = t_dual_split.dx_done; ev.dw_done = t_dual_split.dw_done; (void)take_dual_split(); }
   if (next)
     a.dx.bst = BnStatDev{reinterpret_cast<float2*>(next->partial), next->x, (int)next->ld_x, next->mean, next->invstd, next->scale, next->shift, next->relu};
   hipError_t e;
@@ -623,12 +637,12 @@ int esc_linear_bwd_both_bn(const float* dOut, int64_t ld_dout, const esc_bn_bwd_
   // once the backward's node workgroups keep off the edge GEMMs' CUs altogether)
 #define ESC_T64_2STAGE 64, 64, 32, 2, 2, 2, 2
   if (p.family == plan::F_DMA128_BN) {
-    if (next) e = in_scale ? dma::launch_dual<ESC_T128, true, true, true>(a, 0, s) : dma::launch_dual<ESC_T128, false, true, true>(a, 0, s);
-    else      e = in_scale ? dma::launch_dual<ESC_T128, true, true, false>(a, 0, s) : dma::launch_dual<ESC_T128, false, true, false>(a, 0, s);
+    if (next) e = in_scale ? dma::launch_dual<ESC_T128, true, true, true>(a, 0, s, ESC_K_LINEAR, nullptr, ev) : dma::launch_dual<ESC_T128, false, true, true>(a, 0, s, ESC_K_LINEAR, nullptr, ev);
+    else      e = in_scale ? dma::launch_dual<ESC_T128, true, true, false>(a, 0, s, ESC_K_LINEAR, nullptr, ev) : dma::launch_dual<ESC_T128, false, true, false>(a, 0, s, ESC_K_LINEAR, nullptr, ev);
   } else {
-    if (bn == nullptr) e = in_scale ? dma::launch_dual<ESC_T64, true, false, true>(a, 0, s) : dma::launch_dual<ESC_T64, false, false, true>(a, 0, s);
-    else if (next)     e = in_scale ? dma::launch_dual<ESC_T64_2STAGE, true, true, true>(a, 0, s) : dma::launch_dual<ESC_T64_2STAGE, false, true, true>(a, 0, s);
-    else               e = in_scale ? dma::launch_dual<ESC_T64_2STAGE, true, true, false>(a, 0, s) : dma::launch_dual<ESC_T64_2STAGE, false, true, false>(a, 0, s);
+    if (bn == nullptr) e = in_scale ? dma::launch_dual<ESC_T64, true, false, true>(a, 0, s, ESC_K_LINEAR, nullptr, ev) : dma::launch_dual<ESC_T64, false, false, true>(a, 0, s, ESC_K_LINEAR, nullptr, ev);
+    else if (next)     e = in_scale ? dma::launch_dual<ESC_T64_2STAGE, true, true, true>(a, 0, s, ESC_K_LINEAR, nullptr, ev) : dma::launch_dual<ESC_T64_2STAGE, false, true, true>(a, 0, s, ESC_K_LINEAR, nullptr, ev);
+    else               e = in_scale ? dma::launch_dual<ESC_T64_2STAGE, true, true, false>(a, 0, s, ESC_K_LINEAR, nullptr, ev) : dma::launch_dual<ESC_T64_2STAGE, false, true, false>(a, 0, s, ESC_K_LINEAR, nullptr, ev);
   }
 #undef ESC_T64_2STAGE
   if (dma_check(e, "esc_linear_bwd_both_bn") != hipSuccess) return ESC_ELAUNCH;

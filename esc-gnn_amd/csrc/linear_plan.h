@@ -25,6 +25,7 @@ constexpr int NARROW_DX_N = 16;                                  // linear_narro
 constexpr int64_t PRO_MAX_K = 1280;                              // the LDS-DMA tiles keep the prologue's scale / shift of a whole (padded) K in LDS
 constexpr int64_t BNB_MAX_N = 640;                               // ... and the fused BatchNorm backward's coefficients of N channels
 constexpr int64_t FUSE_FINALIZE_MAX_ROWS = 4096;                 // esc_linear_bn_fwd: last-block finalize up to here (when knob 8 enables it)
+constexpr int LDS_BYTES = 160 * 1024;                            // LDS of a CU
 constexpr int64_t EDGE_ROWS = 8192;                              // "edge-sized": from here the 128-row tiles fill the chip
 
 namespace plan {
@@ -32,7 +33,7 @@ namespace plan {
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// tuning state (esc_tune_set knobs 0..7 and 11, three environment switches): defaults chosen from gemm_bench sweeps on MI355X
+// tuning state (esc_tune_set knobs 0..7, 11 and 14, three environment switches): defaults chosen from gemm_bench sweeps on MI355X
 enum { KNOB_FWD_BIG = 0, KNOB_FWD_SMALL = 1, KNOB_DX_BIG = 2, KNOB_DX_SMALL = 3, KNOB_DW_TILE = 4,
        KNOB_DW_BLOCKS = 5, KNOB_DW_MIN_ROWS = 6, KNOB_DUAL_SMALL = 7, KNOB_COUNT = 8 };
 struct PlanKnobs {
@@ -43,6 +44,11 @@ struct PlanKnobs {
   int tile160 = 0;                        // ESC_TILE160
   int64_t tile160_min_wgs = 150;          // ESC_TILE160_MIN_WGS
   int64_t big_min_wgs = 1LL << 62;        // ESC_BIG_MIN_WGS
+  // knob 14, and the step engine around the readout's edge-stream block (request_dual_split, common.h): the fused LDS-DMA tiles
+  // of esc_linear_bwd_both_bn go out as TWO launches of the same kernel on the same stream, the dX tiles first — whoever waits
+  // for dX only need not wait for the dW slabs.  Same tiles, same slabs, same bits.  A value > 1 is also the least dynamic LDS
+  // (bytes) the dX launch asks for: its workgroups per CU.  Off by default: no default plan changes.
+  int dual_split = 0;
 };
 
 // ---- the r01 tile table: ids are stable (esc_tune_set) --------------------------------------------------------------
@@ -93,6 +99,8 @@ struct Plan {
   BnAfter bn_after = BN_NONE;
   int splits = 0, per_split = 0;   // weight gradient: slabs, reduction rows per slab
   int64_t slab_floats = 0;         // floats of `slabs` written: splits * (N*K + N)
+  int launches = 1;                // both_bn on the LDS-DMA tiles: 2 = the dX tiles and the dW tiles as two launches (PlanKnobs::dual_split)
+  int dx_lds = 0;                  // ... and the least dynamic LDS of the dX launch, bytes (0: what the tile needs)
 };
 
 struct Op { const void* p; int64_t ld; };                  // an operand: base address (for its alignment) and leading dimension
@@ -332,6 +340,7 @@ inline Plan plan_both_bn(const PlanKnobs& k, Op dOut, const BnOps* bn, Op X, Op 
   if (dX.p == nullptr || N > BNB_MAX_N) return p;
   if (!dma_bwd_ok(k, dOut, &X, &W, &dX, slabs, M, N, K)) return p;
   if (next != nullptr && !next_ops_ok(*next, dX, K)) return p;
+  if (k.dual_split > 0) { p.launches = 2; p.dx_lds = k.dual_split > 1 ? (k.dual_split < LDS_BYTES ? k.dual_split : LDS_BYTES) : 0; }
   return dma_wgrad_splits(big ? with_family(p, F_DMA128_BN, 128, 128) : with_family(p, F_DMA64_BN, 64, 64), M, N, K);
 }
 

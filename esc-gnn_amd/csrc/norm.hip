@@ -966,9 +966,11 @@ int esc_bn_eval_coef(const float* running_mean, const float* running_var, const 
 
 // column sums of the BatchNorm backward: coef[c] = (sum g, sum g*xhat) / divisor, dgamma = sum g*xhat, dbeta = sum g
 // (g = dY * act'(.)).  divisor = M for the local BatchNorm; 1 when the sums are still to be all-reduced (SyncBN).
+// ends_call: the reduction's last launch is the caller's last launch (an event armed with arm_last_launch_event binds to it)
 static int bn_bwd_reduce(const BwdArgs& a, const norm::Plan& p, int64_t divisor, float* dgamma, float* dbeta, float2* partial, float2* coef,
-                         hipStream_t s) {
+                         hipStream_t s, bool ends_call = false) {
   const bool fused = p.reduce == norm::R_FUSED;
+  if (fused && ends_call) next_launch_is_last();
   if (p.reduce == norm::R_SCALAR) {
     esc::launch(ESC_K_NORM, bn_bwd_partial_kernel, dim(p.grid[0]), dim3(256), 0, s, a.X, a.ld_x, a.Y, a.ld_y, a.dY, a.ld_dy, (int)a.M, (int)a.C, a.mean,
                 a.invstd, a.relu, a.gamma, a.beta, partial);
@@ -979,6 +981,7 @@ static int bn_bwd_reduce(const BwdArgs& a, const norm::Plan& p, int64_t divisor,
   }
   if (!fused) {
     ESC_CHECK_LAUNCH("esc_bn_bwd.partial");
+    if (ends_call) next_launch_is_last();
     launch_bwd_finalize(partial, divisor, a.C, p.slots, dgamma, dbeta, coef, s);
   }
   ESC_CHECK_LAUNCH("esc_bn_bwd.finalize");
@@ -1092,7 +1095,7 @@ int esc_bn_bwd_coef(const float* X, int64_t ld_x, const float* Y, int64_t ld_y, 
   ESC_REQUIRE(act_code_ok(relu), "esc_bn_bwd_coef: relu must be 0 (none), 1 (ReLU) or 2 (ELU), got %d", relu);
   const BwdArgs a{X, ld_x, Y, ld_y, dY, ld_dy, M, C, mean, invstd, gamma, beta, relu};
   const norm::Plan p = norm::plan_bwd_reduce(knobs(), ops_of(a, nullptr, 0, scratch, nullptr, nullptr, nullptr), M, C, true, true);
-  return bn_bwd_reduce(a, p, M, dgamma, dbeta, (float2*)scratch, (float2*)coef, (hipStream_t)stream);
+  return bn_bwd_reduce(a, p, M, dgamma, dbeta, (float2*)scratch, (float2*)coef, (hipStream_t)stream, true);
 }
 
 int esc_bn_bwd_coef_from_partials(const float* partial, int64_t slots, int64_t M, int64_t C, float* coef, float* dgamma,

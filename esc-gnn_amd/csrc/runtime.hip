@@ -81,6 +81,16 @@ void set_edge_lds_floor(int bytes) { g_edge_lds_floor = bytes < 0 ? 0 : bytes; }
 static thread_local hipEvent_t g_launch_event = nullptr;
 void arm_launch_event(hipEvent_t ev) { g_launch_event = ev; }
 hipEvent_t take_launch_event() { hipEvent_t ev = g_launch_event; g_launch_event = nullptr; return ev; }
+static thread_local hipEvent_t g_last_launch_event = nullptr;
+void arm_last_launch_event(hipEvent_t ev) { g_last_launch_event = ev; }
+void next_launch_is_last() {
+  if (g_last_launch_event != nullptr) { g_launch_event = g_last_launch_event; g_last_launch_event = nullptr; }
+}
+hipEvent_t take_last_launch_event() {
+  hipEvent_t ev = g_last_launch_event != nullptr ? g_last_launch_event : g_launch_event;      // still aside, or armed and not launched
+  g_last_launch_event = nullptr; g_launch_event = nullptr;
+  return ev;
+}
 
 static const bool g_trace_launch = getenv("ESC_TRACE_LAUNCH") != nullptr && atoi(getenv("ESC_TRACE_LAUNCH")) != 0;
 bool trace_launch() { return g_trace_launch; }
@@ -120,13 +130,14 @@ extern "C" {
 //   8     BatchNorm finalize in the GEMM's last workgroup       9   workgroups per column block of the BatchNorm reductions
 //   10    dynamic-LDS floor of the edge stream's GEMMs          11  kernel-family mask of the Linear dispatch (plan::PlanKnobs::use_dma)
 //   12    BatchNorm backward: the apply kernel folds the partials     13  BatchNorm backward in one launch
+//   14    esc_linear_bwd_both_bn: dX tiles and dW tiles as two launches, value > 1 = LDS request of the dX launch (plan::PlanKnobs::dual_split)
 int esc_tune_set(int knob, int value) {
   if (knob == 8) { esc::set_last_block_finalize(value); return ESC_OK; }
   if (knob == 9) { esc::set_norm_rowblock_cap(value); return ESC_OK; }
   if (knob == 12) { esc::set_bn_bwd_fold(value); return ESC_OK; }
   if (knob == 13) { esc::set_bn_bwd_one_launch(value); return ESC_OK; }
   if (knob == 10) { esc::set_edge_lds_floor(value); return ESC_OK; }
-  ESC_REQUIRE(knob == 11 || (knob >= 0 && knob < esc::plan::KNOB_COUNT), "esc_tune_set: unknown knob %d", knob);
+  ESC_REQUIRE(knob == 11 || knob == 14 || (knob >= 0 && knob < esc::plan::KNOB_COUNT), "esc_tune_set: unknown knob %d", knob);
   esc::set_linear_knob(knob, value);
   return ESC_OK;
 }

@@ -266,7 +266,11 @@ int esc_linear_fwd_fold(const float* X, int64_t ld_x, const float* W, int64_t ld
  * knob 11 (default 15): bit mask of the LDS-DMA GEMM family (gemm_dma.h) — bit 0 forward, 1 gradients, 2 the tiny-dimension
  * kernels (linear_small.h), 3 the 64x32 narrow-output tile; 0 = every GEMM on the r01 register-staged tiles (bisecting).
  * knob 12 (default 0): node-sized BatchNorm backward with the finalize folded into the apply kernel (measured 7 % slower).
- * knob 13 (default 0): node-sized BatchNorm backward as ONE launch with a grid barrier (measured 9 % slower). */
+ * knob 13 (default 0): node-sized BatchNorm backward as ONE launch with a grid barrier (measured 9 % slower).
+ * knob 14 (default 0): esc_linear_bwd_both_bn on the fused LDS-DMA tiles as TWO launches of the same kernel on the call's stream,
+ * the dX tiles first, then the dW tiles; a value > 1 is also the least dynamic LDS in bytes that the dX launch asks for (its
+ * workgroups per CU).  Same tiles, slabs and results.  The counting engine asks for this form itself, for the readout Linear's
+ * edge-stream block only (esc_engine_set_side_stream bit 7); the knob is the process-wide form for tests. */
 int esc_tune_set(int knob, int value);
 int esc_debug_gemm_occupancy(int tile_id);   /* resident workgroups/CU the runtime predicts (diagnostics) */
 /* dX[M,K] = dY[M,N] * W[N,K]  (accumulate!=0: dX += ...) */
@@ -509,7 +513,10 @@ typedef struct esc_batch_t {
  * e_0 and e_1 .. e_{L-1}, the head in front of the loss, d_e of every layer's aggregate backward).  Clear: the event is the stop
  * event of that kernel's launch, so nothing is queued behind the kernel on the producing stream.  Set: hipEventRecord behind the
  * launch, as before; its marker packet holds up the producer's next kernel (about 16 us per flagship step over all of them).
- * Same kernels, arguments and results either way (A/B runs: `bench.py --streams 66`). */
+ * Same kernels, arguments and results either way (A/B runs: `bench.py --streams 66`).  Set also implies bit 7.
+ * bit 7 (value 128, default clear): the edge-stream block of the readout Linear's backward (lin1's columns of the layers that are
+ * not the last).  Clear: two launches of its fused kernel, the dX tiles first at one workgroup per CU, and the node chain waits for
+ * those only.  Set: one launch with an event record behind it, as before.  Same tiles and results either way. */
 int esc_engine_set_side_stream(int on);
 /* all three engines: smallest batch (in edges) whose edge pipeline runs on the second stream (default 12 000; 0 = always).
  * Smaller batches — ZINC at bs 128, the 16-graph per-rank slices of a strong-scaling run of the counting model — are launch-latency
