@@ -104,25 +104,7 @@ __global__ __launch_bounds__(64) void mh_fill_kernel(const int64_t* __restrict__
   }
 }
 
-static int mh_check(const char* fn, const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* src, const int64_t* dst,
-                    int64_t G, int64_t total_nodes, int64_t total_edges, int64_t max_nodes, int k) {
-  ESC_REQUIRE(node_ptr && edge_ptr, "%s: null pointer", fn);
-  ESC_REQUIRE((src && dst) || total_edges == 0, "%s: null edge arrays", fn);
-  ESC_REQUIRE(G > 0 && G < (1LL << 31), "%s: bad graph count %ld", fn, (long)G);
-  if (k < 1 || k > MH_K_MAX) {
-    set_error("%s: k=%d outside 1..%d", fn, k, MH_K_MAX);
-    return ESC_ERANGE;
-  }
-  if (max_nodes < 1 || max_nodes > MH_MAX_NODES) {
-    set_error("%s: max_nodes=%ld outside 1..%d", fn, (long)max_nodes, MH_MAX_NODES);
-    return ESC_ERANGE;
-  }
-  if (total_nodes < 0 || total_edges < 0 || total_nodes >= (1LL << 31) - 1 || total_edges >= (1LL << 31) - 1) {
-    set_error("%s: %ld nodes / %ld edges: totals must stay below 2^31", fn, (long)total_nodes, (long)total_edges);
-    return ESC_ERANGE;
-  }
-  return ESC_OK;
-}
+static const ExpandLimits MH_LIMITS = {"k", MH_K_MAX, MH_MAX_NODES, "", false};
 
 }  // namespace esc
 
@@ -133,7 +115,7 @@ extern "C" {
 int esc_multihop_count(const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* src, const int64_t* dst, int64_t G,
                        int64_t total_nodes, int64_t total_edges, int64_t max_nodes, int k, int64_t* pair_ptr, int64_t* d1_ptr,
                        int64_t* dist_count, int32_t* status, void* stream) {
-  const int rc = mh_check("esc_multihop_count", node_ptr, edge_ptr, src, dst, G, total_nodes, total_edges, max_nodes, k);
+  const int rc = expand_check(MH_LIMITS, "esc_multihop_count", node_ptr, edge_ptr, src, dst, G, total_nodes, total_edges, max_nodes, k);
   if (rc) return rc;
   ESC_REQUIRE(pair_ptr && d1_ptr && dist_count && status, "esc_multihop_count: null output");
   hipStream_t s = (hipStream_t)stream;
@@ -158,7 +140,7 @@ int esc_multihop_fill(const int64_t* node_ptr, const int64_t* edge_ptr, const in
                       int64_t total_nodes, int64_t total_edges, int64_t max_nodes, int k, const int64_t* pair_ptr,
                       const int64_t* d1_ptr, int64_t total_pairs, int64_t* row, int64_t* col, int64_t* distance, int32_t* meta,
                       int32_t* status, void* stream) {
-  const int rc = mh_check("esc_multihop_fill", node_ptr, edge_ptr, src, dst, G, total_nodes, total_edges, max_nodes, k);
+  const int rc = expand_check(MH_LIMITS, "esc_multihop_fill", node_ptr, edge_ptr, src, dst, G, total_nodes, total_edges, max_nodes, k);
   if (rc) return rc;
   ESC_REQUIRE(pair_ptr && d1_ptr && status, "esc_multihop_fill: null pointer");
   if (total_pairs < 0 || total_pairs >= (1LL << 31) - 1) {

@@ -1,6 +1,7 @@
 // subgraph_bfs.h — what one root's wave of csrc/subgraphs.hip knows and does, shared with csrc/multihop.hip: the graph of a
-// root, the level-synchronous BFS in LDS, and the host launchers of the per-graph validation and of the two-array scan
-// (the kernels themselves live in subgraphs.hip: a kernel has one translation unit).  Moved here unchanged.
+// root, the level-synchronous BFS in LDS (moved here unchanged), the argument check that every count / fill entry of both
+// files opens with, and the host launchers of the per-graph validation and of the two-array scan (the kernels themselves
+// live in subgraphs.hip: a kernel has one translation unit).
 #pragma once
 #include "common.h"
 
@@ -55,6 +56,39 @@ __device__ __forceinline__ void sub_bfs(const SubRoot& q, const int64_t* __restr
     __syncthreads();
     if (!__any(grew)) break;
   }
+}
+
+// ---- host side: what every count / fill entry of the expansions opens with ---------------------------------------------------
+struct ExpandLimits {
+  const char* depth_name;               // "h" | "k"
+  int depth_max, max_nodes;
+  const char* why;                      // the clause behind "outside 1..depth_max", or ""
+  bool ranges_first;                    // the second-root entries test their ranges before the pointers
+};
+
+inline int expand_check(const ExpandLimits& L, const char* fn, const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* src,
+                        const int64_t* dst, int64_t G, int64_t total_nodes, int64_t total_edges, int64_t max_nodes, int depth) {
+  for (int pass = 0; pass < 2; ++pass) {                    // the ranges and the pointers, in the order the entry has always had
+    if ((pass == 0) == L.ranges_first) {
+      if (depth < 1 || depth > L.depth_max) {
+        set_error("%s: %s=%d outside 1..%d%s", fn, L.depth_name, depth, L.depth_max, L.why);
+        return ESC_ERANGE;
+      }
+      if (max_nodes < 1 || max_nodes > L.max_nodes) {
+        set_error("%s: max_nodes=%ld outside 1..%d", fn, (long)max_nodes, L.max_nodes);
+        return ESC_ERANGE;
+      }
+    } else {
+      ESC_REQUIRE(node_ptr && edge_ptr, "%s: null pointer", fn);
+      ESC_REQUIRE((src && dst) || total_edges == 0, "%s: null edge arrays", fn);
+      ESC_REQUIRE(G > 0 && G < (1LL << 31), "%s: bad graph count %ld", fn, (long)G);
+    }
+  }
+  if (total_nodes < 0 || total_edges < 0 || total_nodes >= (1LL << 31) - 1 || total_edges >= (1LL << 31) - 1) {
+    set_error("%s: %ld nodes / %ld edges: totals must stay below 2^31", fn, (long)total_nodes, (long)total_edges);
+    return ESC_ERANGE;
+  }
+  return ESC_OK;
 }
 
 // sub_validate_kernel (one wave per graph): status[g] = ESC_ERANGE for a graph whose ranges do not tile the arrays, of more

@@ -30,6 +30,8 @@
 namespace esc {
 
 constexpr int SUB_RD_MAX = 96;          // largest subgraph whose two m x m fp64 matrices fit LDS (147 KB); LDS_SUBGRAPH of features.hip
+constexpr int SUB_MAX_NODES = 4096;     // 7 B of LDS tables per node (see sub_fill_lds)
+constexpr int SUB_H_MAX = 98;           // z = hop + 1 and the model's z tables have 100 rows
 // (SUB_INF, sub_find_segment, SubRoot, sub_locate and sub_bfs: subgraph_bfs.h, shared with multihop.hip)
 
 // ---- per-graph validation (one wave per graph): ids inside the graph, graph inside the LDS tables -----------------
@@ -261,24 +263,22 @@ static size_t sub_fill_lds(int n_cap, int ld, bool rd) {
   return with_rd > plain ? with_rd : plain;
 }
 
-static int sub_check(const char* fn, const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* src, const int64_t* dst,
-                     int64_t G, int64_t total_nodes, int64_t total_edges, int64_t max_nodes, int h) {
-  ESC_REQUIRE(node_ptr && edge_ptr, "%s: null pointer", fn);
-  ESC_REQUIRE((src && dst) || total_edges == 0, "%s: null edge arrays", fn);
-  ESC_REQUIRE(G > 0 && G < (1LL << 31), "%s: bad graph count %ld", fn, (long)G);
-  if (h < 1 || h > 98) {
-    set_error("%s: h=%d outside 1..98 (the model's z tables have 100 rows and z = hop + 1)", fn, h);
-    return ESC_ERANGE;
-  }
-  if (max_nodes < 1 || max_nodes > 4096) {
-    set_error("%s: max_nodes=%ld outside 1..4096", fn, (long)max_nodes);
-    return ESC_ERANGE;
-  }
-  if (total_nodes < 0 || total_edges < 0 || total_nodes >= (1LL << 31) - 1 || total_edges >= (1LL << 31) - 1) {
-    set_error("%s: %ld nodes / %ld edges: totals must stay below 2^31", fn, (long)total_nodes, (long)total_edges);
-    return ESC_ERANGE;
-  }
-  return ESC_OK;
+static const ExpandLimits SUB_LIMITS = {"h", SUB_H_MAX, SUB_MAX_NODES, " (the model's z tables have 100 rows and z = hop + 1)", false};
+
+// ---- what the fill entries of both rooted expansions derive from their arguments -------------------------------------------
+static bool sub_totals_ok(int64_t total_sub_nodes, int64_t total_sub_edges) {
+  return total_sub_nodes >= 0 && total_sub_edges >= 0 && total_sub_nodes < (1LL << 31) - 1 && total_sub_edges < (1LL << 31) - 1;
+}
+static int sub_n_cap(int64_t max_nodes) { return (int)((max_nodes + 3) & ~3LL); }
+static int sub_rd_ld(int64_t max_nodes) {
+  const int m_even = (int)((max_nodes + 1) & ~1LL);
+  return m_even < SUB_RD_MAX ? m_even : SUB_RD_MAX;
+}
+// one wave per root; the rd variant may need more dynamic LDS than the default 64 KB
+template <typename FillArgs>
+static void sub_launch_fill(void (*with_rd)(FillArgs), void (*without_rd)(FillArgs), int use_rd, size_t lds, hipStream_t s, const FillArgs& a) {
+  if (use_rd && lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)with_rd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  esc::launch(ESC_K_FEATURES, use_rd ? with_rd : without_rd, dim3((unsigned)a.total_nodes), dim3(64), lds, s, a);
 }
 
 // the two kernels above that multihop.hip launches as well (subgraph_bfs.h)
@@ -534,18 +534,38 @@ static size_t sub2_fill_lds(int n_cap, int ld, bool rd) {
   return rd ? tables + ((size_t)2 * ld * ld + 2 * (size_t)ld + 8) * 8 : tables;
 }
 
-static int sub2_check(const char* fn, const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* src, const int64_t* dst,
-                      int64_t G, int64_t total_nodes, int64_t total_edges, int64_t max_nodes, int h) {
-  if (h < 1 || h > SUB2_H_MAX) {
-    set_error("%s: h=%d outside 1..%d (the model's z tables have 100 rows and the second root's labels reach 2h + 5)", fn, h,
-              SUB2_H_MAX);
-    return ESC_ERANGE;
+static const ExpandLimits SUB2_LIMITS = {"h", SUB2_H_MAX, SUB2_MAX_NODES,
+                                         " (the model's z tables have 100 rows and the second root's labels reach 2h + 5)", true};
+
+// ---- the count pass of both rooted expansions: validation, one wave per root (LDS: hop[n_cap]), the scans.  sub2_ptr: the
+// second-root expansion's third count, or NULL ---------------------------------------------------------------------------------
+static int sub_launched(const char* fn, const char* step) {
+  const hipError_t err = hipGetLastError();
+  if (err == hipSuccess) return ESC_OK;
+  set_error("%s.%s: launch failed: %s", fn, step, hipGetErrorString(err));
+  return ESC_ELAUNCH;
+}
+
+static int sub_count_pass(const char* fn, const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* src, const int64_t* dst,
+                          int64_t G, int64_t total_nodes, int64_t total_edges, int64_t max_nodes, int h, int64_t* sub_node_ptr,
+                          int64_t* sub_edge_ptr, int64_t* sub2_ptr, int32_t* status, hipStream_t s) {
+  sub_launch_validate(node_ptr, edge_ptr, src, dst, G, total_nodes, total_edges, max_nodes, status, s);
+  if (const int rc = sub_launched(fn, "validate")) return rc;
+  if (total_nodes > 0) {
+    const dim3 grid((unsigned)total_nodes);
+    const size_t n_cap = (size_t)sub_n_cap(max_nodes);
+    if (sub2_ptr) {
+      esc::launch(ESC_K_FEATURES, sub2_count_kernel, grid, dim3(64), n_cap, s, node_ptr, edge_ptr, src, dst, (int)G, total_nodes, h,
+                  (const int*)status, sub_node_ptr, sub_edge_ptr, sub2_ptr);
+    } else {
+      esc::launch(ESC_K_FEATURES, sub_count_kernel, grid, dim3(64), n_cap, s, node_ptr, edge_ptr, src, dst, (int)G, total_nodes, h,
+                  (const int*)status, sub_node_ptr, sub_edge_ptr);
+    }
+    if (const int rc = sub_launched(fn, "count")) return rc;
   }
-  if (max_nodes < 1 || max_nodes > SUB2_MAX_NODES) {
-    set_error("%s: max_nodes=%ld outside 1..%d", fn, (long)max_nodes, SUB2_MAX_NODES);
-    return ESC_ERANGE;
-  }
-  return sub_check(fn, node_ptr, edge_ptr, src, dst, G, total_nodes, total_edges, max_nodes, h);
+  sub_launch_scan(sub_node_ptr, sub_edge_ptr, total_nodes, s);
+  if (sub2_ptr) esc::launch(ESC_K_FEATURES, sub_scan_kernel, dim3(1), dim3(1024), 0, s, sub2_ptr, sub2_ptr, total_nodes);
+  return sub_launched(fn, "scan");
 }
 
 }  // namespace esc
@@ -557,22 +577,11 @@ extern "C" {
 int esc_subgraph_count(const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* src, const int64_t* dst, int64_t G,
                        int64_t total_nodes, int64_t total_edges, int64_t max_nodes, int h, int64_t* sub_node_ptr,
                        int64_t* sub_edge_ptr, int32_t* status, void* stream) {
-  const int rc = sub_check("esc_subgraph_count", node_ptr, edge_ptr, src, dst, G, total_nodes, total_edges, max_nodes, h);
+  const int rc = expand_check(SUB_LIMITS, "esc_subgraph_count", node_ptr, edge_ptr, src, dst, G, total_nodes, total_edges, max_nodes, h);
   if (rc) return rc;
   ESC_REQUIRE(sub_node_ptr && sub_edge_ptr && status, "esc_subgraph_count: null output");
-  hipStream_t s = (hipStream_t)stream;
-  esc::launch(ESC_K_FEATURES, sub_validate_kernel, dim3((unsigned)G), dim3(64), 0, s, node_ptr, edge_ptr, src, dst, (int)G,
-              total_nodes, total_edges, max_nodes, status);
-  ESC_CHECK_LAUNCH("esc_subgraph_count.validate");
-  if (total_nodes > 0) {
-    const int n_cap = (int)((max_nodes + 3) & ~3LL);
-    esc::launch(ESC_K_FEATURES, sub_count_kernel, dim3((unsigned)total_nodes), dim3(64), (size_t)n_cap, s, node_ptr, edge_ptr,
-                src, dst, (int)G, total_nodes, h, (const int*)status, sub_node_ptr, sub_edge_ptr);
-    ESC_CHECK_LAUNCH("esc_subgraph_count.count");
-  }
-  esc::launch(ESC_K_FEATURES, sub_scan_kernel, dim3(2), dim3(1024), 0, s, sub_node_ptr, sub_edge_ptr, total_nodes);
-  ESC_CHECK_LAUNCH("esc_subgraph_count.scan");
-  return ESC_OK;
+  return sub_count_pass("esc_subgraph_count", node_ptr, edge_ptr, src, dst, G, total_nodes, total_edges, max_nodes, h, sub_node_ptr,
+                        sub_edge_ptr, nullptr, status, (hipStream_t)stream);
 }
 
 int esc_subgraph_fill(const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* src, const int64_t* dst, int64_t G,
@@ -581,10 +590,10 @@ int esc_subgraph_fill(const int64_t* node_ptr, const int64_t* edge_ptr, const in
                       int64_t* orig_node, int64_t* hop_label, int64_t* hop_paths, int64_t* node_to_subgraph,
                       int64_t* node_to_graph, int64_t* sub_src, int64_t* sub_dst, int64_t* orig_edge, float* rd,
                       int32_t* status, void* stream) {
-  const int rc = sub_check("esc_subgraph_fill", node_ptr, edge_ptr, src, dst, G, total_nodes, total_edges, max_nodes, h);
+  const int rc = expand_check(SUB_LIMITS, "esc_subgraph_fill", node_ptr, edge_ptr, src, dst, G, total_nodes, total_edges, max_nodes, h);
   if (rc) return rc;
   ESC_REQUIRE(sub_node_ptr && sub_edge_ptr && status, "esc_subgraph_fill: null pointer");
-  if (total_sub_nodes < 0 || total_sub_edges < 0 || total_sub_nodes >= (1LL << 31) - 1 || total_sub_edges >= (1LL << 31) - 1) {
+  if (!sub_totals_ok(total_sub_nodes, total_sub_edges)) {
     set_error("esc_subgraph_fill: %ld sub-nodes / %ld sub-edges: totals must stay below 2^31", (long)total_sub_nodes,
               (long)total_sub_edges);
     return ESC_ERANGE;
@@ -593,22 +602,15 @@ int esc_subgraph_fill(const int64_t* node_ptr, const int64_t* edge_ptr, const in
   ESC_REQUIRE(orig_node && hop_label && hop_paths && node_to_subgraph && node_to_graph, "esc_subgraph_fill: null node output");
   ESC_REQUIRE((sub_src && sub_dst && orig_edge) || total_sub_edges == 0, "esc_subgraph_fill: null edge output");
   ESC_REQUIRE(!use_rd || rd, "esc_subgraph_fill: use_rd without an rd output");
-  hipStream_t s = (hipStream_t)stream;
   SubFillArgs a{};
   a.node_ptr = node_ptr; a.edge_ptr = edge_ptr; a.src = src; a.dst = dst; a.sub_node_ptr = sub_node_ptr; a.sub_edge_ptr = sub_edge_ptr;
   a.orig_node = orig_node; a.hop_label = hop_label; a.hop_paths = hop_paths; a.node_to_subgraph = node_to_subgraph;
   a.node_to_graph = node_to_graph; a.sub_src = sub_src; a.sub_dst = sub_dst; a.orig_edge = orig_edge; a.rd = rd; a.status = status;
-  a.total_nodes = total_nodes; a.total_sub_nodes = total_sub_nodes; a.total_sub_edges = total_sub_edges; a.G = (int)G; a.h = h; a.n_cap = (int)((max_nodes + 3) & ~3LL);
-  const int m_even = (int)((max_nodes + 1) & ~1LL);
-  a.ld = m_even < SUB_RD_MAX ? m_even : SUB_RD_MAX;
-  if (use_rd) {
-    const size_t lds = sub_fill_lds(a.n_cap, a.ld, true);
-    ESC_REQUIRE(lds <= 160 * 1024, "esc_subgraph_fill: rd working set %zu B exceeds LDS", lds);
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)sub_fill_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    esc::launch(ESC_K_FEATURES, sub_fill_kernel<true>, dim3((unsigned)total_nodes), dim3(64), lds, s, a);
-  } else {
-    esc::launch(ESC_K_FEATURES, sub_fill_kernel<false>, dim3((unsigned)total_nodes), dim3(64), sub_fill_lds(a.n_cap, a.ld, false), s, a);
-  }
+  a.total_nodes = total_nodes; a.total_sub_nodes = total_sub_nodes; a.total_sub_edges = total_sub_edges; a.G = (int)G; a.h = h;
+  a.n_cap = sub_n_cap(max_nodes); a.ld = sub_rd_ld(max_nodes);
+  const size_t lds = sub_fill_lds(a.n_cap, a.ld, use_rd != 0);
+  ESC_REQUIRE(!use_rd || lds <= 160 * 1024, "esc_subgraph_fill: rd working set %zu B exceeds LDS", lds);
+  sub_launch_fill(sub_fill_kernel<true>, sub_fill_kernel<false>, use_rd, lds, (hipStream_t)stream, a);
   ESC_CHECK_LAUNCH("esc_subgraph_fill.fill");
   return ESC_OK;
 }
@@ -616,23 +618,11 @@ int esc_subgraph_fill(const int64_t* node_ptr, const int64_t* edge_ptr, const in
 int esc_subgraph2_count(const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* src, const int64_t* dst, int64_t G,
                         int64_t total_nodes, int64_t total_edges, int64_t max_nodes, int h, int64_t* sub_node_ptr,
                         int64_t* sub_edge_ptr, int64_t* sub2_ptr, int32_t* status, void* stream) {
-  const int rc = sub2_check("esc_subgraph2_count", node_ptr, edge_ptr, src, dst, G, total_nodes, total_edges, max_nodes, h);
+  const int rc = expand_check(SUB2_LIMITS, "esc_subgraph2_count", node_ptr, edge_ptr, src, dst, G, total_nodes, total_edges, max_nodes, h);
   if (rc) return rc;
   ESC_REQUIRE(sub_node_ptr && sub_edge_ptr && sub2_ptr && status, "esc_subgraph2_count: null output");
-  hipStream_t s = (hipStream_t)stream;
-  esc::launch(ESC_K_FEATURES, sub_validate_kernel, dim3((unsigned)G), dim3(64), 0, s, node_ptr, edge_ptr, src, dst, (int)G,
-              total_nodes, total_edges, max_nodes, status);
-  ESC_CHECK_LAUNCH("esc_subgraph2_count.validate");
-  if (total_nodes > 0) {
-    const int n_cap = (int)((max_nodes + 3) & ~3LL);
-    esc::launch(ESC_K_FEATURES, sub2_count_kernel, dim3((unsigned)total_nodes), dim3(64), (size_t)n_cap, s, node_ptr, edge_ptr,
-                src, dst, (int)G, total_nodes, h, (const int*)status, sub_node_ptr, sub_edge_ptr, sub2_ptr);
-    ESC_CHECK_LAUNCH("esc_subgraph2_count.count");
-  }
-  esc::launch(ESC_K_FEATURES, sub_scan_kernel, dim3(2), dim3(1024), 0, s, sub_node_ptr, sub_edge_ptr, total_nodes);
-  esc::launch(ESC_K_FEATURES, sub_scan_kernel, dim3(1), dim3(1024), 0, s, sub2_ptr, sub2_ptr, total_nodes);
-  ESC_CHECK_LAUNCH("esc_subgraph2_count.scan");
-  return ESC_OK;
+  return sub_count_pass("esc_subgraph2_count", node_ptr, edge_ptr, src, dst, G, total_nodes, total_edges, max_nodes, h, sub_node_ptr,
+                        sub_edge_ptr, sub2_ptr, status, (hipStream_t)stream);
 }
 
 int esc_subgraph2_fill(const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* src, const int64_t* dst, int64_t G,
@@ -642,11 +632,10 @@ int esc_subgraph2_fill(const int64_t* node_ptr, const int64_t* edge_ptr, const i
                        int64_t* node_to_graph, int64_t* sub_src, int64_t* sub_dst, int64_t* orig_edge,
                        int64_t* subgraph2_to_subgraph, int64_t* center_idx, int64_t* s2_node_ptr, float* rd, int32_t* status,
                        void* stream) {
-  const int rc = sub2_check("esc_subgraph2_fill", node_ptr, edge_ptr, src, dst, G, total_nodes, total_edges, max_nodes, h);
+  const int rc = expand_check(SUB2_LIMITS, "esc_subgraph2_fill", node_ptr, edge_ptr, src, dst, G, total_nodes, total_edges, max_nodes, h);
   if (rc) return rc;
   ESC_REQUIRE(sub_node_ptr && sub_edge_ptr && sub2_ptr && status && s2_node_ptr, "esc_subgraph2_fill: null pointer");
-  if (total_sub_nodes < 0 || total_sub_edges < 0 || total_subgraphs2 < 0 || total_sub_nodes >= (1LL << 31) - 1 ||
-      total_sub_edges >= (1LL << 31) - 1 || total_subgraphs2 > total_sub_nodes) {
+  if (!sub_totals_ok(total_sub_nodes, total_sub_edges) || total_subgraphs2 < 0 || total_subgraphs2 > total_sub_nodes) {
     set_error("esc_subgraph2_fill: %ld sub-nodes / %ld sub-edges / %ld subgraph2s: totals must stay below 2^31",
               (long)total_sub_nodes, (long)total_sub_edges, (long)total_subgraphs2);
     return ESC_ERANGE;
@@ -656,7 +645,6 @@ int esc_subgraph2_fill(const int64_t* node_ptr, const int64_t* edge_ptr, const i
               "esc_subgraph2_fill: null node output");
   ESC_REQUIRE((sub_src && sub_dst && orig_edge) || total_sub_edges == 0, "esc_subgraph2_fill: null edge output");
   ESC_REQUIRE(!use_rd || rd, "esc_subgraph2_fill: use_rd without an rd output");
-  hipStream_t s = (hipStream_t)stream;
   Sub2FillArgs a{};
   a.node_ptr = node_ptr; a.edge_ptr = edge_ptr; a.src = src; a.dst = dst;
   a.sub_node_ptr = sub_node_ptr; a.sub_edge_ptr = sub_edge_ptr; a.sub2_ptr = sub2_ptr;
@@ -664,17 +652,11 @@ int esc_subgraph2_fill(const int64_t* node_ptr, const int64_t* edge_ptr, const i
   a.sub_src = sub_src; a.sub_dst = sub_dst; a.orig_edge = orig_edge; a.subgraph2_to_subgraph = subgraph2_to_subgraph;
   a.center_idx = center_idx; a.s2_node_ptr = s2_node_ptr; a.rd = rd; a.status = status;
   a.total_nodes = total_nodes; a.total_sub_nodes = total_sub_nodes; a.total_sub_edges = total_sub_edges; a.total_s2 = total_subgraphs2;
-  a.G = (int)G; a.h = h; a.n_cap = (int)((max_nodes + 3) & ~3LL);
-  const int m_even = (int)((max_nodes + 1) & ~1LL);
-  a.ld = m_even < SUB_RD_MAX ? m_even : SUB_RD_MAX;
+  a.G = (int)G; a.h = h;
+  a.n_cap = sub_n_cap(max_nodes); a.ld = sub_rd_ld(max_nodes);
   const size_t lds = sub2_fill_lds(a.n_cap, a.ld, use_rd != 0);
   ESC_REQUIRE(lds + 16 <= 160 * 1024, "esc_subgraph2_fill: working set %zu B exceeds LDS", lds);
-  if (use_rd) {
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)sub2_fill_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    esc::launch(ESC_K_FEATURES, sub2_fill_kernel<true>, dim3((unsigned)total_nodes), dim3(64), lds, s, a);
-  } else {
-    esc::launch(ESC_K_FEATURES, sub2_fill_kernel<false>, dim3((unsigned)total_nodes), dim3(64), lds, s, a);
-  }
+  sub_launch_fill(sub2_fill_kernel<true>, sub2_fill_kernel<false>, use_rd, lds, (hipStream_t)stream, a);
   ESC_CHECK_LAUNCH("esc_subgraph2_fill.fill");
   return ESC_OK;
 }

@@ -110,6 +110,13 @@ def sharded_batches(store, batch_size, ctx, shuffle, generator=None):
         yield store.collate(ids), n_global
 
 
+def expanded_batches(store, batches, *extra):
+    """The device-expanding baselines (NGNN, I2GNN, GINE+): every plain batch of `batches` through `store.expand(data, *extra)`
+    (expansion.GraphStore), on the device"""
+    for data, n_global in batches:
+        yield store.expand(data, *extra), n_global
+
+
 _prefetch_streams = {}
 
 

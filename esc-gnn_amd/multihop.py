@@ -15,7 +15,8 @@ import copy
 import torch
 
 from . import _native as nv
-from .subgraphs import _device, _pointers, collate_graphs
+from .expansion import (GraphStore, _below_2_31, _column_totals, _count_prologue, _known_sizes, _raise_status as _raise_for,
+                        _sizes_of_list, _tagged_sizes, _wants_check)
 
 K_MAX = 8
 MAX_NODES = 4096             # one byte of LDS per node of the root's graph (csrc/multihop.hip)
@@ -102,43 +103,28 @@ class MultihopPlan(object):
 
 def _count(batch, k, G_known=None, max_nodes=None):
     k = _check_k(k)
-    node_ptr, edge_ptr, G, N, E, nmax = _pointers(batch, G_known)
-    if nmax is None:
-        nmax = max_nodes
-    if nmax is None:
-        nmax = int((node_ptr[1:] - node_ptr[:-1]).max().item()) if G else 1
-    if nmax > MAX_NODES:
-        raise ValueError("multihop: a graph of %d nodes exceeds the limit of %d nodes per graph" % (nmax, MAX_NODES))
-    if N >= 2 ** 31 - 1 or E >= 2 ** 31 - 1:
-        raise ValueError("multihop: %d nodes / %d edges: totals must stay below 2^31" % (N, E))
+    c = _count_prologue(batch, MAX_NODES, "multihop", G_known, max_nodes)
+    G, N = c["G"], c["N"]
+    _below_2_31("multihop", "%d nodes / %d edges", N, c["E"])
     dev = batch.edge_index.device
-    ei = batch.edge_index
-    src, dst = ei[0].contiguous(), ei[1].contiguous()
     pair_ptr = torch.empty(N + 1, dtype=torch.int64, device=dev)
     d1_ptr = torch.empty(N + 1, dtype=torch.int64, device=dev)
     dist_count = torch.empty((max(G, 1), k + 1), dtype=torch.int64, device=dev)
-    status = torch.zeros(max(G, 1), dtype=torch.int32, device=dev)
-    nv.call("esc_multihop_count", nv.ptr(node_ptr), nv.ptr(edge_ptr), nv.ptr(src), nv.ptr(dst), max(G, 1), N, E, max(int(nmax), 1), k,
-            nv.ptr(pair_ptr), nv.ptr(d1_ptr), nv.ptr(dist_count), nv.ptr(status), nv.stream())
-    return dict(node_ptr=node_ptr, edge_ptr=edge_ptr, G=G, N=N, E=E, nmax=max(int(nmax), 1), src=src, dst=dst, k=k,
-                pair_ptr=pair_ptr, d1_ptr=d1_ptr, dist_count=dist_count, status=status)
+    nv.call("esc_multihop_count", nv.ptr(c["node_ptr"]), nv.ptr(c["edge_ptr"]), nv.ptr(c["src"]), nv.ptr(c["dst"]), max(G, 1), N, c["E"],
+            c["nmax"], k, nv.ptr(pair_ptr), nv.ptr(d1_ptr), nv.ptr(dist_count), nv.ptr(c["status"]), nv.stream())
+    c.update(k=k, pair_ptr=pair_ptr, d1_ptr=d1_ptr, dist_count=dist_count)
+    return c
 
 
 def _raise_status(c, what):
-    """raise for the first graph whose status is set, naming the graph and what it can have hit"""
-    st = c["status"].cpu()
-    if bool((st != 0).any()):
-        g = int(torch.nonzero(st)[0])
-        raise ValueError("%s: graph %d cannot be expanded (status %d): a node id outside the graph, edges of one graph not "
-                         "contiguous, a graph of more than %d nodes (limit %d), or a pair total that is not the count pass's"
-                         % (what, g, int(st[g]), c["nmax"], MAX_NODES))
+    _raise_for(c, what, "a node id outside the graph, edges of one graph not contiguous, a graph of more than %d nodes (limit %d), "
+               "or a pair total that is not the count pass's" % (c["nmax"], MAX_NODES))
 
 
 def multihop_sizes(batch_or_list, k, chunk=4096):
     """The count pass alone: int64 [G, k+1] on the host, per graph the number of pairs at every distance 0..k."""
     if isinstance(batch_or_list, (list, tuple)):
-        parts = [multihop_sizes(collate_graphs(batch_or_list[i:i + chunk]), k) for i in range(0, len(batch_or_list), chunk)]
-        return torch.cat(parts, dim=0) if parts else torch.zeros((0, _check_k(k) + 1), dtype=torch.int64)
+        return _sizes_of_list(lambda b: (multihop_sizes(b, k), 0), batch_or_list, chunk, lambda: _check_k(k) + 1)[0]
     c = _count(batch_or_list, k)
     _raise_status(c, "multihop_sizes")
     return c["dist_count"][:c["G"]].cpu()
@@ -159,31 +145,18 @@ def expand_multihop(batch, k, sizes=None, check=None, max_nodes=None):
         plan = MultihopPlan(mei, dist, N, k, torch.zeros(N + 1, dtype=torch.int64, device=dev), z32,
                             torch.zeros(N + 1, dtype=torch.int32, device=dev), z32, [0] * (k + 1))
         return mei, dist, plan
-    G_known = None
-    if sizes is not None:
-        sizes = torch.as_tensor(sizes, dtype=torch.int64).reshape(-1, k + 1)
-        G_known = int(sizes.size(0))
-    if max_nodes is None and sizes is not None:              # n_g = its distance-0 pairs
-        max_nodes = int(sizes[:, 0].max()) if G_known else 1
+    sizes, G_known, max_nodes = _known_sizes(sizes, k + 1, max_nodes)        # n_g = its distance-0 pairs
     c = _count(batch, k, G_known, max_nodes)
-    if G_known is not None and G_known != c["G"]:
-        raise ValueError("expand_multihop: sizes has %d rows for a batch of %d graphs" % (G_known, c["G"]))
-    if sizes is not None:
-        counts = sizes.sum(dim=0).tolist()
-        M = int(sum(counts))
-    else:
-        counts = None
-        M = int(c["pair_ptr"][N].item())                     # (the read-back `sizes` saves)
-    if M >= 2 ** 31 - 1:
-        raise ValueError("expand_multihop: %d pairs: totals must stay below 2^31" % M)
+    # per distance from `sizes`, or the one total that `sizes` saves reading back
+    totals = _column_totals("expand_multihop", c, sizes, G_known, lambda: [c["pair_ptr"][N].item()])
+    M, counts = sum(totals), (None if sizes is None else totals)
+    _below_2_31("expand_multihop", "%d pairs", M)
     out = torch.empty((3, M), dtype=torch.int64, device=dev)          # row | col | distance
     meta = torch.empty((M, 4), dtype=torch.int32, device=dev)
     nv.call("esc_multihop_fill", nv.ptr(c["node_ptr"]), nv.ptr(c["edge_ptr"]), nv.ptr(c["src"]), nv.ptr(c["dst"]), max(c["G"], 1), N, E,
             c["nmax"], k, nv.ptr(c["pair_ptr"]), nv.ptr(c["d1_ptr"]), M, nv.ptr(out[0]), nv.ptr(out[1]), nv.ptr(out[2]),
             nv.ptr(meta), nv.ptr(c["status"]), nv.stream())
-    if check is None:
-        check = sizes is None
-    if check:
+    if _wants_check(check, sizes):
         _raise_status(c, "expand_multihop")
     in_ptr, in_meta = MultihopPlan._group_by_destination(meta, out[1], N)
     mei, dist = out[:2], out[2]
@@ -207,9 +180,7 @@ def make_multihop_edges(data, k):
     back once (MultihopGraphStore.expand reads nothing back)."""
     out = copy.copy(data)
     object.__setattr__(out, "_store", dict(object.__getattribute__(data, "_store")))
-    sizes = object.__getattribute__(data, "__dict__").get("_esc_mh_sizes")
-    if sizes is not None and sizes.size(1) != _check_k(k) + 1:
-        sizes = None
+    sizes = _tagged_sizes(data, "multihop", k)               # (sizes counted for another k are ignored: the total is read back)
     src = data
     if data["batch"] is None:                                # a single graph, as the reference's Data objects are
         src = copy.copy(out)
@@ -220,31 +191,18 @@ def make_multihop_edges(data, k):
     return out
 
 
-class MultihopGraphStore(object):
-    """A split of plain graphs for the GINE+ run, on PlainGraphStore's host collate (subgraphs.collate_graphs): ONE count pass
-    at build time keeps, per graph, the number of pairs at every distance, so that `collate` + `expand` read nothing back."""
+class MultihopGraphStore(GraphStore):
+    """The GINE+ run's split (expansion.GraphStore): the count pass at build time keeps, per graph, the number of pairs at every
+    distance, so that `collate` + `expand` read nothing back."""
+    kind = "multihop"
+    _check_param = staticmethod(_check_k)
+    k = property(lambda self: self.param)
 
-    def __init__(self, data_list, k, device=None):
-        if len(data_list) == 0:
-            raise ValueError("MultihopGraphStore: empty dataset")
-        self.graphs, self.k = list(data_list), _check_k(k)
-        self.device = _device() if device is None else torch.device(device)
-        self.sizes = multihop_sizes(self.graphs, self.k)
-
-    def __len__(self):
-        return len(self.graphs)
-
-    def collate(self, graph_ids):
-        ids = torch.as_tensor(graph_ids, dtype=torch.int64).reshape(-1)
-        if ids.numel() == 0:
-            raise ValueError("collate: empty batch")
-        out = collate_graphs([self.graphs[i] for i in ids.tolist()], self.device)
-        object.__setattr__(out, "_esc_mh_sizes", self.sizes[ids])
-        return out
+    def _count_sizes(self):
+        return multihop_sizes(self.graphs, self.k), None     # (no rooted subgraph, no rd limit)
 
     def expand(self, batch):
         """the batch with `multihop_edge_index`, `distance` and its MultihopPlan (in place: the batch is the store's own)"""
-        sizes = object.__getattribute__(batch, "__dict__").get("_esc_mh_sizes")
-        mei, dist, plan = expand_multihop(batch, self.k, sizes)
+        mei, dist, plan = expand_multihop(batch, self.k, self.sizes_of(batch))
         batch.multihop_edge_index, batch.distance = mei, dist
         return batch

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .harness import Context, default_appendix, open_result_dir, parser_from, prefetched, sharded_batches
+from .harness import Context, default_appendix, expanded_batches, open_result_dir, parser_from, prefetched, sharded_batches
 from .ogb_mol_gnn import GNN
 
 _FLAGS = [  # same names, types and defaults as the reference CLI (its `type=bool` flags included: any non-empty
@@ -140,11 +140,6 @@ def main(argv=None):
         stores = [MultihopGraphStore(p, GINEPLUS_K, ctx.device) for p in parts]
     else:
         stores = [DeviceGraphStore(p, ctx.device) for p in parts]
-
-    def expanded(store, batches):
-        """gine+: every plain batch gets multihop_edge_index / distance and the aggregate's plan, on the device"""
-        for data, n_global in batches:
-            yield store.expand(data), n_global
     evaluator = Evaluator(args.dataset)
     eval_metric = evaluator.eval_metric
     kwargs = dict(num_layer=args.num_layer, residual=args.residual, use_rd=args.use_rd, use_rp=args.use_rp,
@@ -163,8 +158,8 @@ def main(argv=None):
         batches = sharded_batches(stores[0], args.batch_size, ctx, True, gen)
         if args.prefetch:         # the next batch is collated (and its embedding plans built) on a side stream while this one trains
             batches = prefetched(batches, ctx.device, warm)
-        if gineplus:
-            batches = expanded(stores[0], batches)
+        if gineplus:              # every plain batch gets multihop_edge_index / distance and the aggregate's plan, on the device
+            batches = expanded_batches(stores[0], batches)
         for data, _ in batches:
             y = data.y.view(-1, num_tasks)
             if engine is not None and ogb_engine_ready(model, data):
@@ -199,7 +194,7 @@ def main(argv=None):
                 model.load_state_dict(torch.load(ckpt, map_location=ctx.device))
             y_true, y_pred = [], []
             batches = sharded_batches(store, args.batch_size, ctx, False)
-            for data, _ in (expanded(store, batches) if gineplus else batches):
+            for data, _ in (expanded_batches(store, batches) if gineplus else batches):
                 pred = model(data)
                 y_true.append(data.y.view(pred.shape))
                 y_pred.append(pred)

@@ -18,8 +18,8 @@ molecules: the split holds the plain graphs, and every step expands the batch in
 import torch
 
 from . import ops
-from .harness import (Context, default_appendix, fit_regression, open_result_dir, parser_from, prefetched, seed_everything,
-                      sharded_batches)
+from .harness import (Context, default_appendix, expanded_batches, fit_regression, open_result_dir, parser_from, prefetched,
+                      seed_everything, sharded_batches)
 from .zinc_models import NGNN, NestedGIN_eff
 
 _FLAGS = [  # same names, types and defaults as the reference CLI
@@ -146,19 +146,14 @@ def main(argv=None):
     from .engine import ZincStepEngine, zinc_engine_ready, zinc_engine_supports
     engine = ZincStepEngine(model) if zinc_engine_supports(model) else None     # forward + L1 + backward in ONE call
 
-    def expanded(store, batches):
-        """NGNN: every plain batch becomes the disconnected graph of its rooted subgraphs, on the device"""
-        for data, n_global in batches:
-            yield store.expand(data, args.node_label, args.use_rd), n_global
-
     def train(epoch):
         model.train()
         loss_all = torch.zeros((), device=ctx.device)
         batches = sharded_batches(stores[0], args.batch_size, ctx, True, gen)
         if args.prefetch:         # the next batch is collated on a side stream while this one trains
             batches = prefetched(batches, ctx.device)
-        if ngnn:
-            batches = expanded(stores[0], batches)
+        if ngnn:                  # every plain batch becomes the disconnected graph of its rooted subgraphs, on the device
+            batches = expanded_batches(stores[0], batches, args.node_label, args.use_rd)
         for data, n_global in batches:
             if engine is not None and zinc_engine_ready(model, data):           # (a 1-graph tail batch takes the per-op path)
                 n_loc = data.y.numel()
@@ -191,7 +186,7 @@ def main(argv=None):
         tot = torch.zeros(2, device=ctx.device)
         with torch.no_grad():
             batches = sharded_batches(store, args.batch_size, ctx, False)
-            for data, _ in (expanded(store, batches) if ngnn else batches):
+            for data, _ in (expanded_batches(store, batches, args.node_label, args.use_rd) if ngnn else batches):
                 y_hat = model(data)[:, 0]
                 tot[0] += torch.sum(torch.abs(y_hat - data.y.view(-1)))
                 tot[1] += y_hat.numel()

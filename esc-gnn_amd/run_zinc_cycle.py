@@ -24,8 +24,8 @@ step expands the batch into one copy of every rooted subgraph per neighbour of i
 import torch
 
 from . import ops
-from .harness import (Context, default_appendix, fit_regression, open_result_dir, parser_from, prefetched, seed_everything,
-                      sharded_batches)
+from .harness import (Context, default_appendix, expanded_batches, fit_regression, open_result_dir, parser_from, prefetched,
+                      seed_everything, sharded_batches)
 from .zinc_cycle_models import I2GNN, NestedGIN_eff
 
 _FLAGS = [  # same names, types and defaults as the reference CLI
@@ -104,8 +104,8 @@ def main(argv=None):
         raise SystemExit(1)
     i2gnn = args.model == "I2GNN"
     if i2gnn:                                             # what the expansion has no path for: refused before anything is built
-        from .subgraphs2 import _check
-        _check(args.h, args.node_label, args.max_nodes_per_hop, None, args.self_loop)
+        from .subgraphs2 import check_args
+        check_args(args.h, args.node_label, args.max_nodes_per_hop, None, args.self_loop)
     if args.max_nodes_per_hop is not None:
         raise NotImplementedError("max_nodes_per_hop: random neighbour sampling is outside the ESC hot path")
     if not 0 <= args.target < 4:
@@ -155,11 +155,6 @@ def main(argv=None):
     from .engine import ZincStepEngine, zinc_engine_ready, zinc_engine_supports
     engine = ZincStepEngine(model) if zinc_engine_supports(model) else None     # forward + L1 + backward in ONE call
 
-    def expanded(store, batches):
-        """I2GNN: every plain batch becomes the disconnected graph of its subgraph2s, on the device"""
-        for data, n_global in batches:
-            yield store.expand(data), n_global
-
     def train(epoch):
         # loss_all: sum over batches of (node-mean L1) * (graphs in the global batch), reference :272-284
         model.train()
@@ -167,8 +162,8 @@ def main(argv=None):
         batches = sharded_batches(stores[0], args.batch_size, ctx, True, gen)
         if args.prefetch:         # the next batch is collated on a side stream while this one trains
             batches = prefetched(batches, ctx.device)
-        if i2gnn:
-            batches = expanded(stores[0], batches)
+        if i2gnn:                 # every plain batch becomes the disconnected graph of its subgraph2s, on the device
+            batches = expanded_batches(stores[0], batches)
         for data, n_graphs in batches:
             y = data.y[:, target].contiguous()
             n_loc = y.numel()
@@ -204,7 +199,7 @@ def main(argv=None):
         err = torch.zeros(1, device=ctx.device)
         with torch.no_grad():
             batches = sharded_batches(store, args.batch_size, ctx, False)
-            for data, _ in (expanded(store, batches) if i2gnn else batches):
+            for data, _ in (expanded_batches(store, batches) if i2gnn else batches):
                 y_hat = model(data)[:, 0]
                 err += torch.sum(torch.abs(y_hat - data.y[:, target]))
         ctx.all_reduce(err)

@@ -12,14 +12,17 @@ import torch
 
 from . import _native as nv
 from .data import Data
-from .subgraphs import RD_MAX_NODES, PlainGraphStore, _device, _pointers, collate_graphs  # noqa: F401
+from .expansion import (GraphStore, _below_2_31, _column_totals, _count_prologue, _known_sizes, _sizes_of_list, _tag_segments,
+                        _wants_check, collate_graphs)
+from .subgraphs import _raise_status, _refuse_rd
 from .utils_edge_efficient import _check_args
 
 H_MAX = 47                   # labels of the second root reach 2h + 5 on symmetric graphs; the model's tables have 100 rows
 MAX_NODES = 1536             # 9 B of LDS tables per node beside the two 96 x 96 fp64 matrices of the pseudo-inverse
 
 
-def _check(h, node_label="spd", max_nodes_per_hop=None, subgraph_pretransform=None, self_loop=False):
+def check_args(h, node_label="spd", max_nodes_per_hop=None, subgraph_pretransform=None, self_loop=False):
+    """h as an int in 1..H_MAX; raises for what the I2GNN expansion has no path for"""
     if self_loop:
         raise NotImplementedError("self_loop: the reference's node_to_original_node has the wrong length with --self_loop "
                                   "(utils_edge_I2.py:193-196 counts the root's degree without the loop); I2GNN runs without it")
@@ -37,51 +40,24 @@ def _check(h, node_label="spd", max_nodes_per_hop=None, subgraph_pretransform=No
 
 
 def _count(batch, h, G_known=None, max_nodes=None):
-    node_ptr, edge_ptr, G, N, E, nmax = _pointers(batch, G_known)
-    if nmax is None:
-        nmax = max_nodes
-    if nmax is None:
-        nmax = int((node_ptr[1:] - node_ptr[:-1]).max().item()) if G else 1
-    if nmax > MAX_NODES:
-        raise ValueError("subgraphs2: a graph of %d nodes exceeds the limit of %d nodes per graph" % (nmax, MAX_NODES))
-    dev = batch.edge_index.device
-    ei = batch.edge_index
-    src, dst = ei[0].contiguous(), ei[1].contiguous()
-    ptrs = torch.empty((3, N + 1), dtype=torch.int64, device=dev)         # sub-node | sub-edge | subgraph2 pointers per root
-    status = torch.zeros(max(G, 1), dtype=torch.int32, device=dev)
-    nv.call("esc_subgraph2_count", nv.ptr(node_ptr), nv.ptr(edge_ptr), nv.ptr(src), nv.ptr(dst), G, N, E, max(int(nmax), 1), h,
-            nv.ptr(ptrs[0]), nv.ptr(ptrs[1]), nv.ptr(ptrs[2]), nv.ptr(status), nv.stream())
-    return dict(node_ptr=node_ptr, edge_ptr=edge_ptr, G=G, N=N, E=E, nmax=max(int(nmax), 1), src=src, dst=dst, ptrs=ptrs,
-                sub_node_ptr=ptrs[0], sub_edge_ptr=ptrs[1], sub2_ptr=ptrs[2], status=status, h=h)
-
-
-def _raise_status(c, what):
-    """raise for the first graph whose status is set, naming what it hit (as subgraphs._raise_status)"""
-    st = c["status"].cpu()
-    if bool((st != 0).any()):
-        g = int(torch.nonzero(st)[0])
-        a, b = (int(v) for v in c["node_ptr"][g:g + 2].tolist())
-        counted = a < b and int(c["sub_node_ptr"][b]) > int(c["sub_node_ptr"][a])
-        if counted:
-            why = ("with use_rd, a subgraph of more than %d nodes (both m x m matrices of the pseudo-inverse must fit LDS), or "
-                   "output totals that are not those of the count pass" % RD_MAX_NODES)
-        else:
-            why = ("a node id outside the graph, edges of one graph not contiguous, or a graph of more than %d nodes (limit %d)"
-                   % (c["nmax"], MAX_NODES))
-        raise ValueError("%s: graph %d cannot be expanded (status %d): %s" % (what, g, int(st[g]), why))
+    c = _count_prologue(batch, MAX_NODES, "subgraphs2", G_known, max_nodes)
+    # sub-node | sub-edge | subgraph2 pointers per root
+    ptrs = torch.empty((3, c["N"] + 1), dtype=torch.int64, device=batch.edge_index.device)
+    nv.call("esc_subgraph2_count", nv.ptr(c["node_ptr"]), nv.ptr(c["edge_ptr"]), nv.ptr(c["src"]), nv.ptr(c["dst"]), c["G"], c["N"],
+            c["E"], c["nmax"], h, nv.ptr(ptrs[0]), nv.ptr(ptrs[1]), nv.ptr(ptrs[2]), nv.ptr(c["status"]), nv.stream())
+    c.update(ptrs=ptrs, sub_node_ptr=ptrs[0], sub_edge_ptr=ptrs[1], sub2_ptr=ptrs[2], h=h)
+    return c
 
 
 def subgraph2_sizes(batch_or_list, h, chunk=4096, with_largest=False):
     """The count pass alone: int64 [G, 3] on the host, per graph (sub-nodes, sub-edges, subgraph2s) over all its roots and
     copies.  with_largest: also the node count of the largest single rooted subgraph (what the rd limit of 96 is about)."""
-    h = _check(h)
+    h = check_args(h)
     if isinstance(batch_or_list, (list, tuple)):
-        parts = [subgraph2_sizes(collate_graphs(batch_or_list[i:i + chunk]), h, with_largest=True)
-                 for i in range(0, len(batch_or_list), chunk)]
-        sizes = torch.cat([p[0] for p in parts], dim=0) if parts else torch.zeros((0, 3), dtype=torch.int64)
-        return (sizes, max([p[1] for p in parts] or [0])) if with_largest else sizes
+        both = _sizes_of_list(lambda b: subgraph2_sizes(b, h, with_largest=True), batch_or_list, chunk, lambda: 3)
+        return both if with_largest else both[0]
     c = _count(batch_or_list, h)
-    _raise_status(c, "subgraph2_sizes")
+    _raise_status(c, "subgraph2_sizes", MAX_NODES)
     at = c["ptrs"][:, c["node_ptr"]].t().cpu()
     sizes = at[1:] - at[:-1]
     if not with_largest:
@@ -97,23 +73,12 @@ def expand_subgraphs2(batch, h, use_rd=False, sizes=None, node_label="spd", max_
     their sums and nothing is read back; without it the three totals are copied once.  check / max_nodes: as
     subgraphs.expand_subgraphs (with `sizes` the status tensor is returned as `status` and a bad graph has no, or not all, rows;
     I2GraphStore has checked both limits at build)."""
-    h = _check(h, node_label, max_nodes_per_hop, subgraph_pretransform, self_loop)
-    G_known = None
-    if sizes is not None:
-        sizes = torch.as_tensor(sizes, dtype=torch.int64).reshape(-1, 3)
-        G_known = int(sizes.size(0))
-    if max_nodes is None and sizes is not None:           # n_g <= its sub-node total: an upper bound known on the host
-        max_nodes = min(MAX_NODES, int(sizes[:, 0].max()) if G_known else 1)
+    h = check_args(h, node_label, max_nodes_per_hop, subgraph_pretransform, self_loop)
+    sizes, G_known, max_nodes = _known_sizes(sizes, 3, max_nodes, MAX_NODES)
     c = _count(batch, h, G_known, max_nodes)
-    if G_known is not None and G_known != c["G"]:
-        raise ValueError("expand_subgraphs2: sizes has %d rows for a batch of %d graphs" % (G_known, c["G"]))
     N = c["N"]
-    if sizes is not None:
-        Ns, Es, S2 = (int(v) for v in sizes.sum(dim=0).tolist())
-    else:
-        Ns, Es, S2 = (int(v) for v in c["ptrs"][:, N].tolist())
-    if Ns >= 2 ** 31 - 1 or Es >= 2 ** 31 - 1:
-        raise ValueError("expand_subgraphs2: %d sub-nodes / %d sub-edges: totals must stay below 2^31" % (Ns, Es))
+    Ns, Es, S2 = _column_totals("expand_subgraphs2", c, sizes, G_known, lambda: c["ptrs"][:, N].tolist())
+    _below_2_31("expand_subgraphs2", "%d sub-nodes / %d sub-edges", Ns, Es)
     dev = batch.edge_index.device
     nodes = torch.empty((3, Ns), dtype=torch.int64, device=dev)       # orig_node | node_to_subgraph2 | graph
     z = torch.empty((Ns, 4), dtype=torch.int64, device=dev)
@@ -128,10 +93,8 @@ def expand_subgraphs2(batch, h, use_rd=False, sizes=None, node_label="spd", max_
             int(bool(use_rd)), nv.ptr(nodes[0]), nv.ptr(z), nv.ptr(nodes[1]), nv.ptr(nodes[2]), nv.ptr(edges[0]),
             nv.ptr(edges[1]), nv.ptr(edges[2]), nv.ptr(s2_to_sub), nv.ptr(center_idx), nv.ptr(s2_node_ptr), nv.ptr(rd),
             nv.ptr(c["status"]), nv.stream())
-    if check is None:
-        check = sizes is None
-    if check:
-        _raise_status(c, "expand_subgraphs2")
+    if _wants_check(check, sizes):
+        _raise_status(c, "expand_subgraphs2", MAX_NODES)
     out = Data()
     orig_node, orig_edge = nodes[0], edges[2]
     out.z = z
@@ -152,34 +115,29 @@ def expand_subgraphs2(batch, h, use_rd=False, sizes=None, node_label="spd", max_
     out.s2_node_ptr, out.sub2_ptr, out.status = s2_node_ptr, c["sub2_ptr"], c["status"]
     out.sub_node_ptr, out.sub_edge_ptr = c["sub_node_ptr"], c["sub_edge_ptr"]
     # mean / add pooling over the subgraph2s and over the subgraphs: no rebuild, no read-back
-    seg = s2_node_ptr.to(torch.int32)
-    v = out.node_to_subgraph2._version
-    out.node_to_subgraph2._esc_seg = {(v, None): seg, (v, S2): seg}
-    seg = c["sub2_ptr"].to(torch.int32)
-    v = out.subgraph2_to_subgraph._version
-    out.subgraph2_to_subgraph._esc_seg = {(v, None): seg, (v, N): seg}
+    _tag_segments(out.node_to_subgraph2, s2_node_ptr, S2)
+    _tag_segments(out.subgraph2_to_subgraph, c["sub2_ptr"], N)
     return out
 
 
-class I2GraphStore(PlainGraphStore):
-    """A split of plain graphs for the I2GNN run: PlainGraphStore's host collate, the per-graph (sub-nodes, sub-edges,
-    subgraph2s) from one count pass at build time, and both limits checked there, so that no training step reads a size or a
-    status: the rd limit of 96 nodes per rooted subgraph from the count pass, the label limit by the range of h alone (the
-    largest label is 2h + 5 on every graph)."""
+class I2GraphStore(GraphStore):
+    """The I2GNN run's split (expansion.GraphStore): the per-graph (sub-nodes, sub-edges, subgraph2s) from the count pass at
+    build time, and both limits checked there, so that no training step reads a size or a status: the rd limit of 96 nodes per
+    rooted subgraph from the count pass, the label limit by the range of h alone (the largest label is 2h + 5 on every graph,
+    DESIGN.md 6i)."""
+    kind = "subgraph2"
+    _check_param = staticmethod(check_args)
+    h = property(lambda self: self.param)
 
     def __init__(self, data_list, h, use_rd=False, device=None):
-        if len(data_list) == 0:
-            raise ValueError("I2GraphStore: empty dataset")
-        self.graphs, self.h, self.use_rd = list(data_list), _check(h), bool(use_rd)
-        self.device = _device() if device is None else torch.device(device)
-        self.sizes, self.largest_subgraph = subgraph2_sizes(self.graphs, self.h, with_largest=True)
-        if self.use_rd and self.largest_subgraph > RD_MAX_NODES:
-            raise ValueError("I2GraphStore: use_rd with a subgraph of %d nodes at h=%d: rd covers subgraphs of at most %d nodes"
-                             % (self.largest_subgraph, self.h, RD_MAX_NODES))
+        GraphStore.__init__(self, data_list, h, device)
+        self.use_rd = bool(use_rd)
+        _refuse_rd(self, self.use_rd)
+
+    def _count_sizes(self):
+        return subgraph2_sizes(self.graphs, self.h, with_largest=True)
 
     def expand(self, batch, use_rd=None):
         use_rd = self.use_rd if use_rd is None else bool(use_rd)
-        if use_rd and self.largest_subgraph > RD_MAX_NODES:
-            raise ValueError("I2GraphStore: use_rd with a subgraph of %d nodes at h=%d: rd covers subgraphs of at most %d nodes"
-                             % (self.largest_subgraph, self.h, RD_MAX_NODES))
-        return expand_subgraphs2(batch, self.h, use_rd, object.__getattribute__(batch, "__dict__").get("_esc_sub_sizes"))
+        _refuse_rd(self, use_rd)
+        return expand_subgraphs2(batch, self.h, use_rd, self.sizes_of(batch))

@@ -1,10 +1,11 @@
 """harness.sharded_ids, the id-level half of the graph-sharded batch order: rank r takes a contiguous slice of every
 global batch, a remainder smaller than the rank count is dropped in training and goes to rank 0 in evaluation, and the
-shuffled order is the same on every rank.  CPU only: a stand-in context and a store that has nothing but a length."""
+shuffled order is the same on every rank.  CPU only: a stand-in context and a store that has nothing but a length.
+And harness.expanded_batches, the generator the device-expanding baselines put behind their batches."""
 import pytest
 import torch
 
-from esc_gnn_amd.harness import sharded_ids
+from esc_gnn_amd.harness import expanded_batches, sharded_ids
 
 G, BATCH = 10, 4          # two full global batches and a remainder of 2, which is smaller than world 3
 WORLDS = (1, 2, 3)
@@ -84,3 +85,25 @@ def test_same_seed_gives_all_ranks_the_same_order(world):
 def test_only_the_length_of_the_store_is_read():
     ids, n = next(sharded_ids(_Store(), BATCH, _Ctx(2, 1), False))
     assert ids.device.type == "cpu" and ids.tolist() == [2, 3] and n == 4
+
+
+class _ExpandingStore(object):
+    """records every expand call and returns something that names its arguments"""
+
+    def __init__(self):
+        self.calls = []
+
+    def expand(self, data, *extra):
+        self.calls.append((data,) + extra)
+        return ("expanded", data) + extra
+
+
+@pytest.mark.parametrize("extra", ((), ("drnl", True)))
+def test_expanded_batches_yields_every_batch_through_the_stores_expand_in_order(extra):
+    store = _ExpandingStore()
+    batches = [("a", 4), ("b", 4), ("c", 2)]
+    it = expanded_batches(store, iter(batches), *extra)
+    assert store.calls == []                                  # a generator: nothing is expanded before it is asked for
+    assert next(it) == (("expanded", "a") + extra, 4) and store.calls == [("a",) + extra]      # one batch at a time
+    assert list(it) == [(("expanded", "b") + extra, 4), (("expanded", "c") + extra, 2)]
+    assert store.calls == [(d,) + extra for d, _ in batches]                       # the extra arguments reach every call
