@@ -84,6 +84,14 @@ except OSError as exc:
     raise NativeLibraryError("esc_gnn_amd: cannot read the C header %s the binding is derived from (%s)" % (LAPPE_HEADER, exc)) from exc
 LAPPE_SIGNATURES = {name: args for name, (args, _) in _LAPPE.functions.items()}
 _RET.update({name: ret for name, (_, ret) in _LAPPE.functions.items()})
+# the sixth extension header (escgnn_rwse.h: the random-walk landing probabilities and the gather from their resident table)
+RWSE_HEADER = os.path.join(os.path.dirname(_abi.HEADER), "escgnn_rwse.h")
+try:
+    _RWSE = _abi.load(RWSE_HEADER)
+except OSError as exc:
+    raise NativeLibraryError("esc_gnn_amd: cannot read the C header %s the binding is derived from (%s)" % (RWSE_HEADER, exc)) from exc
+RWSE_SIGNATURES = {name: args for name, (args, _) in _RWSE.functions.items()}
+_RET.update({name: ret for name, (_, ret) in _RWSE.functions.items()})
 KIND = {name[len("ESC_K_"):].lower(): v for name, v in _ABI.enum.items() if name != "ESC_K_COUNT"}
 
 CollateArgs = struct("esc_collate_args")
@@ -107,7 +115,7 @@ def lib():
             "esc_gnn_amd: %s not found. The HIP hot path has no fallback — build it with "
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C esc-gnn_amd/csrc`." % LIB_PATH)
     h = ctypes.CDLL(LIB_PATH)
-    for name, args in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()) + list(I2GNN_SIGNATURES.items()) + list(GINEPLUS_SIGNATURES.items()) + list(GPS_SIGNATURES.items()) + list(LAPPE_SIGNATURES.items()):
+    for name, args in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()) + list(I2GNN_SIGNATURES.items()) + list(GINEPLUS_SIGNATURES.items()) + list(GPS_SIGNATURES.items()) + list(LAPPE_SIGNATURES.items()) + list(RWSE_SIGNATURES.items()):
         try:
             fn = getattr(h, name)
         except AttributeError as exc:

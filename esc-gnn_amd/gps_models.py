@@ -18,16 +18,19 @@ checkpoints load, and take no part in the forward.
 The yaml's node encoder is TypeDictNode+LapPE.  GPSModel(lap_pe=True) builds it as the reference's Concat2NodeEncoder does:
 encoder1 = the type embedding at width dim_hidden - dim_pe, encoder2 = nn.LapPENodeEncoder over the batch's EigVals / EigVecs
 (lappe.py computes them on the device), the node state their concatenation.  The default, lap_pe=False, is TypeDictNode at full
-width with the state_dict that has.
+width with the state_dict that has.  GPSModel(rwse=True) is TypeDictNode+RWSE the same way (encoder2 = nn.RWSENodeEncoder over the
+batch's pestat_RWSE, rwse.py), and both flags give the reference's only three-way encoder, TypeDictNode+LapPE+RWSE
+(Concat3NodeEncoder: encoder2 = LapPE, encoder3 = RWSE).
 
 Out of scope: BiasedTransformer / attn_bias, Performer and BigBird, the other local GNN types, layer_norm, the other positional
-encodings and LapPE's Transformer model, graphgym's config system and wandb, a whole-step engine, data parallelism."""
+encodings (SignNet, EquivStableLapPE, HKdiagSE, ElstaticSE) and LapPE's Transformer model, graphgym's config system and wandb,
+a whole-step engine, data parallelism."""
 import torch
 from torch.nn import Dropout, ModuleList, Sequential
 
 from . import nested
 from .nested import Z_TABLE_ROWS
-from .nn import BatchNorm1d, Embedding, GINEConv, GraphMultiheadAttention, LapPENodeEncoder, Linear, ReLU, global_add_pool
+from .nn import BatchNorm1d, Embedding, GINEConv, GraphMultiheadAttention, LapPENodeEncoder, Linear, ReLU, RWSENodeEncoder, global_add_pool
 from .plan import graph_ptr_of, plan_of
 
 
@@ -82,28 +85,39 @@ class _TypeDict(torch.nn.Module):
         return self.encoder(index)
 
 
-class _Concat2(torch.nn.Module):
-    """Concat2NodeEncoder for TypeDictNode+LapPE (graphgps/encoder/composed_encoders.py:35-58): the type embedding at width
-    dim_emb - dim_pe, then the LapPE encoder (expand_x False), concatenated"""
+class _ConcatPE(torch.nn.Module):
+    """Concat2NodeEncoder / Concat3NodeEncoder (graphgps/encoder/composed_encoders.py:35-82) for TypeDictNode+LapPE,
+    TypeDictNode+RWSE and TypeDictNode+LapPE+RWSE: encoder1 = the type embedding at the width the encodings leave, then
+    encoder2 (and encoder3) = the positional encoders (expand_x False) in the reference's order, all concatenated.
+    `pes`: [(name, dim_pe, constructor)] - constructed after encoder1 and in order, so equal seeds give equal weights."""
 
-    def __init__(self, num_types, dim_emb, dim_pe, max_freqs):
+    def __init__(self, num_types, dim_emb, pes):
         super().__init__()
-        if not 0 < dim_pe < dim_emb:
-            raise ValueError("LapPE size %d is too large for desired embedding size of %d." % (dim_pe, dim_emb))
-        self.encoder1 = _TypeDict(num_types, dim_emb - dim_pe)
-        self.encoder2 = LapPENodeEncoder(dim_pe, max_freqs)
+        left = dim_emb - sum(dim_pe for _, dim_pe, _ in pes)
+        if left <= 0 or any(dim_pe <= 0 for _, dim_pe, _ in pes):
+            raise ValueError("%s size %s is too large for desired embedding size of %d."
+                             % ("+".join(name for name, _, _ in pes), "+".join(str(dim_pe) for _, dim_pe, _ in pes), dim_emb))
+        self.encoder1 = _TypeDict(num_types, left)
+        for k, (_, _, make) in enumerate(pes):
+            setattr(self, "encoder%d" % (k + 2), make())
+        self.count = len(pes)
 
     def forward(self, index, data):
-        return torch.cat([self.encoder1(index), self.encoder2(data)], 1)
+        return torch.cat([self.encoder1(index)] + [getattr(self, "encoder%d" % (k + 2))(data) for k in range(self.count)], 1)
 
 
 class FeatureEncoder(torch.nn.Module):
-    """gps_model.py:12-51 with node_encoder TypeDictNode (lap_pe: TypeDictNode+LapPE), edge_encoder TypeDictEdge and no encoder
-    BatchNorm"""
+    """gps_model.py:12-51 with node_encoder TypeDictNode (lap_pe: TypeDictNode+LapPE, rwse: TypeDictNode+RWSE, both:
+    TypeDictNode+LapPE+RWSE), edge_encoder TypeDictEdge and no encoder BatchNorm"""
 
-    def __init__(self, dim_inner, node_types, edge_types, lap_pe=False, dim_pe=8, max_freqs=8):
+    def __init__(self, dim_inner, node_types, edge_types, lap_pe=False, dim_pe=8, max_freqs=8, rwse=None):
         super().__init__()
-        self.node_encoder = _Concat2(node_types, dim_inner, dim_pe, max_freqs) if lap_pe else _TypeDict(node_types, dim_inner)
+        pes = []
+        if lap_pe:
+            pes.append(("LapPE", dim_pe, lambda: LapPENodeEncoder(dim_pe, max_freqs)))
+        if rwse:
+            pes.append(("RWSE", rwse["dim_pe"], lambda: RWSENodeEncoder(**rwse)))
+        self.node_encoder = _ConcatPE(node_types, dim_inner, pes) if pes else _TypeDict(node_types, dim_inner)
         self.edge_encoder = _TypeDict(edge_types, dim_inner)
 
 
@@ -128,13 +142,18 @@ class GPSModel(torch.nn.Module):
     """gps_model.py:54-108 under zinc-GPS.yaml; defaults = that file's values.  forward(data) -> [G, dim_out] predictions.
     The largest graph of the batch is read off `data._esc_max_nodes` when the loader left it there (the device store knows it
     on the host); otherwise the attention op reads it back once per batch.  lap_pe=True: the batch must carry EigVals / EigVecs
-    (lappe.add_lap_pe, lappe.LapPETable.attach)."""
+    (lappe.add_lap_pe, lappe.LapPETable.attach).  rwse=True: the node encoder gains nn.RWSENodeEncoder(rwse_dim_pe, rwse_steps,
+    rwse_model, rwse_layers, rwse_raw_norm) as its last part and the batch must carry pestat_RWSE [N, rwse_steps]
+    (rwse.add_rwse, rwse.RWSETable.attach); the rwse_* defaults are upstream GraphGPS's usual ZINC values - the reference ships
+    no configuration that enables RWSE."""
 
     def __init__(self, layers=10, dim_hidden=64, n_heads=4, dropout=0.0, attn_dropout=0.5, node_types=28, edge_types=4, dim_out=1,
-                 lap_pe=False, dim_pe=8, max_freqs=8):
+                 lap_pe=False, dim_pe=8, max_freqs=8, rwse=False, rwse_dim_pe=28, rwse_steps=20, rwse_model="linear", rwse_layers=1,
+                 rwse_raw_norm="batchnorm"):
         super().__init__()
-        self.lap_pe = bool(lap_pe)
-        self.encoder = FeatureEncoder(dim_hidden, node_types, edge_types, self.lap_pe, dim_pe, max_freqs)
+        self.lap_pe, self.rwse = bool(lap_pe), bool(rwse)
+        rw = dict(dim_pe=rwse_dim_pe, num_steps=rwse_steps, model=rwse_model, layers=rwse_layers, raw_norm=rwse_raw_norm) if self.rwse else None
+        self.encoder = FeatureEncoder(dim_hidden, node_types, edge_types, self.lap_pe, dim_pe, max_freqs, rw)
         self.layers = Sequential(*[GPSLayer(dim_hidden, n_heads, dropout, attn_dropout) for _ in range(layers)])
         self.post_mp = SANGraphHead(dim_hidden, dim_out)
 
@@ -144,7 +163,7 @@ class GPSModel(torch.nn.Module):
         graph_ptr, num_graphs = graph_ptr_of(data, plan)
         max_nodes = getattr(data, "_esc_max_nodes", None)
         types = data.x.view(data.x.size(0), -1)[:, 0]                                 # type_dict_encoder.py:96: the first column
-        h = self.encoder.node_encoder(types, data) if self.lap_pe else self.encoder.node_encoder(types)
+        h = self.encoder.node_encoder(types, data) if (self.lap_pe or self.rwse) else self.encoder.node_encoder(types)
         edge_attr = self.encoder.edge_encoder(data.edge_attr.view(-1))
         for layer in self.layers:
             h, edge_attr = layer(h, edge_attr, data, plan, graph_ptr, max_nodes)

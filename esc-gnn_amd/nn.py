@@ -211,3 +211,44 @@ class LapPENodeEncoder(torch.nn.Module):
             signs = torch.where(torch.rand(vecs.size(1), device=vecs.device) >= 0.5, 1.0, -1.0)
         lin = self.pe_encoder[1]
         return ops.lappe_encode(vecs, vals, signs, self.linear_A.weight, self.linear_A.bias, lin.weight, lin.bias)
+
+
+class RWSENodeEncoder(torch.nn.Module):
+    """The reference's RWSENodeEncoder (KernelPENodeEncoder with kernel_type 'RWSE', GraphGPS/graphgps/encoder/
+    kernel_pos_encoder.py:8-110) as the composed node encoders build it (expand_x False): raw_norm = BatchNorm1d(num_steps) for
+    'batchnorm' (anything else: None, as in the reference), pe_encoder = Linear(num_steps, dim_pe) for model 'linear' or the
+    reference's Sequential of Linear / ReLU pairs for 'mlp'.  The same parameters, names and construction order, so equal seeds
+    give equal weights; built from this module's Linear, ReLU and BatchNorm1d: forward and backward run the library's kernels.
+    forward(batch) -> [N, dim_pe], the rows the reference concatenates to batch.x, off batch.pestat_RWSE [N, num_steps]
+    (rwse.add_rwse, rwse.RWSETable.attach)."""
+
+    def __init__(self, dim_pe, num_steps, model="linear", layers=1, raw_norm="batchnorm", expand_x=False, pass_as_var=False):
+        super().__init__()
+        if expand_x or pass_as_var:
+            raise ValueError("RWSENodeEncoder: expand_x and pass_as_var are not supported (the composed node encoders use neither)")
+        self.dim_pe, self.num_steps = int(dim_pe), int(num_steps)
+        self.raw_norm = BatchNorm1d(self.num_steps) if str(raw_norm).lower() == "batchnorm" else None
+        model_type = str(model).lower()
+        if model_type == "mlp":
+            seq = []
+            if layers == 1:
+                seq += [Linear(self.num_steps, self.dim_pe), ReLU()]
+            else:
+                seq += [Linear(self.num_steps, 2 * self.dim_pe), ReLU()]
+                for _ in range(layers - 2):
+                    seq += [Linear(2 * self.dim_pe, 2 * self.dim_pe), ReLU()]
+                seq += [Linear(2 * self.dim_pe, self.dim_pe), ReLU()]
+            self.pe_encoder = torch.nn.Sequential(*seq)
+        elif model_type == "linear":
+            self.pe_encoder = Linear(self.num_steps, self.dim_pe)
+        else:
+            raise ValueError(f"{self.__class__.__name__}: Does not support '{model_type}' encoder model.")
+
+    def forward(self, batch):
+        if not hasattr(batch, "pestat_RWSE"):
+            raise ValueError(f"Precomputed 'pestat_RWSE' variable is required for {self.__class__.__name__}; set config "
+                             f"'posenc_RWSE.enable' to True, and also set 'posenc.kernel.times' values")
+        pos_enc = batch.pestat_RWSE
+        if self.raw_norm is not None:
+            pos_enc = self.raw_norm(pos_enc)
+        return self.pe_encoder(pos_enc)

@@ -1314,6 +1314,22 @@ def _index_vector(t, what, dtype):
     return t.contiguous()
 
 
+def _ragged_graphs(who, edge_index, graph_ptr, edge_ptr):
+    """the argument checks the per-graph kernels share (laplacian_eig, rw_landing): a device edge_index [2, E] and the two
+    offset vectors of its G graphs"""
+    if not torch.is_tensor(edge_index) or edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.size(0) != 2:
+        raise TypeError("%s: edge_index must be an int64 [2, E] tensor" % who)
+    if not edge_index.is_cuda:
+        raise RuntimeError("esc_gnn_amd: the hot path runs on the HIP device only (got a %s tensor); there is no CPU fallback"
+                           % edge_index.device)
+    for name, t in (("graph_ptr", graph_ptr), ("edge_ptr", edge_ptr)):
+        if not torch.is_tensor(t) or t.dtype not in (torch.int32, torch.int64) or t.dim() != 1 or t.numel() < 1:
+            raise TypeError("%s: %s must be a 1-D int32 or int64 tensor of G+1 offsets" % (who, name))
+    _on(edge_index.device, graph_ptr, edge_ptr)
+    if graph_ptr.numel() != edge_ptr.numel():
+        raise ValueError("%s: graph_ptr has %d entries, edge_ptr %d" % (who, graph_ptr.numel(), edge_ptr.numel()))
+
+
 def laplacian_eig(edge_index, graph_ptr, edge_ptr, max_freqs, max_nodes=None, edges_local=False, num_nodes=None):
     """The max_freqs smallest eigenpairs of L = D - A of every graph of a ragged set, one workgroup per graph, one launch: the
     reference's compute_posenc_stats for pe_types ['LapPE'] with laplacian_norm none and eigvec_norm L2
@@ -1324,18 +1340,7 @@ def laplacian_eig(edge_index, graph_ptr, edge_ptr, max_freqs, max_nodes=None, ed
     max_nodes: the largest graph as the HOST knows it, num_nodes: N likewise; None costs one read-back of graph_ptr each.
     Limits: laplacian_eig_limits()[0] = 256 nodes per graph, max_freqs <= 32; beyond them RuntimeError, raised before anything
     is launched."""
-    if not torch.is_tensor(edge_index) or edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.size(0) != 2:
-        raise TypeError("laplacian_eig: edge_index must be an int64 [2, E] tensor")
-    if not edge_index.is_cuda:
-        raise RuntimeError("esc_gnn_amd: the hot path runs on the HIP device only (got a %s tensor); there is no CPU fallback"
-                           % edge_index.device)
-    dev = edge_index.device
-    for name, t in (("graph_ptr", graph_ptr), ("edge_ptr", edge_ptr)):
-        if not torch.is_tensor(t) or t.dtype not in (torch.int32, torch.int64) or t.dim() != 1 or t.numel() < 1:
-            raise TypeError("laplacian_eig: %s must be a 1-D int32 or int64 tensor of G+1 offsets" % name)
-    _on(dev, graph_ptr, edge_ptr)
-    if graph_ptr.numel() != edge_ptr.numel():
-        raise ValueError("laplacian_eig: graph_ptr has %d entries, edge_ptr %d" % (graph_ptr.numel(), edge_ptr.numel()))
+    _ragged_graphs("laplacian_eig", edge_index, graph_ptr, edge_ptr)
     K = int(max_freqs)
     if not 1 <= K <= 32:
         raise RuntimeError("laplacian_eig: max_freqs %d outside 1..32" % K)
@@ -1457,3 +1462,92 @@ def lappe_encode(eigvecs, eigvals, signs, wA, bA, w1, b1):
         raise ValueError("lappe_encode: signs must be [%d]" % K)
     cont = [t.contiguous() for t in (eigvecs.detach(), eigvals.detach(), wA, bA, w1, b1)]
     return _LapPEEncode.apply(cont[0], cont[1], None if signs is None else signs.detach().contiguous(), cont[2], cont[3], cont[4], cont[5])
+
+
+# ---- random-walk structural encoding (csrc/rwse.hip, include/escgnn_rwse.h) ------------------------------------------------------
+def rw_landing_limits():
+    """(most nodes, most edges) of one graph esc_rw_landing takes"""
+    h = nv.lib()
+    return int(h.esc_rw_landing_max_nodes()), int(h.esc_rw_landing_max_edges())
+
+
+def rw_step_mask(ksteps):
+    """the step list as esc_rw_landing takes it: bit k - 1 set for every step k.  ValueError for an empty list, a step outside
+    1..63, a repeat or a list that is not ascending (the columns come out in ascending order: the list must say so itself)."""
+    try:
+        steps = [int(k) for k in ksteps]
+        whole = all(k == s for k, s in zip(ksteps, steps))
+    except (TypeError, ValueError):
+        steps, whole = [], False
+    if not steps or not whole:
+        raise ValueError("rw_landing: ksteps must be a non-empty list of ints, got %r" % (ksteps,))
+    if min(steps) < 1 or max(steps) > 63:
+        raise ValueError("rw_landing: steps outside 1..63 in %r" % (steps,))
+    if len(set(steps)) != len(steps):
+        raise ValueError("rw_landing: a step is repeated in %r" % (steps,))
+    if steps != sorted(steps):
+        raise ValueError("rw_landing: the steps must be ascending, got %r" % (steps,))
+    return sum(1 << (k - 1) for k in steps)
+
+
+def rw_landing(edge_index, graph_ptr, edge_ptr, ksteps, max_nodes=None, max_edges=None, edges_local=False, num_nodes=None):
+    """The landing probabilities (P^k)[i, i], P = D^-1 A, of the k-step random walk for every node of a ragged set of graphs and
+    every k of `ksteps` (a list of ascending ints in 1..63), one workgroup per graph, one launch: the reference's
+    get_rw_landing_probs with edge_weight None and space_dim 0 (GraphGPS/graphgps/transform/posenc_stats.py:185-231).  The edge
+    list is directed and counts as listed: self-loops are kept, duplicates add up, a node without out-edges has a zero row.
+    edge_index, graph_ptr, edge_ptr, edges_local: as in laplacian_eig.  Returns pestat_RWSE [N, K] fp32 - fp64 arithmetic
+    rounded once.  Not differentiable: the statistics are data.
+    max_nodes, max_edges: the largest graph as the HOST knows it, num_nodes: N likewise; None costs one read-back each.
+    Limits: rw_landing_limits() = (256, 7678) nodes and edges per graph; beyond them RuntimeError, raised before anything is
+    launched."""
+    mask = rw_step_mask(ksteps)
+    _ragged_graphs("rw_landing", edge_index, graph_ptr, edge_ptr)
+    dev = edge_index.device
+    node_limit, edge_limit = rw_landing_limits()
+    G = graph_ptr.numel() - 1
+    if max_nodes is None:
+        max_nodes = int((graph_ptr[1:] - graph_ptr[:-1]).max()) if G else 0
+    if max_edges is None:
+        max_edges = int((edge_ptr[1:] - edge_ptr[:-1]).max()) if G else 0
+    max_nodes, max_edges = int(max_nodes), int(max_edges)
+    if max_nodes > node_limit:
+        raise RuntimeError("rw_landing: a graph of %d nodes exceeds the limit of %d nodes per graph" % (max_nodes, node_limit))
+    if max_edges > edge_limit:
+        raise RuntimeError("rw_landing: a graph of %d edges exceeds the limit of %d edges per graph" % (max_edges, edge_limit))
+    if num_nodes is None:
+        num_nodes = int(graph_ptr[-1])
+    N, K = int(num_nodes), bin(mask).count("1")
+    src, dst = edge_index[0].contiguous(), edge_index[1].contiguous()
+    node_ptr, edge_ptr = graph_ptr.to(torch.int64).contiguous(), edge_ptr.to(torch.int64).contiguous()
+    out = torch.empty((N, K), dtype=torch.float32, device=dev)
+    nv.call("esc_rw_landing", nv.ptr(src), nv.ptr(dst), src.numel(), nv.ptr(node_ptr), nv.ptr(edge_ptr), G, N, int(bool(edges_local)), mask,
+            max(max_nodes, 0), max(max_edges, 0), nv.ptr(out), K, nv.stream())
+    return out
+
+
+def rwse_gather(table, node_ptr_all, graph_ids, graph_ptr, num_nodes):
+    """The batch's rows of a split's resident pestat_RWSE table (what the reference's collate does to that key), one launch.
+    table [N_all, K] fp32; node_ptr_all int64 [G_all+1] (device); graph_ids: the batch's graphs in batch order, a HOST int64
+    tensor or list - checked here, an id out of range raises IndexError before anything is launched; graph_ptr int32 [B+1]: the
+    batch's node ranges; num_nodes: the batch's N.  Returns [N, K]."""
+    _dev(table)
+    dev = table.device
+    if table.dim() != 2 or not table.is_contiguous() or table.dtype != torch.float32:
+        raise ValueError("rwse_gather: the table must be a contiguous fp32 [N_all, K] tensor")
+    node_ptr_all = _index_vector(node_ptr_all, "rwse_gather: node_ptr_all", torch.int64)
+    graph_ptr = _index_vector(graph_ptr, "rwse_gather: graph_ptr", torch.int32)
+    _on(dev, node_ptr_all, graph_ptr)
+    G_all, B = node_ptr_all.numel() - 1, graph_ptr.numel() - 1
+    if torch.is_tensor(graph_ids) and graph_ids.is_cuda:
+        raise RuntimeError("rwse_gather: graph_ids must live on the host (they are checked there, without a read-back)")
+    ids_h = torch.as_tensor(graph_ids, dtype=torch.int64).reshape(-1)
+    if ids_h.numel() != B:
+        raise ValueError("rwse_gather: %d graph ids for a batch of %d graphs" % (ids_h.numel(), B))
+    if B and (int(ids_h.min()) < 0 or int(ids_h.max()) >= G_all):
+        raise IndexError("rwse_gather: graph id out of range (the table holds %d graphs)" % G_all)
+    N, K = int(num_nodes), table.size(1)
+    ids_d = ids_h.to(dev, non_blocking=True)
+    out = torch.empty((N, K), dtype=torch.float32, device=dev)
+    nv.call("esc_rwse_gather", nv.ptr(table), nv.ptr(node_ptr_all), G_all, table.size(0), nv.ptr(ids_d), nv.ptr(graph_ptr), B, N, K,
+            nv.ptr(out), K, nv.stream())
+    return out

@@ -15,8 +15,15 @@ max_freqs 8, DeepSet, dim_pe 8, 2 layers): one lappe.LapPETable per split is com
 each), every batch gets its rows with one gather launch, and checkpoints carry the reference's key layout
 (encoder.node_encoder.encoder1.* / encoder2.*).  The default, 0, is TypeDictNode at full width.
 
+--posenc_RWSE 1 adds the random-walk structural encoding GraphGPS is normally run with on ZINC (node encoder TypeDictNode+RWSE,
+or TypeDictNode+LapPE+RWSE with --posenc_LapPE 1 as well): one rwse.RWSETable per split - the landing probabilities of
+--posenc_RWSE_ksteps steps, one launch each - and one more gather launch per batch.  The reference ships no yaml that enables
+RWSE: the posenc_RWSE_* defaults (20 steps, dim_pe 28, linear, BatchNorm on the raw statistics) are upstream GraphGPS's usual
+ZINC values, this project's choice.
+
 Out of scope: BiasedTransformer / attn_bias, Performer and BigBird, the other local GNN types, layer_norm, the other positional
-encodings, graphgym's config system and wandb, a whole-step engine, and data parallelism (WORLD_SIZE > 1 is refused).
+encodings (SignNet, EquivStableLapPE, HKdiagSE, ElstaticSE), graphgym's config system and wandb, a whole-step engine, and data
+parallelism (WORLD_SIZE > 1 is refused).
 
     python -m esc_gnn_amd.run_zinc_gps --h 3 --epochs 2000 --posenc_LapPE 1
 """
@@ -52,6 +59,15 @@ _FLAGS = [  # defaults: GraphGPS/configs/GPS/zinc-GPS.yaml (gt.*, train.batch_si
     ("--posenc_LapPE", dict(type=int, default=0, help="1: node encoder TypeDictNode+LapPE (the reference yaml), 0: TypeDictNode")),
     ("--posenc_LapPE_max_freqs", dict(type=int, default=8, help="posenc_LapPE.eigen.max_freqs")),
     ("--posenc_LapPE_dim_pe", dict(type=int, default=8, help="posenc_LapPE.dim_pe (model DeepSet, layers 2)")),
+    # the reference ships no yaml that enables RWSE: these defaults are upstream GraphGPS's usual ZINC values, this project's choice
+    ("--posenc_RWSE", dict(type=int, default=0, choices=(0, 1), help="1: add the random-walk structural encoding to the node encoder "
+                                                                      "(TypeDictNode+RWSE, with --posenc_LapPE 1 TypeDictNode+LapPE+RWSE)")),
+    ("--posenc_RWSE_ksteps", dict(type=int, default=20, help="posenc_RWSE.kernel.times = range(1, ksteps + 1); default: upstream "
+                                                             "GraphGPS's usual ZINC value, not a file of the reference")),
+    ("--posenc_RWSE_dim_pe", dict(type=int, default=28, help="posenc_RWSE.dim_pe (default: upstream GraphGPS's usual ZINC value)")),
+    ("--posenc_RWSE_model", dict(default="linear", help="posenc_RWSE.model: linear or mlp (default: upstream's usual ZINC value)")),
+    ("--posenc_RWSE_layers", dict(type=int, default=1, help="posenc_RWSE.layers, for model mlp")),
+    ("--posenc_RWSE_raw_norm_type", dict(default="BatchNorm", help="posenc_RWSE.raw_norm_type: BatchNorm or none")),
 ]
 
 
@@ -88,20 +104,37 @@ def main(argv=None):
     stores = [DeviceGraphStore(part, ctx.device) for part in (tr, va, te)]
     widest = [int((s.h_node_ptr[1:] - s.h_node_ptr[:-1]).max()) for s in stores]      # the largest graph of each store: host data
     n_train = len(tr)
-    tables = None
+    tables = [[] for _ in stores]                   # the resident encoding tables of every split, attached to each of its batches in order
     if args.posenc_LapPE:
         from .lappe import LapPETable
         limit = ops.laplacian_eig_limits()[0]
         if max(widest) > limit:
             raise SystemExit("run_zinc_gps: the largest graph has %d nodes, the Laplacian eigen-solver takes at most %d" % (max(widest), limit))
         t12 = time.time()
-        tables = [LapPETable(s, args.posenc_LapPE_max_freqs) for s in stores]
+        for t, s in zip(tables, stores):
+            t.append(LapPETable(s, args.posenc_LapPE_max_freqs))
         torch.cuda.synchronize()
         ctx.say("LapPE table build time cost: {}s,".format(time.time() - t12))
+    if args.posenc_RWSE:
+        from .rwse import RWSETable
+        node_limit, edge_limit = ops.rw_landing_limits()
+        most_edges = max(int((s.h_edge_ptr[1:] - s.h_edge_ptr[:-1]).max()) for s in stores)
+        if max(widest) > node_limit or most_edges > edge_limit:
+            raise SystemExit("run_zinc_gps: the largest graph has %d nodes and %d edges, the random-walk kernel takes at most %d nodes "
+                             "and %d edges per graph" % (max(widest), most_edges, node_limit, edge_limit))
+        if not 1 <= args.posenc_RWSE_ksteps <= 63:
+            raise SystemExit("run_zinc_gps: --posenc_RWSE_ksteps %d outside 1..63" % args.posenc_RWSE_ksteps)
+        t13 = time.time()
+        for t, s in zip(tables, stores):
+            t.append(RWSETable(s, list(range(1, args.posenc_RWSE_ksteps + 1))))
+        torch.cuda.synchronize()
+        ctx.say("RWSE table build time cost: {}s,".format(time.time() - t13))
 
     model = GPSModel(layers=args.layers, dim_hidden=args.dim_hidden, n_heads=args.n_heads, dropout=args.dropout,
                      attn_dropout=args.attn_dropout, node_types=args.node_encoder_num_types, edge_types=args.edge_encoder_num_types,
-                     lap_pe=bool(args.posenc_LapPE), dim_pe=args.posenc_LapPE_dim_pe, max_freqs=args.posenc_LapPE_max_freqs)
+                     lap_pe=bool(args.posenc_LapPE), dim_pe=args.posenc_LapPE_dim_pe, max_freqs=args.posenc_LapPE_max_freqs,
+                     rwse=bool(args.posenc_RWSE), rwse_dim_pe=args.posenc_RWSE_dim_pe, rwse_steps=args.posenc_RWSE_ksteps,
+                     rwse_model=args.posenc_RWSE_model, rwse_layers=args.posenc_RWSE_layers, rwse_raw_norm=args.posenc_RWSE_raw_norm_type)
     limit = ops.attention_max_nodes(args.dim_hidden // args.n_heads)
     if max(widest) > limit:
         raise SystemExit("run_zinc_gps: the largest graph has %d nodes, the attention kernels take at most %d at head_dim %d"
@@ -115,13 +148,15 @@ def main(argv=None):
     gen = torch.Generator().manual_seed(args.seed)
 
     def batches(which, shuffle):
-        if tables is None:
+        if not tables[which]:
             for data, _ in sharded_batches(stores[which], args.batch_size, ctx, shuffle, gen if shuffle else None):
                 data._esc_max_nodes = widest[which]        # an upper bound of this batch's largest graph, known without a read-back
                 yield data
             return
         for ids, _ in sharded_ids(stores[which], args.batch_size, ctx, shuffle, gen if shuffle else None):
-            data = tables[which].attach(stores[which].collate(ids), ids)      # sharded_batches' collate, plus the batch's PE rows
+            data = stores[which].collate(ids)              # sharded_batches' collate, plus the batch's PE rows
+            for table in tables[which]:
+                table.attach(data, ids)
             data._esc_max_nodes = widest[which]
             yield data
 

@@ -1,0 +1,46 @@
+"""Random-walk structural encodings for the graph transformer: the MI355X twin of the reference's compute_posenc_stats for
+pe_types ['RWSE'] (GraphGPS/graphgps/transform/posenc_stats.py:97-104,185-231) - the landing probabilities (P^k)[i, i] of the
+k-step random walk, P = D^-1 A over the edge list as it stands - computed on the device by esc_rw_landing (csrc/rwse.hip), one
+workgroup per graph, K sparse matrix-vector steps per start node instead of the reference's dense n x n matrix powers.
+
+add_rwse(data_or_batch, ksteps) sets the reference's key on one graph or on a collated batch; RWSETable(store, ksteps) computes
+it for a whole split in ONE launch at build time, keeps it in HBM and hands every batch its rows with one gather launch: what the
+reference's dataset pre-transform plus collate do.  The encoder that consumes the key is nn.RWSENodeEncoder.  The twin of
+lappe.py."""
+from . import ops
+from .lappe import _ranges
+
+
+def add_rwse(data, ksteps):
+    """Sets pestat_RWSE [N, K] (fp32) on a graph or a collated batch whose tensors are on the device, and returns it.  Torch
+    plumbing for the ranges plus one launch; the largest node and edge count of a graph are read back (the node count is not
+    when the batch carries `_esc_max_nodes`)."""
+    graph_ptr, edge_ptr, G, widest, N = _ranges(data)
+    data.pestat_RWSE = ops.rw_landing(data.edge_index, graph_ptr, edge_ptr, ksteps, max_nodes=widest, num_nodes=N)
+    return data
+
+
+class RWSETable(object):
+    """The RWSE of every graph of a DeviceGraphStore, resident in HBM: pestat [N_all, K].  Built with one esc_rw_landing launch
+    over the store's flat (graph-local) edge arrays, the largest graph taken from the store's host offsets; attach() is one
+    esc_rwse_gather launch."""
+
+    def __init__(self, store, ksteps):
+        import torch
+        self.store, self.ksteps = store, [int(k) for k in ksteps]
+        n = store.h_node_ptr[1:] - store.h_node_ptr[:-1]           # host data
+        m = store.h_edge_ptr[1:] - store.h_edge_ptr[:-1]
+        self.max_nodes, self.max_edges = int(n.max()), int(m.max())
+        edge_index = torch.stack([store.esrc_all, store.edst_all])
+        self.pestat = ops.rw_landing(edge_index, store.node_ptr, store.edge_ptr, self.ksteps, max_nodes=self.max_nodes,
+                                     max_edges=self.max_edges, edges_local=True, num_nodes=int(store.h_node_ptr[-1]))
+
+    def attach(self, batch, graph_ids):
+        """Sets pestat_RWSE of a batch that store.collate(graph_ids) made; graph_ids on the host (checked there: an id out of
+        range raises IndexError).  One launch, no device-to-host copy."""
+        plan = getattr(batch, "_esc_plan", None)
+        graph_ptr = getattr(plan, "graph_ptr", None)
+        if graph_ptr is None:
+            raise ValueError("RWSETable.attach: the batch does not come from DeviceGraphStore.collate")
+        batch.pestat_RWSE = ops.rwse_gather(self.pestat, self.store.node_ptr, graph_ids, graph_ptr, batch.x.size(0))
+        return batch
