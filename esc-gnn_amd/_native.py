@@ -92,6 +92,14 @@ except OSError as exc:
     raise NativeLibraryError("esc_gnn_amd: cannot read the C header %s the binding is derived from (%s)" % (RWSE_HEADER, exc)) from exc
 RWSE_SIGNATURES = {name: args for name, (args, _) in _RWSE.functions.items()}
 _RET.update({name: ret for name, (_, ret) in _RWSE.functions.items()})
+# the seventh extension header (escgnn_step.h: the optimiser step on the counting engine's two streams and its fast seam)
+STEP_HEADER = os.path.join(os.path.dirname(_abi.HEADER), "escgnn_step.h")
+try:
+    _STEP = _abi.load(STEP_HEADER)
+except OSError as exc:
+    raise NativeLibraryError("esc_gnn_amd: cannot read the C header %s the binding is derived from (%s)" % (STEP_HEADER, exc)) from exc
+STEP_SIGNATURES = {name: args for name, (args, _) in _STEP.functions.items()}
+_RET.update({name: ret for name, (_, ret) in _STEP.functions.items()})
 KIND = {name[len("ESC_K_"):].lower(): v for name, v in _ABI.enum.items() if name != "ESC_K_COUNT"}
 
 CollateArgs = struct("esc_collate_args")
@@ -115,7 +123,7 @@ def lib():
             "esc_gnn_amd: %s not found. The HIP hot path has no fallback — build it with "
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C esc-gnn_amd/csrc`." % LIB_PATH)
     h = ctypes.CDLL(LIB_PATH)
-    for name, args in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()) + list(I2GNN_SIGNATURES.items()) + list(GINEPLUS_SIGNATURES.items()) + list(GPS_SIGNATURES.items()) + list(LAPPE_SIGNATURES.items()) + list(RWSE_SIGNATURES.items()):
+    for name, args in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()) + list(I2GNN_SIGNATURES.items()) + list(GINEPLUS_SIGNATURES.items()) + list(GPS_SIGNATURES.items()) + list(LAPPE_SIGNATURES.items()) + list(RWSE_SIGNATURES.items()) + list(STEP_SIGNATURES.items()):
         try:
             fn = getattr(h, name)
         except AttributeError as exc:

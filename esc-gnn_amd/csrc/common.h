@@ -70,6 +70,14 @@ void arm_last_launch_event(hipEvent_t ev);
 void next_launch_is_last();
 hipEvent_t take_last_launch_event();
 
+// The Adam update over [0, n) of one flat buffer as one launch on `stream` (optim.hip): what esc_adam_step_scaled runs, and what
+// esc_engine_adam_step (engine.hip) runs once per part on the step engine's two streams.
+int adam_launch(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double lr, double beta1, double beta2,
+                double eps, int64_t step, const float* grad_denom, void* stream);
+// the step engine forgets that its last step can be continued in edge-stream order (engine.hip, Seam): called by every update of
+// the parameters that the engine did not order itself
+void seam_reset();
+
 template <typename... KArgs, typename... Args>
 inline void launch(int kind, void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t s,
                    Args... args) {

@@ -13,6 +13,7 @@
 // Model composition followed: /root/reference/run_graphcount.py:134-194 (graph_pred=False, dropout=0,
 // use_cycle=True — the configuration run_graphcount.py:465 instantiates).
 #include "common.h"
+#include "../../include/escgnn_step.h"
 
 #include <map>
 #include <vector>
@@ -131,6 +132,7 @@ struct Ctx {
   int act = 1;                                   // 1 ReLU (counting model), 2 ELU (ZINC): materialised activations
   const float* l1_target = nullptr;              // train_step: the prediction head also leaves d L1 / d pred (forward(), train_step_impl())
   int64_t l1_denom = 0;
+  bool fast_seam = false;                        // the edge pipeline starts in edge-stream order, without the z_ready chain (see Seam)
 };
 
 struct LdsFloorGuard {            // occupancy cap for the GEMMs launched while it lives (edge stream only, forward and backward)
@@ -208,6 +210,7 @@ struct EdgeStream {
   hipStream_t stream = nullptr;
   hipEvent_t z_ready = nullptr, joined = nullptr, lin1_fork = nullptr, lin1_rest = nullptr, lin1_dw = nullptr, e_ready[ESC_MAX_LAYERS] = {}, de_ready[ESC_MAX_LAYERS] = {},
              agg_done[ESC_MAX_LAYERS] = {};
+  hipEvent_t caller_done = nullptr, late_done = nullptr;     // the step boundary (see Seam)
   bool ok = false;
 };
 static int g_use_edge_stream = 1;     // esc_engine_set_side_stream() bit 1
@@ -231,6 +234,8 @@ static EdgeStream& edge_stream() {
     good = good && hipEventCreateWithFlags(&es.lin1_fork, hipEventDisableTiming) == hipSuccess;
     good = good && hipEventCreateWithFlags(&es.lin1_rest, hipEventDisableTiming) == hipSuccess;
     good = good && hipEventCreateWithFlags(&es.lin1_dw, hipEventDisableTiming) == hipSuccess;
+    good = good && hipEventCreateWithFlags(&es.caller_done, hipEventDisableTiming) == hipSuccess;
+    good = good && hipEventCreateWithFlags(&es.late_done, hipEventDisableTiming) == hipSuccess;
     for (int l = 0; l < ESC_MAX_LAYERS; ++l) {
       good = good && hipEventCreateWithFlags(&es.e_ready[l], hipEventDisableTiming) == hipSuccess;
       good = good && hipEventCreateWithFlags(&es.de_ready[l], hipEventDisableTiming) == hipSuccess;
@@ -519,7 +524,12 @@ static int forward(const Ctx& c) {
   EdgeStream& es = edge_stream_for(E);
   Ctx ce = c;
   if (es.ok) {
-    ESC_TRY(chain(es.z_ready, (hipStream_t)c.s, es.stream));       // the batch arrays were produced on the caller's stream
+    // the batch arrays were produced on the caller's stream.  Fast seam: ONE launch, the ESC bag, goes out in edge-stream order —
+    // its index arrays were queued in front of caller_done, which the edge stream has waited for ahead of its Adam launch
+    // (esc_engine_adam_step), and its table was updated by that launch; it writes workspace only.  The chain follows behind it (seam_chain
+    // below): everything else the edge pipeline reads or writes — the other parameters, the BatchNorm running statistics — is ordered
+    // behind the caller's stream as always, and the record's way to the edge stream is hidden behind the bag's 24 us.
+    if (!c.fast_seam) ESC_TRY(chain(es.z_ready, (hipStream_t)c.s, es.stream));
     ce = edge_ctx(c, es.stream);
   }
   // ESC bag (esc_bag_fwd_rows; the LDS-staged table slices are an option that is off by default); in training mode its epilogue
@@ -527,10 +537,12 @@ static int forward(const Ctx& c) {
   const int64_t bag_block = (c.train && !sync_on(ce)) ? esc_bag_fwd_stats_block_rows(m->z_table, m->z_rows, H, y.Zb, H, E) : 0;
   if (bag_block > 0) {
     ESC_TRY(esc_bag_fwd_rows(m->z_table, m->z_rows, H, b->row_ptr, b->bag_idx, b->bag_val, E, y.Zb, H, 0, ce.y.col_stats, ce.s));
+    if (c.fast_seam) ESC_TRY(chain(es.z_ready, (hipStream_t)c.s, es.stream));       // seam_chain
     ESC_TRY(esc_bn_stats_from_partials_rows(ce.y.col_stats, E, H, bag_block, m->zbn0.eps, m->zbn0.momentum, y.zb0.mean, y.zb0.invstd,
                                             m->zbn0.running_mean, m->zbn0.running_var, m->zbn0.gamma, m->zbn0.beta, y.zb0.scale, y.zb0.shift, ce.s));
   } else {
     ESC_TRY(esc_bag_fwd_rows(m->z_table, m->z_rows, H, b->row_ptr, b->bag_idx, b->bag_val, E, y.Zb, H, 0, nullptr, ce.s));
+    if (c.fast_seam) ESC_TRY(chain(es.z_ready, (hipStream_t)c.s, es.stream));       // seam_chain
     ESC_TRY(bn_coeffs(ce, y.Zb, H, E, m->zbn0, y.zb0));
   }
   // Edge-sized activations are materialised: the affine+ReLU prologue costs the edge-row GEMMs ~25 % (VALU-bound staging), more
@@ -634,23 +646,77 @@ static int forward(const Ctx& c) {
 struct Pending {
   bool open = false;
   bool join = false;
+  bool halves = false;             // opened by esc_engine_train_step_begin: the caller enqueues work between the two halves
   hipStream_t stream = nullptr;
+  const float* workspace = nullptr;
+  const float *z_table = nullptr, *dz_table = nullptr;      // one parameter of the edge pipeline and its gradient (see Seam)
   std::vector<esc_reduce_job> edge_jobs;
 };
 static Pending& pending() {
   static thread_local Pending p;
   return p;
 }
+
+// ---- the step boundary (DESIGN.md *Step engine, step boundary*).  The edge stream ends a step (bag gradient, its last slab
+// reduce) and begins the next one (ESC bag, z_embedding, the edge terms); between the two only the Adam update of the parameters it
+// reads is NEEDED.  The seam used to cross to the caller's stream and back: joined -> [caller] reduce, Adam over every parameter ->
+// z_ready -> [edge] bag, two event hops on the critical path while the GPU is close to idle.  Now the edge stream runs its last
+// reduce itself (backward()), esc_engine_adam_step() puts the update of the optimiser's LATE bucket behind it on the edge stream
+// (the rest beside it on the caller's stream), and a step that follows at once starts its edge pipeline in stream order, without
+// the z_ready chain in front of its first launch: the FAST SEAM.  Only that launch, the ESC bag, goes out unordered against the
+// caller's stream (forward()); the chain follows behind it, so the rest of the edge pipeline (the other parameters, the BatchNorm
+// running statistics it updates) keeps its order against whatever the caller queued.  The late Adam launch itself is ordered
+// behind _end, not behind later work of the caller: FlatAdam.step() takes esc_adam_step_scaled when a torch op has written
+// gradients, parameters or state since.  The seam is taken only when the engine knows that nothing else can have touched what the
+// bag reads:
+//   stage 1  esc_engine_train_step_end has just closed a two-stream step that was run in two halves.  caller_done was recorded on the
+//            caller's stream in front of its wait for `joined`: behind it are the node pipeline's last launch (every reader of the
+//            workspace, every gradient the node stream finishes) and whatever the caller queued between the halves (the next collate).
+//   stage 2  ... and esc_engine_adam_step ran next, on that stream, over buffers that hold the step's z_table / dz_table in their late part.
+//   claimed  esc_engine_claim_fast_seam: the caller says that the arrays of the next batch were queued before that _end.
+// Every other engine entry (enter_engine), esc_adam_step[_scaled] (seam_reset, common.h) and esc_engine_drop_fast_seam put the
+// stage back to 0, and the next step takes the z_ready chain.  g_legacy_seam (bit 8 of esc_engine_set_side_stream) keeps the former
+// seam altogether: A/B runs and the tests' reference.
+static int g_legacy_seam = 0;
+struct Seam {
+  int stage = 0;
+  bool claimed = false;
+  hipStream_t stream = nullptr;
+  const float* workspace = nullptr;
+  const float *z_table = nullptr, *dz_table = nullptr;
+  const float *late_lo = nullptr, *late_hi = nullptr;        // parameters the last split update wrote in edge-stream order
+  int64_t taken = 0, split_steps = 0;
+};
+static Seam& seam() {
+  static thread_local Seam s;
+  return s;
+}
+void seam_reset() { seam().stage = 0; seam().claimed = false; }
+
 static int finish_pending(Pending& p) {
   if (!p.open) return ESC_OK;
   p.open = false;
   EdgeStream& es = edge_stream();
+  const bool edge_reduced = p.join && p.edge_jobs.empty();      // (backward(): the edge stream has run its last reduce itself)
+  if (p.join && p.halves && !g_legacy_seam && hipEventRecord(es.caller_done, p.stream) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
   if (p.join && hipStreamWaitEvent(p.stream, es.joined, 0) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
   if (!p.edge_jobs.empty()) ESC_TRY(esc_slab_reduce_jobs(p.edge_jobs.data(), (int)p.edge_jobs.size(), p.stream));
   p.edge_jobs.clear();
   mark(PH_END, p.stream);
   if (phases().on) ++phases().steps;
+  Seam& sm = seam();
+  seam_reset();
+  if (p.halves && edge_reduced && !g_legacy_seam) {
+    sm.stage = 1;
+    sm.stream = p.stream; sm.workspace = p.workspace; sm.z_table = p.z_table; sm.dz_table = p.dz_table;
+  }
   return ESC_OK;
+}
+// every entry but the two that continue a seam: an open step is closed, and whatever follows starts from the z_ready chain
+static int enter_engine() {
+  const int rc = finish_pending(pending());
+  seam_reset();
+  return rc;
 }
 
 static int backward(const Ctx& c, Pending* defer) {
@@ -808,10 +874,20 @@ static int backward(const Ctx& c, Pending* defer) {
   if (k0_split && hipStreamWaitEvent((hipStream_t)c.s, es.lin1_dw, 0) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
   if (c.jobs && !c.jobs->empty()) ESC_TRY(esc_slab_reduce_jobs(c.jobs->data(), (int)c.jobs->size(), c.s));
   if (es.ok) {
-    if (hipEventRecord(es.joined, es.stream) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
+    if (!g_legacy_seam) {
+      // the edge pipeline's last slabs (z_embedding's Linear) are reduced where they were made, behind the bag gradient: the caller's
+      // stream waits for `joined` as before, but nothing of the step is left to do behind that wait, and what follows on the edge
+      // stream (the late bucket's Adam, the next step's bag) needs no hop to the caller's stream and back.  `joined` is the stop
+      // event of the reduce launch.  Same launch, same jobs: the same bits.
+      const ArmedEvent arm(es.joined, !edge_jobs.empty());
+      if (!edge_jobs.empty()) ESC_TRY(esc_slab_reduce_jobs(edge_jobs.data(), (int)edge_jobs.size(), es.stream));
+      edge_jobs.clear();
+      ESC_TRY(chain_armed(es.joined, arm, es.stream, nullptr));
+    } else if (hipEventRecord(es.joined, es.stream) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
     Pending local;
     Pending& p = defer ? *defer : local;
-    p.open = true; p.join = true; p.stream = (hipStream_t)c.s;
+    p.open = true; p.join = true; p.halves = defer != nullptr; p.stream = (hipStream_t)c.s;
+    p.workspace = nullptr; p.z_table = m->z_table; p.dz_table = m->dz_table;      // (train_step_impl names the workspace)
     p.edge_jobs.swap(edge_jobs);
     if (!defer) return finish_pending(p);
   }
@@ -1396,14 +1472,61 @@ int esc_engine_set_two_stream_min_edges(int64_t edges) {
 }
 
 /* bit 1: the edge pipeline on a second stream; bit 6: every cross-stream dependency an event record (see ArmedEvent) and the readout
- * block one launch; bit 7: the readout Linear's edge-stream block one launch (see kReadoutDxLds).  The other bits selected schedules
+ * block one launch; bit 7: the readout Linear's edge-stream block one launch (see kReadoutDxLds); bit 8: the former boundary between
+ * two steps, through the caller's stream (see Seam).  The other bits selected schedules
  * that have been retired (DESIGN.md *Retired step-engine switches*) and are ignored. */
 int esc_engine_set_side_stream(int on) {
   g_use_edge_stream = (on & 2) != 0;
   g_plain_events = (on & 64) != 0;
   g_readout_one_launch = (on & 128) != 0;
+  g_legacy_seam = (on & 256) != 0;
+  seam_reset();
   return ESC_OK;
 }
+
+/* ---- the step boundary (escgnn_step.h; see Seam) -------------------------------------------------------------------------- */
+int esc_engine_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, int64_t n_early,
+                         double lr, double beta1, double beta2, double eps, int64_t step, void* stream) {
+  ESC_REQUIRE(param && grad && exp_avg && exp_avg_sq, "esc_engine_adam_step: null pointer");
+  ESC_REQUIRE(n >= 0 && n_early >= 0 && n_early <= n && step >= 1, "esc_engine_adam_step: bad n/n_early/step");
+  Seam& sm = seam();
+  // the buffers are the ones the step that has just ended trained: its edge parameters and their gradients lie in the late part
+  const bool split = sm.stage == 1 && !g_legacy_seam && sm.stream == (hipStream_t)stream && n_early < n &&
+                     sm.z_table >= param + n_early && sm.z_table < param + n && sm.dz_table >= grad + n_early && sm.dz_table < grad + n;
+  seam_reset();
+  if (!split) return adam_launch(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, nullptr, stream);
+  EdgeStream& es = edge_stream();          // (stage 1: the step ran on it)
+  if (!es.ok) return adam_launch(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, nullptr, stream);
+  // the late part on the edge stream, behind its last reduce and behind caller_done (the gradients of that part which the node
+  // stream finishes: conv[0].lin's, reduced with the node-side jobs); late_done is the stop event of the launch
+  if (hipStreamWaitEvent(es.stream, es.caller_done, 0) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
+  {
+    const ArmedEvent arm(es.late_done, true);
+    ESC_TRY(adam_launch(param + n_early, grad + n_early, exp_avg + n_early, exp_avg_sq + n_early, n - n_early, lr, beta1, beta2, eps, step,
+                        nullptr, es.stream));
+    ESC_TRY(chain_armed(es.late_done, arm, es.stream, nullptr));
+  }
+  // ... the rest beside it; the caller's stream then holds every parameter in its order, as after one launch over all of them
+  ESC_TRY(adam_launch(param, grad, exp_avg, exp_avg_sq, n_early, lr, beta1, beta2, eps, step, nullptr, stream));
+  if (hipStreamWaitEvent((hipStream_t)stream, es.late_done, 0) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
+  sm.stage = 2;
+  sm.late_lo = param + n_early; sm.late_hi = param + n;
+  ++sm.split_steps;
+  return ESC_OK;
+}
+
+int esc_engine_claim_fast_seam(void) {
+  Seam& sm = seam();
+  sm.claimed = sm.stage == 2;
+  return ESC_OK;
+}
+
+int esc_engine_drop_fast_seam(void) {
+  seam_reset();
+  return ESC_OK;
+}
+
+int64_t esc_engine_seam_count(int which) { return which == 0 ? seam().taken : which == 1 ? seam().split_steps : -1; }
 
 /* diagnostics: mean milliseconds between the phase marks of the last recorded steps (ESC_PHASE_TIMING=1); call after a
  * device synchronise.  out[0..5]: start->edge-forward done, start->node-forward done, node-forward done->node-backward done,
@@ -1453,20 +1576,25 @@ static int train_step_impl(const esc_nested_gin_t* m, const esc_batch_t* b, floa
 
 int esc_engine_train_step(const esc_nested_gin_t* m, const esc_batch_t* b, float* workspace,
                           int64_t loss_denom, float* loss, float* pred, void* stream) {
-  ESC_TRY(finish_pending(pending()));
+  ESC_TRY(enter_engine());
   return train_step_impl(m, b, workspace, loss_denom, loss, pred, stream, nullptr);
 }
 
 int esc_engine_train_step_begin(const esc_nested_gin_t* m, const esc_batch_t* b, float* workspace,
                                 int64_t loss_denom, float* loss, float* pred, void* stream) {
-  ESC_TRY(finish_pending(pending()));
+  ESC_TRY(finish_pending(pending()));      // (not enter_engine: a split optimiser step in front of this call keeps its seam)
   return train_step_impl(m, b, workspace, loss_denom, loss, pred, stream, &pending());
 }
+
 
 int esc_engine_train_step_end(void) { return finish_pending(pending()); }
 
 static int train_step_impl(const esc_nested_gin_t* m, const esc_batch_t* b, float* workspace,
                            int64_t loss_denom, float* loss, float* pred, void* stream, Pending* defer) {
+  // (a claim is for this call only, whatever becomes of it: taken off before the first return)
+  Seam& sm = seam();
+  const bool seam_offered = defer != nullptr && sm.stage == 2 && sm.claimed && !g_legacy_seam;
+  seam_reset();
   int rc = check(m, b, workspace, true);
   if (rc) return rc;
   ESC_REQUIRE(loss, "esc_engine_train_step: null loss pointer");
@@ -1478,6 +1606,11 @@ static int train_step_impl(const esc_nested_gin_t* m, const esc_batch_t* b, floa
   const bool head_l1 = es.ok && m->hidden <= 1024 &&
                        esc_linear_fwd_l1_ok(c.y.Yl, m->hidden, m->lin2.w, m->hidden, c.y.bl.scale, c.y.bl.shift) != 0;
   if (head_l1) { c.l1_target = b->y; c.l1_denom = denom; }
+  // the fast seam (see Seam): this call follows a split optimiser step at once, on the same stream and workspace, the caller has
+  // claimed the batch, and the one parameter the ESC bag reads was updated on the edge stream
+  c.fast_seam = seam_offered && es.ok && !sync_on(c) && sm.stream == (hipStream_t)stream && sm.workspace == workspace &&
+                m->z_table >= sm.late_lo && m->z_table < sm.late_hi;
+  if (c.fast_seam) ++sm.taken;
   ESC_TRY(forward(c));
   if (head_l1) {              // the loss VALUE: on the edge stream (idle here), ordered behind the head by forward(); the step's join covers it
     ESC_TRY(esc_l1_loss(c.y.pred, b->y, b->N, denom, 1.0f, loss, nullptr, es.stream));
@@ -1486,7 +1619,9 @@ static int train_step_impl(const esc_nested_gin_t* m, const esc_batch_t* b, floa
   }
   mark(PH_NODE_FWD_DONE, stream);
   if (pred) ESC_TRY(copy_floats(pred, c.y.pred, b->N, stream, "esc_engine_train_step"));
-  return backward(c, defer);
+  rc = backward(c, defer);
+  if (defer != nullptr) defer->workspace = workspace;      // (what the next call's argument is compared with)
+  return rc;
 }
 
 // The step as an autograd node: forward in training mode (batch statistics, activations kept in `workspace`), then —
@@ -1494,7 +1629,7 @@ static int train_step_impl(const esc_nested_gin_t* m, const esc_batch_t* b, floa
 // between.  This is what lets `NestedGIN_eff.forward` itself run on the engine inside a user's own training loop.
 int esc_engine_forward_train(const esc_nested_gin_t* m, const esc_batch_t* b, float* workspace, float* pred,
                              void* stream) {
-  ESC_TRY(finish_pending(pending()));
+  ESC_TRY(enter_engine());
   int rc = check(m, b, workspace, true, false);
   if (rc) return rc;
   ESC_REQUIRE(pred, "esc_engine_forward_train: null output");
@@ -1507,7 +1642,7 @@ int esc_engine_forward_train(const esc_nested_gin_t* m, const esc_batch_t* b, fl
 
 int esc_engine_backward(const esc_nested_gin_t* m, const esc_batch_t* b, float* workspace, const float* dpred,
                         void* stream) {
-  ESC_TRY(finish_pending(pending()));
+  ESC_TRY(enter_engine());
   int rc = check(m, b, workspace, true, false);
   if (rc) return rc;
   ESC_REQUIRE(dpred, "esc_engine_backward: null gradient");
@@ -1520,7 +1655,7 @@ int esc_engine_backward(const esc_nested_gin_t* m, const esc_batch_t* b, float* 
 
 int esc_engine_predict(const esc_nested_gin_t* m, const esc_batch_t* b, float* workspace, float* pred,
                        void* stream) {
-  ESC_TRY(finish_pending(pending()));
+  ESC_TRY(enter_engine());
   int rc = check(m, b, workspace, false);
   if (rc) return rc;
   ESC_REQUIRE(pred, "esc_engine_predict: null output");
@@ -1540,7 +1675,7 @@ static int64_t zinc_rows(const esc_zinc_gin_t* m, const esc_mol_batch_t* b) { re
 
 int esc_zinc_train_step(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, float* workspace, int64_t loss_denom,
                         float* loss, float* pred, void* stream) {
-  ESC_TRY(finish_pending(pending()));
+  ESC_TRY(enter_engine());
   int rc = check_zinc(m, b, workspace, true, true);
   if (rc) return rc;
   ESC_REQUIRE(loss, "esc_zinc_train_step: null loss pointer");
@@ -1555,7 +1690,7 @@ int esc_zinc_train_step(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, float
 }
 
 int esc_zinc_forward_train(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, float* workspace, float* pred, void* stream) {
-  ESC_TRY(finish_pending(pending()));
+  ESC_TRY(enter_engine());
   int rc = check_zinc(m, b, workspace, true, false);
   if (rc) return rc;
   ESC_REQUIRE(pred, "esc_zinc_forward_train: null output");
@@ -1567,7 +1702,7 @@ int esc_zinc_forward_train(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, fl
 }
 
 int esc_zinc_backward(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, float* workspace, const float* dpred, void* stream) {
-  ESC_TRY(finish_pending(pending()));
+  ESC_TRY(enter_engine());
   int rc = check_zinc(m, b, workspace, true, false);
   if (rc) return rc;
   ESC_REQUIRE(dpred, "esc_zinc_backward: null gradient");
@@ -1579,7 +1714,7 @@ int esc_zinc_backward(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, float* 
 }
 
 int esc_zinc_predict(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, float* workspace, float* pred, void* stream) {
-  ESC_TRY(finish_pending(pending()));
+  ESC_TRY(enter_engine());
   int rc = check_zinc(m, b, workspace, false, false);
   if (rc) return rc;
   ESC_REQUIRE(pred, "esc_zinc_predict: null output");
@@ -1597,7 +1732,7 @@ int64_t esc_ogb_workspace_floats(const esc_ogb_gnn_t* m, int64_t N, int64_t E, i
 
 int esc_ogb_train_step(const esc_ogb_gnn_t* m, const esc_ogb_batch_t* b, float* workspace, int64_t loss_denom, float* loss,
                        float* logits, void* stream) {
-  ESC_TRY(finish_pending(pending()));
+  ESC_TRY(enter_engine());
   int rc = check_ogb(m, b, workspace, true, true);
   if (rc) return rc;
   ESC_REQUIRE(loss, "esc_ogb_train_step: null loss pointer");
@@ -1611,7 +1746,7 @@ int esc_ogb_train_step(const esc_ogb_gnn_t* m, const esc_ogb_batch_t* b, float* 
 }
 
 int esc_ogb_forward_train(const esc_ogb_gnn_t* m, const esc_ogb_batch_t* b, float* workspace, float* logits, void* stream) {
-  ESC_TRY(finish_pending(pending()));
+  ESC_TRY(enter_engine());
   int rc = check_ogb(m, b, workspace, true, false);
   if (rc) return rc;
   ESC_REQUIRE(logits, "esc_ogb_forward_train: null output");
@@ -1623,7 +1758,7 @@ int esc_ogb_forward_train(const esc_ogb_gnn_t* m, const esc_ogb_batch_t* b, floa
 }
 
 int esc_ogb_backward(const esc_ogb_gnn_t* m, const esc_ogb_batch_t* b, float* workspace, const float* dlogits, void* stream) {
-  ESC_TRY(finish_pending(pending()));
+  ESC_TRY(enter_engine());
   int rc = check_ogb(m, b, workspace, true, false);
   if (rc) return rc;
   ESC_REQUIRE(dlogits, "esc_ogb_backward: null gradient");
@@ -1635,7 +1770,7 @@ int esc_ogb_backward(const esc_ogb_gnn_t* m, const esc_ogb_batch_t* b, float* wo
 }
 
 int esc_ogb_predict(const esc_ogb_gnn_t* m, const esc_ogb_batch_t* b, float* workspace, float* logits, void* stream) {
-  ESC_TRY(finish_pending(pending()));
+  ESC_TRY(enter_engine());
   int rc = check_ogb(m, b, workspace, false, false);
   if (rc) return rc;
   ESC_REQUIRE(logits, "esc_ogb_predict: null output");

@@ -87,6 +87,24 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   }
 }
 
+// One launch over [0, n).  The update of element i reads and writes element i of the four buffers and nothing else, and its
+// arithmetic does not depend on n, on the grid or on which thread runs it: a launch over [0, n) and two launches over [0, k) and
+// [k, n) — on any streams — leave the same bits (esc_engine_adam_step splits the flat buffer that way).
+int adam_launch(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double lr, double beta1, double beta2,
+                double eps, int64_t step, const float* grad_denom, void* stream) {
+  ESC_REQUIRE(param && grad && exp_avg && exp_avg_sq, "esc_adam_step: null pointer");
+  ESC_REQUIRE(n >= 0 && step >= 1, "esc_adam_step: bad n/step");
+  if (n == 0) return ESC_OK;
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
+  const unsigned blocks = (unsigned)(cdiv(n, 256) < 2048 ? cdiv(n, 256) : 2048);
+  esc::launch(-1, adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n,
+                     (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)sqrt(bc2), (float)eps,
+                     (float)(-lr / bc1), grad_denom);
+  ESC_CHECK_LAUNCH("esc_adam_step");
+  return ESC_OK;
+}
+
 }  // namespace esc
 
 using namespace esc;
@@ -119,17 +137,8 @@ int esc_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
 int esc_adam_step_scaled(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                          double lr, double beta1, double beta2, double eps, int64_t step,
                          const float* grad_denom, void* stream) {
-  ESC_REQUIRE(param && grad && exp_avg && exp_avg_sq, "esc_adam_step: null pointer");
-  ESC_REQUIRE(n >= 0 && step >= 1, "esc_adam_step: bad n/step");
-  if (n == 0) return ESC_OK;
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  const unsigned blocks = (unsigned)(cdiv(n, 256) < 2048 ? cdiv(n, 256) : 2048);
-  esc::launch(-1, adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n,
-                     (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)sqrt(bc2), (float)eps,
-                     (float)(-lr / bc1), grad_denom);
-  ESC_CHECK_LAUNCH("esc_adam_step");
-  return ESC_OK;
+  esc::seam_reset();        // an update the step engine did not order: its next step starts from the caller's stream (engine.hip, Seam)
+  return esc::adam_launch(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, grad_denom, stream);
 }
 
 }  // extern "C"

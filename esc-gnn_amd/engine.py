@@ -762,6 +762,7 @@ class _FamilyEngine(_AddressGuard):
         self._dev = fam.device(m)
         self._counters = _bn_counters(m) if fam.py_counters else []
         self._open = None
+        self._seam_mark = None
         self._guard_arm()
 
     def _workspace(self, b):
@@ -783,6 +784,8 @@ class _FamilyEngine(_AddressGuard):
         ws = self._workspace(b)
         loss = torch.empty(1, dtype=torch.float32, device=self._dev)
         pred = torch.empty(fam.pred_shape(m, b), dtype=torch.float32, device=self._dev) if return_pred else None
+        if entry.endswith("_begin") and self._claims_fast_seam(keep):
+            nv.call("esc_engine_claim_fast_seam")                         # (the call right in front of the step: escgnn_step.h)
         nv.call(fam.prefix + entry, ctypes.byref(self._desc), ctypes.byref(b), ws.data_ptr(), int(loss_denom or 0),
                 loss.data_ptr(), nv.ptr(pred), nv.stream())
         self._mark_bucket_written()
@@ -820,8 +823,39 @@ class StepEngine(_FamilyEngine):
         return self._step("train_step_begin", data, loss_denom, return_pred)
 
     def end_step(self):
+        from .store import collate_seq
         nv.call("esc_engine_train_step_end")
         self._open = None
+        self._seam_mark = collate_seq()          # every batch collated so far was queued in front of this call
+        bucket = _bucket_of(self._guard_params[0])
+        if hasattr(bucket, "write_versions"):    # FlatAdam: what torch has written so far; step() and begin_step() compare
+            bucket._seam_versions = bucket.write_versions()
+
+    def _claims_fast_seam(self, keep):
+        """May the library start this step's edge pipeline behind its own Adam launch, without waiting for the current stream
+        (escgnn_step.h, DESIGN.md *Step engine, step boundary*)?  Yes for a batch that DeviceGraphStore.collate queued on this
+        stream before the last end_step() and whose arrays are still the ones it filled: same plan (plan_of rebuilds it when an
+        index tensor was replaced or edited), same x and y storage, same in-place versions.  The library takes the claim only
+        when FlatAdam.step() was the call in front of this one and ran split over the engine's two streams."""
+        x, y, plan = keep
+        stamp, mark = getattr(plan, "_collate_stamp", None), getattr(self, "_seam_mark", None)
+        if stamp is None or mark is None:
+            return False
+        bucket = _bucket_of(self._guard_params[0])
+        if not hasattr(bucket, "write_versions") or bucket._seam_versions != bucket.write_versions():
+            return False                         # a torch op wrote parameters, gradients or optimiser state since end_step()
+        seq, sig_x, sig_y, stream = stamp
+        return (seq <= mark and stream == nv.stream() and sig_x[0] == x.data_ptr() and sig_x[2] == x._version and
+                sig_y[0] == y.data_ptr() and sig_y[2] == y._version)
+
+    def drop_fast_seam(self):
+        """For a caller that, between end_step() and the next begin_step(), wrote gradients, parameters, optimiser state or the
+        next batch's arrays in a way torch's version counters do not show (through `.data`, by raw address, from another library):
+        the next FlatAdam.step() is then one launch on the current stream and the next step starts behind everything queued there.
+        Writes by ordinary torch ops are seen (FlatAdam.write_versions, the batch's stamp) and need no call.  Also for a caller
+        that READS edge-pipeline parameters or the optimiser's moment buffers on the current stream between end_step() and
+        FlatAdam.step() (an EMA or checkpoint copy taken just there): the late bucket's update is not ordered behind such a read."""
+        nv.call("esc_engine_drop_fast_seam")
 
 
 class ZincStepEngine(_FamilyEngine):

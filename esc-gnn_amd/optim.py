@@ -11,6 +11,11 @@ from . import _native as nv
 from .parallel import FlatBucket
 
 
+def _several_ranks():
+    import torch.distributed as dist
+    return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+
+
 class FlatAdam(FlatBucket):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, late=None, weight_decay=0.0):
         """weight_decay: decoupled (torch.optim.AdamW: p *= 1 - lr * weight_decay before the update), as one scaling of the flat
@@ -25,6 +30,15 @@ class FlatAdam(FlatBucket):
         if weight_decay:                                  # (the key exists only then: checkpoints without decay keep their layout)
             self.param_groups[0]["weight_decay"] = weight_decay
         self.step_count = 0
+        self._seam_versions = None        # write_versions() as StepEngine.end_step() saw them
+
+    def write_versions(self):
+        """torch's in-place version counters of everything step() reads or writes: the gradient store (every p.grad is a view
+        of it), the flat parameter buffer and every parameter (a re-homed parameter keeps a counter of its own), the two moment
+        buffers.  A torch op that writes one of them moves a counter; the library's own launches, which go by raw address, and
+        writes through `.data` do not."""
+        return (self._grad_store._version, self.flat_param._version, self.exp_avg._version, self.exp_avg_sq._version,
+                tuple(p._version for p in self.params))
 
     def step(self, grad_denom=None):
         """One Adam update.  grad_denom: device scalar the gradients are divided by inside the launch (the global
@@ -33,6 +47,17 @@ class FlatAdam(FlatBucket):
         self.step_count += 1
         if g.get("weight_decay"):
             self.flat_param.mul_(1.0 - float(g["lr"]) * float(g["weight_decay"]))
+        elif (grad_denom is None and self.early_numel < self.numel and self._seam_versions is not None and
+              self._seam_versions == self.write_versions() and not _several_ranks()):
+            # the plain step of a bucket with a `late` part: behind a two-stream StepEngine step over these very buffers the library
+            # updates that part on the engine's edge stream (escgnn_step.h); it finds out by the addresses, and anywhere else this
+            # is the call below.  That launch is NOT ordered behind what the caller queued on its stream since end_step(): only
+            # when no torch op has written a gradient, a parameter or the optimiser state since then (clipping, scaling,
+            # accumulation, a weight clamp: all of them show in the version counters end_step() noted).
+            nv.call("esc_engine_adam_step", nv.ptr(self.flat_param), nv.ptr(self.flat_grad), nv.ptr(self.exp_avg),
+                    nv.ptr(self.exp_avg_sq), self.flat_param.numel(), self.early_numel, float(g["lr"]), float(g["betas"][0]),
+                    float(g["betas"][1]), float(g["eps"]), self.step_count, nv.stream())
+            return
         nv.call("esc_adam_step_scaled", nv.ptr(self.flat_param), nv.ptr(self.flat_grad), nv.ptr(self.exp_avg),
                 nv.ptr(self.exp_avg_sq), self.flat_param.numel(), float(g["lr"]), float(g["betas"][0]),
                 float(g["betas"][1]), float(g["eps"]), self.step_count, nv.ptr(grad_denom), nv.stream())

@@ -18,6 +18,16 @@ from .plan import BatchPlan, plan_key, _sig
 
 N_COLS = 1800
 
+# Every collate takes the next number and leaves it on the batch's plan with the identity of the arrays it filled.  StepEngine
+# compares it with the number it saw at end_step: a batch collated before that call, and not touched since, may start the next
+# step's edge pipeline without waiting for the caller's stream (engine.py, StepEngine._claims_fast_seam).
+_collate_seq = [0]
+
+
+def collate_seq():
+    """number of the last collate of this process"""
+    return _collate_seq[0]
+
 
 def _stable_group(key, n_keys):
     """positions grouped by key (stable) -> (ptr int64[n_keys+1], perm int64)."""
@@ -352,6 +362,8 @@ class DeviceGraphStore(object):
                 out[k]._esc_known_range = (rng, out[k]._version)
         plan._key = plan_key(out, N_COLS)                    # valid as long as nobody swaps or edits the index tensors
         object.__setattr__(out, "_esc_plan", plan)
+        _collate_seq[0] += 1
+        plan._collate_stamp = (_collate_seq[0], _sig(out.x), _sig(out.y), s)      # (s: the stream the arrays were queued on)
         has_attr = self.edge_attr_all is not None
 
         def lazy_slices():            # Batch.to_data_list bookkeeping (reference batch.py:151-211), only when asked for

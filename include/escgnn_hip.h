@@ -516,7 +516,11 @@ typedef struct esc_batch_t {
  * Same kernels, arguments and results either way (A/B runs: `bench.py --streams 66`).  Set also implies bit 7.
  * bit 7 (value 128, default clear): the edge-stream block of the readout Linear's backward (lin1's columns of the layers that are
  * not the last).  Clear: two launches of its fused kernel, the dX tiles first at one workgroup per CU, and the node chain waits for
- * those only.  Set: one launch with an event record behind it, as before.  Same tiles and results either way. */
+ * those only.  Set: one launch with an event record behind it, as before.  Same tiles and results either way.
+ * bit 8 (value 256, default clear): the boundary between two steps (escgnn_step.h).  Clear: the edge stream runs its last slab
+ * reduce itself, esc_engine_adam_step updates the optimiser's late bucket there, and a claimed next step starts its edge pipeline
+ * in edge-stream order.  Set: the last reduce behind the join on the caller's stream, esc_engine_adam_step one launch on the
+ * caller's stream, every step behind the z_ready record, as before.  Same kernels and results either way. */
 int esc_engine_set_side_stream(int on);
 /* all three engines: smallest batch (in edges) whose edge pipeline runs on the second stream (default 12 000; 0 = always).
  * Smaller batches — ZINC at bs 128, the 16-graph per-rank slices of a strong-scaling run of the counting model — are launch-latency

@@ -25,7 +25,7 @@ for mode in modes:
         nv.call("esc_engine_set_side_stream", mode)
     torch.manual_seed(0)
     m = E.NestedGIN_eff(None, 4, 256, use_rd=True, graph_pred=False, dropout=0, edge_nest=True, use_cycle=True).to(DEV)
-    opt = E.optim.FlatAdam(m.parameters(), lr=1e-3)
+    opt = E.optim.FlatAdam(m.parameters(), lr=1e-3, late=E.parallel.edge_pipeline_parameters(m))     # bench.py's optimiser
     m.train()
     eng = E.StepEngine(m)
     nxt = store.collate(ids[0])
