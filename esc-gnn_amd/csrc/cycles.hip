@@ -10,47 +10,20 @@
 // four nested loops below).  A cycle through r is such a path in each of its two directions, so the int32 count is halved.
 // The closing step needs no loop of its own: the paths of length k that close are popcount(candidates & adj[r]).
 // Work per root is at most deg * (deg-1)^3 mask steps (750 at degree 6): bound by LDS latency, microseconds per launch.
-#include "common.h"
+#include "ragged_graphs.h"
 
 namespace esc {
-
-constexpr int CYCLE_MAX_NODES = 64;
 
 __global__ __launch_bounds__(64) void cycle_counts_kernel(const int64_t* __restrict__ node_ptr,
                                                           const int64_t* __restrict__ edge_ptr,
                                                           const int64_t* __restrict__ src, const int64_t* __restrict__ dst,
                                                           int64_t total_nodes, int64_t total_edges,
                                                           float* __restrict__ out, int32_t* __restrict__ status) {
-  __shared__ unsigned long long adj[CYCLE_MAX_NODES];
+  __shared__ unsigned long long adj[ADJ_MAX_NODES];
   __shared__ int bad;
-  const int g = blockIdx.x, lane = threadIdx.x;
-  const int64_t n0 = node_ptr[g], n1 = node_ptr[g + 1];
-  const int64_t e0 = edge_ptr[g], e1 = edge_ptr[g + 1];
-  const int64_t n = n1 - n0;
-  if (n0 < 0 || n < 0 || n1 > total_nodes || e0 < 0 || e1 < e0 || e1 > total_edges) {
-    if (lane == 0) status[g] = ESC_EINVAL;
-    return;
-  }
-  if (n > CYCLE_MAX_NODES) {                         // uniform: the whole workgroup leaves, nothing is written
-    if (lane == 0) status[g] = ESC_ERANGE;
-    return;
-  }
-  adj[lane] = 0ull;
-  if (lane == 0) bad = 0;
-  __syncthreads();
-  for (int64_t e = e0 + lane; e < e1; e += 64) {
-    const int64_t a = src[e], b = dst[e];
-    if (a < 0 || b < 0 || a >= n || b >= n) { bad = 1; continue; }
-    if (a == b) continue;                            // remove_self_loops
-    atomicOr(&adj[a], 1ull << b);                    // to_undirected: both directions, duplicates collapse in the mask
-    atomicOr(&adj[b], 1ull << a);
-  }
-  __syncthreads();
-  if (bad) {
-    if (lane == 0) status[g] = ESC_EINVAL;
-    return;
-  }
-  if (lane == 0) status[g] = ESC_OK;
+  const int lane = threadIdx.x;
+  int64_t n0, n;
+  if (!adjacency_masks(node_ptr, edge_ptr, src, dst, total_nodes, total_edges, status, adj, bad, n0, n)) return;
   if (lane >= n) return;
   const int r = lane;
   const unsigned long long rbit = 1ull << r, close = adj[r];

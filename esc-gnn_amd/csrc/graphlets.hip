@@ -23,11 +23,10 @@
 // The apex column walks the adjacent pairs s1 < s2 of N(v) and the feet f1 of s1: c8 += |N(f1) & N(s2) - {v, s1}|.
 // Work per node is at most d^3/2 mask steps (108 at degree 6).  Every column fits int32 at n <= 64: the largest is the
 // house in K64, 14 295 960 in columns 9 and 10.  Integer arithmetic only: the output is deterministic.
-#include "common.h"
+#include "ragged_graphs.h"
 
 namespace esc {
 
-constexpr int GRAPHLET_MAX_NODES = 64;
 constexpr int GRAPHLET_COLS = 11;
 
 __global__ __launch_bounds__(64) void graphlet_counts_kernel(const int64_t* __restrict__ node_ptr,
@@ -36,37 +35,12 @@ __global__ __launch_bounds__(64) void graphlet_counts_kernel(const int64_t* __re
                                                              int64_t total_nodes, int64_t total_edges,
                                                              int32_t* __restrict__ out, int64_t ld_out,
                                                              int32_t* __restrict__ status) {
-  __shared__ unsigned long long adj[GRAPHLET_MAX_NODES];
-  __shared__ int tri[GRAPHLET_MAX_NODES];
+  __shared__ unsigned long long adj[ADJ_MAX_NODES];
+  __shared__ int tri[ADJ_MAX_NODES];
   __shared__ int bad;
-  const int g = blockIdx.x, lane = threadIdx.x;
-  const int64_t n0 = node_ptr[g], n1 = node_ptr[g + 1];
-  const int64_t e0 = edge_ptr[g], e1 = edge_ptr[g + 1];
-  const int64_t n = n1 - n0;
-  if (n0 < 0 || n < 0 || n1 > total_nodes || e0 < 0 || e1 < e0 || e1 > total_edges) {
-    if (lane == 0) status[g] = ESC_EINVAL;
-    return;
-  }
-  if (n > GRAPHLET_MAX_NODES) {                      // uniform: the whole workgroup leaves, nothing is written
-    if (lane == 0) status[g] = ESC_ERANGE;
-    return;
-  }
-  adj[lane] = 0ull;
-  if (lane == 0) bad = 0;
-  __syncthreads();
-  for (int64_t e = e0 + lane; e < e1; e += 64) {
-    const int64_t a = src[e], b = dst[e];
-    if (a < 0 || b < 0 || a >= n || b >= n) { bad = 1; continue; }
-    if (a == b) continue;                            // self loops dropped
-    atomicOr(&adj[a], 1ull << b);                    // symmetrised; duplicates collapse in the mask
-    atomicOr(&adj[b], 1ull << a);
-  }
-  __syncthreads();
-  if (bad) {                                         // uniform
-    if (lane == 0) status[g] = ESC_EINVAL;
-    return;
-  }
-  if (lane == 0) status[g] = ESC_OK;
+  const int lane = threadIdx.x;
+  int64_t n0, n;
+  if (!adjacency_masks(node_ptr, edge_ptr, src, dst, total_nodes, total_edges, status, adj, bad, n0, n)) return;
   const int v = lane;
   const unsigned long long vbit = 1ull << v, nv = adj[v];     // lanes >= n hold an empty row
   const int dv = __popcll(nv);

@@ -11,13 +11,13 @@
 // the column heads over all 32 double-wide bank pairs.  The workgroup size and every loop bound depend on the graph alone
 // (never on max_nodes or the launch), and the file is built without FMA contraction, so a graph's bits are the same alone
 // and in any batch.
-// esc_lappe_gather: one workgroup per graph of the batch copies its n x K rows of the two resident tables.
+// esc_lappe_gather: one workgroup per graph of the batch copies its n x K rows of the two resident tables (ragged_graphs.h).
 // esc_lappe_encode_fwd: one thread per node, the (zero-padded) weights in LDS, read as broadcasts.
 // esc_lappe_encode_bwd: launch 1 — a workgroup per block of ENC_ROWS rows; its row x frequency terms go through LDS in chunks:
 // phase 1, a thread per term, recomputes the hidden activations and leaves [a | dh | da | v | l | 1] of the term as one LDS row;
 // phase 2, a thread per parameter, adds the products of two columns of those rows over the chunk in term order (in fp64: one chain
 // runs over a thousand terms of either sign).  Launch 2 adds the workgroups' partials in workgroup order.  No atomics anywhere.
-#include "common.h"
+#include "ragged_graphs.h"
 #include "jacobi_pinv.h"
 #include "../../include/escgnn_lappe.h"
 
@@ -62,7 +62,8 @@ __device__ __forceinline__ void eig_graph(const EigArgs& a, double* __restrict__
   }
   __syncthreads();
   for (int64_t e = e0 + tid; e < e1; e += EIG_NT) {          // A symmetrised: plain stores of one value, order free
-    const int s = (int)(a.src[e] - base), t = (int)(a.dst[e] - base);
+    int64_t s, t;
+    (void)edge_ends(a.src, a.dst, e, base, n, s, t);          // (checked by the caller's pass over the same edges)
     if (s != t) {
       Gm[(size_t)t * ld + s] = -1.0;
       Gm[(size_t)s * ld + t] = -1.0;
@@ -116,16 +117,16 @@ __device__ __forceinline__ void eig_graph(const EigArgs& a, double* __restrict__
 __global__ __launch_bounds__(EIG_NT) void lap_eig_kernel(EigArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
-  const int64_t n0 = a.node_ptr[blockIdx.x], n1 = a.node_ptr[blockIdx.x + 1];
-  const int64_t e0 = a.edge_ptr[blockIdx.x], e1 = a.edge_ptr[blockIdx.x + 1];
+  const GraphRange r = graph_range(a.node_ptr, a.edge_ptr, blockIdx.x, a.N, a.E);
+  const int64_t n0 = r.n0, e0 = r.e0, e1 = r.e1;
   // (all of this is uniform over the workgroup: it leaves together)
-  if (!(n0 >= 0 && n1 > n0 && n1 <= a.N && n1 - n0 <= a.cap && e0 >= 0 && e1 >= e0 && e1 <= a.E)) return;
-  const int n = (int)(n1 - n0);
+  if (!(r.ok && r.n1 > n0 && r.n1 - n0 <= a.cap)) return;     // an empty graph and one over max_nodes are skipped
+  const int n = (int)(r.n1 - n0);
   const int64_t base = a.local ? 0 : n0;
   int bad = 0;
   for (int64_t e = e0 + tid; e < e1; e += EIG_NT) {
-    const int64_t s = a.src[e] - base, t = a.dst[e] - base;
-    if (s < 0 || s >= n || t < 0 || t >= n) bad = 1;
+    int64_t s, t;
+    if (!edge_ends(a.src, a.dst, e, base, n, s, t)) bad = 1;
   }
   if (__syncthreads_or(bad)) return;
   double* lam = reinterpret_cast<double*>(smem);
@@ -142,20 +143,6 @@ __global__ __launch_bounds__(EIG_NT) void lap_eig_kernel(EigArgs a) {
     double* Gm = a.scratch + off;
     eig_graph(a, Gm, Gm + (size_t)ld * n, n, ld, n0, base, e0, e1, lam, red, nrm, order);
   }
-}
-
-__global__ __launch_bounds__(256) void lappe_gather_kernel(const float* __restrict__ vecs_all, const float* __restrict__ vals_all,
-                                                           const int64_t* __restrict__ node_ptr_all, int64_t G_all, int64_t N_all,
-                                                           const int64_t* __restrict__ ids, const int32_t* __restrict__ graph_ptr,
-                                                           int64_t N, int K, float* __restrict__ vecs, float* __restrict__ vals) {
-  const int64_t id = ids[blockIdx.x];
-  if (id < 0 || id >= G_all) return;
-  const int64_t s0 = node_ptr_all[id], n = node_ptr_all[id + 1] - s0;
-  const int64_t d0 = graph_ptr[blockIdx.x];
-  if (!(n > 0 && s0 >= 0 && s0 <= N_all - n && d0 >= 0 && d0 <= N - n && (int64_t)graph_ptr[blockIdx.x + 1] - d0 == n)) return;
-  const float* sv = vecs_all + s0 * K; const float* sl = vals_all + s0 * K;
-  float* dv = vecs + d0 * K; float* dl = vals + d0 * K;
-  for (int64_t t = threadIdx.x; t < n * K; t += blockDim.x) { dv[t] = sv[t]; dl[t] = sl[t]; }
 }
 
 // ---- the DeepSet encoder ---------------------------------------------------------------------------------------------------------
@@ -387,8 +374,8 @@ int esc_lappe_gather(const float* vecs_all, const float* vals_all, const int64_t
               "esc_lappe_gather: bad sizes G_all=%ld N_all=%ld B=%ld N=%ld", (long)G_all, (long)N_all, (long)B, (long)N);
   if (B == 0 || N == 0 || G_all == 0) return ESC_OK;
   ESC_REQUIRE(vecs_all && vals_all && node_ptr_all && graph_ids && graph_ptr && vecs && vals, "esc_lappe_gather: null pointer");
-  esc::launch(-1, lappe_gather_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, vecs_all, vals_all, node_ptr_all, G_all, N_all,
-              graph_ids, graph_ptr, N, K, vecs, vals);
+  esc::launch(-1, table_gather_kernel<2>, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, GatherTables<2>{{vecs_all, vals_all}, {vecs, vals}},
+              node_ptr_all, G_all, N_all, graph_ids, graph_ptr, N, K, (int64_t)K);
   ESC_CHECK_LAUNCH("esc_lappe_gather");
   return ESC_OK;
 }

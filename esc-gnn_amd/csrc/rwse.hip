@@ -15,8 +15,8 @@
 //      wave runs every round, a wave without a start node idles through it).
 // Every loop bound depends on the graph and the step mask alone (never on max_nodes, max_edges or the launch), and the file is
 // built without FMA contraction, so a graph's bits are the same alone and in any batch.
-// esc_rwse_gather: one workgroup per graph of the batch copies its n x K rows of the resident table.
-#include "common.h"
+// esc_rwse_gather: one workgroup per graph of the batch copies its n x K rows of the resident table (ragged_graphs.h).
+#include "ragged_graphs.h"
 #include "../../include/escgnn_rwse.h"
 
 namespace esc {
@@ -59,11 +59,11 @@ struct RwArgs {
 __global__ __launch_bounds__(RW_NT) void rw_landing_kernel(RwArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
-  const int64_t n0 = a.node_ptr[blockIdx.x], n1 = a.node_ptr[blockIdx.x + 1];
-  const int64_t e0 = a.edge_ptr[blockIdx.x], e1 = a.edge_ptr[blockIdx.x + 1];
+  const GraphRange r = graph_range(a.node_ptr, a.edge_ptr, blockIdx.x, a.N, a.E);
+  const int64_t n0 = r.n0, e0 = r.e0;
   // (all of this is uniform over the workgroup: it leaves together)
-  if (!(n0 >= 0 && n1 > n0 && n1 <= a.N && n1 - n0 <= a.cap && e0 >= 0 && e1 >= e0 && e1 <= a.E && e1 - e0 <= a.ecap)) return;
-  const int n = (int)(n1 - n0), m = (int)(e1 - e0);
+  if (!(r.ok && r.n1 > n0 && r.n1 - n0 <= a.cap && r.e1 - e0 <= a.ecap)) return;     // empty, or over max_nodes / max_edges: skipped
+  const int n = (int)(r.n1 - n0), m = (int)(r.e1 - e0);
   const int64_t base = a.local ? 0 : n0;
   double* y = reinterpret_cast<double*>(smem);
   double* invdeg = y + (size_t)2 * RW_WAVES * a.cap;
@@ -75,8 +75,8 @@ __global__ __launch_bounds__(RW_NT) void rw_landing_kernel(RwArgs a) {
   if (tid == 0) *flag = 0;
   __syncthreads();
   for (int e = tid; e < m; e += RW_NT) {                      // 1. read-only: check, and stage in LDS
-    const int64_t s = a.src[e0 + e] - base, t = a.dst[e0 + e] - base;
-    if (s < 0 || s >= n || t < 0 || t >= n) *flag = 1;        // (plain stores of one value; nothing writes it after the barrier)
+    int64_t s, t;
+    if (!edge_ends(a.src, a.dst, e0 + e, base, n, s, t)) *flag = 1;     // (plain stores of one value; nothing writes it after the barrier)
     es[e] = (uint16_t)s;
     ed[e] = (uint16_t)t;
   }
@@ -129,20 +129,6 @@ __global__ __launch_bounds__(RW_NT) void rw_landing_kernel(RwArgs a) {
   }
 }
 
-__global__ __launch_bounds__(256) void rwse_gather_kernel(const float* __restrict__ table, const int64_t* __restrict__ node_ptr_all,
-                                                          int64_t G_all, int64_t N_all, const int64_t* __restrict__ ids,
-                                                          const int32_t* __restrict__ graph_ptr, int64_t N, int K, float* __restrict__ out,
-                                                          int64_t ldo) {
-  const int64_t id = ids[blockIdx.x];
-  if (id < 0 || id >= G_all) return;
-  const int64_t s0 = node_ptr_all[id], n = node_ptr_all[id + 1] - s0;
-  const int64_t d0 = graph_ptr[blockIdx.x];
-  if (!(n > 0 && s0 >= 0 && s0 <= N_all - n && d0 >= 0 && d0 <= N - n && (int64_t)graph_ptr[blockIdx.x + 1] - d0 == n)) return;
-  const float* s = table + s0 * K;
-  float* d = out + d0 * ldo;
-  for (int64_t t = threadIdx.x; t < n * K; t += blockDim.x) d[(t / K) * ldo + t % K] = s[t];
-}
-
 }  // namespace esc
 
 using namespace esc;
@@ -182,8 +168,8 @@ int esc_rwse_gather(const float* table, const int64_t* node_ptr_all, int64_t G_a
   ESC_REQUIRE(ld_out >= K, "esc_rwse_gather: leading dimension of out %ld below the %d steps", (long)ld_out, K);
   if (B == 0 || N == 0 || G_all == 0) return ESC_OK;
   ESC_REQUIRE(table && node_ptr_all && graph_ids && graph_ptr && out, "esc_rwse_gather: null pointer");
-  esc::launch(-1, rwse_gather_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, table, node_ptr_all, G_all, N_all, graph_ids,
-              graph_ptr, N, K, out, ld_out);
+  esc::launch(-1, table_gather_kernel<1>, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, GatherTables<1>{{table}, {out}}, node_ptr_all,
+              G_all, N_all, graph_ids, graph_ptr, N, K, ld_out);
   ESC_CHECK_LAUNCH("esc_rwse_gather");
   return ESC_OK;
 }

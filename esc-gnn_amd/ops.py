@@ -1314,9 +1314,11 @@ def _index_vector(t, what, dtype):
     return t.contiguous()
 
 
-def _ragged_graphs(who, edge_index, graph_ptr, edge_ptr):
-    """the argument checks the per-graph kernels share (laplacian_eig, rw_landing): a device edge_index [2, E] and the two
-    offset vectors of its G graphs"""
+def _ragged_graphs(who, node_limit, edge_index, graph_ptr, edge_ptr, max_nodes, num_nodes):
+    """A ragged set of graphs as a per-graph kernel takes it (laplacian_eig, rw_landing; csrc/ragged_graphs.h): a device
+    edge_index [2, E] and the two offset vectors of its G graphs, checked; G, N and the largest graph resolved - max_nodes or
+    num_nodes None costs one read-back of graph_ptr each - and the largest graph held against node_limit, the kernel's.  Returns
+    (src, dst, node_ptr, edge_ptr, G, N, max_nodes), the four vectors contiguous int64."""
     if not torch.is_tensor(edge_index) or edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.size(0) != 2:
         raise TypeError("%s: edge_index must be an int64 [2, E] tensor" % who)
     if not edge_index.is_cuda:
@@ -1328,6 +1330,41 @@ def _ragged_graphs(who, edge_index, graph_ptr, edge_ptr):
     _on(edge_index.device, graph_ptr, edge_ptr)
     if graph_ptr.numel() != edge_ptr.numel():
         raise ValueError("%s: graph_ptr has %d entries, edge_ptr %d" % (who, graph_ptr.numel(), edge_ptr.numel()))
+    G = graph_ptr.numel() - 1
+    if max_nodes is None:
+        max_nodes = int((graph_ptr[1:] - graph_ptr[:-1]).max()) if G else 0
+    max_nodes = int(max_nodes)
+    if max_nodes > node_limit:
+        raise RuntimeError("%s: a graph of %d nodes exceeds the limit of %d nodes per graph" % (who, max_nodes, node_limit))
+    if num_nodes is None:
+        num_nodes = int(graph_ptr[-1])
+    return (edge_index[0].contiguous(), edge_index[1].contiguous(), graph_ptr.to(torch.int64).contiguous(),
+            edge_ptr.to(torch.int64).contiguous(), G, int(num_nodes), max_nodes)
+
+
+def _checked_gather(who, tables, table_rule, node_ptr_all, graph_ids, graph_ptr, num_nodes):
+    """What lappe_gather and rwse_gather share: the resident tables (fp32, contiguous [N_all, K], one shape) and the index
+    vectors checked, graph_ids checked on the HOST (count, range) and uploaded, one output [N, K] per table.  Returns
+    (node_ptr_all, ids_d, graph_ptr, (G_all, N_all, B, N, K), outputs)."""
+    _dev(*tables)
+    dev = tables[0].device
+    if any(t.dim() != 2 or t.shape != tables[0].shape or not t.is_contiguous() for t in tables):
+        raise ValueError("%s: %s" % (who, table_rule))
+    node_ptr_all = _index_vector(node_ptr_all, "%s: node_ptr_all" % who, torch.int64)
+    graph_ptr = _index_vector(graph_ptr, "%s: graph_ptr" % who, torch.int32)
+    _on(dev, node_ptr_all, graph_ptr)
+    G_all, B = node_ptr_all.numel() - 1, graph_ptr.numel() - 1
+    if torch.is_tensor(graph_ids) and graph_ids.is_cuda:
+        raise RuntimeError("%s: graph_ids must live on the host (they are checked there, without a read-back)" % who)
+    ids_h = torch.as_tensor(graph_ids, dtype=torch.int64).reshape(-1)
+    if ids_h.numel() != B:
+        raise ValueError("%s: %d graph ids for a batch of %d graphs" % (who, ids_h.numel(), B))
+    if B and (int(ids_h.min()) < 0 or int(ids_h.max()) >= G_all):
+        raise IndexError("%s: graph id out of range (the table holds %d graphs)" % (who, G_all))
+    N, K = int(num_nodes), tables[0].size(1)
+    ids_d = ids_h.to(dev, non_blocking=True)
+    outs = [torch.empty((N, K), dtype=torch.float32, device=dev) for _ in tables]
+    return node_ptr_all, ids_d, graph_ptr, (G_all, tables[0].size(0), B, N, K), outs
 
 
 def laplacian_eig(edge_index, graph_ptr, edge_ptr, max_freqs, max_nodes=None, edges_local=False, num_nodes=None):
@@ -1340,27 +1377,12 @@ def laplacian_eig(edge_index, graph_ptr, edge_ptr, max_freqs, max_nodes=None, ed
     max_nodes: the largest graph as the HOST knows it, num_nodes: N likewise; None costs one read-back of graph_ptr each.
     Limits: laplacian_eig_limits()[0] = 256 nodes per graph, max_freqs <= 32; beyond them RuntimeError, raised before anything
     is launched."""
-    _ragged_graphs("laplacian_eig", edge_index, graph_ptr, edge_ptr)
     K = int(max_freqs)
     if not 1 <= K <= 32:
         raise RuntimeError("laplacian_eig: max_freqs %d outside 1..32" % K)
-    limit = laplacian_eig_limits()[0]
-    G = graph_ptr.numel() - 1
-    if max_nodes is None:
-        max_nodes = int((graph_ptr[1:] - graph_ptr[:-1]).max()) if G else 0
-    max_nodes = int(max_nodes)
-    if max_nodes > limit:
-        raise RuntimeError("laplacian_eig: a graph of %d nodes exceeds the limit of %d nodes per graph" % (max_nodes, limit))
-    if num_nodes is None:
-        num_nodes = int(graph_ptr[-1])
-    return _laplacian_eig(edge_index, graph_ptr.to(torch.int64).contiguous(), edge_ptr.to(torch.int64).contiguous(), G, int(num_nodes), K,
-                          max_nodes, edges_local)
-
-
-def _laplacian_eig(edge_index, node_ptr, edge_ptr, G, N, K, max_nodes, edges_local):
-    """the launch itself: int64 pointers, every size known on the host"""
-    dev = edge_index.device
-    src, dst = edge_index[0].contiguous(), edge_index[1].contiguous()
+    src, dst, node_ptr, edge_ptr, G, N, max_nodes = _ragged_graphs("laplacian_eig", laplacian_eig_limits()[0], edge_index, graph_ptr,
+                                                                   edge_ptr, max_nodes, num_nodes)
+    dev = src.device
     vecs = torch.empty((N, K), dtype=torch.float32, device=dev)
     vals = torch.empty((N, K), dtype=torch.float32, device=dev)
     need = int(nv.lib().esc_laplacian_eig_scratch_bytes(N, max_nodes))
@@ -1375,27 +1397,11 @@ def lappe_gather(vecs_all, vals_all, node_ptr_all, graph_ids, graph_ptr, num_nod
     launch.  vecs_all, vals_all [N_all, K] fp32; node_ptr_all int64 [G_all+1] (device); graph_ids: the batch's graphs in batch
     order, a HOST int64 tensor or list - checked here, an id out of range raises IndexError before anything is launched;
     graph_ptr int32 [B+1]: the batch's node ranges; num_nodes: the batch's N.  Returns (vals [N, K, 1], vecs [N, K])."""
-    _dev(vecs_all, vals_all)
-    dev = vecs_all.device
-    if vecs_all.dim() != 2 or vals_all.shape != vecs_all.shape or not (vecs_all.is_contiguous() and vals_all.is_contiguous()):
-        raise ValueError("lappe_gather: the two tables must be contiguous [N_all, K] tensors of one shape")
-    node_ptr_all = _index_vector(node_ptr_all, "lappe_gather: node_ptr_all", torch.int64)
-    graph_ptr = _index_vector(graph_ptr, "lappe_gather: graph_ptr", torch.int32)
-    _on(dev, node_ptr_all, graph_ptr)
-    G_all, B = node_ptr_all.numel() - 1, graph_ptr.numel() - 1
-    if torch.is_tensor(graph_ids) and graph_ids.is_cuda:
-        raise RuntimeError("lappe_gather: graph_ids must live on the host (they are checked there, without a read-back)")
-    ids_h = torch.as_tensor(graph_ids, dtype=torch.int64).reshape(-1)
-    if ids_h.numel() != B:
-        raise ValueError("lappe_gather: %d graph ids for a batch of %d graphs" % (ids_h.numel(), B))
-    if B and (int(ids_h.min()) < 0 or int(ids_h.max()) >= G_all):
-        raise IndexError("lappe_gather: graph id out of range (the table holds %d graphs)" % G_all)
-    N, K = int(num_nodes), vecs_all.size(1)
-    ids_d = ids_h.to(dev, non_blocking=True)
-    vecs = torch.empty((N, K), dtype=torch.float32, device=dev)
-    vals = torch.empty((N, K), dtype=torch.float32, device=dev)
-    nv.call("esc_lappe_gather", nv.ptr(vecs_all), nv.ptr(vals_all), nv.ptr(node_ptr_all), G_all, vecs_all.size(0), nv.ptr(ids_d),
-            nv.ptr(graph_ptr), B, N, K, nv.ptr(vecs), nv.ptr(vals), nv.stream())
+    node_ptr_all, ids_d, graph_ptr, (G_all, N_all, B, N, K), (vecs, vals) = _checked_gather(
+        "lappe_gather", (vecs_all, vals_all), "the two tables must be contiguous [N_all, K] tensors of one shape", node_ptr_all, graph_ids,
+        graph_ptr, num_nodes)
+    nv.call("esc_lappe_gather", nv.ptr(vecs_all), nv.ptr(vals_all), nv.ptr(node_ptr_all), G_all, N_all, nv.ptr(ids_d), nv.ptr(graph_ptr), B, N, K,
+            nv.ptr(vecs), nv.ptr(vals), nv.stream())
     return vals.view(N, K, 1), vecs
 
 
@@ -1501,25 +1507,15 @@ def rw_landing(edge_index, graph_ptr, edge_ptr, ksteps, max_nodes=None, max_edge
     Limits: rw_landing_limits() = (256, 7678) nodes and edges per graph; beyond them RuntimeError, raised before anything is
     launched."""
     mask = rw_step_mask(ksteps)
-    _ragged_graphs("rw_landing", edge_index, graph_ptr, edge_ptr)
-    dev = edge_index.device
     node_limit, edge_limit = rw_landing_limits()
-    G = graph_ptr.numel() - 1
-    if max_nodes is None:
-        max_nodes = int((graph_ptr[1:] - graph_ptr[:-1]).max()) if G else 0
+    src, dst, node_ptr, edge_ptr, G, N, max_nodes = _ragged_graphs("rw_landing", node_limit, edge_index, graph_ptr, edge_ptr, max_nodes, num_nodes)
     if max_edges is None:
         max_edges = int((edge_ptr[1:] - edge_ptr[:-1]).max()) if G else 0
-    max_nodes, max_edges = int(max_nodes), int(max_edges)
-    if max_nodes > node_limit:
-        raise RuntimeError("rw_landing: a graph of %d nodes exceeds the limit of %d nodes per graph" % (max_nodes, node_limit))
+    max_edges = int(max_edges)
     if max_edges > edge_limit:
         raise RuntimeError("rw_landing: a graph of %d edges exceeds the limit of %d edges per graph" % (max_edges, edge_limit))
-    if num_nodes is None:
-        num_nodes = int(graph_ptr[-1])
-    N, K = int(num_nodes), bin(mask).count("1")
-    src, dst = edge_index[0].contiguous(), edge_index[1].contiguous()
-    node_ptr, edge_ptr = graph_ptr.to(torch.int64).contiguous(), edge_ptr.to(torch.int64).contiguous()
-    out = torch.empty((N, K), dtype=torch.float32, device=dev)
+    K = bin(mask).count("1")
+    out = torch.empty((N, K), dtype=torch.float32, device=src.device)
     nv.call("esc_rw_landing", nv.ptr(src), nv.ptr(dst), src.numel(), nv.ptr(node_ptr), nv.ptr(edge_ptr), G, N, int(bool(edges_local)), mask,
             max(max_nodes, 0), max(max_edges, 0), nv.ptr(out), K, nv.stream())
     return out
@@ -1530,24 +1526,8 @@ def rwse_gather(table, node_ptr_all, graph_ids, graph_ptr, num_nodes):
     table [N_all, K] fp32; node_ptr_all int64 [G_all+1] (device); graph_ids: the batch's graphs in batch order, a HOST int64
     tensor or list - checked here, an id out of range raises IndexError before anything is launched; graph_ptr int32 [B+1]: the
     batch's node ranges; num_nodes: the batch's N.  Returns [N, K]."""
-    _dev(table)
-    dev = table.device
-    if table.dim() != 2 or not table.is_contiguous() or table.dtype != torch.float32:
-        raise ValueError("rwse_gather: the table must be a contiguous fp32 [N_all, K] tensor")
-    node_ptr_all = _index_vector(node_ptr_all, "rwse_gather: node_ptr_all", torch.int64)
-    graph_ptr = _index_vector(graph_ptr, "rwse_gather: graph_ptr", torch.int32)
-    _on(dev, node_ptr_all, graph_ptr)
-    G_all, B = node_ptr_all.numel() - 1, graph_ptr.numel() - 1
-    if torch.is_tensor(graph_ids) and graph_ids.is_cuda:
-        raise RuntimeError("rwse_gather: graph_ids must live on the host (they are checked there, without a read-back)")
-    ids_h = torch.as_tensor(graph_ids, dtype=torch.int64).reshape(-1)
-    if ids_h.numel() != B:
-        raise ValueError("rwse_gather: %d graph ids for a batch of %d graphs" % (ids_h.numel(), B))
-    if B and (int(ids_h.min()) < 0 or int(ids_h.max()) >= G_all):
-        raise IndexError("rwse_gather: graph id out of range (the table holds %d graphs)" % G_all)
-    N, K = int(num_nodes), table.size(1)
-    ids_d = ids_h.to(dev, non_blocking=True)
-    out = torch.empty((N, K), dtype=torch.float32, device=dev)
-    nv.call("esc_rwse_gather", nv.ptr(table), nv.ptr(node_ptr_all), G_all, table.size(0), nv.ptr(ids_d), nv.ptr(graph_ptr), B, N, K,
-            nv.ptr(out), K, nv.stream())
+    node_ptr_all, ids_d, graph_ptr, (G_all, N_all, B, N, K), (out,) = _checked_gather(
+        "rwse_gather", (table,), "the table must be a contiguous fp32 [N_all, K] tensor", node_ptr_all, graph_ids, graph_ptr, num_nodes)
+    nv.call("esc_rwse_gather", nv.ptr(table), nv.ptr(node_ptr_all), G_all, N_all, nv.ptr(ids_d), nv.ptr(graph_ptr), B, N, K, nv.ptr(out), K,
+            nv.stream())
     return out

@@ -105,18 +105,13 @@ def main(argv=None):
     widest = [int((s.h_node_ptr[1:] - s.h_node_ptr[:-1]).max()) for s in stores]      # the largest graph of each store: host data
     n_train = len(tr)
     tables = [[] for _ in stores]                   # the resident encoding tables of every split, attached to each of its batches in order
-    if args.posenc_LapPE:
-        from .lappe import LapPETable
+
+    def lap_pe_limits():
         limit = ops.laplacian_eig_limits()[0]
         if max(widest) > limit:
             raise SystemExit("run_zinc_gps: the largest graph has %d nodes, the Laplacian eigen-solver takes at most %d" % (max(widest), limit))
-        t12 = time.time()
-        for t, s in zip(tables, stores):
-            t.append(LapPETable(s, args.posenc_LapPE_max_freqs))
-        torch.cuda.synchronize()
-        ctx.say("LapPE table build time cost: {}s,".format(time.time() - t12))
-    if args.posenc_RWSE:
-        from .rwse import RWSETable
+
+    def rwse_limits():
         node_limit, edge_limit = ops.rw_landing_limits()
         most_edges = max(int((s.h_edge_ptr[1:] - s.h_edge_ptr[:-1]).max()) for s in stores)
         if max(widest) > node_limit or most_edges > edge_limit:
@@ -124,11 +119,19 @@ def main(argv=None):
                              "and %d edges per graph" % (max(widest), most_edges, node_limit, edge_limit))
         if not 1 <= args.posenc_RWSE_ksteps <= 63:
             raise SystemExit("run_zinc_gps: --posenc_RWSE_ksteps %d outside 1..63" % args.posenc_RWSE_ksteps)
-        t13 = time.time()
+
+    from .lappe import LapPETable
+    from .rwse import RWSETable
+    for name, on, cls, what, check in (("LapPE", args.posenc_LapPE, LapPETable, args.posenc_LapPE_max_freqs, lap_pe_limits),
+                                       ("RWSE", args.posenc_RWSE, RWSETable, list(range(1, args.posenc_RWSE_ksteps + 1)), rwse_limits)):
+        if not on:
+            continue
+        check()
+        t12 = time.time()
         for t, s in zip(tables, stores):
-            t.append(RWSETable(s, list(range(1, args.posenc_RWSE_ksteps + 1))))
+            t.append(cls(s, what))
         torch.cuda.synchronize()
-        ctx.say("RWSE table build time cost: {}s,".format(time.time() - t13))
+        ctx.say("{} table build time cost: {}s,".format(name, time.time() - t12))
 
     model = GPSModel(layers=args.layers, dim_hidden=args.dim_hidden, n_heads=args.n_heads, dropout=args.dropout,
                      attn_dropout=args.attn_dropout, node_types=args.node_encoder_num_types, edge_types=args.edge_encoder_num_types,

@@ -8,39 +8,27 @@ it for a whole split in ONE launch at build time, keeps it in HBM and hands ever
 reference's dataset pre-transform plus collate do.  The encoder that consumes the key is nn.RWSENodeEncoder.  The twin of
 lappe.py."""
 from . import ops
-from .lappe import _ranges
+from .ragged import StoreTable, graph_ranges
 
 
 def add_rwse(data, ksteps):
     """Sets pestat_RWSE [N, K] (fp32) on a graph or a collated batch whose tensors are on the device, and returns it.  Torch
     plumbing for the ranges plus one launch; the largest node and edge count of a graph are read back (the node count is not
     when the batch carries `_esc_max_nodes`)."""
-    graph_ptr, edge_ptr, G, widest, N = _ranges(data)
+    graph_ptr, edge_ptr, G, widest, N = graph_ranges(data)
     data.pestat_RWSE = ops.rw_landing(data.edge_index, graph_ptr, edge_ptr, ksteps, max_nodes=widest, num_nodes=N)
     return data
 
 
-class RWSETable(object):
+class RWSETable(StoreTable):
     """The RWSE of every graph of a DeviceGraphStore, resident in HBM: pestat [N_all, K].  Built with one esc_rw_landing launch
     over the store's flat (graph-local) edge arrays, the largest graph taken from the store's host offsets; attach() is one
     esc_rwse_gather launch."""
 
     def __init__(self, store, ksteps):
-        import torch
-        self.store, self.ksteps = store, [int(k) for k in ksteps]
-        n = store.h_node_ptr[1:] - store.h_node_ptr[:-1]           # host data
-        m = store.h_edge_ptr[1:] - store.h_edge_ptr[:-1]
-        self.max_nodes, self.max_edges = int(n.max()), int(m.max())
-        edge_index = torch.stack([store.esrc_all, store.edst_all])
-        self.pestat = ops.rw_landing(edge_index, store.node_ptr, store.edge_ptr, self.ksteps, max_nodes=self.max_nodes,
-                                     max_edges=self.max_edges, edges_local=True, num_nodes=int(store.h_node_ptr[-1]))
+        super().__init__(store)
+        self.ksteps = [int(k) for k in ksteps]
+        self.pestat = self._build(ops.rw_landing, self.ksteps, max_edges=self.max_edges)
 
-    def attach(self, batch, graph_ids):
-        """Sets pestat_RWSE of a batch that store.collate(graph_ids) made; graph_ids on the host (checked there: an id out of
-        range raises IndexError).  One launch, no device-to-host copy."""
-        plan = getattr(batch, "_esc_plan", None)
-        graph_ptr = getattr(plan, "graph_ptr", None)
-        if graph_ptr is None:
-            raise ValueError("RWSETable.attach: the batch does not come from DeviceGraphStore.collate")
-        batch.pestat_RWSE = ops.rwse_gather(self.pestat, self.store.node_ptr, graph_ids, graph_ptr, batch.x.size(0))
-        return batch
+    def _gather(self, batch, graph_ids, graph_ptr, N):
+        batch.pestat_RWSE = ops.rwse_gather(self.pestat, self.store.node_ptr, graph_ids, graph_ptr, N)

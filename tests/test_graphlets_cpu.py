@@ -81,3 +81,38 @@ def test_task_label_column_selection_and_ranges():
         task_label_column("count_cycle", 4)
     with pytest.raises(ValueError, match=r"0\.\.1"):
         task_label_column("count_graphlet", 1, 2)
+
+
+# ---- the packing and the status decoder the label wrappers share (esc_gnn_amd/ragged.py) --------------------------------
+def test_shared_edge_list_packing():
+    import torch
+    from esc_gnn_amd.ragged import pack_edge_lists, split_rows
+    none = torch.zeros((2, 0), dtype=torch.int64)
+    tri = torch.tensor([[0, 1, 2], [1, 2, 0]])
+    node_ptr, edge_ptr, ends = pack_edge_lists([4, 0, 3], [none, none, tri])
+    assert node_ptr.tolist() == [0, 4, 4, 7] and edge_ptr.tolist() == [0, 0, 0, 3]
+    assert ends.dtype == node_ptr.dtype == edge_ptr.dtype == torch.int64 and torch.equal(ends, tri)
+    flat = pack_edge_lists([4, 0, 3], [none, none.reshape(-1), tri.reshape(-1).to(torch.int32)])      # 2m entries: taken as [2, m]
+    assert all(torch.equal(a, b) and a.dtype == b.dtype for a, b in zip(flat, (node_ptr, edge_ptr, ends)))
+    rows = torch.arange(7 * 4).view(7, 4)
+    parts = split_rows(rows, node_ptr)
+    assert [p.shape for p in parts] == [(4, 4), (0, 4), (3, 4)] and torch.equal(torch.cat(parts), rows)
+    node_ptr, edge_ptr, ends = pack_edge_lists([], [])                               # the empty call
+    assert node_ptr.tolist() == [0] and edge_ptr.tolist() == [0] and ends.shape == (2, 0)
+    assert split_rows(torch.zeros(0, 4), node_ptr) == []
+
+
+def test_shared_status_decoder_names_the_first_offending_graph():
+    import torch
+    from esc_gnn_amd.ragged import ESC_ERANGE, MAX_NODES, raise_for_status
+    assert MAX_NODES == 64 and ESC_ERANGE != 0
+    node_ptr = torch.tensor([0, 3, 68, 70, 75])
+    raise_for_status("cycle_counts", "cycle", torch.zeros(4, dtype=torch.int32), node_ptr)             # all ESC_OK: nothing
+    raise_for_status("cycle_counts", "cycle", torch.zeros(0, dtype=torch.int32), torch.tensor([0]))
+    other = 1 if ESC_ERANGE != 1 else 2
+    with pytest.raises(ValueError, match=r"^cycle_counts: graph 1 has 65 nodes; the cycle-count kernel takes graphs of at most 64 nodes$"):
+        raise_for_status("cycle_counts", "cycle", torch.tensor([0, ESC_ERANGE, other, ESC_ERANGE], dtype=torch.int32), node_ptr)
+    with pytest.raises(ValueError, match=r"^graphlet_counts: graph 2 has a node id outside \[0, 2\)$"):
+        raise_for_status("graphlet_counts", "graphlet", torch.tensor([0, 0, other, ESC_ERANGE], dtype=torch.int32), node_ptr)
+    with pytest.raises(ValueError, match=r"^graphlet_counts: graph 3 has a node id outside \[0, 5\)$"):     # any other non-zero code
+        raise_for_status("graphlet_counts", "graphlet", torch.tensor([0, 0, 0, -7], dtype=torch.int32), node_ptr)

@@ -218,6 +218,22 @@ def test_table_attach_equals_add_lap_pe_on_the_collated_batch(E):
         table.attach(store.collate(ids), ids[:3])
 
 
+@pytest.mark.parametrize("k", [1, 32])
+def test_gather_of_two_tables_in_any_order(E, k):
+    """the shared gather kernel with two tables: graphs of 1, 2 and 3 nodes whose rows hold their own flat index (the last
+    graph's last row NaN, with a payload: compared as bits), gathered in reversed order with a repeat"""
+    vecs_all = torch.arange(6 * k, dtype=torch.float32, device=DEV).view(6, k).clone()
+    vals_all = -1.0 - vecs_all
+    vecs_all.view(torch.int32)[5] = 0x7fc00123
+    vals_all.view(torch.int32)[5] = 0x7fc00000
+    ptr_all, ids, graph_ptr = dev([0, 1, 3, 6], torch.int64), [2, 0, 2], dev([0, 3, 4, 7], torch.int32)
+    rows = torch.tensor([3, 4, 5, 0, 3, 4, 5], device=DEV)
+    vals, vecs = E.ops.lappe_gather(vecs_all, vals_all, ptr_all, ids, graph_ptr, 7)
+    assert vals.shape == (7, k, 1) and vecs.shape == (7, k)
+    assert torch.equal(bits(vecs), bits(vecs_all[rows])) and torch.equal(bits(vals.view(7, k)), bits(vals_all[rows]))
+    assert int(bits(vecs)[2, k - 1]) == 0x7fc00123 and int(bits(vecs)[6, 0]) == 0x7fc00123
+
+
 # ---- 4. the encoder ---------------------------------------------------------------------------------------------------------------
 _ENC = {}
 

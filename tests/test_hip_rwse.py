@@ -333,6 +333,22 @@ def test_gather_guards(E):
     nv.call("esc_rwse_gather", None, None, 0, 0, None, None, 0, 0, K, None, K, nv.stream())
 
 
+@pytest.mark.parametrize("k", [1, 63])
+def test_gather_of_one_table_in_any_order_and_at_a_leading_dimension(E, k):
+    """the shared gather kernel with one table: graphs of 1, 2 and 3 nodes whose rows hold their own flat index, gathered in
+    reversed order with a repeat; through the op (ld_out = K) and through the C ABI into a wider, sentinel-filled output"""
+    nv = E._native
+    table = torch.arange(6 * k, dtype=torch.float32, device=DEV).view(6, k)
+    ptr_all, ids, graph_ptr = dev([0, 1, 3, 6], torch.int64), [2, 0, 2], dev([0, 3, 4, 7], torch.int32)
+    want = table[torch.tensor([3, 4, 5, 0, 3, 4, 5], device=DEV)]
+    out = E.ops.rwse_gather(table, ptr_all, ids, graph_ptr, 7)
+    assert out.shape == (7, k) and torch.equal(out, want)
+    wide = torch.full((7, k + 3), FILL, device=DEV)
+    ids_d = dev(ids, torch.int64)
+    nv.call("esc_rwse_gather", nv.ptr(table), nv.ptr(ptr_all), 3, 6, nv.ptr(ids_d), nv.ptr(graph_ptr), 3, 7, k, nv.ptr(wide), k + 3, nv.stream())
+    assert torch.equal(wide[:, :k], want) and bool((wide[:, k:] == FILL).all())
+
+
 # ---- 4. the encoder ---------------------------------------------------------------------------------------------------------------
 def rel(got, want):
     got, want = got.detach().cpu().double(), want.detach().double()

@@ -97,6 +97,12 @@ def test_cycle_kernel_size_limit(E):
         _kernel([3, 65], [small, ei65])
     with pytest.raises(ValueError, match="outside"):
         _kernel([3], [np.array([[0, 1], [1, 3]], dtype=np.int64)])
+    none = np.zeros((2, 0), dtype=np.int64)
+    got = _kernel([4, 3], [none, small])                       # an edgeless graph, beside one with edges
+    assert got[0].shape == (4, 4) and not got[0].any() and np.array_equal(got[1], zco.cycle_labels(3, small))
+    got = _kernel([5], [none])                                 # no edge at all in the call
+    assert got[0].shape == (5, 4) and not got[0].any()
+    assert _kernel([], []) == []
 
 
 def _und_edges(pairs):
