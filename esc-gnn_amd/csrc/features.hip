@@ -35,44 +35,22 @@
 //                computed once, in the count pass, and kept in `work` for the fill pass.
 // Integer work bound by LDS/L2 latency, not HBM.
 #include "common.h"
+#include "graph_wave.h"
 #include "jacobi_pinv.h"
 
 namespace esc {
 
 constexpr int HIST_BINS = 1800;
 constexpr int RD_BINS = 100;
-constexpr int LDS_SUBGRAPH = 96;        // largest ego-net whose two m x m fp64 matrices fit LDS (147 KB)
-constexpr unsigned char HOP_INF = 255;
+constexpr int LDS_SUBGRAPH = GRAPH_RD_MAX;   // largest ego-net whose two m x m fp64 matrices fit LDS (the name DESIGN.md uses)
 constexpr int N_BUCKETS = 4;            // ego-net size classes: <=32, <=64, <=96 (LDS), larger (global slab)
 
-// ---- exclusive scan of int32 counts into int64 offsets (single workgroup, chunked with carry) -----
+// ---- exclusive scan of int32 counts into int64 offsets (block_exclusive_scan: single workgroup, chunked with carry) -----
 __global__ __launch_bounds__(1024) void scan_counts_kernel(const int* __restrict__ cnt, int64_t n,
                                                            int64_t* __restrict__ out) {
-  __shared__ int64_t wsum[16];
-  __shared__ int64_t carry_s;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (int64_t base = 0; base < n; base += 1024) {
-    const int64_t i = base + threadIdx.x;
-    int64_t v = (i < n) ? (int64_t)cnt[i] : 0;
-    int64_t incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int64_t t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int64_t woff = 0;
-    for (int k = 0; k < w; ++k) woff += wsum[k];
-    const int64_t carry = carry_s;
-    if (i < n) out[i] = carry + woff + incl - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry_s = carry + woff + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[n] = carry_s;
+  const int64_t total = block_exclusive_scan<int64_t>(n, [&](int64_t i) { return (int64_t)cnt[i]; },
+                                                      [&](int64_t i, int64_t v) { out[i] = v; });
+  if (threadIdx.x == 0) out[n] = total;
 }
 
 // ---- pass 0: per-graph edge-list normalisation (one wave per graph) -------------------------------
@@ -100,12 +78,8 @@ __global__ __launch_bounds__(64) void feat_prepare_kernel(const int64_t* __restr
       if (s < 0 || s >= n || d < 0 || d >= n) bad = 1;
       keep = !(self_loop && s == d);
     }
-    const unsigned long long m = __ballot(keep);
-    if (keep) {
-      const int p = base + __popcll(m & ((1ull << lane) - 1ull));
-      w_src[wo + p] = (int)s; w_dst[wo + p] = (int)d; w_in[wo + p] = (int)(j - e0);
-    }
-    base += __popcll(m);
+    const int p = ballot_compact(keep, base);
+    if (keep) { w_src[wo + p] = (int)s; w_dst[wo + p] = (int)d; w_in[wo + p] = (int)(j - e0); }
   }
   if (self_loop) {
     for (int64_t i = lane; i < n; i += 64) {
@@ -123,46 +97,13 @@ __global__ __launch_bounds__(64) void feat_prepare_kernel(const int64_t* __restr
 // prefix sums of n_g^2: where graph g's hop table (and its class-flag bits) start
 __global__ __launch_bounds__(1024) void feat_sq_scan_kernel(const int64_t* __restrict__ node_ptr, int64_t G,
                                                             int64_t* __restrict__ out) {
-  __shared__ int64_t wsum[16];
-  __shared__ int64_t carry_s;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (int64_t base = 0; base < G; base += 1024) {
-    const int64_t i = base + threadIdx.x;
-    int64_t v = 0;
-    if (i < G) { const int64_t n = node_ptr[i + 1] - node_ptr[i]; v = n * n; }
-    int64_t incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int64_t t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int64_t woff = 0;
-    for (int k = 0; k < w; ++k) woff += wsum[k];
-    const int64_t carry = carry_s;
-    if (i < G) out[i] = carry + woff + incl - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry_s = carry + woff + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[G] = carry_s;
-}
-
-// last g with ptr[g] <= i
-__device__ __forceinline__ int find_segment(const int64_t* __restrict__ ptr, int G, int64_t i) {
-  int lo = 0, hi = G;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (ptr[mid] <= i) lo = mid; else hi = mid;
-  }
-  return lo;
+  const int64_t total = block_exclusive_scan<int64_t>(
+      G, [&](int64_t i) { const int64_t n = node_ptr[i + 1] - node_ptr[i]; return n * n; }, [&](int64_t i, int64_t v) { out[i] = v; });
+  if (threadIdx.x == 0) out[G] = total;
 }
 
 // ---- hop tables: one wave per root node ------------------------------------------------------------
-// hop[sq_ptr[g] + r*n + x] = d(r,x) walking target -> source, HOP_INF beyond h; root_hash = hash of the reach SET
+// hop[sq_ptr[g] + r*n + x] = d(r,x) walking target -> source, GRAPH_HOP_INF beyond h; root_hash = hash of the reach SET
 __global__ __launch_bounds__(64) void feat_bfs_kernel(const int64_t* __restrict__ node_ptr, const int64_t* __restrict__ edge_ptr,
                                                       const int* __restrict__ w_src, const int* __restrict__ w_dst,
                                                       const int* __restrict__ e_out, const int64_t* __restrict__ sq_ptr,
@@ -181,26 +122,14 @@ __global__ __launch_bounds__(64) void feat_bfs_kernel(const int64_t* __restrict_
   const int* __restrict__ es = w_src + wo;
   const int* __restrict__ ed = w_dst + wo;
   unsigned char* hop = smem;
-  for (int x = lane; x < n; x += 64) hop[x] = HOP_INF;
-  __syncthreads();
-  if (lane == 0) hop[r] = 0;
-  __syncthreads();
-  for (int d = 1; d <= h; ++d) {
-    int grew = 0;
-    for (int j = lane; j < Eg; j += 64) {
-      const int s = es[j], t = ed[j];
-      if (hop[t] == d - 1 && hop[s] == HOP_INF) { hop[s] = (unsigned char)d; grew = 1; }
-    }
-    __syncthreads();
-    if (!__any(grew)) break;
-  }
+  wave_bfs(n, r, Eg, h, hop, [&](int j, int& s, int& t) { s = es[j]; t = ed[j]; return true; });
   unsigned char* __restrict__ row = hop_tab + sq_ptr[g] + (int64_t)r * n;
   unsigned long long hsh = 0x9E3779B97F4A7C15ull;
   for (int x0 = 0; x0 < n; x0 += 64) {
     const int x = x0 + lane;
-    const unsigned char v = x < n ? hop[x] : HOP_INF;
+    const unsigned char v = x < n ? hop[x] : GRAPH_HOP_INF;
     if (x < n) row[x] = v;
-    const unsigned long long msk = __ballot(v != HOP_INF);
+    const unsigned long long msk = __ballot(v != GRAPH_HOP_INF);
     hsh = (hsh ^ msk) * 0xFF51AFD7ED558CCDull;
     hsh ^= hsh >> 33;
   }
@@ -232,7 +161,7 @@ __global__ __launch_bounds__(64) void feat_canon_kernel(const int64_t* __restric
       cand &= cand - 1;
       const unsigned char* __restrict__ other = tab + (int64_t)q * n;
       int diff = 0;
-      for (int x = lane; x < n; x += 64) diff |= ((mine[x] != HOP_INF) != (other[x] != HOP_INF));
+      for (int x = lane; x < n; x += 64) diff |= ((mine[x] != GRAPH_HOP_INF) != (other[x] != GRAPH_HOP_INF));
       if (!__any(diff)) { found = q; break; }
     }
   }
@@ -267,7 +196,7 @@ __global__ __launch_bounds__(64) void feat_class_mark_kernel(ClassArgs a) {
   int m = 0;
   for (int x0 = 0; x0 < n; x0 += 64) {
     const int x = x0 + lane;
-    m += __popcll(__ballot(x < n && (hu[x] != HOP_INF || hv[x] != HOP_INF)));
+    m += __popcll(__ballot(x < n && (hu[x] != GRAPH_HOP_INF || hv[x] != GRAPH_HOP_INF)));
   }
   if (lane == 0) {
     const int cu = a.canon[n0 + u], cv = a.canon[n0 + v];
@@ -336,7 +265,7 @@ __global__ __launch_bounds__(HUGE ? 256 : 64) void feat_rd_class_kernel(ClassArg
     for (int x0 = 0; x0 < n; x0 += NT) {
       const int x = x0 + tid;
       int mb = 0;
-      if (x < n) { mb = (ha[x] != HOP_INF ? 1 : 0) | (hb[x] != HOP_INF ? 2 : 0); memb[x] = (unsigned char)mb; }
+      if (x < n) { mb = (ha[x] != GRAPH_HOP_INF ? 1 : 0) | (hb[x] != GRAPH_HOP_INF ? 2 : 0); memb[x] = (unsigned char)mb; }
       if (HUGE) {
         // ranks across 4 waves: per-wave ballots exchanged through red[] (as ints)
         const unsigned long long msk = __ballot(mb != 0);
@@ -349,47 +278,23 @@ __global__ __launch_bounds__(HUGE ? 256 : 64) void feat_rd_class_kernel(ClassArg
         if (x < n) loc[x] = mb ? (short)(m + before + __popcll(msk & ((1ull << (tid & 63)) - 1ull))) : (short)-1;
         m += all;
       } else {
-        const unsigned long long msk = __ballot(mb != 0);
-        if (x < n) loc[x] = mb ? (short)(m + __popcll(msk & ((1ull << tid) - 1ull))) : (short)-1;
-        m += __popcll(msk);
+        const int p = ballot_compact(mb != 0, m);
+        if (x < n) loc[x] = mb ? (short)p : (short)-1;
       }
     }
-    for (int idx = tid; idx < m * m; idx += NT) {
-      const int cc = idx / m, rr = idx % m;
-      Gm[(size_t)cc * ld + rr] = 0.0;
-      Vm[(size_t)cc * ld + rr] = (cc == rr) ? 1.0 : 0.0;
-    }
+    laplacian_clear<NT>(Gm, Vm, m, ld);
     __syncthreads();
     // L = D_in - A over the non-loop sub-edges (union of the two induced edge sets)
     for (int j = tid; j < Eg; j += NT) {
       const int s = es[j], t = ed[j];
       if (s == t) continue;
       if (!(memb[s] & memb[t])) continue;                     // both in S_a, or both in S_b
-      const int ls = loc[s], lt = loc[t];
-      atomicAdd(&Gm[(size_t)lt * ld + ls], -1.0);             // L[s][t] -= 1   (column-major: [col t][row s])
-      atomicAdd(&Gm[(size_t)lt * ld + lt], 1.0);              // L[t][t] += 1   (in-degree, loops excluded)
+      laplacian_add_edge(Gm, ld, loc[s], loc[t]);
     }
     __syncthreads();
     const double null2 = jacobi_orthogonalise<NT>(Gm, Vm, m, ld, red);
     __syncthreads();
-    // squared singular values = squared column norms; numerically-null ones are dropped (pinv cutoff)
-    for (int j = tid; j < m; j += NT) {
-      double s2 = 0.0;
-      for (int i = 0; i < m; ++i) { const double t = Gm[(size_t)j * ld + i]; s2 += t * t; }
-      inv_s2[j] = (s2 > null2) ? 1.0 / s2 : 0.0;
-    }
-    __syncthreads();
-    // P = V diag(1/s^2) G^T, written over V row by row: P[i][j'] = sum_j V[i][j] G[j'][j] / s_j^2
-    for (int i = 0; i < m; ++i) {
-      for (int j = tid; j < m; j += NT) vrow[j] = Vm[(size_t)j * ld + i] * inv_s2[j];
-      __syncthreads();
-      for (int jp = tid; jp < m; jp += NT) {
-        double acc = 0.0;
-        for (int j = 0; j < m; ++j) acc += vrow[j] * Gm[(size_t)j * ld + jp];
-        Vm[(size_t)jp * ld + i] = acc;
-      }
-      __syncthreads();
-    }
+    pinv_from_jacobi<NT>(Gm, Vm, m, ld, null2, inv_s2, vrow);
     const double* __restrict__ P = Vm;                        // P[i][j] at P[j*ld + i]
     // member edges of this class, each against its own root
     for (int k0 = 0; k0 < Eg; k0 += 64) {
@@ -411,12 +316,10 @@ __global__ __launch_bounds__(HUGE ? 256 : 64) void feat_rd_class_kernel(ClassArg
         const int r = loc[u];
         for (int b = tid; b < RD_BINS; b += NT) rdh[b] = 0;
         __syncthreads();
-        const double prr = phantom ? 0.0 : P[(size_t)r * ld + r];
         for (int x = tid; x < n; x += NT) {
           const int i = loc[x];
           if (i < 0) continue;
-          const double pii = P[(size_t)i * ld + i];
-          const double rd64 = phantom ? pii : (((prr + pii) - P[(size_t)i * ld + r]) - P[(size_t)r * ld + i]);
+          const double rd64 = phantom ? P[(size_t)i * ld + i] : resistance(P, ld, r, i);
           const float rd32 = (float)rd64;
           if (!(rd32 > -1.0f && rd32 < 100.0f)) { bad_s = 1; continue; }
           atomicAdd(&rdh[(int)rd32], 1);                      // (int) truncates toward zero like .long()
@@ -479,12 +382,12 @@ __global__ __launch_bounds__(64) void feat_encode_kernel(EncodeArgs a) {
   for (int j = lane; j < Eg; j += 64) {
     const int s = es[j], t = ed[j];
     const unsigned char us = hop_u[s], ut = hop_u[t], vs = hop_v[s], vt = hop_v[t];
-    const bool in_sub = (us != HOP_INF && ut != HOP_INF) || (vs != HOP_INF && vt != HOP_INF);
+    const bool in_sub = (us != GRAPH_HOP_INF && ut != GRAPH_HOP_INF) || (vs != GRAPH_HOP_INF && vt != GRAPH_HOP_INF);
     if (!in_sub) continue;
     atomicAdd(&deg[s], 1);
     if (s != t) {
-      const int z0s = us == HOP_INF ? far : us, z1s = vs == HOP_INF ? far : vs;
-      const int z0t = ut == HOP_INF ? far : ut, z1t = vt == HOP_INF ? far : vt;
+      const int z0s = us == GRAPH_HOP_INF ? far : us, z1s = vs == GRAPH_HOP_INF ? far : vs;
+      const int z0t = ut == GRAPH_HOP_INF ? far : ut, z1t = vt == GRAPH_HOP_INF ? far : vt;
       const int code = 216 * z0s + 36 * z1s + 6 * z0t + z1t;
       if (code >= 1300) { bad = true; } else { atomicAdd(&hist[off_edge + code], 1); }
     }
@@ -493,12 +396,12 @@ __global__ __launch_bounds__(64) void feat_encode_kernel(EncodeArgs a) {
   // node terms
   for (int x = lane; x < n; x += 64) {
     const unsigned char hu = hop_u[x], hv = hop_v[x];
-    if (hu == HOP_INF && hv == HOP_INF) continue;
+    if (hu == GRAPH_HOP_INF && hv == GRAPH_HOP_INF) continue;
     const int dg = deg[x];
     if (dg >= 200) { bad = true; continue; }
     atomicAdd(&hist[dg], 1);
-    atomicAdd(&hist[200 + (hu == HOP_INF ? far : hu)], 1);
-    atomicAdd(&hist[300 + (hv == HOP_INF ? far : hv)], 1);
+    atomicAdd(&hist[200 + (hu == GRAPH_HOP_INF ? far : hu)], 1);
+    atomicAdd(&hist[300 + (hv == GRAPH_HOP_INF ? far : hv)], 1);
   }
   if (do_rd) {
     const short* __restrict__ row = a.rd_rows + k_glob * RD_BINS;
@@ -524,12 +427,8 @@ __global__ __launch_bounds__(64) void feat_encode_kernel(EncodeArgs a) {
   for (int i0 = 0; i0 < HIST_BINS; i0 += 64) {
     const int i = i0 + lane;
     const int val = (i < HIST_BINS) ? hist[i] : 0;
-    const unsigned long long msk = __ballot(val != 0);
-    if (FILL && val != 0) {
-      const int64_t p = base + cnt + __popcll(msk & ((1ull << lane) - 1ull));
-      a.pos_enc[p] = val; a.pos_index[p] = i; a.pos_batch[p] = k;
-    }
-    cnt += __popcll(msk);
+    const int64_t p = base + ballot_compact(val != 0, cnt);
+    if (FILL && val != 0) { a.pos_enc[p] = val; a.pos_index[p] = i; a.pos_batch[p] = k; }
   }
   if (!FILL && lane == 0) a.nnz_cnt[k_glob] = cnt;
 }

@@ -5,6 +5,30 @@
 
 namespace esc {
 
+// ---- the Laplacian L = D_in - A of a node set, column-major with leading dimension ld (scipy csgraph.laplacian) ------------
+// Gm = 0, Vm = I over the leading m x m; a barrier follows before the first laplacian_add_edge
+template <int NT>
+__device__ __forceinline__ void laplacian_clear(double* Gm, double* Vm, int m, int ld) {
+  for (int idx = threadIdx.x; idx < m * m; idx += NT) {
+    const int cc = idx / m, rr = idx % m;
+    Gm[(size_t)cc * ld + rr] = 0.0;
+    Vm[(size_t)cc * ld + rr] = (cc == rr) ? 1.0 : 0.0;
+  }
+}
+
+// the non-loop sub-edge ls -> lt (local indices; which edges enter L is the caller's membership test).  Integer values: the
+// order of the atomics is free.
+__device__ __forceinline__ void laplacian_add_edge(double* Gm, int ld, int ls, int lt) {
+  atomicAdd(&Gm[(size_t)lt * ld + ls], -1.0);               // L[s][t] -= 1   (column-major: [col t][row s])
+  atomicAdd(&Gm[(size_t)lt * ld + lt], 1.0);                // L[t][t] += 1   (in-degree, loops excluded)
+}
+
+// resistance distance of local nodes a and b from the pseudo-inverse P (P[i][j] at P[j*ld + i]): l_aa + l_bb - l_ab - l_ba, in
+// exactly this association (the reference's fp64 expression; the result is rounded to fp32 and, in features.hip, truncated)
+__device__ __forceinline__ double resistance(const double* __restrict__ P, int ld, int a, int b) {
+  return ((P[(size_t)a * ld + a] + P[(size_t)b * ld + b]) - P[(size_t)b * ld + a]) - P[(size_t)a * ld + b];
+}
+
 // ---- one-sided Jacobi SVD based pseudo-inverse probe, NT threads, column-major matrices (LDS or global) -----
 // On entry Gm = L (m x m), Vm = I.  On exit Gm = L*V with mutually orthogonal columns.
 // Returns the squared-norm threshold below which a column counts as numerically null:

@@ -12,10 +12,10 @@
 // One wave per root, twice, in the manner of subgraphs.hip: the count pass sizes the output (and counts, per graph, the pairs at
 // every distance, which is what a dataset keeps so that no step reads a size back), the fill pass repeats the BFS and writes
 // with ballot-prefix compaction in node order, which IS ascending column order: no sort.  sub_locate, sub_bfs, the validation
-// and the scan are those of subgraphs.hip (subgraph_bfs.h); sub_bfs walks target -> source, so it is handed (dst, src) to walk
+// and the scan are those of subgraphs.hip (graph_wave.h); sub_bfs walks target -> source, so it is handed (dst, src) to walk
 // the out-edges.  LDS: one byte per node of the root's graph.  Integer work bound by LDS / L2 latency.
 #include "common.h"
-#include "subgraph_bfs.h"
+#include "graph_wave.h"
 #include "../../include/escgnn_gineplus.h"
 
 namespace esc {
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(64) void mh_count_kernel(const int64_t* __restrict_
   for (int d = 0; d <= MH_K_MAX; ++d) cnt[d] = 0;
   for (int x0 = 0; x0 < q.n; x0 += 64) {
     const int x = x0 + lane;
-    const int hx = x < q.n ? (int)hop[x] : (int)SUB_INF;
+    const int hx = x < q.n ? (int)hop[x] : (int)GRAPH_HOP_INF;
 #pragma unroll
     for (int d = 0; d <= MH_K_MAX; ++d) cnt[d] += __popcll(__ballot(hx == d));
   }
@@ -86,21 +86,19 @@ __global__ __launch_bounds__(64) void mh_fill_kernel(const int64_t* __restrict__
   int base = 0, base1 = 0;
   for (int x0 = 0; x0 < q.n; x0 += 64) {
     const int x = x0 + lane;
-    const int hx = x < q.n ? (int)hop[x] : (int)SUB_INF;
-    const bool mine = hx != (int)SUB_INF, one = hx == 1;
-    const unsigned long long msk = __ballot(mine), msk1 = __ballot(one), below = (1ull << lane) - 1ull;
+    const int hx = x < q.n ? (int)hop[x] : (int)GRAPH_HOP_INF;
+    const bool mine = hx != (int)GRAPH_HOP_INF, one = hx == 1;
+    const int slot = ballot_compact(mine, base), slot1 = ballot_compact(one, base1);
     if (mine) {
-      const int64_t p = p0 + base + __popcll(msk & below);
+      const int64_t p = p0 + slot;
       if (p < p1) {                                         // (holds by construction: the same BFS sized the range)
         const int64_t j = q.n0 + x;
         row[p] = r_glob; col[p] = j; distance[p] = hx;
         int4 m;
-        m.x = (int)r_glob; m.y = (int)j; m.z = hx; m.w = one ? (int)(r1 + base1 + __popcll(msk1 & below)) : -1;
+        m.x = (int)r_glob; m.y = (int)j; m.z = hx; m.w = one ? (int)(r1 + slot1) : -1;
         *reinterpret_cast<int4*>(meta + 4 * p) = m;
       }
     }
-    base += __popcll(msk);
-    base1 += __popcll(msk1);
   }
 }
 

@@ -10,6 +10,7 @@
 // — 1 pass for keys < 256, 2 for < 65 536 (nodes, histogram bins), 3 for < 2^24; then the segment pointers from an
 // integer histogram + scan.  Integer work, bit-exact by construction (stable = ascending position inside a key).
 #include "common.h"
+#include "graph_wave.h"
 
 namespace esc {
 
@@ -34,35 +35,12 @@ __global__ __launch_bounds__(256) void plan_hist_kernel(const int64_t* __restric
   hist[(size_t)threadIdx.x * nblk + blockIdx.x] = cnt[threadIdx.x];      // [digit][block]
 }
 
-// exclusive scan of n ints by ONE workgroup (n up to a few 10^5: 256 digits x blocks, or the key counts) -> out[n] (+ total
-// at out[n] when with_total)
+// exclusive scan of n ints by ONE workgroup (block_exclusive_scan of graph_wave.h; n up to a few 10^5: 256 digits x blocks, or
+// the key counts) -> out[n] (+ total at out[n] when with_total)
 __global__ __launch_bounds__(1024) void plan_scan_kernel(const int* __restrict__ in, int64_t n, int* __restrict__ out,
                                                          int with_total) {
-  __shared__ int wsum[16];
-  __shared__ int carry_s;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (int64_t base = 0; base < n; base += 1024) {
-    const int64_t i = base + threadIdx.x;
-    const int v = (i < n) ? in[i] : 0;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int woff = 0;
-    for (int k = 0; k < w; ++k) woff += wsum[k];
-    const int carry = carry_s;
-    if (i < n) out[i] = carry + woff + incl - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry_s = carry + woff + incl;
-    __syncthreads();
-  }
-  if (with_total && threadIdx.x == 0) out[n] = carry_s;
+  const int total = block_exclusive_scan<int>(n, [&](int64_t i) { return in[i]; }, [&](int64_t i, int v) { out[i] = v; });
+  if (with_total && threadIdx.x == 0) out[n] = total;
 }
 
 // one wave per block walks its chunk IN ORDER, 64 positions at a time: lanes with equal digits are matched by 8 ballots,
@@ -87,12 +65,11 @@ __global__ __launch_bounds__(64) void plan_scatter_kernel(const int64_t* __restr
       const unsigned long long m = __ballot((d >> b) & 1);
       same &= ((d >> b) & 1) ? m : ~m;
     }
-    const unsigned long long lower = same & ((1ull << lane) - 1ull);
-    const int rank = __popcll(lower);
+    const int rank = lane_rank(same);
     int dst = 0;
     if (live) dst = run[d] + rank;
     __syncthreads();                                   // every lane has read the counters of this group
-    if (live && lower == 0ull) run[d] += __popcll(same);
+    if (live && rank == 0) run[d] += __popcll(same);
     __syncthreads();
     if (live) idx_out[dst] = pos;
     if (base + (g + 1) * 64 >= n) break;               // wave-uniform

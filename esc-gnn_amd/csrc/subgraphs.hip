@@ -20,19 +20,20 @@
 // tables between the passes) and writes with stable ballot-prefix compaction.  Integer work bound by LDS / L2 latency.
 //
 // The second half of the file is the I2GNN baseline's expansion (esc_subgraph2_count / _fill, include/escgnn_i2gnn.h): the same
-// subgraphs, once per neighbour of their root, labelled with the distances to both.  It reuses the helpers above unchanged.
+// subgraphs, once per neighbour of their root, labelled with the distances to both.  Both halves are written on the primitives
+// of graph_wave.h (BFS, canonical positions, sub-edge compaction, the scan) and of jacobi_pinv.h (the Laplacian, its
+// pseudo-inverse, the resistance distance).
 #include "common.h"
+#include "graph_wave.h"
 #include "jacobi_pinv.h"
-#include "subgraph_bfs.h"
 #include "../../include/escgnn_subgraphs.h"
 #include "../../include/escgnn_i2gnn.h"
 
 namespace esc {
 
-constexpr int SUB_RD_MAX = 96;          // largest subgraph whose two m x m fp64 matrices fit LDS (147 KB); LDS_SUBGRAPH of features.hip
 constexpr int SUB_MAX_NODES = 4096;     // 7 B of LDS tables per node (see sub_fill_lds)
 constexpr int SUB_H_MAX = 98;           // z = hop + 1 and the model's z tables have 100 rows
-// (SUB_INF, sub_find_segment, SubRoot, sub_locate and sub_bfs: subgraph_bfs.h, shared with multihop.hip)
+// (GRAPH_HOP_INF, GRAPH_RD_MAX, SubRoot, sub_locate and sub_bfs: graph_wave.h, shared with multihop.hip)
 
 // ---- per-graph validation (one wave per graph): ids inside the graph, graph inside the LDS tables -----------------
 __global__ __launch_bounds__(64) void sub_validate_kernel(const int64_t* __restrict__ node_ptr,
@@ -60,65 +61,73 @@ __global__ __launch_bounds__(64) void sub_validate_kernel(const int64_t* __restr
   if (lane == 0) status[g] = bad ? ESC_ERANGE : 0;
 }
 
-// ---- count pass: |S_r| and the number of sub-edges of every root, left in the pointer arrays for the scan ----------
+// ---- count pass: |S_r| and the number of sub-edges of every root, left in the pointer arrays for the scan.  SECOND (the
+// I2GNN expansion, second half of the file): a root has one copy of its subgraph per neighbour, and cnt_s2 takes that number ----
+template <bool SECOND>
 __global__ __launch_bounds__(64) void sub_count_kernel(const int64_t* __restrict__ node_ptr, const int64_t* __restrict__ edge_ptr,
                                                        const int64_t* __restrict__ src, const int64_t* __restrict__ dst, int G,
                                                        int64_t total_nodes, int h, const int* __restrict__ status,
-                                                       int64_t* __restrict__ cnt_nodes, int64_t* __restrict__ cnt_edges) {
+                                                       int64_t* __restrict__ cnt_nodes, int64_t* __restrict__ cnt_edges,
+                                                       int64_t* __restrict__ cnt_s2) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x;
   const int64_t r_glob = blockIdx.x;
   if (r_glob >= total_nodes) return;
   const SubRoot q = sub_locate(node_ptr, edge_ptr, G, r_glob);
   if (status[q.g] != 0) {
-    if (lane == 0) { cnt_nodes[r_glob] = 0; cnt_edges[r_glob] = 0; }
+    if (lane == 0) { cnt_nodes[r_glob] = 0; cnt_edges[r_glob] = 0; if (SECOND) cnt_s2[r_glob] = 0; }
     return;
   }
   unsigned char* hop = smem;
   sub_bfs(q, src, dst, h, hop);
-  int nn = 0, ne = 0;
+  int nn = 0, ne = 0, nk = 0;
   for (int x0 = 0; x0 < q.n; x0 += 64) {
     const int x = x0 + lane;
-    nn += __popcll(__ballot(x < q.n && hop[x] != SUB_INF));
+    nn += __popcll(__ballot(x < q.n && hop[x] != GRAPH_HOP_INF));
   }
   for (int j0 = 0; j0 < q.Eg; j0 += 64) {
     const int j = j0 + lane;
-    bool keep = false;
-    if (j < q.Eg) keep = hop[src[q.e0 + j] - q.n0] != SUB_INF && hop[dst[q.e0 + j] - q.n0] != SUB_INF;
+    bool keep = false, nb = false;
+    if (j < q.Eg) {
+      const int s = (int)(src[q.e0 + j] - q.n0);
+      keep = hop[s] != GRAPH_HOP_INF && hop[dst[q.e0 + j] - q.n0] != GRAPH_HOP_INF;
+      nb = keep && s == q.r;
+    }
     ne += __popcll(__ballot(keep));
+    if (SECOND) nk += __popcll(__ballot(nb));
   }
-  if (lane == 0) { cnt_nodes[r_glob] = nn; cnt_edges[r_glob] = ne; }
+  const int64_t mult = nk > 0 ? nk : 1;
+  if (lane == 0) { cnt_nodes[r_glob] = mult * nn; cnt_edges[r_glob] = mult * ne; if (SECOND) cnt_s2[r_glob] = mult; }
 }
 
-// ---- in-place exclusive scan of int64 counts (scan_counts_kernel's scheme: one workgroup, 1024-wide chunks with a carry);
-// blockIdx.x picks the array ------------------------------------------------------------------------------------------
+// ---- in-place exclusive scan of int64 counts (block_exclusive_scan); blockIdx.x picks the array ------------------------------
 __global__ __launch_bounds__(1024) void sub_scan_kernel(int64_t* __restrict__ a0, int64_t* __restrict__ a1, int64_t n) {
-  __shared__ int64_t wsum[16];
-  __shared__ int64_t carry_s;
   int64_t* __restrict__ buf = blockIdx.x == 0 ? a0 : a1;
-  if (threadIdx.x == 0) carry_s = 0;
+  const int64_t total = block_exclusive_scan<int64_t>(n, [&](int64_t i) { return buf[i]; }, [&](int64_t i, int64_t v) { buf[i] = v; });
+  if (threadIdx.x == 0) buf[n] = total;
+}
+
+// ---- rd of both fill kernels: P = pinv(D_in - A) over the non-loop sub-edges of S_r, m nodes at their canonical positions.
+// mem: Gm[ld*ld] Vm[ld*ld] inv_s2[ld] vrow[ld] red[8] doubles of LDS.  Returns P, P[i][j] at P[j*ld + i] --------------------------
+__device__ __forceinline__ const double* sub_rooted_pinv(const SubRoot& q, const int64_t* __restrict__ src, const int64_t* __restrict__ dst,
+                                                         const unsigned char* hop, const short* loc, int m, int ld, unsigned char* mem) {
+  double* Gm = reinterpret_cast<double*>(mem);
+  double* Vm = Gm + (size_t)ld * ld;
+  double* inv_s2 = Vm + (size_t)ld * ld;
+  double* vrow = inv_s2 + ld;
+  double* red = vrow + ld;
+  laplacian_clear<64>(Gm, Vm, m, ld);
   __syncthreads();
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (int64_t base = 0; base < n; base += 1024) {
-    const int64_t i = base + threadIdx.x;
-    const int64_t v = (i < n) ? buf[i] : 0;
-    int64_t incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int64_t t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int64_t woff = 0;
-    for (int k = 0; k < w; ++k) woff += wsum[k];
-    const int64_t carry = carry_s;
-    if (i < n) buf[i] = carry + woff + incl - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry_s = carry + woff + incl;
-    __syncthreads();
+  for (int j = threadIdx.x; j < q.Eg; j += 64) {
+    const int s = (int)(src[q.e0 + j] - q.n0), t = (int)(dst[q.e0 + j] - q.n0);
+    if (s == t || hop[s] == GRAPH_HOP_INF || hop[t] == GRAPH_HOP_INF) continue;
+    laplacian_add_edge(Gm, ld, loc[s], loc[t]);
   }
-  if (threadIdx.x == 0) buf[n] = carry_s;
+  __syncthreads();
+  const double null2 = jacobi_orthogonalise<64>(Gm, Vm, m, ld, red);
+  __syncthreads();
+  pinv_from_jacobi<64>(Gm, Vm, m, ld, null2, inv_s2, vrow);
+  return Vm;
 }
 
 // ---- fill pass ------------------------------------------------------------------------------------------------------
@@ -153,84 +162,30 @@ __global__ __launch_bounds__(64) void sub_fill_kernel(SubFillArgs a) {
   short* loc = reinterpret_cast<short*>(hop + a.n_cap);     // [n_cap]
   int* paths = reinterpret_cast<int*>(loc + a.n_cap);       // [n_cap]
   sub_bfs(q, a.src, a.dst, a.h, hop);
-  // canonical positions: level by level, ascending node id inside a level (the root is the only node of level 0)
-  int m = 0;
-  for (int d = 0; d <= a.h; ++d) {
-    const int before = m;
-    for (int x0 = 0; x0 < q.n; x0 += 64) {
-      const int x = x0 + lane;
-      const bool mine = x < q.n && hop[x] == d;
-      const unsigned long long msk = __ballot(mine);
-      if (mine) loc[x] = (short)(m + __popcll(msk & ((1ull << lane) - 1ull)));
-      m += __popcll(msk);
-    }
-    if (m == before) break;                                 // an empty level ends the BFS
-  }
-  for (int x = lane; x < q.n; x += 64) { paths[x] = 0; if (hop[x] == SUB_INF) loc[x] = -1; }
+  const int m = canonical_positions(q, a.h, hop, loc);
+  for (int x = lane; x < q.n; x += 64) { paths[x] = 0; if (hop[x] == GRAPH_HOP_INF) loc[x] = -1; }
   __syncthreads();
   const int64_t sn0 = a.sub_node_ptr[r_glob], se0 = a.sub_edge_ptr[r_glob];
   // sub-edges in their original order, relabelled to global sub-node ids; and the frontier edges into every node
-  int base = 0;
-  for (int j0 = 0; j0 < q.Eg; j0 += 64) {
-    const int j = j0 + lane;
-    bool keep = false;
-    int s = 0, t = 0;
-    if (j < q.Eg) {
-      s = (int)(a.src[q.e0 + j] - q.n0); t = (int)(a.dst[q.e0 + j] - q.n0);
-      keep = hop[s] != SUB_INF && hop[t] != SUB_INF;
-    }
-    const unsigned long long msk = __ballot(keep);
-    if (keep) {
-      const int64_t p = se0 + base + __popcll(msk & ((1ull << lane) - 1ull));
-      a.sub_src[p] = sn0 + loc[s]; a.sub_dst[p] = sn0 + loc[t]; a.orig_edge[p] = q.e0 + j;
-      if ((int)hop[t] + 1 == (int)hop[s]) atomicAdd(&paths[s], 1);
-    }
-    base += __popcll(msk);
-  }
+  relabel_sub_edges(q, a.src, a.dst, hop, loc, sn0, se0, a.sub_src, a.sub_dst, a.orig_edge,
+                    [&](int s, int t) { if ((int)hop[t] + 1 == (int)hop[s]) atomicAdd(&paths[s], 1); });
   __syncthreads();
   for (int x = lane; x < q.n; x += 64) {
-    if (hop[x] == SUB_INF) continue;
+    if (hop[x] == GRAPH_HOP_INF) continue;
     const int64_t p = sn0 + loc[x];
     a.orig_node[p] = q.n0 + x; a.hop_label[p] = (int64_t)hop[x] + 1; a.hop_paths[p] = paths[x];
     a.node_to_subgraph[p] = r_glob; a.node_to_graph[p] = q.g;
   }
   if (!RD) return;
-  if (m > SUB_RD_MAX || m > a.ld) {                          // wave-uniform
+  if (m > GRAPH_RD_MAX || m > a.ld) {                       // wave-uniform
     if (lane == 0) a.status[q.g] = ESC_ERANGE;
     return;
   }
   const int ld = a.ld;
   __syncthreads();                                          // `paths` has been read: the matrices take its place
   const size_t off = ((size_t)a.n_cap * 3 + 15) & ~(size_t)15;
-  double* Gm = reinterpret_cast<double*>(smem + off);
-  double* Vm = Gm + (size_t)ld * ld;
-  double* inv_s2 = Vm + (size_t)ld * ld;
-  double* vrow = inv_s2 + ld;
-  double* red = vrow + ld;
-  for (int idx = lane; idx < m * m; idx += 64) {
-    const int cc = idx / m, rr = idx % m;
-    Gm[(size_t)cc * ld + rr] = 0.0;
-    Vm[(size_t)cc * ld + rr] = (cc == rr) ? 1.0 : 0.0;
-  }
-  __syncthreads();
-  // L = D_in - A over the non-loop sub-edges (scipy csgraph.laplacian), column-major
-  for (int j = lane; j < q.Eg; j += 64) {
-    const int s = (int)(a.src[q.e0 + j] - q.n0), t = (int)(a.dst[q.e0 + j] - q.n0);
-    if (s == t || hop[s] == SUB_INF || hop[t] == SUB_INF) continue;
-    const int ls = loc[s], lt = loc[t];
-    atomicAdd(&Gm[(size_t)lt * ld + ls], -1.0);             // L[s][t] -= 1   ([col t][row s]); integer values: order free
-    atomicAdd(&Gm[(size_t)lt * ld + lt], 1.0);              // L[t][t] += 1   (in-degree, loops excluded)
-  }
-  __syncthreads();
-  const double null2 = jacobi_orthogonalise<64>(Gm, Vm, m, ld, red);
-  __syncthreads();
-  pinv_from_jacobi<64>(Gm, Vm, m, ld, null2, inv_s2, vrow);
-  const double* __restrict__ P = Vm;                        // P[i][j] at P[j*ld + i]; the root is local node 0
-  const double p00 = P[0];
-  for (int i = lane; i < m; i += 64) {
-    const double rd64 = ((p00 + P[(size_t)i * ld + i]) - P[(size_t)i * ld]) - P[i];   // lxx + lyy - lxy - lyx (:73): 0 at the root
-    a.rd[sn0 + i] = (float)rd64;
-  }
+  const double* P = sub_rooted_pinv(q, a.src, a.dst, hop, loc, m, ld, smem + off);
+  for (int i = lane; i < m; i += 64) a.rd[sn0 + i] = (float)resistance(P, ld, 0, i);   // lxx + lyy - lxy - lyx (:73), the root is local node 0: 0 there
 }
 
 // ---- subgraph_pooling = 'center': the first row of every segment ---------------------------------------------------------
@@ -272,7 +227,7 @@ static bool sub_totals_ok(int64_t total_sub_nodes, int64_t total_sub_edges) {
 static int sub_n_cap(int64_t max_nodes) { return (int)((max_nodes + 3) & ~3LL); }
 static int sub_rd_ld(int64_t max_nodes) {
   const int m_even = (int)((max_nodes + 1) & ~1LL);
-  return m_even < SUB_RD_MAX ? m_even : SUB_RD_MAX;
+  return m_even < GRAPH_RD_MAX ? m_even : GRAPH_RD_MAX;
 }
 // one wave per root; the rd variant may need more dynamic LDS than the default 64 KB
 template <typename FillArgs>
@@ -281,7 +236,7 @@ static void sub_launch_fill(void (*with_rd)(FillArgs), void (*without_rd)(FillAr
   esc::launch(ESC_K_FEATURES, use_rd ? with_rd : without_rd, dim3((unsigned)a.total_nodes), dim3(64), lds, s, a);
 }
 
-// the two kernels above that multihop.hip launches as well (subgraph_bfs.h)
+// the two kernels above that multihop.hip launches as well (graph_wave.h)
 void sub_launch_validate(const int64_t* node_ptr, const int64_t* edge_ptr, const int64_t* src, const int64_t* dst, int64_t G,
                          int64_t total_nodes, int64_t total_edges, int64_t max_nodes, int* status, hipStream_t s) {
   esc::launch(ESC_K_FEATURES, sub_validate_kernel, dim3((unsigned)G), dim3(64), 0, s, node_ptr, edge_ptr, src, dst, (int)G, total_nodes,
@@ -298,42 +253,6 @@ void sub_launch_scan(int64_t* a0, int64_t* a1, int64_t n, hipStream_t s) {
 // neighbour has one copy whose second label pair and second rd column repeat the first.
 constexpr int SUB2_MAX_NODES = 1536;    // 9 B of LDS tables per node beside the two 96 x 96 fp64 matrices (see sub2_fill_lds)
 constexpr int SUB2_H_MAX = 47;          // the largest label is 2h + 5 and the model's z tables have 100 rows
-
-__global__ __launch_bounds__(64) void sub2_count_kernel(const int64_t* __restrict__ node_ptr, const int64_t* __restrict__ edge_ptr,
-                                                        const int64_t* __restrict__ src, const int64_t* __restrict__ dst, int G,
-                                                        int64_t total_nodes, int h, const int* __restrict__ status,
-                                                        int64_t* __restrict__ cnt_nodes, int64_t* __restrict__ cnt_edges,
-                                                        int64_t* __restrict__ cnt_s2) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int lane = threadIdx.x;
-  const int64_t r_glob = blockIdx.x;
-  if (r_glob >= total_nodes) return;
-  const SubRoot q = sub_locate(node_ptr, edge_ptr, G, r_glob);
-  if (status[q.g] != 0) {
-    if (lane == 0) { cnt_nodes[r_glob] = 0; cnt_edges[r_glob] = 0; cnt_s2[r_glob] = 0; }
-    return;
-  }
-  unsigned char* hop = smem;
-  sub_bfs(q, src, dst, h, hop);
-  int nn = 0, ne = 0, nk = 0;
-  for (int x0 = 0; x0 < q.n; x0 += 64) {
-    const int x = x0 + lane;
-    nn += __popcll(__ballot(x < q.n && hop[x] != SUB_INF));
-  }
-  for (int j0 = 0; j0 < q.Eg; j0 += 64) {
-    const int j = j0 + lane;
-    bool keep = false, nb = false;
-    if (j < q.Eg) {
-      const int s = (int)(src[q.e0 + j] - q.n0);
-      keep = hop[s] != SUB_INF && hop[dst[q.e0 + j] - q.n0] != SUB_INF;
-      nb = keep && s == q.r;
-    }
-    ne += __popcll(__ballot(keep));
-    nk += __popcll(__ballot(nb));
-  }
-  const int64_t mult = nk > 0 ? nk : 1;
-  if (lane == 0) { cnt_nodes[r_glob] = mult * nn; cnt_edges[r_glob] = mult * ne; cnt_s2[r_glob] = mult; }
-}
 
 struct Sub2FillArgs {
   const int64_t* node_ptr; const int64_t* edge_ptr; const int64_t* src; const int64_t* dst;
@@ -371,19 +290,8 @@ __global__ __launch_bounds__(64) void sub2_fill_kernel(Sub2FillArgs a) {
   short* loc = reinterpret_cast<short*>(hopj + a.n_cap);    // [n_cap]
   int* cnt = reinterpret_cast<int*>(loc + a.n_cap);         // [n_cap] frontier edges into the node, of the BFS at hand
   sub_bfs(q, a.src, a.dst, a.h, hop);
-  int m = 0;
-  for (int d = 0; d <= a.h; ++d) {
-    const int before = m;
-    for (int x0 = 0; x0 < q.n; x0 += 64) {
-      const int x = x0 + lane;
-      const bool mine = x < q.n && hop[x] == d;
-      const unsigned long long msk = __ballot(mine);
-      if (mine) loc[x] = (short)(m + __popcll(msk & ((1ull << lane) - 1ull)));
-      m += __popcll(msk);
-    }
-    if (m == before) break;
-  }
-  for (int x = lane; x < q.n; x += 64) { cnt[x] = 0; if (hop[x] == SUB_INF) loc[x] = -1; }
+  const int m = canonical_positions(q, a.h, hop, loc);
+  for (int x = lane; x < q.n; x += 64) { cnt[x] = 0; if (hop[x] == GRAPH_HOP_INF) loc[x] = -1; }
   __syncthreads();
   int e = 0, K = 0;
   for (int j0 = 0; j0 < q.Eg; j0 += 64) {
@@ -391,7 +299,7 @@ __global__ __launch_bounds__(64) void sub2_fill_kernel(Sub2FillArgs a) {
     bool keep = false, nb = false;
     if (j < q.Eg) {
       const int s = (int)(a.src[q.e0 + j] - q.n0), t = (int)(a.dst[q.e0 + j] - q.n0);
-      keep = hop[s] != SUB_INF && hop[t] != SUB_INF;
+      keep = hop[s] != GRAPH_HOP_INF && hop[t] != GRAPH_HOP_INF;
       nb = keep && s == q.r;
       if (keep && (int)hop[t] + 1 == (int)hop[s]) atomicAdd(&cnt[s], 1);
     }
@@ -410,34 +318,11 @@ __global__ __launch_bounds__(64) void sub2_fill_kernel(Sub2FillArgs a) {
   const int ld = a.ld;
   const double* P = nullptr;                                // P[i][j] at P[j*ld + i]; the root is local node 0
   if (RD) {
-    if (m > SUB_RD_MAX || m > ld) {                         // wave-uniform; the rd rows of this root stay unwritten
+    if (m > GRAPH_RD_MAX || m > ld) {                       // wave-uniform; the rd rows of this root stay unwritten
       if (lane == 0) a.status[q.g] = ESC_ERANGE;
       rd_ok = false;
     } else {
-      const size_t off = ((size_t)a.n_cap * 9 + 15) & ~(size_t)15;
-      double* Gm = reinterpret_cast<double*>(smem + off);
-      double* Vm = Gm + (size_t)ld * ld;
-      double* inv_s2 = Vm + (size_t)ld * ld;
-      double* vrow = inv_s2 + ld;
-      double* red = vrow + ld;
-      for (int idx = lane; idx < m * m; idx += 64) {
-        const int cc = idx / m, rr = idx % m;
-        Gm[(size_t)cc * ld + rr] = 0.0;
-        Vm[(size_t)cc * ld + rr] = (cc == rr) ? 1.0 : 0.0;
-      }
-      __syncthreads();
-      for (int j = lane; j < q.Eg; j += 64) {               // L = D_in - A over the non-loop sub-edges, as sub_fill_kernel
-        const int s = (int)(a.src[q.e0 + j] - q.n0), t = (int)(a.dst[q.e0 + j] - q.n0);
-        if (s == t || hop[s] == SUB_INF || hop[t] == SUB_INF) continue;
-        const int ls = loc[s], lt = loc[t];
-        atomicAdd(&Gm[(size_t)lt * ld + ls], -1.0);
-        atomicAdd(&Gm[(size_t)lt * ld + lt], 1.0);
-      }
-      __syncthreads();
-      const double null2 = jacobi_orthogonalise<64>(Gm, Vm, m, ld, red);
-      __syncthreads();
-      pinv_from_jacobi<64>(Gm, Vm, m, ld, null2, inv_s2, vrow);
-      P = Vm;
+      P = sub_rooted_pinv(q, a.src, a.dst, hop, loc, m, ld, smem + (((size_t)a.n_cap * 9 + 15) & ~(size_t)15));
     }
   }
   __syncthreads();
@@ -453,13 +338,12 @@ __global__ __launch_bounds__(64) void sub2_fill_kernel(Sub2FillArgs a) {
         int t = 0;
         if (j < q.Eg) {
           t = (int)(a.dst[q.e0 + j] - q.n0);
-          nb = (int)(a.src[q.e0 + j] - q.n0) == q.r && hop[t] != SUB_INF;
+          nb = (int)(a.src[q.e0 + j] - q.n0) == q.r && hop[t] != GRAPH_HOP_INF;
         }
-        const unsigned long long msk = __ballot(nb);
-        if (nb && base + __popcll(msk & ((1ull << lane) - 1ull)) == c) jsel = t;
-        base += __popcll(msk);
+        const int p = ballot_compact(nb, base);
+        if (nb && p == c) jsel = t;
       }
-      for (int x = lane; x < q.n; x += 64) { hopj[x] = SUB_INF; cnt[x] = 0; }
+      for (int x = lane; x < q.n; x += 64) { hopj[x] = GRAPH_HOP_INF; cnt[x] = 0; }
       __syncthreads();
       jx = jsel;
       if (lane == 0) hopj[jx] = 0;
@@ -467,59 +351,36 @@ __global__ __launch_bounds__(64) void sub2_fill_kernel(Sub2FillArgs a) {
       // the reference's unbounded BFS from the neighbour over the sub-edges only, target -> source.  It ends within h + 1
       // levels on any graph: the sub-edge r -> j puts r at distance 1 of j, and every node of S_r reaches r inside S_r in
       // hop <= h steps, so d_j <= h + 1, every node of S_r is reached and the largest label is (h + 2) + (h + 3) <= 99
-      for (int d = 1; d <= a.h + 1; ++d) {
-        int grew = 0;
-        for (int j = lane; j < q.Eg; j += 64) {
-          const int s = (int)(a.src[q.e0 + j] - q.n0), t = (int)(a.dst[q.e0 + j] - q.n0);
-          if (hop[s] != SUB_INF && hopj[t] == d - 1 && hopj[s] == SUB_INF) { hopj[s] = (unsigned char)d; grew = 1; }
-        }
-        __syncthreads();
-        if (!__any(grew)) break;
-      }
+      wave_bfs_levels(q.Eg, a.h + 1, hopj, [&](int j, int& s, int& t) {
+        s = (int)(a.src[q.e0 + j] - q.n0); t = (int)(a.dst[q.e0 + j] - q.n0);
+        return hop[s] != GRAPH_HOP_INF;
+      });
       for (int j = lane; j < q.Eg; j += 64) {
         const int s = (int)(a.src[q.e0 + j] - q.n0), t = (int)(a.dst[q.e0 + j] - q.n0);
-        if (hop[s] != SUB_INF && hopj[t] != SUB_INF && (int)hopj[t] + 1 == (int)hopj[s]) atomicAdd(&cnt[s], 1);
+        if (hop[s] != GRAPH_HOP_INF && hopj[t] != GRAPH_HOP_INF && (int)hopj[t] + 1 == (int)hopj[s]) atomicAdd(&cnt[s], 1);
       }
       __syncthreads();
     }
     const int lj = loc[jx];
     const int64_t shift = a.h + 3;
     for (int x = lane; x < q.n; x += 64) {
-      if (hop[x] == SUB_INF) continue;
+      if (hop[x] == GRAPH_HOP_INF) continue;
       const int k = loc[x];
       const int64_t p = n_at + k;
       const int64_t z0 = (int64_t)hop[x] + 1, z1 = two[x] ? z0 : 0;
       int64_t z2 = z0, z3 = z1;                             // no neighbour: the root's pair tiled twice
       if (K > 0) {
-        const int64_t dj = hopj[x] == SUB_INF ? 0 : (int64_t)hopj[x] + 1;
+        const int64_t dj = hopj[x] == GRAPH_HOP_INF ? 0 : (int64_t)hopj[x] + 1;
         z2 = dj + shift; z3 = (cnt[x] >= 2 ? dj : 0) + shift;
       }
       a.orig_node[p] = q.n0 + x;
       a.z[4 * p] = z0; a.z[4 * p + 1] = z1; a.z[4 * p + 2] = z2; a.z[4 * p + 3] = z3;
       a.node_to_subgraph2[p] = s20 + c; a.node_to_graph[p] = q.g;
       if (RD && rd_ok) {
-        const double pkk = P[(size_t)k * ld + k];
-        const double r0 = ((P[0] + pkk) - P[(size_t)k * ld]) - P[k];                          // l_00 + l_kk - L[0,k] - L[k,0]
-        const double rj = ((P[(size_t)lj * ld + lj] + pkk) - P[(size_t)k * ld + lj]) - P[(size_t)lj * ld + k];
-        a.rd[2 * p] = (float)r0; a.rd[2 * p + 1] = (float)rj;
+        a.rd[2 * p] = (float)resistance(P, ld, 0, k); a.rd[2 * p + 1] = (float)resistance(P, ld, lj, k);
       }
     }
-    int base = 0;
-    for (int j0 = 0; j0 < q.Eg; j0 += 64) {
-      const int j = j0 + lane;
-      bool keep = false;
-      int s = 0, t = 0;
-      if (j < q.Eg) {
-        s = (int)(a.src[q.e0 + j] - q.n0); t = (int)(a.dst[q.e0 + j] - q.n0);
-        keep = hop[s] != SUB_INF && hop[t] != SUB_INF;
-      }
-      const unsigned long long msk = __ballot(keep);
-      if (keep) {
-        const int64_t p = e_at + base + __popcll(msk & ((1ull << lane) - 1ull));
-        a.sub_src[p] = n_at + loc[s]; a.sub_dst[p] = n_at + loc[t]; a.orig_edge[p] = q.e0 + j;
-      }
-      base += __popcll(msk);
-    }
+    relabel_sub_edges(q, a.src, a.dst, hop, loc, n_at, e_at, a.sub_src, a.sub_dst, a.orig_edge, [](int, int) {});
     if (lane == 0) {
       a.subgraph2_to_subgraph[s20 + c] = r_glob;
       a.center_idx[2 * (s20 + c)] = n_at; a.center_idx[2 * (s20 + c) + 1] = n_at + lj;
@@ -554,13 +415,8 @@ static int sub_count_pass(const char* fn, const int64_t* node_ptr, const int64_t
   if (total_nodes > 0) {
     const dim3 grid((unsigned)total_nodes);
     const size_t n_cap = (size_t)sub_n_cap(max_nodes);
-    if (sub2_ptr) {
-      esc::launch(ESC_K_FEATURES, sub2_count_kernel, grid, dim3(64), n_cap, s, node_ptr, edge_ptr, src, dst, (int)G, total_nodes, h,
-                  (const int*)status, sub_node_ptr, sub_edge_ptr, sub2_ptr);
-    } else {
-      esc::launch(ESC_K_FEATURES, sub_count_kernel, grid, dim3(64), n_cap, s, node_ptr, edge_ptr, src, dst, (int)G, total_nodes, h,
-                  (const int*)status, sub_node_ptr, sub_edge_ptr);
-    }
+    esc::launch(ESC_K_FEATURES, sub2_ptr ? sub_count_kernel<true> : sub_count_kernel<false>, grid, dim3(64), n_cap, s, node_ptr, edge_ptr,
+                src, dst, (int)G, total_nodes, h, (const int*)status, sub_node_ptr, sub_edge_ptr, sub2_ptr);
     if (const int rc = sub_launched(fn, "count")) return rc;
   }
   sub_launch_scan(sub_node_ptr, sub_edge_ptr, total_nodes, s);

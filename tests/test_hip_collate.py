@@ -124,6 +124,24 @@ def test_plan_csr_kernel_is_a_stable_sort(E, n, n_keys, seed):
             _csr(bad.to(DEV), n_keys)
 
 
+@pytest.mark.parametrize("n_keys", [1023, 1024, 1025, 2049])
+def test_segment_pointers_across_the_scan_chunk_with_empty_keys(E, n_keys):
+    """plan_scan_kernel with the total stored, on either side of its 1024-wide chunk and over two carries: a sorted key vector
+    with zero to three positions per key, the first key, the last key and a run around the chunk boundary empty"""
+    from esc_gnn_amd.plan import _csr
+    counts = torch.randint(0, 4, (n_keys,), generator=torch.Generator().manual_seed(n_keys))
+    counts[0] = counts[-1] = 0
+    counts[1020:1023] = 0
+    key = torch.repeat_interleave(torch.arange(n_keys), counts)
+    want = torch.zeros(n_keys + 1, dtype=torch.int64)
+    want[1:] = torch.bincount(key, minlength=n_keys).cumsum(0)
+    assert int(want[-1]) == key.numel() > n_keys
+    ptr, none = _csr(key.to(DEV), n_keys, want_perm=False)
+    assert none is None and ptr.dtype == torch.int32 and torch.equal(ptr.cpu().long(), want)
+    ptr2, perm = _csr(key.to(DEV), n_keys)
+    assert torch.equal(ptr2, ptr) and torch.equal(perm.cpu().long(), torch.arange(key.numel()))   # already grouped: the identity
+
+
 def test_plan_cache_follows_the_index_tensors(E):
     """plan_of() caches the CSR/CSC plan on the Data object; replacing or editing edge_index (edge dropout, augmentation,
     a re-used Batch) must rebuild it instead of aggregating over the stale one."""

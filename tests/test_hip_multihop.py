@@ -63,6 +63,34 @@ def test_batch_without_edges_gives_empty_tensors(E):
     assert tuple(mei.shape) == (2, 0) and tuple(dist.shape) == (0,) and mei.dtype == torch.int64 and dist.dtype == torch.int64
 
 
+def test_expansion_of_more_than_1024_roots_against_oracle(E):
+    """a batch shaped like the fresh sweeps of test_hip_ngnn.py and test_hip_i2gnn.py: a graph without edges first and last, a
+    one-node graph, rings of 63, 64, 65 and 130 nodes (wavefront boundaries, more than two ballot chunks), a directed graph and 30
+    molecules, so that the batch has more than 1024 + 64 roots and the two-array scan of esc_multihop_count carries"""
+    from esc_gnn_amd.datasets import synthetic_zinc_graphs
+    rng = np.random.RandomState(23)
+    none = np.zeros((2, 0), dtype=np.int64)
+    gs = [(5, none), (1, none)]
+    for n in (63, 64, 65, 130):
+        chords = [(int(a), int(b)) for a, b in rng.randint(0, n, (n // 8, 2)) if a != b]
+        gs.append((n, mo._und([(i, (i + 1) % n) for i in range(n)] + chords)))
+    gs.append((66, np.stack([rng.randint(0, 66, 140), rng.randint(0, 66, 140)]).astype(np.int64)))    # directed, three edge chunks
+    gs += [(int(d.num_nodes), d.edge_index.numpy()) for d in synthetic_zinc_graphs(100, 30)]
+    gs.append((3, none))
+    assert sum(n for n, _ in gs) > 1024 + 64
+    k = 2
+    got_mei, got_dist = _expand(E, [_graph(E, n, ei) for n, ei in gs], k)
+    want = mo.multihop_batch([n for n, _ in gs], [ei for _, ei in gs], k)
+    assert got_mei.dtype == torch.int64 and got_dist.dtype == torch.int64
+    assert np.array_equal(got_mei.cpu().numpy(), want[0]) and np.array_equal(got_dist.cpu().numpy(), want[1])
+    plan = got_mei._esc_multihop_plan
+    assert int(plan.status.abs().sum()) == 0
+    # the two scanned arrays themselves: the pair ranges of the roots, and the ranks of the distance-1 pairs
+    assert np.array_equal(plan.out_ptr.cpu().numpy(), np.searchsorted(want[0][0], np.arange(plan.num_nodes + 1)))
+    meta, d1 = plan.meta.cpu().numpy(), want[1] == 1
+    assert np.array_equal(meta[d1, 3], np.arange(d1.sum())) and (meta[~d1, 3] == -1).all()
+
+
 def _molecule_graphs(E, raws):
     return [_graph(E, r["x"].shape[0], r["edge_index"], r["x"], r["edge_attr"], r["y"]) for r in raws]
 
