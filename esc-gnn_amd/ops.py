@@ -35,13 +35,65 @@ def _plan_on(dev, plan, *fields):
         _on(dev, getattr(plan, f))
 
 
-def _rows(t):
-    """2-D, unit inner stride view + its leading dimension."""
-    if t.dim() != 2:
-        raise ValueError("expected a 2-D tensor, got shape %s" % (tuple(t.shape),))
-    if t.stride(1) != 1 or (t.size(0) > 1 and t.stride(0) < t.size(1)):
+def _rows(t, width=None):
+    """The row-operand rule, stated once: a 2-D tensor (of `width` columns when one is required) as a kernel reads it, and its
+    leading dimension.  Unit inner stride with rows that do not overlap is taken in place (a column slice of wider rows keeps
+    its row stride); anything else is made contiguous.  PyTorch leaves stride(0) of a tensor of at most one row arbitrary, so
+    such a tensor is re-strided to (width, 1) - a view, no copy.  The tensor returned therefore has stride(0) == ld, and
+    _rows of it returns it unchanged: every launch, forward and backward, takes the pair from here."""
+    if width is None:
+        if t.dim() != 2:
+            raise ValueError("expected a 2-D tensor, got shape %s" % (tuple(t.shape),))
+    elif t.dim() != 2 or t.size(1) != width:
+        raise ValueError("expected a [N, %d] tensor, got shape %s" % (width, tuple(t.shape)))
+    M, C = t.shape
+    if t.stride(1) != 1 or (M > 1 and t.stride(0) < C):
         t = t.contiguous()
-    return t, (t.stride(0) if t.size(0) > 1 else t.size(1))
+    if M <= 1 and t.stride() != (C, 1):
+        t = t.as_strided((M, C), (C, 1))
+    return t, t.stride(0)
+
+
+def _empty(dev, *shape):
+    """an uninitialised fp32 buffer on `dev`"""
+    return torch.empty(shape, dtype=torch.float32, device=dev)
+
+
+def _zeros(dev, *shape):
+    return torch.zeros(shape, dtype=torch.float32, device=dev)
+
+
+def _cached(t, attr, key, build):
+    """build() once per (tensor, its _version, key): the value rides on the tensor under `attr`, so everything that looks the
+    same index tensor up again (every layer, both directions) shares it, and an in-place edit of the tensor drops it."""
+    key = (t._version, key)
+    hit = getattr(t, attr, None)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    value = build()
+    setattr(t, attr, (key, value))
+    return value
+
+
+def _bag_rows(table, row_ptr, idx32, ones, n_out):
+    """esc_bag_fwd: out[r] = sum of table[idx32[j]] * ones[j] over the entries j of row r"""
+    table = table.contiguous()
+    H = table.size(1)
+    out = _empty(table.device, n_out, H)
+    nv.call("esc_bag_fwd", nv.ptr(table), H, nv.ptr(row_ptr), nv.ptr(idx32), nv.ptr(ones), n_out, nv.ptr(out), H, nv.stream())
+    return out
+
+
+def _bag_table_grad(g, H, col_ptr, c_row, c_val, c_col, nnz, rows, bag_rows=None):
+    """The table gradient [rows, H] of a bag launch from the CSC grouping of its nnz entries (deterministic segmented sum) with
+    its scratch: esc_bag_bwd_table, or esc_bag_bwd_table_rows when the plan's bag row count is given."""
+    g, ld = _rows(g)
+    dtable = _empty(g.device, rows, H)
+    scratch = _empty(g.device, max(1, nv.lib().esc_bag_bwd_scratch(nnz, H)))
+    tail = (rows,) if bag_rows is None else (rows, bag_rows, 0)
+    nv.call("esc_bag_bwd_table" if bag_rows is None else "esc_bag_bwd_table_rows", nv.ptr(g), ld, H, nv.ptr(col_ptr), nv.ptr(c_row),
+            nv.ptr(c_val), nv.ptr(c_col), nnz, *tail, nv.ptr(dtable), nv.ptr(scratch), nv.stream())
+    return dtable
 
 
 class _Bag(Function):
@@ -56,7 +108,7 @@ class _Bag(Function):
             raise ValueError("batch has no pos_enc/pos_index/pos_batch")
         _plan_on(table.device, plan, "row_ptr", "bag_idx", "bag_val", "col_ptr", "col_row", "col_val", "col_col")
         E, H = plan.num_edges, table.size(1)
-        out = torch.empty((E, H), dtype=torch.float32, device=table.device)
+        out = _empty(table.device, E, H)
         nv.call("esc_bag_fwd_rows", nv.ptr(table), table.size(0), H, nv.ptr(plan.row_ptr), nv.ptr(plan.bag_idx),
                 nv.ptr(plan.bag_val), E, nv.ptr(out), H, 0, None, nv.stream())
         ctx.plan, ctx.shape = plan, tuple(table.shape)
@@ -66,35 +118,32 @@ class _Bag(Function):
     def backward(ctx, dz):
         plan = ctx.plan
         rows, H = ctx.shape
-        dz, ld = _rows(dz)
-        dtable = torch.empty((rows, H), dtype=torch.float32, device=dz.device)
-        scratch = torch.empty(max(1, nv.lib().esc_bag_bwd_scratch(plan.nnz, H)), dtype=torch.float32, device=dz.device)
-        nv.call("esc_bag_bwd_table_rows", nv.ptr(dz), ld, H, nv.ptr(plan.col_ptr), nv.ptr(plan.col_row),
-                nv.ptr(plan.col_val), nv.ptr(plan.col_col), plan.nnz, rows, plan.num_edges, 0, nv.ptr(dtable),
-                nv.ptr(scratch), nv.stream())
-        return dtable, None
+        return _bag_table_grad(dz, H, plan.col_ptr, plan.col_row, plan.col_val, plan.col_col, plan.nnz, rows, plan.num_edges), None
 
 
 def esc_bag(table, plan):
     return _Bag.apply(table, plan)
 
 
-class _GineAggregate(Function):
-    """out = sum_{k: dst_k=i} relu(x[src_k] + e_k) + (1+eps) x_i — PyG GINEConv propagate + self term
-    (run_graphcount.py:161,169; gine_conv_layer.py:56-84)."""
+class _Aggregate(Function):
+    """out = sum_{k: dst_k=i} relu(x[src_k] (+ e_k)) (+ (1+eps) x_i).  With e and eps it is PyG GINEConv propagate + self term
+    (run_graphcount.py:161,169; gine_conv_layer.py:56-84); with eps None and e optional, the per-distance message sum of
+    GINEPLUS / NAIVEGINEPLUS (modules/gine_operations.py:306-362).  `gine` selects the shape check of the first."""
 
     @staticmethod
-    def forward(ctx, x, e, eps, plan):
+    def forward(ctx, x, e, eps, plan, gine):
         _dev(x, e, eps)
         _on(x.device, e, eps)
         _plan_on(x.device, plan, "in_ptr", "in_edge", "in_src", "out_ptr", "out_edge", "out_dst")
         x, ldx = _rows(x)
-        e, lde = _rows(e)
+        e, lde = _rows(e) if (gine or e is not None) else (None, 0)
         N, C = x.shape
-        if e.shape != (plan.num_edges, C) or N != plan.num_nodes:
+        if gine and (e.shape != (plan.num_edges, C) or N != plan.num_nodes):
             raise ValueError("aggregate: x %s / e %s do not match the batch (N=%d, E=%d)"
                              % (tuple(x.shape), tuple(e.shape), plan.num_nodes, plan.num_edges))
-        out = torch.empty((N, C), dtype=torch.float32, device=x.device)
+        if not gine and e is not None and e.shape != (plan.num_edges, C):
+            raise ValueError("neighbour_sum: edge term %s does not match %d edges x %d" % (tuple(e.shape), plan.num_edges, C))
+        out = _empty(x.device, N, C)
         nv.call("esc_gine_aggregate_fwd", nv.ptr(x), ldx, nv.ptr(e), lde, nv.ptr(plan.in_ptr),
                 nv.ptr(plan.in_edge), nv.ptr(plan.in_src), nv.ptr(eps), N, C, nv.ptr(out), C, nv.stream())
         ctx.save_for_backward(x, e, eps)
@@ -105,25 +154,31 @@ class _GineAggregate(Function):
     def backward(ctx, g):
         x, e, eps = ctx.saved_tensors
         plan = ctx.plan
+        x, ldx = _rows(x)
+        e, lde = _rows(e) if e is not None else (None, 0)
         g, ldg = _rows(g)
         N, C = x.shape
-        need_dx, need_de, need_eps = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        d_e = torch.empty_like(e)
-        dx = torch.empty((N, C), dtype=torch.float32, device=x.device) if need_dx else None
-        slots = int(nv.lib().esc_gine_aggregate_bwd_deps_slots(C))       # partial dot products per row (see the header)
-        part = torch.empty(N * slots, dtype=torch.float32, device=x.device) if need_eps else None
-        nv.call("esc_gine_aggregate_bwd", nv.ptr(x), x.stride(0), nv.ptr(e), e.stride(0), nv.ptr(g), ldg,
+        need_dx, need_de, need_eps = ctx.needs_input_grad[:3]
+        d_e = _empty(x.device, *e.shape) if e is not None else None
+        dx = _empty(x.device, N, C) if need_dx else None
+        slots = int(nv.lib().esc_gine_aggregate_bwd_deps_slots(C)) if need_eps else 0    # partial dot products per row (see the header)
+        part = _empty(x.device, N * slots) if need_eps else None
+        nv.call("esc_gine_aggregate_bwd", nv.ptr(x), ldx, nv.ptr(e), lde, nv.ptr(g), ldg,
                 nv.ptr(plan.out_ptr), nv.ptr(plan.out_edge), nv.ptr(plan.out_dst), nv.ptr(eps), N, C,
-                nv.ptr(d_e), d_e.stride(0), nv.ptr(dx), C, 0, nv.ptr(part), nv.stream())
+                nv.ptr(d_e), C if d_e is not None else 0, nv.ptr(dx), C, 0, nv.ptr(part), nv.stream())
         deps = None
         if need_eps:
-            deps = torch.empty(1, dtype=torch.float32, device=x.device)
+            deps = _empty(x.device, 1)
             nv.call("esc_reduce_sum", nv.ptr(part), N * slots, nv.ptr(deps), nv.stream())
-        return dx, (d_e if need_de else None), deps, None
+        return dx, (d_e if need_de else None), deps, None, None
 
 
 def gine_aggregate(x, e, eps, plan):
-    return _GineAggregate.apply(x, e, eps, plan)
+    return _Aggregate.apply(x, e, eps, plan, True)
+
+
+def neighbour_sum(x, e, plan):
+    return _Aggregate.apply(x, e, None, plan, False)
 
 
 class _Linear(Function):
@@ -139,7 +194,7 @@ class _Linear(Function):
         N = weight.size(0)
         if weight.size(1) != K:
             raise ValueError("linear: x %s vs weight %s" % (tuple(x.shape), tuple(weight.shape)))
-        y = torch.empty((M, N), dtype=torch.float32, device=x.device)
+        y = _empty(x.device, M, N)
         nv.call("esc_linear_fwd", nv.ptr(x), ldx, nv.ptr(weight), K, nv.ptr(bias), None, None, M, N, K,
                 nv.ptr(y), N, None, nv.stream())
         ctx.save_for_backward(x, weight)
@@ -149,31 +204,79 @@ class _Linear(Function):
     @staticmethod
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
+        x, ldx = _rows(x)
         dy, ldy = _rows(dy)
         M, K = x.shape
-        N = weight.size(0)
+        N, dev = weight.size(0), x.device
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx = torch.empty((M, K), dtype=torch.float32, device=x.device)
+            dx = _empty(dev, M, K)
             nv.call("esc_linear_bwd_input", nv.ptr(dy), ldy, nv.ptr(weight), K, M, N, K, nv.ptr(dx), K, 0,
                     nv.stream())
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            dw = torch.empty((N, K), dtype=torch.float32, device=x.device)
-            db = torch.empty(N, dtype=torch.float32, device=x.device) if ctx.has_bias else None
+            dw = _empty(dev, N, K)
+            db = _empty(dev, N) if ctx.has_bias else None
             if M == 0:
                 dw.zero_()
                 if db is not None:
                     db.zero_()
             else:
-                slabs = torch.empty(nv.lib().esc_linear_bwd_weight_scratch(M, N, K), dtype=torch.float32,
-                                    device=x.device)
-                nv.call("esc_linear_bwd_weight", nv.ptr(dy), ldy, nv.ptr(x), x.stride(0), None, None, M, N, K,
+                slabs = _empty(dev, nv.lib().esc_linear_bwd_weight_scratch(M, N, K))
+                nv.call("esc_linear_bwd_weight", nv.ptr(dy), ldy, nv.ptr(x), ldx, None, None, M, N, K,
                         nv.ptr(dw), K, nv.ptr(db), nv.ptr(slabs), nv.stream())
         return dx, dw, db
 
 
 def linear(x, weight, bias=None):
     return _Linear.apply(x, weight, bias)
+
+
+def _bn_stats(x, ldx, eps, momentum, running_mean, running_var, s, launch=True):
+    """esc_bn_stats with its buffers -> (mean, invstd, scratch); the launch also updates the running statistics it is given"""
+    M, C = x.shape
+    mean, invstd, scratch = _empty(x.device, C), _empty(x.device, C), _empty(x.device, nv.lib().esc_bn_scratch(C))
+    if launch:
+        nv.call("esc_bn_stats", nv.ptr(x), ldx, M, C, float(eps), float(momentum), nv.ptr(mean), nv.ptr(invstd),
+                nv.ptr(running_mean), nv.ptr(running_var), None, None, None, None, nv.ptr(scratch), s)
+    return mean, invstd, scratch
+
+
+def _bn_apply(x, ldx, mean, invstd, gamma, beta, act, s):
+    """esc_bn_apply -> y [M, C] (nothing is launched for no rows)"""
+    M, C = x.shape
+    y = _empty(x.device, M, C)
+    if M > 0:
+        nv.call("esc_bn_apply", nv.ptr(x), ldx, M, C, nv.ptr(mean), nv.ptr(invstd), nv.ptr(gamma), nv.ptr(beta),
+                int(act), nv.ptr(y), C, s)
+    return y
+
+
+def _bn_bwd_operands(x, y, dy, mean, invstd, gamma, beta, act):
+    """The thirteen leading arguments that esc_bn_bwd, esc_bn_bwd_sums and esc_bn_bwd_apply share, and the row operands they
+    point into (the caller holds these until the launches are queued): (x, dy, arguments)."""
+    x, ldx = _rows(x)
+    dy, ldg = _rows(dy)
+    M, C = x.shape
+    return x, dy, (nv.ptr(x), ldx, nv.ptr(y), C, nv.ptr(dy), ldg, M, C, nv.ptr(mean), nv.ptr(invstd), nv.ptr(gamma), nv.ptr(beta),
+                   int(act))          # act: 0 none, 1 relu, 2 elu
+
+
+def _bn_bwd_sums(x, head, sums, scratch, s):
+    """esc_bn_bwd_sums into `sums` [2C] -> (dgamma, dbeta), which stay zero for no rows"""
+    M, C = x.shape
+    dgamma, dbeta = _zeros(x.device, C), _zeros(x.device, C)
+    if M > 0:
+        nv.call("esc_bn_bwd_sums", *head, nv.ptr(sums), nv.ptr(dgamma), nv.ptr(dbeta), nv.ptr(scratch), s)
+    return dgamma, dbeta
+
+
+def _bn_bwd_apply(x, head, coef, s):
+    """esc_bn_bwd_apply with the batch terms `coef` [2C] -> dx [M, C]"""
+    M, C = x.shape
+    dx = _empty(x.device, M, C)
+    if M > 0:
+        nv.call("esc_bn_bwd_apply", *head, nv.ptr(coef), nv.ptr(dx), C, s)
+    return dx
 
 
 class _BatchNormAct(Function):
@@ -185,19 +288,11 @@ class _BatchNormAct(Function):
         _dev(x, gamma, beta)
         _on(x.device, gamma, beta, running_mean, running_var)
         x, ldx = _rows(x)
-        M, C = x.shape
-        if M <= 1:
+        if x.size(0) <= 1:
             raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
-        dev = x.device
-        mean = torch.empty(C, dtype=torch.float32, device=dev)
-        invstd = torch.empty(C, dtype=torch.float32, device=dev)
-        scratch = torch.empty(nv.lib().esc_bn_scratch(C), dtype=torch.float32, device=dev)
-        y = torch.empty((M, C), dtype=torch.float32, device=dev)
         s = nv.stream()
-        nv.call("esc_bn_stats", nv.ptr(x), ldx, M, C, float(eps), float(momentum), nv.ptr(mean), nv.ptr(invstd),
-                nv.ptr(running_mean), nv.ptr(running_var), None, None, None, None, nv.ptr(scratch), s)
-        nv.call("esc_bn_apply", nv.ptr(x), ldx, M, C, nv.ptr(mean), nv.ptr(invstd), nv.ptr(gamma), nv.ptr(beta),
-                int(relu), nv.ptr(y), C, s)
+        mean, invstd, scratch = _bn_stats(x, ldx, eps, momentum, running_mean, running_var, s)
+        y = _bn_apply(x, ldx, mean, invstd, gamma, beta, relu, s)
         ctx.save_for_backward(x, y if relu else None, gamma, mean, invstd)
         ctx.relu, ctx.scratch = int(relu), scratch        # 0 none, 1 relu, 2 elu
         return y
@@ -205,14 +300,10 @@ class _BatchNormAct(Function):
     @staticmethod
     def backward(ctx, dy):
         x, y, gamma, mean, invstd = ctx.saved_tensors
-        dy, ldg = _rows(dy)
+        x, dy, head = _bn_bwd_operands(x, y, dy, mean, invstd, gamma, None, ctx.relu)
         M, C = x.shape
-        dx = torch.empty((M, C), dtype=torch.float32, device=x.device)
-        dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
-        dbeta = torch.empty(C, dtype=torch.float32, device=x.device)
-        nv.call("esc_bn_bwd", nv.ptr(x), x.stride(0), nv.ptr(y), C, nv.ptr(dy), ldg, M, C, nv.ptr(mean),
-                nv.ptr(invstd), nv.ptr(gamma), None, int(ctx.relu), nv.ptr(dx), C, nv.ptr(dgamma), nv.ptr(dbeta),
-                nv.ptr(ctx.scratch), nv.stream())
+        dx, dgamma, dbeta = _empty(x.device, M, C), _empty(x.device, C), _empty(x.device, C)
+        nv.call("esc_bn_bwd", *head, nv.ptr(dx), C, nv.ptr(dgamma), nv.ptr(dbeta), nv.ptr(ctx.scratch), nv.stream())
         return dx, (dgamma if gamma is not None else None), (dbeta if gamma is not None else None), None, None, None, None, None
 
 
@@ -234,16 +325,11 @@ class _SyncBatchNormAct(Function):
         _on(x.device, gamma, beta, running_mean, running_var)
         x, ldx = _rows(x)
         M, C = x.shape
-        dev = x.device
-        mean = torch.empty(C, dtype=torch.float32, device=dev)
-        invstd = torch.empty(C, dtype=torch.float32, device=dev)
-        scratch = torch.empty(nv.lib().esc_bn_scratch(C), dtype=torch.float32, device=dev)
         s = nv.stream()
-        pack = torch.zeros(2 * C + 1, dtype=torch.float64, device=dev)
+        pack = torch.zeros(2 * C + 1, dtype=torch.float64, device=x.device)
         pack[0] = M
+        mean, invstd, scratch = _bn_stats(x, ldx, eps, momentum, None, None, s, launch=M > 1)     # the local statistics
         if M > 1:
-            nv.call("esc_bn_stats", nv.ptr(x), ldx, M, C, float(eps), float(momentum), nv.ptr(mean), nv.ptr(invstd),
-                    None, None, None, None, None, None, nv.ptr(scratch), s)
             pack[1:C + 1] = mean.double()
             pack[C + 1:] = (1.0 / invstd.double().pow(2) - float(eps)).clamp_min(0.0) * M        # M2 = var * n
         elif M == 1:
@@ -267,10 +353,7 @@ class _SyncBatchNormAct(Function):
         if running_mean is not None:
             running_mean.mul_(1.0 - momentum).add_(mean, alpha=momentum)
             running_var.mul_(1.0 - momentum).add_((m2 / (n - 1)).float(), alpha=momentum)
-        y = torch.empty((M, C), dtype=torch.float32, device=dev)
-        if M > 0:
-            nv.call("esc_bn_apply", nv.ptr(x), ldx, M, C, nv.ptr(mean), nv.ptr(invstd), nv.ptr(gamma), nv.ptr(beta),
-                    int(relu), nv.ptr(y), C, s)
+        y = _bn_apply(x, ldx, mean, invstd, gamma, beta, relu, s)
         ctx.save_for_backward(x, y if relu else None, gamma, mean, invstd)
         ctx.relu, ctx.scratch, ctx.group, ctx.n_global = int(relu), scratch, group, float(n)
         return y
@@ -279,23 +362,12 @@ class _SyncBatchNormAct(Function):
     def backward(ctx, dy):
         import torch.distributed as dist
         x, y, gamma, mean, invstd = ctx.saved_tensors
-        dy, ldg = _rows(dy)
-        M, C = x.shape
-        dev = x.device
-        sums = torch.zeros(2 * C, dtype=torch.float32, device=dev)
-        dgamma = torch.zeros(C, dtype=torch.float32, device=dev)
-        dbeta = torch.zeros(C, dtype=torch.float32, device=dev)
+        x, dy, head = _bn_bwd_operands(x, y, dy, mean, invstd, gamma, None, ctx.relu)
         s = nv.stream()
-        if M > 0:
-            nv.call("esc_bn_bwd_sums", nv.ptr(x), x.stride(0), nv.ptr(y), C, nv.ptr(dy), ldg, M, C, nv.ptr(mean),
-                    nv.ptr(invstd), nv.ptr(gamma), None, int(ctx.relu), nv.ptr(sums), nv.ptr(dgamma), nv.ptr(dbeta),
-                    nv.ptr(ctx.scratch), s)
+        sums = _zeros(x.device, 2 * x.size(1))
+        dgamma, dbeta = _bn_bwd_sums(x, head, sums, ctx.scratch, s)
         dist.all_reduce(sums, group=ctx.group)
-        coef = sums / ctx.n_global
-        dx = torch.empty((M, C), dtype=torch.float32, device=dev)
-        if M > 0:
-            nv.call("esc_bn_bwd_apply", nv.ptr(x), x.stride(0), nv.ptr(y), C, nv.ptr(dy), ldg, M, C, nv.ptr(mean),
-                    nv.ptr(invstd), nv.ptr(gamma), None, int(ctx.relu), nv.ptr(coef), nv.ptr(dx), C, s)
+        dx = _bn_bwd_apply(x, head, sums / ctx.n_global, s)
         return dx, dgamma, dbeta, None, None, None, None, None, None
 
 
@@ -316,11 +388,11 @@ class _BnEvalAct(Function):
         x, ldx = _rows(x)
         M, C = x.shape
         dev = x.device
-        scale, shift = torch.empty(C, dtype=torch.float32, device=dev), torch.empty(C, dtype=torch.float32, device=dev)
+        scale, shift = _empty(dev, C), _empty(dev, C)
         s = nv.stream()
         nv.call("esc_bn_eval_coef", nv.ptr(running_mean), nv.ptr(running_var), nv.ptr(gamma), nv.ptr(beta), float(eps), C,
                 nv.ptr(scale), nv.ptr(shift), s)
-        y = torch.empty((M, C), dtype=torch.float32, device=dev)
+        y = _empty(dev, M, C)
         if M > 0:
             nv.call("esc_affine_act", nv.ptr(x), ldx, M, C, nv.ptr(scale), nv.ptr(shift), int(relu), nv.ptr(y), C, s)
         ctx.save_for_backward(x, y if relu else None, gamma, beta, running_mean, running_var)
@@ -330,22 +402,13 @@ class _BnEvalAct(Function):
     @staticmethod
     def backward(ctx, dy):
         x, y, gamma, beta, rm, rv = ctx.saved_tensors
-        dy, ldg = _rows(dy)
-        M, C = x.shape
-        dev = x.device
+        dev, C = x.device, x.size(1)
         s = nv.stream()
-        invstd, unused = torch.empty(C, dtype=torch.float32, device=dev), torch.empty(C, dtype=torch.float32, device=dev)
+        invstd, unused = _empty(dev, C), _empty(dev, C)
         nv.call("esc_bn_eval_coef", nv.ptr(rm), nv.ptr(rv), None, None, ctx.eps, C, nv.ptr(invstd), nv.ptr(unused), s)
-        dx = torch.empty((M, C), dtype=torch.float32, device=dev)
-        dgamma, dbeta = torch.zeros(C, dtype=torch.float32, device=dev), torch.zeros(C, dtype=torch.float32, device=dev)
-        if M > 0:
-            scratch = torch.empty(nv.lib().esc_bn_scratch(C), dtype=torch.float32, device=dev)
-            sums = torch.empty(2 * C, dtype=torch.float32, device=dev)
-            nv.call("esc_bn_bwd_sums", nv.ptr(x), x.stride(0), nv.ptr(y), C, nv.ptr(dy), ldg, M, C, nv.ptr(rm), nv.ptr(invstd),
-                    nv.ptr(gamma), nv.ptr(beta), ctx.relu, nv.ptr(sums), nv.ptr(dgamma), nv.ptr(dbeta), nv.ptr(scratch), s)
-            zero = torch.zeros(2 * C, dtype=torch.float32, device=dev)       # no batch-statistics terms in eval mode
-            nv.call("esc_bn_bwd_apply", nv.ptr(x), x.stride(0), nv.ptr(y), C, nv.ptr(dy), ldg, M, C, nv.ptr(rm), nv.ptr(invstd),
-                    nv.ptr(gamma), nv.ptr(beta), ctx.relu, nv.ptr(zero), nv.ptr(dx), C, s)
+        x, dy, head = _bn_bwd_operands(x, y, dy, rm, invstd, gamma, beta, ctx.relu)
+        dgamma, dbeta = _bn_bwd_sums(x, head, _empty(dev, 2 * C), _empty(dev, nv.lib().esc_bn_scratch(C)), s)
+        dx = _bn_bwd_apply(x, head, _zeros(dev, 2 * C), s)                  # no batch-statistics terms in eval mode
         return dx, (dgamma if gamma is not None else None), (dbeta if beta is not None else None), None, None, None, None
 
 
@@ -354,74 +417,55 @@ def bn_eval_act(x, gamma, beta, running_mean, running_var, eps, relu):
     return _BnEvalAct.apply(x, gamma, beta, running_mean, running_var, eps, relu)
 
 
-class _L1Loss(Function):
-    """torch.nn.L1Loss()(pred, y) (run_graphcount.py:500-501); `denom` overrides the mean's divisor
-    (global node count under graph-sharded data parallelism)."""
+# name -> (entry point, the divisor is M unless `denom` is given (else the entry point counts: 0), arguments between the divisor
+# and the outputs, targets cast with .float())
+_LOSS_HEADS = {"l1_loss": ("esc_l1_loss", True, (1.0,), False),
+               "mse_loss": ("esc_mse_loss", True, (1.0,), False),
+               "bce_with_logits_loss": ("esc_bce_logits_loss", False, (), True)}
+
+
+class _ElementwiseLoss(Function):
+    """The three elementwise loss heads: one launch leaves the loss and d loss / d pred, the backward scales the latter and
+    returns it in pred's shape.  `denom` overrides the divisor (the global count under graph-sharded data parallelism).
+      l1_loss: torch.nn.L1Loss()(pred, y) (run_graphcount.py:500-501)
+      mse_loss: F.mse_loss(pred, y) (reference run_qm9.py:348), squares summed in fp64 by esc_mse_loss
+      bce_with_logits_loss: BCEWithLogitsLoss()(pred[is_labeled], y[is_labeled]), is_labeled = (y == y) (run_ogb_mol.py:65-72)"""
 
     @staticmethod
-    def forward(ctx, pred, y, denom):
+    def forward(ctx, pred, y, denom, name):
+        kernel, over_m, scale, cast = _LOSS_HEADS[name]
         _dev(pred, y)
         _on(pred.device, y)
         ctx.shape = pred.shape
         pred = pred.contiguous().view(-1)
         y = y.contiguous().view(-1)
+        if cast:
+            y = y.float()
         if pred.numel() != y.numel():
-            raise ValueError("l1_loss: %d predictions vs %d targets" % (pred.numel(), y.numel()))
+            raise ValueError("%s: %d predictions vs %d targets" % (name, pred.numel(), y.numel()))
         M = pred.numel()
-        loss = torch.empty(1, dtype=torch.float32, device=pred.device)
-        dpred = torch.empty(M, dtype=torch.float32, device=pred.device)
-        nv.call("esc_l1_loss", nv.ptr(pred), nv.ptr(y), M, int(denom or M), 1.0, nv.ptr(loss), nv.ptr(dpred), nv.stream())
+        loss, dpred = _empty(pred.device, 1), _empty(pred.device, M)
+        nv.call(kernel, nv.ptr(pred), nv.ptr(y), M, int(denom or (M if over_m else 0)), *scale, nv.ptr(loss), nv.ptr(dpred),
+                nv.stream())
         ctx.save_for_backward(dpred)
         return loss.view(())
 
     @staticmethod
     def backward(ctx, g):
         (dpred,) = ctx.saved_tensors
-        return (dpred * g).view(ctx.shape), None, None
+        return (dpred * g).view(ctx.shape), None, None, None
 
 
 def l1_loss(pred, y, denom=None):
-    return _L1Loss.apply(pred, y, denom)
-
-
-class _MseLoss(Function):
-    """F.mse_loss(pred, y) (reference run_qm9.py:348): squares summed in fp64 by esc_mse_loss; `denom` overrides the mean's
-    divisor (the global graph count under graph-sharded data parallelism)."""
-
-    @staticmethod
-    def forward(ctx, pred, y, denom):
-        _dev(pred, y)
-        _on(pred.device, y)
-        ctx.shape = pred.shape
-        pred = pred.contiguous().view(-1)
-        y = y.contiguous().view(-1)
-        if pred.numel() != y.numel():
-            raise ValueError("mse_loss: %d predictions vs %d targets" % (pred.numel(), y.numel()))
-        M = pred.numel()
-        loss = torch.empty(1, dtype=torch.float32, device=pred.device)
-        dpred = torch.empty(M, dtype=torch.float32, device=pred.device)
-        nv.call("esc_mse_loss", nv.ptr(pred), nv.ptr(y), M, int(denom or M), 1.0, nv.ptr(loss), nv.ptr(dpred), nv.stream())
-        ctx.save_for_backward(dpred)
-        return loss.view(())
-
-    @staticmethod
-    def backward(ctx, g):
-        (dpred,) = ctx.saved_tensors
-        return (dpred * g).view(ctx.shape), None, None
+    return _ElementwiseLoss.apply(pred, y, denom, "l1_loss")
 
 
 def mse_loss(pred, y, denom=None):
-    return _MseLoss.apply(pred, y, denom)
+    return _ElementwiseLoss.apply(pred, y, denom, "mse_loss")
 
 
-def _rows_ld(t, width):
-    """2-D [N, width] float32 view with unit inner stride (a column slice of wider rows is taken as it is) + its leading
-    dimension"""
-    if t.dim() != 2 or t.size(1) != width:
-        raise ValueError("expected a [N, %d] tensor, got shape %s" % (width, tuple(t.shape)))
-    if t.stride(1) != 1 or (t.size(0) > 1 and t.stride(0) < width):
-        t = t.contiguous()
-    return t, (t.stride(0) if t.size(0) > 1 else max(width, t.stride(0)))
+def bce_with_logits_loss(pred, y, denom=None):
+    return _ElementwiseLoss.apply(pred, y, denom, "bce_with_logits_loss")
 
 
 class _NodeInput(Function):
@@ -438,13 +482,13 @@ class _NodeInput(Function):
         if F < 1 or table.dim() != 2 or table.size(1) != F + 3:
             raise ValueError("node_input: x %s and pos %s need a table of %d columns, got %s"
                              % (tuple(x.shape), tuple(pos.shape), F + 3, tuple(table.shape)))
-        x, ldx = _rows_ld(x, F)
-        pos, ldp = _rows_ld(pos, 3)
+        x, ldx = _rows(x, F)              # a column slice of wider rows is taken as it is
+        pos, ldp = _rows(pos, 3)
         node_type = node_type.reshape(-1).contiguous()
         if pos.size(0) != N or node_type.numel() != N:
             raise ValueError("node_input: %d rows of x, %d of pos, %d node types" % (N, pos.size(0), node_type.numel()))
         table = table.contiguous()
-        out = torch.empty((N, F + 3), dtype=torch.float32, device=table.device)
+        out = _empty(table.device, N, F + 3)
         bad = torch.zeros(1, dtype=torch.int32, device=table.device)
         nv.call("esc_node_input_fwd", nv.ptr(x), ldx, nv.ptr(pos), ldp, nv.ptr(node_type), nv.ptr(table), table.size(0), F, N,
                 nv.ptr(out), F + 3, nv.ptr(bad), nv.stream())
@@ -460,7 +504,7 @@ class _NodeInput(Function):
     def backward(ctx, g):
         (node_type,) = ctx.saved_tensors
         g, ld = _rows(g)
-        dtable = torch.empty((ctx.rows, ctx.F + 3), dtype=torch.float32, device=g.device)
+        dtable = _empty(g.device, ctx.rows, ctx.F + 3)
         nv.call("esc_node_input_bwd", nv.ptr(g), ld, nv.ptr(node_type), node_type.numel(), ctx.rows, ctx.F, nv.ptr(dtable),
                 nv.stream())
         return None, None, None, dtable
@@ -473,19 +517,21 @@ def node_input(x, pos, node_type, table):
 ACT_CODES = {"relu": 1, "elu": 2}
 
 
-class _Act(Function):
-    """A bare ReLU / ELU(alpha = 1) (reference run_csl.py:152-169,219: no BatchNorm in front to fuse it behind).  Only the
-    output is saved: the backward reads d act / d v off Y."""
+class _RowMap(Function):
+    """y = f(x) on [M, C] rows by the entry points `kernel`_fwd / `kernel`_bwd (with the extra arguments `code`); only the output
+    is saved: the backward reads the derivative off Y.
+      esc_act: a bare ReLU / ELU(alpha = 1) (reference run_csl.py:152-169,219: no BatchNorm in front to fuse it behind)
+      esc_log_softmax: F.log_softmax(x, dim=1) (run_sr.py:211, run_exp.py:215): one wave per row, maximum taken off first"""
 
     @staticmethod
-    def forward(ctx, x, code):
+    def forward(ctx, x, kernel, *code):
         _dev(x)
         x, ldx = _rows(x)
         M, C = x.shape
-        y = torch.empty((M, C), dtype=torch.float32, device=x.device)
-        nv.call("esc_act_fwd", nv.ptr(x), ldx, M, C, code, nv.ptr(y), C, nv.stream())
+        y = _empty(x.device, M, C)
+        nv.call(kernel + "_fwd", nv.ptr(x), ldx, M, C, *code, nv.ptr(y), C, nv.stream())
         ctx.save_for_backward(y)
-        ctx.code = code
+        ctx.kernel, ctx.code = kernel, code
         return y
 
     @staticmethod
@@ -494,9 +540,9 @@ class _Act(Function):
         _dev(dy)
         dy, ldg = _rows(dy)
         M, C = y.shape
-        dx = torch.empty((M, C), dtype=torch.float32, device=y.device)
-        nv.call("esc_act_bwd", nv.ptr(y), C, nv.ptr(dy), ldg, M, C, ctx.code, nv.ptr(dx), C, nv.stream())
-        return dx, None
+        dx = _empty(y.device, M, C)
+        nv.call(ctx.kernel + "_bwd", nv.ptr(y), C, nv.ptr(dy), ldg, M, C, *ctx.code, nv.ptr(dx), C, nv.stream())
+        return (dx, None) + (None,) * len(ctx.code)
 
 
 def act(x, kind):
@@ -504,7 +550,7 @@ def act(x, kind):
     place through its row stride, any other layout is made contiguous first"""
     if kind not in ACT_CODES:
         raise ValueError("act: kind must be 'relu' or 'elu', got %r" % (kind,))
-    return _Act.apply(x, ACT_CODES[kind])
+    return _RowMap.apply(x, "esc_act", ACT_CODES[kind])
 
 
 def elu(x):
@@ -515,35 +561,16 @@ def relu(x):
     return act(x, "relu")
 
 
-class _BceLogits(Function):
-    """BCEWithLogitsLoss()(pred[is_labeled], y[is_labeled]), is_labeled = (y == y) (run_ogb_mol.py:65-72);
-    `denom` overrides the divisor (global labeled count under graph sharding)."""
-
-    @staticmethod
-    def forward(ctx, pred, y, denom):
-        _dev(pred, y)
-        _on(pred.device, y)
-        shape = pred.shape
-        pred = pred.contiguous().view(-1)
-        y = y.contiguous().view(-1).float()
-        if pred.numel() != y.numel():
-            raise ValueError("bce_with_logits_loss: %d predictions vs %d targets" % (pred.numel(), y.numel()))
-        loss = torch.empty(1, dtype=torch.float32, device=pred.device)
-        dpred = torch.empty(pred.numel(), dtype=torch.float32, device=pred.device)
-        nv.call("esc_bce_logits_loss", nv.ptr(pred), nv.ptr(y), pred.numel(), int(denom or 0), nv.ptr(loss), nv.ptr(dpred),
-                nv.stream())
-        ctx.save_for_backward(dpred)
-        ctx.shape = shape
-        return loss.view(())
-
-    @staticmethod
-    def backward(ctx, g):
-        (dpred,) = ctx.saved_tensors
-        return (dpred * g).view(ctx.shape), None, None
-
-
-def bce_with_logits_loss(pred, y, denom=None):
-    return _BceLogits.apply(pred, y, denom)
+def _segment_rows(spread, x, seg_ptr, G, n, mean):
+    """The two segment kernels over G sorted segments of n rows, each the transpose of the other: esc_segment_pool_fwd sums (or
+    averages) the rows of every segment, [n, C] -> [G, C]; `spread`, esc_segment_pool_bwd copies row g (over the segment's size
+    for a mean) to the rows of segment g, [G, C] -> [n, C], G being the rows it is given."""
+    x, ld = _rows(x)
+    G, C = (x.size(0) if spread else G), x.size(1)
+    out = _empty(x.device, n if spread else G, C)
+    nv.call("esc_segment_pool_bwd" if spread else "esc_segment_pool_fwd", nv.ptr(x), ld, nv.ptr(seg_ptr), G, C, int(mean),
+            nv.ptr(out), C, nv.stream())
+    return out
 
 
 class _SegmentPool(Function):
@@ -553,21 +580,13 @@ class _SegmentPool(Function):
     def forward(ctx, x, seg_ptr, mean):
         _dev(x)
         _on(x.device, seg_ptr)
-        x, ldx = _rows(x)
-        G, C = seg_ptr.numel() - 1, x.size(1)
-        out = torch.empty((G, C), dtype=torch.float32, device=x.device)
-        nv.call("esc_segment_pool_fwd", nv.ptr(x), ldx, nv.ptr(seg_ptr), G, C, int(mean), nv.ptr(out), C, nv.stream())
+        out = _segment_rows(False, x, seg_ptr, seg_ptr.numel() - 1, None, mean)
         ctx.seg_ptr, ctx.mean, ctx.n = seg_ptr, bool(mean), x.size(0)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        g, ldg = _rows(g)
-        G, C = g.shape
-        dx = torch.empty((ctx.n, C), dtype=torch.float32, device=g.device)
-        nv.call("esc_segment_pool_bwd", nv.ptr(g), ldg, nv.ptr(ctx.seg_ptr), G, C, int(ctx.mean), nv.ptr(dx), C,
-                nv.stream())
-        return dx, None, None
+        return _segment_rows(True, g, ctx.seg_ptr, None, ctx.n, ctx.mean), None, None
 
 
 def _seg_ptr(batch, size=None):
@@ -609,8 +628,7 @@ class _Embedding(Function):
         row_ptr = torch.arange(n + 1, dtype=torch.int32, device=dev)
         idx32 = idx.to(torch.int32)
         ones = torch.ones(n, dtype=torch.int32, device=dev)
-        out = torch.empty((n, H), dtype=torch.float32, device=dev)
-        nv.call("esc_bag_fwd", nv.ptr(weight), H, nv.ptr(row_ptr), nv.ptr(idx32), nv.ptr(ones), n, nv.ptr(out), H, nv.stream())
+        out = _bag_rows(weight, row_ptr, idx32, ones, n)
         ctx.save_for_backward(idx)
         ctx.rows, ctx.H = weight.size(0), H
         return out.view(*index.shape, H)
@@ -618,17 +636,12 @@ class _Embedding(Function):
     @staticmethod
     def backward(ctx, g):
         (idx,) = ctx.saved_tensors
-        g, ld = _rows(g.reshape(-1, ctx.H))
-        n, dev = idx.numel(), g.device
+        n = idx.numel()
         from .plan import _csr
         col_ptr, c_row = _csr(idx, ctx.rows)                 # stable grouping of the positions by table row (csrc/plan.hip)
-        c_val = torch.ones(n, dtype=torch.int32, device=dev)
+        c_val = torch.ones(n, dtype=torch.int32, device=g.device)
         c_col = idx[c_row.long()].to(torch.int32)
-        dw = torch.empty((ctx.rows, ctx.H), dtype=torch.float32, device=dev)
-        scratch = torch.empty(max(1, nv.lib().esc_bag_bwd_scratch(n, ctx.H)), dtype=torch.float32, device=dev)
-        nv.call("esc_bag_bwd_table", nv.ptr(g), ld, ctx.H, nv.ptr(col_ptr), nv.ptr(c_row), nv.ptr(c_val), nv.ptr(c_col),
-                n, ctx.rows, nv.ptr(dw), nv.ptr(scratch), nv.stream())
-        return dw, None
+        return _bag_table_grad(g.reshape(-1, ctx.H), ctx.H, col_ptr, c_row, c_val, c_col, n, ctx.rows), None
 
 
 def embedding(weight, index):
@@ -642,9 +655,10 @@ def embed_plan(index, dims, known_range=None):
     known_range = (per-column minima, per-column maxima) of the DATASET the rows were gathered from (the device store
     computes them once): when they lie inside `dims` the per-batch range check — a device read-back that drains the
     stream — is skipped."""
-    cache = getattr(index, "_esc_embed", None)
-    if cache is not None and cache[0] == (dims, index._version):
-        return cache[1]
+    return _cached(index, "_esc_embed", dims, lambda: _build_embed_plan(index, dims, known_range))
+
+
+def _build_embed_plan(index, dims, known_range):
     if index.device.type != "cuda":
         raise RuntimeError("esc_gnn_amd: embedding plans are built on the GPU (got a %s tensor)" % index.device.type)
     n, k = index.shape
@@ -680,10 +694,8 @@ def embed_plan(index, dims, known_range=None):
                 nv.ptr(col_ptr), nv.ptr(c_row), nv.ptr(c_col), nv.ptr(scratch), nv.ptr(flag), nv.stream())
     if not trusted and total and int(flag[0].item()):    # one check per index tensor, not per lookup (ids known in range: no read-back)
         raise IndexError("embedding index out of range")
-    plan = dict(idx32=idx32, row_ptr=row_ptr, ones=ones, col_ptr=col_ptr, c_row=c_row, c_col=c_col, entries=total, rows=rows,
+    return dict(idx32=idx32, row_ptr=row_ptr, ones=ones, col_ptr=col_ptr, c_row=c_row, c_col=c_col, entries=total, rows=rows,
                 _slab=slab)
-    index._esc_embed = ((dims, index._version), plan)
-    return plan
 
 
 class _EmbeddingSum(Function):
@@ -701,7 +713,7 @@ class _EmbeddingSum(Function):
         n, k = index.shape
         H, dev = table.size(1), table.device
         plan = embed_plan(index, dims)
-        out = torch.empty((n, H), dtype=torch.float32, device=dev)
+        out = _empty(dev, n, H)
         nv.call("esc_bag_fwd_rows", nv.ptr(table), table.size(0), H, nv.ptr(plan["row_ptr"]), nv.ptr(plan["idx32"]), nv.ptr(plan["ones"]), n,
                 nv.ptr(out), H, 0, None, nv.stream())
         ctx.plan, ctx.rows, ctx.H, ctx.nk = plan, table.size(0), H, n * k
@@ -709,13 +721,8 @@ class _EmbeddingSum(Function):
 
     @staticmethod
     def backward(ctx, g):
-        plan = ctx.plan
-        g, ld = _rows(g.reshape(-1, ctx.H))
-        dw = torch.empty((ctx.rows, ctx.H), dtype=torch.float32, device=g.device)
-        scratch = torch.empty(max(1, nv.lib().esc_bag_bwd_scratch(ctx.nk, ctx.H)), dtype=torch.float32, device=g.device)
-        nv.call("esc_bag_bwd_table", nv.ptr(g), ld, ctx.H, nv.ptr(plan["col_ptr"]), nv.ptr(plan["c_row"]),
-                nv.ptr(plan["ones"]), nv.ptr(plan["c_col"]), ctx.nk, ctx.rows, nv.ptr(dw), nv.ptr(scratch), nv.stream())
-        return dw, None, None
+        p = ctx.plan
+        return _bag_table_grad(g.reshape(-1, ctx.H), ctx.H, p["col_ptr"], p["c_row"], p["ones"], p["c_col"], ctx.nk, ctx.rows), None, None
 
 
 def embedding_sum(weights, index):
@@ -726,46 +733,9 @@ def embedding_sum(weights, index):
     return _EmbeddingSum.apply(torch.cat(list(weights), dim=0), index, dims)
 
 
-class _NeighbourSum(Function):
-    """out[i] = sum_{k: dst_k=i} relu(x[src_k] (+ e_k)) — GINE aggregate without the self term and with an
-    optional edge term: the per-distance message sum of GINEPLUS / NAIVEGINEPLUS
-    (modules/gine_operations.py:306-362)."""
-
-    @staticmethod
-    def forward(ctx, x, e, plan):
-        _dev(x, e)
-        _on(x.device, e)
-        _plan_on(x.device, plan, "in_ptr", "in_edge", "in_src", "out_ptr", "out_edge", "out_dst")
-        x, ldx = _rows(x)
-        N, C = x.shape
-        lde = 0
-        if e is not None:
-            e, lde = _rows(e)
-            if e.shape != (plan.num_edges, C):
-                raise ValueError("neighbour_sum: edge term %s does not match %d edges x %d" % (tuple(e.shape), plan.num_edges, C))
-        out = torch.empty((N, C), dtype=torch.float32, device=x.device)
-        nv.call("esc_gine_aggregate_fwd", nv.ptr(x), ldx, nv.ptr(e), lde, nv.ptr(plan.in_ptr), nv.ptr(plan.in_edge),
-                nv.ptr(plan.in_src), None, N, C, nv.ptr(out), C, nv.stream())
-        ctx.save_for_backward(x, e)
-        ctx.plan = plan
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        x, e = ctx.saved_tensors
-        plan = ctx.plan
-        g, ldg = _rows(g)
-        N, C = x.shape
-        d_e = torch.empty_like(e) if e is not None else None
-        dx = torch.empty((N, C), dtype=torch.float32, device=x.device)
-        nv.call("esc_gine_aggregate_bwd", nv.ptr(x), x.stride(0), nv.ptr(e), e.stride(0) if e is not None else 0,
-                nv.ptr(g), ldg, nv.ptr(plan.out_ptr), nv.ptr(plan.out_edge), nv.ptr(plan.out_dst), None, N, C,
-                nv.ptr(d_e), C if d_e is not None else 0, nv.ptr(dx), C, 0, None, nv.stream())
-        return dx, d_e, None
-
-
-def neighbour_sum(x, e, plan):
-    return _NeighbourSum.apply(x, e, plan)
+def _four_rows(rows):
+    """the four (pointer, leading dimension) slots of the GINE+ entry points from k <= 4 row operands, the rest NULL"""
+    return [a for x, ld in rows + [(None, 0)] * (4 - len(rows)) for a in (nv.ptr(x), ld)]
 
 
 class _GinePlusAggregate(Function):
@@ -793,33 +763,30 @@ class _GinePlusAggregate(Function):
         e, lde = _rows(e)
         if tuple(e.shape) != (M1, C):
             raise ValueError("gineplus_aggregate: edge term %s does not match %d distance-1 pairs x %d" % (tuple(e.shape), M1, C))
-        out = torch.empty((N, C), dtype=torch.float32, device=dev)
-        xa = []
-        for t in range(4):
-            x, ld = rows[t] if t < k else (None, 0)
-            xa += [nv.ptr(x), ld]
-        nv.call("esc_gineplus_aggregate_fwd", *xa, nv.ptr(e) if M1 else None, lde, nv.ptr(plan.in_ptr),
+        out = _empty(dev, N, C)
+        nv.call("esc_gineplus_aggregate_fwd", *_four_rows(rows), nv.ptr(e) if M1 else None, lde, nv.ptr(plan.in_ptr),
                 nv.ptr(plan.in_meta) if plan.num_pairs else None, nv.ptr(eps), N, C, k, M1, nv.ptr(out), C, nv.stream())
         ctx.save_for_backward(e, eps, *[x for x, _ in rows])
-        ctx.plan, ctx.k, ctx.xa, ctx.lde = plan, k, xa, lde
+        ctx.plan, ctx.k = plan, k
         return out
 
     @staticmethod
     def backward(ctx, g):
         e, eps = ctx.saved_tensors[:2]
-        xs = ctx.saved_tensors[2:]
+        rows = [_rows(x) for x in ctx.saved_tensors[2:]]
         plan, k = ctx.plan, ctx.k
+        e, lde = _rows(e)
         g, ldg = _rows(g)
-        N, C = xs[0].shape
+        N, C = rows[0][0].shape
         M1, dev = e.size(0), g.device
         need_e, need_eps = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        dx = torch.empty((k, N, C), dtype=torch.float32, device=dev)
-        d_e = torch.empty((M1, C), dtype=torch.float32, device=dev) if need_e else None
+        dx = _empty(dev, k, N, C)
+        d_e = _empty(dev, M1, C) if need_e else None
         part = d_eps = None
         if need_eps:
-            part = torch.empty((int(nv.lib().esc_gineplus_bwd_blocks(N)), (k + 1) * C), dtype=torch.float32, device=dev)
-            d_eps = torch.empty((k + 1, C), dtype=torch.float32, device=dev)
-        nv.call("esc_gineplus_aggregate_bwd", *ctx.xa, nv.ptr(e) if M1 else None, ctx.lde, nv.ptr(g), ldg, nv.ptr(plan.out_ptr),
+            part = _empty(dev, int(nv.lib().esc_gineplus_bwd_blocks(N)), (k + 1) * C)
+            d_eps = _empty(dev, k + 1, C)
+        nv.call("esc_gineplus_aggregate_bwd", *_four_rows(rows), nv.ptr(e) if M1 else None, lde, nv.ptr(g), ldg, nv.ptr(plan.out_ptr),
                 nv.ptr(plan.meta) if plan.num_pairs else None, nv.ptr(eps), N, C, k, M1, nv.ptr(dx), nv.ptr(d_e) if M1 else None,
                 nv.ptr(part), nv.ptr(d_eps), nv.stream())
         return (None, d_e, d_eps) + tuple(dx[t] for t in range(k))
@@ -842,20 +809,13 @@ class _SegmentBroadcast(Function):
     def forward(ctx, rows, seg_ptr, n):
         _dev(rows)
         _on(rows.device, seg_ptr)
-        rows, ld = _rows(rows)
-        G, C = rows.shape
-        out = torch.empty((n, C), dtype=torch.float32, device=rows.device)
-        nv.call("esc_segment_pool_bwd", nv.ptr(rows), ld, nv.ptr(seg_ptr), G, C, 0, nv.ptr(out), C, nv.stream())
-        ctx.seg_ptr, ctx.G = seg_ptr, G
+        out = _segment_rows(True, rows, seg_ptr, None, n, False)
+        ctx.seg_ptr, ctx.G = seg_ptr, rows.size(0)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        g, ld = _rows(g)
-        C = g.size(1)
-        d = torch.empty((ctx.G, C), dtype=torch.float32, device=g.device)
-        nv.call("esc_segment_pool_fwd", nv.ptr(g), ld, nv.ptr(ctx.seg_ptr), ctx.G, C, 0, nv.ptr(d), C, nv.stream())
-        return d, None, None
+        return _segment_rows(False, g, ctx.seg_ptr, ctx.G, None, False), None, None
 
 
 def segment_broadcast(rows, batch, size=None):
@@ -864,32 +824,9 @@ def segment_broadcast(rows, batch, size=None):
 
 
 # ---- classification head (csrc/classify.hip) -------------------------------------------------------------------------
-class _LogSoftmax(Function):
-    """F.log_softmax(x, dim=1) (run_sr.py:211, run_exp.py:215): one wave per row, maximum taken off first."""
-
-    @staticmethod
-    def forward(ctx, x):
-        _dev(x)
-        x, ldx = _rows(x)
-        M, C = x.shape
-        y = torch.empty((M, C), dtype=torch.float32, device=x.device)
-        nv.call("esc_log_softmax_fwd", nv.ptr(x), ldx, M, C, nv.ptr(y), C, nv.stream())
-        ctx.save_for_backward(y)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        (y,) = ctx.saved_tensors
-        dy, ldg = _rows(dy)
-        M, C = y.shape
-        dx = torch.empty((M, C), dtype=torch.float32, device=y.device)
-        nv.call("esc_log_softmax_bwd", nv.ptr(y), C, nv.ptr(dy), ldg, M, C, nv.ptr(dx), C, nv.stream())
-        return dx
-
-
 def log_softmax(x):
     """row-wise log-softmax of a [M, C] tensor"""
-    return _LogSoftmax.apply(x)
+    return _RowMap.apply(x, "esc_log_softmax")
 
 
 def _targets(target, M, dev):
@@ -918,92 +855,69 @@ def _head_info(info, C):
     return correct
 
 
-def _nll_raw(logp, target, denom, want_grad):
-    logp, ld = _rows(logp)
-    M, C = logp.shape
-    target = _targets(target, M, logp.device)
-    loss = torch.empty(1, dtype=torch.float32, device=logp.device)
-    info = torch.empty(2, dtype=torch.int32, device=logp.device)
-    dlogp = torch.empty((M, C), dtype=torch.float32, device=logp.device) if want_grad else None
-    rows = torch.empty(2 * M, dtype=torch.float32, device=logp.device)
-    nv.call("esc_nll_loss", nv.ptr(logp), ld, nv.ptr(target), M, C, denom, 1.0, nv.ptr(loss), nv.ptr(dlogp), C,
-            info[1:].data_ptr(), info.data_ptr(), nv.ptr(rows), nv.stream())
-    return loss.view(()), dlogp, _head_info(info, C)
+def _head_raw(x, target, denom, want_grad, fused=True):
+    """One launch of the classification head on [M, C] rows: esc_log_softmax_nll on logits (`fused`: also leaves logp), or
+    esc_nll_loss on log-probabilities.  Returns (loss, logp or None, d loss / d x or None, correct): targets, the info pair,
+    the row scratch and the one read-back are the same for both."""
+    x, ld = _rows(x)
+    M, C = x.shape
+    dev = x.device
+    target = _targets(target, M, dev)
+    loss = _empty(dev, 1)
+    info = torch.empty(2, dtype=torch.int32, device=dev)
+    logp = _empty(dev, M, C) if fused else None
+    dx = _empty(dev, M, C) if want_grad else None
+    rows = _empty(dev, 2 * M)
+    outs = (nv.ptr(logp), C, nv.ptr(loss)) if fused else (nv.ptr(loss),)
+    nv.call("esc_log_softmax_nll" if fused else "esc_nll_loss", nv.ptr(x), ld, nv.ptr(target), M, C, denom, 1.0, *outs,
+            nv.ptr(dx), C, info[1:].data_ptr(), info.data_ptr(), nv.ptr(rows), nv.stream())
+    return loss.view(()), logp, dx, _head_info(info, C)
 
 
-class _NllLoss(Function):
-    """F.nll_loss(logp, target, reduction=...) (run_exp.py:235,248), deterministic; the accuracy count of
-    run_exp.py:261-264 rides on the same launch."""
+class _HeadLoss(Function):
+    """F.nll_loss(logp, target, reduction=...) (run_exp.py:235,248), deterministic; the accuracy count of run_exp.py:261-264
+    rides on the same launch.  `fused`: nll_loss(log_softmax(logits), target) with its gradient (softmax - onehot) / denom in
+    ONE launch; logp and the loss equal the two-op composition bit for bit."""
 
     @staticmethod
-    def forward(ctx, logp, target, denom):
-        _dev(logp)
-        loss, dlogp, ctx.correct = _nll_raw(logp, target, denom, True)
-        ctx.save_for_backward(dlogp)
-        return loss
+    def forward(ctx, x, target, denom, fused):
+        _dev(x)
+        loss, logp, dx, ctx.correct = _head_raw(x, target, denom, True, fused)
+        ctx.save_for_backward(dx)
+        if not fused:
+            return loss
+        ctx.mark_non_differentiable(logp)
+        return loss, logp
 
     @staticmethod
-    def backward(ctx, g):
-        (dlogp,) = ctx.saved_tensors
-        return dlogp * g, None, None
+    def backward(ctx, g, _glogp=None):
+        (dx,) = ctx.saved_tensors
+        return dx * g, None, None, None
+
+
+def _head_loss(fused, x, target, reduction, denom):
+    """(loss, logp or None, correct) through autograd when x asks for a gradient, else by the bare launch"""
+    denom = _denom(reduction, denom)
+    if torch.is_grad_enabled() and x.requires_grad:
+        res = _HeadLoss.apply(x, target, denom, fused)
+        loss, logp = res if fused else (res, None)
+        return loss, logp, loss.grad_fn.correct
+    _dev(x)
+    loss, logp, _, correct = _head_raw(x, target, denom, False, fused)
+    return loss, logp, correct
 
 
 def nll_loss(logp, target, reduction="mean", denom=None, return_correct=False):
     """-sum_i logp[i, target_i] / denom; `denom` overrides the divisor that `reduction` implies.  A target outside
     [0, C) raises RuntimeError.  return_correct: also the number of rows whose argmax equals the target."""
-    denom = _denom(reduction, denom)
-    if torch.is_grad_enabled() and logp.requires_grad:
-        loss = _NllLoss.apply(logp, target, denom)
-        correct = loss.grad_fn.correct
-    else:
-        _dev(logp)
-        loss, _, correct = _nll_raw(logp, target, denom, False)
+    loss, _, correct = _head_loss(False, logp, target, reduction, denom)
     return (loss, correct) if return_correct else loss
-
-
-def _head_raw(logits, target, denom, want_grad):
-    x, ldx = _rows(logits)
-    M, C = x.shape
-    dev = x.device
-    target = _targets(target, M, dev)
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
-    info = torch.empty(2, dtype=torch.int32, device=dev)
-    logp = torch.empty((M, C), dtype=torch.float32, device=dev)
-    dx = torch.empty((M, C), dtype=torch.float32, device=dev) if want_grad else None
-    rows = torch.empty(2 * M, dtype=torch.float32, device=dev)
-    nv.call("esc_log_softmax_nll", nv.ptr(x), ldx, nv.ptr(target), M, C, denom, 1.0, nv.ptr(logp), C, nv.ptr(loss),
-            nv.ptr(dx), C, info[1:].data_ptr(), info.data_ptr(), nv.ptr(rows), nv.stream())
-    return loss.view(()), logp, dx, _head_info(info, C)
-
-
-class _LogSoftmaxNll(Function):
-    """nll_loss(log_softmax(logits), target) with its gradient (softmax - onehot) / denom in ONE launch; logp and the
-    loss equal the two-op composition bit for bit."""
-
-    @staticmethod
-    def forward(ctx, logits, target, denom):
-        _dev(logits)
-        loss, logp, dx, ctx.correct = _head_raw(logits, target, denom, True)
-        ctx.save_for_backward(dx)
-        ctx.mark_non_differentiable(logp)
-        return loss, logp
-
-    @staticmethod
-    def backward(ctx, g, _glogp):
-        (dx,) = ctx.saved_tensors
-        return dx * g, None, None
 
 
 def log_softmax_nll(logits, target, reduction="mean", denom=None, return_aux=False):
     """The fused classification head: loss = nll_loss(log_softmax(logits), target).  return_aux: (loss, logp, correct)
     with logp the (non-differentiable) log-probabilities and correct the number of rows whose argmax is the target."""
-    denom = _denom(reduction, denom)
-    if torch.is_grad_enabled() and logits.requires_grad:
-        loss, logp = _LogSoftmaxNll.apply(logits, target, denom)
-        correct = loss.grad_fn.correct
-    else:
-        _dev(logits)
-        loss, logp, _, correct = _head_raw(logits, target, denom, False)
+    loss, logp, correct = _head_loss(True, logits, target, reduction, denom)
     return (loss, logp, correct) if return_aux else loss
 
 
@@ -1016,7 +930,7 @@ def pdist(x, threshold=None):
     M, C = x.shape
     if C == 0:
         raise ValueError("pdist: rows have no columns")
-    out = torch.empty(M * (M - 1) // 2, dtype=torch.float32, device=x.device)
+    out = _empty(x.device, M * (M - 1) // 2)
     below = torch.empty(1, dtype=torch.int32, device=x.device) if threshold is not None else None
     nv.call("esc_pdist", nv.ptr(x), ldx, M, C, nv.ptr(out), float(threshold if threshold is not None else 0.0),
             nv.ptr(below), nv.stream())
@@ -1038,7 +952,7 @@ class _SegmentFirst(Function):
         S, C = ptr.numel() - 1, x.size(1)
         if node_to_segment.numel() != x.size(0):
             raise ValueError("segment_first: %d rows but %d segment ids" % (x.size(0), node_to_segment.numel()))
-        out = torch.empty((S, C), dtype=torch.float32, device=x.device)
+        out = _empty(x.device, S, C)
         nv.call("esc_segment_first_fwd", nv.ptr(x), ldx, nv.ptr(ptr), S, C, nv.ptr(out), nv.stream())
         ctx.ptr, ctx.seg, ctx.n = ptr, node_to_segment, x.size(0)
         return out
@@ -1047,7 +961,7 @@ class _SegmentFirst(Function):
     def backward(ctx, g):
         g, ldg = _rows(g)
         C = g.size(1)
-        dx = torch.empty((ctx.n, C), dtype=torch.float32, device=g.device)
+        dx = _empty(g.device, ctx.n, C)
         nv.call("esc_segment_first_bwd", nv.ptr(g), ldg, nv.ptr(ctx.ptr), nv.ptr(ctx.seg), ctx.n, C, nv.ptr(dx), nv.stream())
         return dx, None, None
 
@@ -1075,7 +989,7 @@ class _PoolMeanCenterSide(Function):
             raise ValueError("pool_mean_center_side: center_idx %s for %d segments" % (tuple(center_idx.shape), S))
         if node_to_segment.numel() != x.size(0):
             raise ValueError("pool_mean_center_side: %d rows but %d segment ids" % (x.size(0), node_to_segment.numel()))
-        out = torch.empty((S, 3 * C), dtype=torch.float32, device=x.device)
+        out = _empty(x.device, S, 3 * C)
         nv.call("esc_pool_mean_center_side_fwd", nv.ptr(x), ldx, nv.ptr(ptr), center_idx.data_ptr(), center_idx.data_ptr() + 8, 2,
                 S, C, nv.ptr(out), 3 * C, nv.stream())
         ctx.ptr, ctx.ci, ctx.seg, ctx.n = ptr, center_idx, node_to_segment, x.size(0)
@@ -1085,7 +999,7 @@ class _PoolMeanCenterSide(Function):
     def backward(ctx, g):
         g, ldg = _rows(g)
         C = g.size(1) // 3
-        dx = torch.empty((ctx.n, C), dtype=torch.float32, device=g.device)
+        dx = _empty(g.device, ctx.n, C)
         nv.call("esc_pool_mean_center_side_bwd", nv.ptr(g), ldg, nv.ptr(ctx.ptr), ctx.ci.data_ptr(), ctx.ci.data_ptr() + 8, 2,
                 nv.ptr(ctx.seg), ctx.n, C, nv.ptr(dx), C, nv.stream())
         return dx, None, None, None
@@ -1110,21 +1024,19 @@ class _SigmoidMul(Function):
         if a.shape != x.shape:
             raise ValueError("sigmoid_mul: shapes %s and %s differ" % (tuple(a.shape), tuple(x.shape)))
         M, C = a.shape
-        y = torch.empty((M, C), dtype=torch.float32, device=a.device)
+        y = _empty(a.device, M, C)
         nv.call("esc_sigmoid_mul_fwd", nv.ptr(a), lda, nv.ptr(x), ldx, M, C, nv.ptr(y), C, nv.stream())
         ctx.save_for_backward(a, x)
         return y
 
     @staticmethod
     def backward(ctx, g):
-        a, x = ctx.saved_tensors
-        g, ldg = _rows(g)
+        (a, lda), (x, ldx), (g, ldg) = (_rows(t) for t in ctx.saved_tensors + (g,))
         M, C = a.shape
-        da = torch.empty((M, C), dtype=torch.float32, device=g.device) if ctx.needs_input_grad[0] else None
-        dx = torch.empty((M, C), dtype=torch.float32, device=g.device) if ctx.needs_input_grad[1] else None
+        da = _empty(g.device, M, C) if ctx.needs_input_grad[0] else None
+        dx = _empty(g.device, M, C) if ctx.needs_input_grad[1] else None
         if da is not None or dx is not None:
-            nv.call("esc_sigmoid_mul_bwd", nv.ptr(a), a.stride(0) if M > 1 else C, nv.ptr(x), x.stride(0) if M > 1 else C,
-                    nv.ptr(g), ldg, M, C, nv.ptr(da), nv.ptr(dx), nv.stream())
+            nv.call("esc_sigmoid_mul_bwd", nv.ptr(a), lda, nv.ptr(x), ldx, nv.ptr(g), ldg, M, C, nv.ptr(da), nv.ptr(dx), nv.stream())
         return da, dx
 
 
@@ -1137,28 +1049,16 @@ def group_plan(index, n_keys):
     bag launches below need: built once per index tensor and cached on it, shared by every layer and both directions (I2GNN's
     node_to_original_node: the context mean and the gather back).  No read-back: the keys come from the expansion kernel, and a
     key outside [0, n_keys) only sets `bad`."""
-    from .plan import _csr
-    cache = getattr(index, "_esc_group", None)
-    key = (index._version, int(n_keys))
-    if cache is not None and cache[0] == key:
-        return cache[1]
-    dev, n = index.device, index.numel()
-    bad = torch.zeros(1, dtype=torch.int32, device=dev)
-    col_ptr, c_row = _csr(index, int(n_keys), bad=bad)
-    counts = (col_ptr[1:] - col_ptr[:-1]).clamp(min=1).to(torch.float32)
-    plan = dict(n=n, n_keys=int(n_keys), idx32=index.to(torch.int32), row_ptr=torch.arange(n + 1, dtype=torch.int32, device=dev),
-                ones=torch.ones(n, dtype=torch.int32, device=dev), col_ptr=col_ptr, c_row=c_row, bad=bad,
-                inv_count=(1.0 / counts).view(-1, 1))
-    index._esc_group = (key, plan)
-    return plan
-
-
-def _bag_rows(table, row_ptr, idx32, ones, n_out):
-    table = table.contiguous()
-    H = table.size(1)
-    out = torch.empty((n_out, H), dtype=torch.float32, device=table.device)
-    nv.call("esc_bag_fwd", nv.ptr(table), H, nv.ptr(row_ptr), nv.ptr(idx32), nv.ptr(ones), n_out, nv.ptr(out), H, nv.stream())
-    return out
+    def build():
+        from .plan import _csr
+        dev, n = index.device, index.numel()
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        col_ptr, c_row = _csr(index, int(n_keys), bad=bad)
+        counts = (col_ptr[1:] - col_ptr[:-1]).clamp(min=1).to(torch.float32)
+        return dict(n=n, n_keys=int(n_keys), idx32=index.to(torch.int32), row_ptr=torch.arange(n + 1, dtype=torch.int32, device=dev),
+                    ones=torch.ones(n, dtype=torch.int32, device=dev), col_ptr=col_ptr, c_row=c_row, bad=bad,
+                    inv_count=(1.0 / counts).view(-1, 1))
+    return _cached(index, "_esc_group", int(n_keys), build)
 
 
 class _GatherRows(Function):
@@ -1208,14 +1108,12 @@ def group_mean(x, plan):
 def _pair_ptr(graph_ptr):
     """int64 [G+1] exclusive scan of n_g^2 on the device (torch plumbing, no read-back), cached on the graph_ptr tensor the way
     _seg_ptr caches segment pointers: the ten attention layers of a step share it"""
-    cache = getattr(graph_ptr, "_esc_pairs", None)
-    if cache is not None and cache[0] == graph_ptr._version:
-        return cache[1]
-    n = (graph_ptr[1:] - graph_ptr[:-1]).to(torch.int64)
-    pair_ptr = torch.zeros(graph_ptr.numel(), dtype=torch.int64, device=graph_ptr.device)
-    torch.cumsum(n * n, 0, out=pair_ptr[1:])
-    graph_ptr._esc_pairs = (graph_ptr._version, pair_ptr)
-    return pair_ptr
+    def build():
+        n = (graph_ptr[1:] - graph_ptr[:-1]).to(torch.int64)
+        pair_ptr = torch.zeros(graph_ptr.numel(), dtype=torch.int64, device=graph_ptr.device)
+        torch.cumsum(n * n, 0, out=pair_ptr[1:])
+        return pair_ptr
+    return _cached(graph_ptr, "_esc_pairs", None, build)
 
 
 def attention_max_nodes(head_dim):
@@ -1234,8 +1132,8 @@ class _GraphAttention(Function):
         qkv, ld = _rows(qkv)
         N, H = qkv.size(0), heads * head_dim
         G, dev = graph_ptr.numel() - 1, qkv.device
-        out = torch.empty((N, H), dtype=torch.float32, device=dev)
-        lse = torch.empty((heads, N), dtype=torch.float32, device=dev)
+        out = _empty(dev, N, H)
+        lse = _empty(dev, heads, N)
         mask_pairs = N * max_nodes if p > 0.0 else 0           # >= sum n_g^2, known without reading graph_ptr back
         mask = torch.empty(heads * mask_pairs, dtype=torch.uint8, device=dev) if p > 0.0 else None
         nv.call("esc_graph_attention_fwd", nv.ptr(qkv), ld, nv.ptr(graph_ptr), nv.ptr(pair_ptr), G, N, mask_pairs, max_nodes,
@@ -1253,9 +1151,10 @@ class _GraphAttention(Function):
         qkv, lse, mask = ctx.saved_tensors
         graph_ptr, pair_ptr, G, N, mask_pairs, max_nodes, heads, head_dim, p = ctx.args
         _dev(d_out)
+        qkv, ld = _rows(qkv)
         d_out, ldg = _rows(d_out)
-        d_qkv = torch.empty((N, 3 * heads * head_dim), dtype=torch.float32, device=qkv.device)
-        nv.call("esc_graph_attention_bwd", nv.ptr(qkv), qkv.stride(0) if N > 1 else qkv.size(1), nv.ptr(d_out), ldg, nv.ptr(lse),
+        d_qkv = _empty(qkv.device, N, 3 * heads * head_dim)
+        nv.call("esc_graph_attention_bwd", nv.ptr(qkv), ld, nv.ptr(d_out), ldg, nv.ptr(lse),
                 nv.ptr(mask), nv.ptr(graph_ptr), nv.ptr(pair_ptr), G, N, mask_pairs, max_nodes, heads, head_dim, p, nv.ptr(d_qkv),
                 nv.stream())
         return d_qkv, None, None, None, None, None, None, None
@@ -1283,11 +1182,8 @@ def graph_attention(qkv, graph_ptr, heads, p=0.0, training=False, max_nodes=None
         raise RuntimeError("graph_attention: head_dim %d must be a multiple of 4 and at most 64" % head_dim)
     graph_ptr = graph_ptr.contiguous()
     if max_nodes is None:
-        cache = getattr(graph_ptr, "_esc_max_nodes", None)
-        if cache is None or cache[0] != graph_ptr._version:
-            widest = int((graph_ptr[1:] - graph_ptr[:-1]).max()) if graph_ptr.numel() > 1 else 0
-            cache = graph_ptr._esc_max_nodes = (graph_ptr._version, widest)
-        max_nodes = cache[1]
+        max_nodes = _cached(graph_ptr, "_esc_max_nodes", None,
+                            lambda: int((graph_ptr[1:] - graph_ptr[:-1]).max()) if graph_ptr.numel() > 1 else 0)
     max_nodes = int(max_nodes)
     if max_nodes > limit:
         raise RuntimeError("graph_attention: a graph of %d nodes exceeds the limit of %d nodes per graph at head_dim %d"
@@ -1363,7 +1259,7 @@ def _checked_gather(who, tables, table_rule, node_ptr_all, graph_ids, graph_ptr,
         raise IndexError("%s: graph id out of range (the table holds %d graphs)" % (who, G_all))
     N, K = int(num_nodes), tables[0].size(1)
     ids_d = ids_h.to(dev, non_blocking=True)
-    outs = [torch.empty((N, K), dtype=torch.float32, device=dev) for _ in tables]
+    outs = [_empty(dev, N, K) for _ in tables]
     return node_ptr_all, ids_d, graph_ptr, (G_all, tables[0].size(0), B, N, K), outs
 
 
@@ -1383,8 +1279,8 @@ def laplacian_eig(edge_index, graph_ptr, edge_ptr, max_freqs, max_nodes=None, ed
     src, dst, node_ptr, edge_ptr, G, N, max_nodes = _ragged_graphs("laplacian_eig", laplacian_eig_limits()[0], edge_index, graph_ptr,
                                                                    edge_ptr, max_nodes, num_nodes)
     dev = src.device
-    vecs = torch.empty((N, K), dtype=torch.float32, device=dev)
-    vals = torch.empty((N, K), dtype=torch.float32, device=dev)
+    vecs = _empty(dev, N, K)
+    vals = _empty(dev, N, K)
     need = int(nv.lib().esc_laplacian_eig_scratch_bytes(N, max_nodes))
     scratch = torch.empty(need // 8, dtype=torch.float64, device=dev) if need else None
     nv.call("esc_laplacian_eig", nv.ptr(src), nv.ptr(dst), src.numel(), nv.ptr(node_ptr), nv.ptr(edge_ptr), G, N, int(bool(edges_local)), K,
@@ -1419,7 +1315,7 @@ class _LapPEEncode(Function):
     def forward(ctx, eigvecs, eigvals, signs, wA, bA, w1, b1):
         N, K = eigvecs.shape
         P = w1.size(0)
-        out = torch.empty((N, P), dtype=torch.float32, device=eigvecs.device)
+        out = _empty(eigvecs.device, N, P)
         nv.call("esc_lappe_encode_fwd", nv.ptr(eigvecs), nv.ptr(eigvals), nv.ptr(signs), nv.ptr(wA), nv.ptr(bA), nv.ptr(w1), nv.ptr(b1),
                 N, K, P, nv.ptr(out), P, nv.stream())
         ctx.save_for_backward(eigvecs, eigvals, signs, wA, bA, w1, b1)
@@ -1433,8 +1329,8 @@ class _LapPEEncode(Function):
         _dev(d_out)
         d_out, ldg = _rows(d_out)
         need = int(nv.lib().esc_lappe_encode_scratch_floats(N, P))
-        scratch = torch.empty(max(need, 1), dtype=torch.float32, device=eigvecs.device)
-        flat = torch.empty(2 * P * P + 7 * P, dtype=torch.float32, device=eigvecs.device)
+        scratch = _empty(eigvecs.device, max(need, 1))
+        flat = _empty(eigvecs.device, 2 * P * P + 7 * P)
         d_wA, d_bA, d_w1, d_b1 = flat[:4 * P].view(2 * P, 2), flat[4 * P:6 * P], flat[6 * P:6 * P + 2 * P * P].view(P, 2 * P), flat[6 * P + 2 * P * P:]
         nv.call("esc_lappe_encode_bwd", nv.ptr(eigvecs), nv.ptr(eigvals), nv.ptr(signs), nv.ptr(wA), nv.ptr(bA), nv.ptr(w1), nv.ptr(b1),
                 nv.ptr(d_out), ldg, N, K, P, nv.ptr(scratch), need, nv.ptr(d_wA), nv.ptr(d_bA), nv.ptr(d_w1), nv.ptr(d_b1), nv.stream())
@@ -1515,7 +1411,7 @@ def rw_landing(edge_index, graph_ptr, edge_ptr, ksteps, max_nodes=None, max_edge
     if max_edges > edge_limit:
         raise RuntimeError("rw_landing: a graph of %d edges exceeds the limit of %d edges per graph" % (max_edges, edge_limit))
     K = bin(mask).count("1")
-    out = torch.empty((N, K), dtype=torch.float32, device=src.device)
+    out = _empty(src.device, N, K)
     nv.call("esc_rw_landing", nv.ptr(src), nv.ptr(dst), src.numel(), nv.ptr(node_ptr), nv.ptr(edge_ptr), G, N, int(bool(edges_local)), mask,
             max(max_nodes, 0), max(max_edges, 0), nv.ptr(out), K, nv.stream())
     return out

@@ -166,6 +166,39 @@ def test_loss_through_ops_and_autograd(E, name):
             assert same_bits(loss, first[0]) and same_bits(grad.reshape(-1), first[1]), what
 
 
+@pytest.mark.parametrize("denom", [None, 7])
+@pytest.mark.parametrize("M", [1, 2, 6])
+@pytest.mark.parametrize("entry", ["l1", "mse", "bce"])
+def test_elementwise_loss_heads_return_the_gradient_in_the_shape_of_pred(E, entry, M, denom):
+    """The three heads are one Function behind a table: each keeps its divisor (M, M, the labelled count), bce takes a NaN
+    label, and the gradient comes back as [M], [M, 1] or [2, M // 2], whichever pred was (DESIGN.md: ops.l1_loss's backward once
+    returned [M, 1] whatever it was given).  [2, 0], what M = 1 makes of the third shape, is refused like every empty batch."""
+    fn = {"l1": E.ops.l1_loss, "mse": E.ops.mse_loss, "bce": E.ops.bce_with_logits_loss}[entry]
+    case = lc.Loss("heads-%s-%d-%s" % (entry, M, denom), entry, M, 1, "plain", denom, 1.0, True, 1.0)
+    g = torch.Generator().manual_seed(lc.seed_of(case.name))
+    pred, y = torch.randn(M, generator=g), torch.randn(M, generator=g)
+    if entry == "bce":
+        pred, y = pred * 3, (torch.rand(M, generator=g) > 0.5).float()
+        y[M - 1] = NAN
+    loss64, grad64 = lc.loss_ref64(case, pred, y)
+    l32, g32 = lc.loss_torch(case, pred, y, torch.float32)
+    floor_l, floor_g = lc.loss_floors(case, pred, y, loss64, grad64)
+    for shape in ((M,), (M, 1), (2, M // 2)):
+        what = "%s %s" % (case.name, list(shape))
+        if 2 * (M // 2) != M and len(shape) == 2 and shape[0] == 2:
+            with pytest.raises(RuntimeError):
+                fn(torch.zeros(shape, device=DEV, requires_grad=True), torch.zeros(0, device=DEV), denom=denom)
+            continue
+        leaf = pred.reshape(shape).to(DEV).requires_grad_(True)
+        loss = fn(leaf, y.to(DEV), denom=denom)
+        assert loss.shape == ()
+        loss.backward()
+        assert leaf.grad.shape == torch.Size(shape), (what, tuple(leaf.grad.shape))
+        lc.check(what + " loss", loss, l32, loss64, floor_l)
+        lc.check(what + " grad", leaf.grad, g32, grad64, floor_g)
+        exact_properties(case, pred, y, loss.detach().cpu(), leaf.grad.cpu(), what)
+
+
 def test_loss_bad_arguments_raise_and_leave_the_device_usable(E):
     nv, ops = E._native, E.ops
     x, t = torch.randn(8, 1, device=DEV), torch.randn(8, device=DEV)

@@ -1009,3 +1009,76 @@ def test_bag_forward_with_lds_staged_table_slices(E, H, spread):
     _chk(invstd, 1.0 / torch.sqrt(ref.double().var(0, unbiased=False) + 1e-5), "invstd from the bag epilogue")
     with pytest.raises(RuntimeError):                              # fewer edges than the tiled kernel serves: no statistics
         nv.call("esc_bag_fwd_rows", nv.ptr(Wd), rows, H, nv.ptr(rp), nv.ptr(ix), nv.ptr(vl), 100, nv.ptr(new), H, 0, nv.ptr(stats), nv.stream())
+
+
+def _one_row(v, dev):
+    """(leaf [C, 1], its transpose): ONE row of C columns whose stride(0) is 1, below its width - what PyTorch hands on for a
+    transposed column.  The backward of an op must read it with the leading dimension its forward used (ops._rows)."""
+    leaf = v.reshape(-1, 1).to(dev).requires_grad_(True)
+    row = leaf.t()
+    assert tuple(row.shape) == (1, v.numel()) and row.stride(0) == 1
+    return leaf, row
+
+
+@pytest.mark.parametrize("K,N", [(4, 3), (256, 256)])          # 256 x 256: the matrix-core branch
+def test_one_row_operand_linear(E, K, N):
+    torch.manual_seed(K)
+    dev = torch.device("cuda:0")
+    x, w, bias = torch.randn(1, K), torch.randn(N, K) / K ** 0.5, torch.randn(N)
+    leaf, row = _one_row(x, dev)
+    wd, bd = (t.to(dev).requires_grad_(True) for t in (w, bias))
+    y = E.ops.linear(row, wd, bd)
+    x64, w64, b64 = (t.double().requires_grad_(True) for t in (x, w, bias))
+    r = x64 @ w64.t() + b64
+    assert torch.allclose(y.cpu().double(), r, **TOL)
+    g = torch.randn(1, N)
+    y.backward(g.to(dev))
+    r.backward(g.double())
+    assert torch.allclose(leaf.grad.t().cpu().double(), x64.grad, **TOL)
+    scale = max(1.0, float(w64.grad.abs().max()))
+    assert torch.allclose(wd.grad.cpu().double() / scale, w64.grad / scale, **TOL)
+    assert torch.allclose(bd.grad.cpu().double() / scale, b64.grad / scale, **TOL)
+
+
+@pytest.mark.parametrize("act", [0, 1])
+@pytest.mark.parametrize("C", [10, 256])
+def test_one_row_operand_bn_eval_act(E, C, act):
+    torch.manual_seed(C + act)
+    dev = torch.device("cuda:0")
+    x = torch.randn(1, C) * 3 + 5
+    gamma, beta, rm0, rv0 = torch.rand(C) + 0.5, torch.randn(C), torch.randn(C) + 5, torch.rand(C) * 9 + 0.5
+    leaf, row = _one_row(x, dev)
+    gd, bd = (t.to(dev).requires_grad_(True) for t in (gamma, beta))
+    y = E.ops.bn_eval_act(row, gd, bd, rm0.to(dev), rv0.to(dev), 1e-5, act)
+    x64, g64, b64 = (t.double().requires_grad_(True) for t in (x, gamma, beta))
+    r = (x64 - rm0.double()) / torch.sqrt(rv0.double() + 1e-5) * g64 + b64
+    r = r.relu() if act else r
+    assert torch.allclose(y.cpu().double(), r, **TOL)
+    g = torch.randn(1, C)
+    y.backward(g.to(dev))
+    r.backward(g.double())
+    _chk(leaf.grad.t(), x64.grad, "dx")
+    _chk(gd.grad, g64.grad, "dgamma")
+    _chk(bd.grad, b64.grad, "dbeta")
+
+
+@pytest.mark.parametrize("C", [10, 64])
+def test_one_row_operand_gine_aggregate(E, C):
+    """one node with one self-loop: out = relu(x + e) + (1 + eps) x"""
+    torch.manual_seed(C)
+    dev = torch.device("cuda:0")
+    plan = E.BatchPlan.from_tensors(torch.zeros(2, 1, dtype=torch.long, device=dev), 1)
+    x, e, eps = torch.randn(1, C), torch.randn(1, C), torch.tensor([0.3])
+    xl, xrow = _one_row(x, dev)
+    el, erow = _one_row(e, dev)
+    epsd = eps.to(dev).requires_grad_(True)
+    out = E.ops.gine_aggregate(xrow, erow, epsd, plan)
+    x64, e64, eps64 = (t.double().requires_grad_(True) for t in (x, e, eps))
+    r = (x64 + e64).relu() + (1 + eps64) * x64
+    assert torch.allclose(out.cpu().double(), r, **TOL)
+    g = torch.randn(1, C)
+    out.backward(g.to(dev))
+    r.backward(g.double())
+    assert torch.allclose(xl.grad.t().cpu().double(), x64.grad, **TOL)
+    assert torch.allclose(el.grad.t().cpu().double(), e64.grad, **TOL)
+    assert torch.allclose(epsd.grad.cpu().double(), eps64.grad, rtol=1e-5, atol=1e-4)
