@@ -100,6 +100,14 @@ except OSError as exc:
     raise NativeLibraryError("esc_gnn_amd: cannot read the C header %s the binding is derived from (%s)" % (STEP_HEADER, exc)) from exc
 STEP_SIGNATURES = {name: args for name, (args, _) in _STEP.functions.items()}
 _RET.update({name: ret for name, (_, ret) in _STEP.functions.items()})
+# the eighth extension header (escgnn_gatedgcn.h: the gate of the GatedGCN local layer, forward and backward)
+GATEDGCN_HEADER = os.path.join(os.path.dirname(_abi.HEADER), "escgnn_gatedgcn.h")
+try:
+    _GATED = _abi.load(GATEDGCN_HEADER)
+except OSError as exc:
+    raise NativeLibraryError("esc_gnn_amd: cannot read the C header %s the binding is derived from (%s)" % (GATEDGCN_HEADER, exc)) from exc
+GATEDGCN_SIGNATURES = {name: args for name, (args, _) in _GATED.functions.items()}
+_RET.update({name: ret for name, (_, ret) in _GATED.functions.items()})
 KIND = {name[len("ESC_K_"):].lower(): v for name, v in _ABI.enum.items() if name != "ESC_K_COUNT"}
 
 CollateArgs = struct("esc_collate_args")
@@ -123,7 +131,7 @@ def lib():
             "esc_gnn_amd: %s not found. The HIP hot path has no fallback — build it with "
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C esc-gnn_amd/csrc`." % LIB_PATH)
     h = ctypes.CDLL(LIB_PATH)
-    for name, args in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()) + list(I2GNN_SIGNATURES.items()) + list(GINEPLUS_SIGNATURES.items()) + list(GPS_SIGNATURES.items()) + list(LAPPE_SIGNATURES.items()) + list(RWSE_SIGNATURES.items()) + list(STEP_SIGNATURES.items()):
+    for name, args in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()) + list(I2GNN_SIGNATURES.items()) + list(GINEPLUS_SIGNATURES.items()) + list(GPS_SIGNATURES.items()) + list(LAPPE_SIGNATURES.items()) + list(RWSE_SIGNATURES.items()) + list(STEP_SIGNATURES.items()) + list(GATEDGCN_SIGNATURES.items()):
         try:
             fn = getattr(h, name)
         except AttributeError as exc:

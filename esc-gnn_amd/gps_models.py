@@ -22,7 +22,12 @@ width with the state_dict that has.  GPSModel(rwse=True) is TypeDictNode+RWSE th
 batch's pestat_RWSE, rwse.py), and both flags give the reference's only three-way encoder, TypeDictNode+LapPE+RWSE
 (Concat3NodeEncoder: encoder2 = LapPE, encoder3 = RWSE).
 
-Out of scope: BiasedTransformer / attn_bias, Performer and BigBird, the other local GNN types, layer_norm, the other positional
+GPSLayer / GPSModel(local_gnn_type='CustomGatedGCN') swaps the GINE layer for nn.GatedGCNLayer (gatedgcn_layer.py), the one other
+local type the fork implements: it also returns new edge attributes, which the next layer's ESC term is added to;
+global_model_type='None' drops the attention branch (self_attn None, no keys; norm1_attn stays, unused, as in the reference).
+
+Out of scope: BiasedTransformer / attn_bias, Performer and BigBird, the local GNN types GCN / GIN / GENConv / GAT / PNA, the
+EquivStableLapPE gate of GINE and GatedGCN, a fused BatchNorm on GatedGCN's edge rows, layer_norm, the other positional
 encodings (SignNet, EquivStableLapPE, HKdiagSE, ElstaticSE) and LapPE's Transformer model, graphgym's config system and wandb,
 a whole-step engine, data parallelism."""
 import torch
@@ -30,23 +35,37 @@ from torch.nn import Dropout, ModuleList, Sequential
 
 from . import nested
 from .nested import Z_TABLE_ROWS
-from .nn import BatchNorm1d, Embedding, GINEConv, GraphMultiheadAttention, LapPENodeEncoder, Linear, ReLU, RWSENodeEncoder, global_add_pool
+from .nn import BatchNorm1d, Embedding, GatedGCNLayer, GINEConv, GraphMultiheadAttention, LapPENodeEncoder, Linear, ReLU, RWSENodeEncoder, global_add_pool
 from .plan import graph_ptr_of, plan_of
 
 
 class GPSLayer(torch.nn.Module):
-    """Local GINE + full graph attention + feed-forward (gps_layer.py:19-302 for local_gnn_type 'GINE', global_model_type
-    'Transformer', act 'relu', batch_norm)."""
+    """Local message passing + full graph attention + feed-forward (gps_layer.py:19-302 with act 'relu' and batch_norm).
+    local_gnn_type 'GINE' (the yaml's) or 'CustomGatedGCN' (gps_layer.py:94-99: nn.GatedGCNLayer with its own dropout and
+    residual, whose edge output becomes the layer's edge attributes, :197-208); global_model_type 'Transformer' or 'None'
+    (self_attn None: the attention branch is skipped; norm1_attn exists all the same, :150-152)."""
 
-    def __init__(self, dim_h, num_heads, dropout=0.0, attn_dropout=0.0):
+    def __init__(self, dim_h, num_heads, dropout=0.0, attn_dropout=0.0, local_gnn_type="GINE", global_model_type="Transformer"):
         super().__init__()
         self.dim_h, self.num_heads = dim_h, num_heads
-        self.local_model = GINEConv(Sequential(Linear(dim_h, dim_h), ReLU(), Linear(dim_h, dim_h)))     # constant eps = 0, no edge Linear
+        if local_gnn_type == "GINE":
+            self.local_model = GINEConv(Sequential(Linear(dim_h, dim_h), ReLU(), Linear(dim_h, dim_h)))  # constant eps = 0, no edge Linear
+        elif local_gnn_type == "CustomGatedGCN":
+            self.local_model = GatedGCNLayer(dim_h, dim_h, dropout=dropout, residual=True)
+        else:
+            raise ValueError(f"Unsupported local GNN model: {local_gnn_type}")
+        self.local_gnn_type = local_gnn_type
         self.edge_attn_emb = torch.nn.Embedding(101, num_heads, padding_idx=100)                         # unused: see the module docstring
         self.edge_attn_linear = Sequential(torch.nn.Linear(num_heads, num_heads), torch.nn.ReLU(),
                                            torch.nn.Linear(num_heads, num_heads), torch.nn.ReLU(),
                                            torch.nn.Linear(num_heads, num_heads))
-        self.self_attn = GraphMultiheadAttention(dim_h, num_heads, dropout=attn_dropout)
+        if global_model_type == "None":
+            self.self_attn = None
+        elif global_model_type == "Transformer":
+            self.self_attn = GraphMultiheadAttention(dim_h, num_heads, dropout=attn_dropout)
+        else:
+            raise ValueError(f"Unsupported global x-former model: {global_model_type}")
+        self.global_model_type = global_model_type
         self.norm1_local = BatchNorm1d(dim_h)
         self.norm1_attn = BatchNorm1d(dim_h)
         self.dropout_local = Dropout(dropout)
@@ -64,11 +83,17 @@ class GPSLayer(torch.nn.Module):
         """(node states, edge attributes) -> the same after this layer; the edge attributes carry this layer's ESC term on"""
         if "pos_index" in data:
             edge_attr = edge_attr + self.z_embedding(nested.edge_term(self.z_initial, data, plan))
-        h_local = self.dropout_local(self.local_model(h, data.edge_index, edge_attr, plan))
-        h_local = self.norm1_local(h + h_local)
-        h_attn = self.dropout_attn(self.self_attn(h, graph_ptr, max_nodes))
-        h_attn = self.norm1_attn(h + h_attn)
-        h = h_local + h_attn
+        if self.local_gnn_type == "CustomGatedGCN":          # it drops out and adds its residuals itself (gps_layer.py:206-208)
+            h_local, edge_attr = self.local_model(h, edge_attr, plan)
+            h_local = self.norm1_local(h_local)
+        else:
+            h_local = self.dropout_local(self.local_model(h, data.edge_index, edge_attr, plan))
+            h_local = self.norm1_local(h + h_local)
+        if self.self_attn is not None:
+            h_attn = self.dropout_attn(self.self_attn(h, graph_ptr, max_nodes))
+            h = h_local + self.norm1_attn(h + h_attn)
+        else:
+            h = h_local
         ff = self.ff_dropout1(self.act_fn_ff(self.ff_linear1(h)))
         h = h + self.ff_dropout2(self.ff_linear2(ff))
         return self.norm2(h), edge_attr
@@ -149,19 +174,21 @@ class GPSModel(torch.nn.Module):
 
     def __init__(self, layers=10, dim_hidden=64, n_heads=4, dropout=0.0, attn_dropout=0.5, node_types=28, edge_types=4, dim_out=1,
                  lap_pe=False, dim_pe=8, max_freqs=8, rwse=False, rwse_dim_pe=28, rwse_steps=20, rwse_model="linear", rwse_layers=1,
-                 rwse_raw_norm="batchnorm"):
+                 rwse_raw_norm="batchnorm", local_gnn_type="GINE", global_model_type="Transformer"):
         super().__init__()
         self.lap_pe, self.rwse = bool(lap_pe), bool(rwse)
         rw = dict(dim_pe=rwse_dim_pe, num_steps=rwse_steps, model=rwse_model, layers=rwse_layers, raw_norm=rwse_raw_norm) if self.rwse else None
         self.encoder = FeatureEncoder(dim_hidden, node_types, edge_types, self.lap_pe, dim_pe, max_freqs, rw)
-        self.layers = Sequential(*[GPSLayer(dim_hidden, n_heads, dropout, attn_dropout) for _ in range(layers)])
+        self.layers = Sequential(*[GPSLayer(dim_hidden, n_heads, dropout, attn_dropout, local_gnn_type, global_model_type)
+                                   for _ in range(layers)])
+        self.has_attention = global_model_type != "None"
         self.post_mp = SANGraphHead(dim_hidden, dim_out)
 
     def forward(self, data):
         data.to(self.post_mp.FC_layers[0].weight.device)
         plan = plan_of(data, Z_TABLE_ROWS)
         graph_ptr, num_graphs = graph_ptr_of(data, plan)
-        max_nodes = getattr(data, "_esc_max_nodes", None)
+        max_nodes = getattr(data, "_esc_max_nodes", None) if self.has_attention else None
         types = data.x.view(data.x.size(0), -1)[:, 0]                                 # type_dict_encoder.py:96: the first column
         h = self.encoder.node_encoder(types, data) if (self.lap_pe or self.rwse) else self.encoder.node_encoder(types)
         edge_attr = self.encoder.edge_encoder(data.edge_attr.view(-1))

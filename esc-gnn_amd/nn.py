@@ -141,6 +141,42 @@ class GINEConv(torch.nn.Module):
         return "{}(nn={})".format(self.__class__.__name__, self.nn)
 
 
+class GatedGCNLayer(torch.nn.Module):
+    """The reference's GatedGCNLayer (GraphGPS/graphgps/layer/gatedgcn_layer.py:11-136, Residual Gated Graph ConvNets) without
+    EquivStableLapPE: the same parameters, names and construction order - A, B, C, D, E (this module's Linear), bn_node_x,
+    bn_edge_e (this module's BatchNorm1d with the ReLU that follows it absorbed) - so equal seeds give equal weights and a
+    reference checkpoint loads.  forward(x, e, plan) -> (x, e): the five Linears, ops.gated_gcn_aggregate (one launch), the two
+    BatchNorm+ReLU, F.dropout on both and, with `residual`, the two residual adds.  The edge attributes leave the layer
+    updated: the only local layer of the reference's GPSLayer that carries them on."""
+
+    def __init__(self, in_dim, out_dim, dropout, residual, act="relu", equivstable_pe=False):
+        super().__init__()
+        if equivstable_pe:
+            raise ValueError("GatedGCNLayer: equivstable_pe (the EquivStableLapPE gate r_ij) is not supported")
+        if act != "relu":
+            raise ValueError("GatedGCNLayer: only act 'relu' is supported (got %r)" % (act,))
+        if residual and in_dim != out_dim:
+            raise ValueError("GatedGCNLayer: residual needs in_dim == out_dim (got %d and %d)" % (in_dim, out_dim))
+        self.A = Linear(in_dim, out_dim, bias=True)
+        self.B = Linear(in_dim, out_dim, bias=True)
+        self.C = Linear(in_dim, out_dim, bias=True)
+        self.D = Linear(in_dim, out_dim, bias=True)
+        self.E = Linear(in_dim, out_dim, bias=True)
+        self.bn_node_x = BatchNorm1d(out_dim, fuse_relu=True)
+        self.bn_edge_e = BatchNorm1d(out_dim, fuse_relu=True)
+        self.dropout = dropout
+        self.residual = residual
+
+    def forward(self, x, e, plan):
+        Ax, Bx, Ce, Dx, Ex = self.A(x), self.B(x), self.C(e), self.D(x), self.E(x)       # gatedgcn_layer.py:57-61
+        h, e_ij = ops.gated_gcn_aggregate(Ax, Bx, Dx, Ex, Ce, plan)
+        h = torch.nn.functional.dropout(self.bn_node_x(h), self.dropout, training=self.training)
+        e_ij = torch.nn.functional.dropout(self.bn_edge_e(e_ij), self.dropout, training=self.training)
+        if self.residual:
+            h, e_ij = x + h, e + e_ij
+        return h, e_ij
+
+
 def global_add_pool(x, batch, size=None):
     """PyG global_add_pool: segment sum by graph id (HIP segment_pool kernels)."""
     return ops.segment_pool(x, batch, size, mean=False)

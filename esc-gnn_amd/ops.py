@@ -181,6 +181,67 @@ def neighbour_sum(x, e, plan):
     return _Aggregate.apply(x, e, None, plan, False)
 
 
+def gated_gcn_max_channels():
+    """the widest row esc_gated_gcn_fwd / _bwd take (a multiple of 4 from 4 up to this)"""
+    return int(nv.lib().esc_gated_gcn_max_channels())
+
+
+class _GatedGCN(Function):
+    """e_ij = Dx_i + Ex_j + Ce_k, out_i = Ax_i + sum_k sigmoid(e_ij) Bx_j / (sum_k sigmoid(e_ij) + 1e-6) and e_ij itself: message,
+    aggregate and update of the reference's GatedGCNLayer (GraphGPS/graphgps/layer/gatedgcn_layer.py:67-70,90-136) in one
+    launch, their backward in two (csrc/gatedgcn.hip).  Kept for the backward: e_out and out (outputs anyway), den, Ax, Bx."""
+
+    @staticmethod
+    def forward(ctx, Ax, Bx, Dx, Ex, Ce, plan):
+        _dev(Ax, Bx, Dx, Ex, Ce)
+        _on(Ax.device, Bx, Dx, Ex, Ce)
+        _plan_on(Ax.device, plan, "in_ptr", "in_edge", "in_src", "out_ptr", "out_edge", "out_dst")
+        (Ax, lda), (Bx, ldb), (Dx, ldd), (Ex, lde), (Ce, ldc) = (_rows(t) for t in (Ax, Bx, Dx, Ex, Ce))
+        N, C = Ax.shape
+        E = plan.num_edges
+        limit = gated_gcn_max_channels()
+        if C % 4 or not 4 <= C <= limit:
+            raise ValueError("gated_gcn_aggregate: width %d: the kernels take a multiple of 4 with 4 <= C <= %d" % (C, limit))
+        if any(tuple(t.shape) != (N, C) for t in (Bx, Dx, Ex)) or Ce.size(1) != C or N != plan.num_nodes:
+            raise ValueError("gated_gcn_aggregate: Ax %s, Bx %s, Dx %s, Ex %s, Ce %s must share one width and the batch's %d nodes"
+                             % (tuple(Ax.shape), tuple(Bx.shape), tuple(Dx.shape), tuple(Ex.shape), tuple(Ce.shape), plan.num_nodes))
+        if Ce.size(0) != E:
+            raise ValueError("gated_gcn_aggregate: Ce has %d rows, the batch has %d edges" % (Ce.size(0), E))
+        dev = Ax.device
+        out, e_out, den = _empty(dev, N, C), _empty(dev, E, C), _empty(dev, N, C)
+        edge = (lambda t: nv.ptr(t)) if E else (lambda t: None)
+        nv.call("esc_gated_gcn_fwd", nv.ptr(Ax), lda, nv.ptr(Bx), ldb, nv.ptr(Dx), ldd, nv.ptr(Ex), lde, edge(Ce), ldc,
+                nv.ptr(plan.in_ptr), edge(plan.in_edge), edge(plan.in_src), N, E, C, nv.ptr(out), C, edge(e_out), C, nv.ptr(den),
+                nv.stream())
+        ctx.save_for_backward(Ax, Bx, out, e_out, den)
+        ctx.plan = plan
+        ctx.set_materialize_grads(False)         # an unused output's gradient arrives as None: g_e NULL, no zero rows are made
+        return out, e_out
+
+    @staticmethod
+    def backward(ctx, g_out, g_e):
+        Ax, Bx, out, e_out, den = ctx.saved_tensors
+        plan = ctx.plan
+        N, C = Ax.shape
+        E, dev = plan.num_edges, Ax.device
+        (Ax, lda), (Bx, ldb) = _rows(Ax), _rows(Bx)
+        g_out, ldg = _rows(g_out if g_out is not None else _zeros(dev, N, C))
+        g_e, ldge = _rows(g_e) if g_e is not None else (None, 0)
+        d_Ce, d_Dx, d_Ex, d_Bx = _empty(dev, E, C), _empty(dev, N, C), _empty(dev, N, C), _empty(dev, N, C)
+        edge = (lambda t: nv.ptr(t)) if E else (lambda t: None)
+        nv.call("esc_gated_gcn_bwd", nv.ptr(g_out), ldg, edge(g_e), ldge, edge(e_out), C, nv.ptr(den), nv.ptr(out), C, nv.ptr(Ax), lda,
+                nv.ptr(Bx), ldb, nv.ptr(plan.in_ptr), edge(plan.in_edge), edge(plan.in_src), nv.ptr(plan.out_ptr),
+                edge(plan.out_edge), edge(plan.out_dst), N, E, C, edge(d_Ce), C, nv.ptr(d_Dx), C, nv.ptr(d_Ex), C, nv.ptr(d_Bx), C,
+                nv.stream())
+        return g_out, d_Bx, d_Dx, d_Ex, d_Ce, None
+
+
+def gated_gcn_aggregate(Ax, Bx, Dx, Ex, Ce, plan):
+    """(out [N, C], e_out [E, C]) of the GatedGCN gate over the batch's plan; differentiable in all five operands and through
+    both outputs.  ValueError: a width outside the kernels' limits, operands of different widths, Ce rows != plan.num_edges."""
+    return _GatedGCN.apply(Ax, Bx, Dx, Ex, Ce, plan)
+
+
 class _Linear(Function):
     """torch.nn.Linear on the fp32 matrix cores (every Linear of run_graphcount.py:54-121,183-189)."""
 

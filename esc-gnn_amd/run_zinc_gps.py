@@ -21,7 +21,13 @@ or TypeDictNode+LapPE+RWSE with --posenc_LapPE 1 as well): one rwse.RWSETable pe
 RWSE: the posenc_RWSE_* defaults (20 steps, dim_pe 28, linear, BatchNorm on the raw statistics) are upstream GraphGPS's usual
 ZINC values, this project's choice.
 
-Out of scope: BiasedTransformer / attn_bias, Performer and BigBird, the other local GNN types, layer_norm, the other positional
+--gt_layer_type picks the two halves of every layer as the yaml's gt.layer_type does: the local GNN is GINE (the yaml's) or
+CustomGatedGCN (nn.GatedGCNLayer on the fused gate kernel, csrc/gatedgcn.hip; it also updates the edge attributes from layer to
+layer, so the ESC term of layer l is carried and re-gated), the global model Transformer or None (no attention branch).  A
+checkpoint of one layout is refused by another (load_state_dict's own error).
+
+Out of scope: BiasedTransformer / attn_bias, Performer and BigBird, the local GNN types GCN / GIN / GENConv / GAT / PNA, the
+EquivStableLapPE gate of GINE and GatedGCN, layer_norm, the other positional
 encodings (SignNet, EquivStableLapPE, HKdiagSE, ElstaticSE), graphgym's config system and wandb, a whole-step engine, and data
 parallelism (WORLD_SIZE > 1 is refused).
 
@@ -56,6 +62,8 @@ _FLAGS = [  # defaults: GraphGPS/configs/GPS/zinc-GPS.yaml (gt.*, train.batch_si
     ("--load_model", dict(default=None)),
     ("--eval", dict(default=0, type=int)),
     ("--synthetic_graphs", dict(type=int, default=12000, help="train+val+test molecules (10:1:1 like ZINC-12k)")),
+    ("--gt_layer_type", dict(default="GINE+Transformer", help="gt.layer_type, <local GNN>+<global model>: " + ", ".join(
+        ("GINE+Transformer", "CustomGatedGCN+Transformer", "GINE+None", "CustomGatedGCN+None")))),
     ("--posenc_LapPE", dict(type=int, default=0, help="1: node encoder TypeDictNode+LapPE (the reference yaml), 0: TypeDictNode")),
     ("--posenc_LapPE_max_freqs", dict(type=int, default=8, help="posenc_LapPE.eigen.max_freqs")),
     ("--posenc_LapPE_dim_pe", dict(type=int, default=8, help="posenc_LapPE.dim_pe (model DeepSet, layers 2)")),
@@ -71,8 +79,19 @@ _FLAGS = [  # defaults: GraphGPS/configs/GPS/zinc-GPS.yaml (gt.*, train.batch_si
 ]
 
 
+LAYER_TYPES = ("GINE+Transformer", "CustomGatedGCN+Transformer", "GINE+None", "CustomGatedGCN+None")
+
+
 def build_parser():
     return parser_from(_FLAGS, "ESC-GNN inside a GraphGPS transformer for ZINC graphs (MI355X hot path).")
+
+
+def layer_type_of(name):
+    """gt.layer_type -> (local_gnn_type, global_model_type), split at '+' as graphgps/network/gps_model.py:72-76 does"""
+    if name not in LAYER_TYPES:
+        raise SystemExit("run_zinc_gps: --gt_layer_type %r is not supported; accepted: %s" % (name, ", ".join(LAYER_TYPES)))
+    local_gnn_type, global_model_type = name.split("+")
+    return local_gnn_type, global_model_type
 
 
 def _load_splits(args):
@@ -90,6 +109,7 @@ def main(argv=None):
     from .store import DeviceGraphStore
 
     args = build_parser().parse_args(argv)
+    local_gnn_type, global_model_type = layer_type_of(args.gt_layer_type)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("run_zinc_gps: data parallelism is out of scope for the graph transformer (WORLD_SIZE must be 1)")
     ctx = Context()
@@ -137,9 +157,10 @@ def main(argv=None):
                      attn_dropout=args.attn_dropout, node_types=args.node_encoder_num_types, edge_types=args.edge_encoder_num_types,
                      lap_pe=bool(args.posenc_LapPE), dim_pe=args.posenc_LapPE_dim_pe, max_freqs=args.posenc_LapPE_max_freqs,
                      rwse=bool(args.posenc_RWSE), rwse_dim_pe=args.posenc_RWSE_dim_pe, rwse_steps=args.posenc_RWSE_ksteps,
-                     rwse_model=args.posenc_RWSE_model, rwse_layers=args.posenc_RWSE_layers, rwse_raw_norm=args.posenc_RWSE_raw_norm_type)
+                     rwse_model=args.posenc_RWSE_model, rwse_layers=args.posenc_RWSE_layers, rwse_raw_norm=args.posenc_RWSE_raw_norm_type,
+                     local_gnn_type=local_gnn_type, global_model_type=global_model_type)
     limit = ops.attention_max_nodes(args.dim_hidden // args.n_heads)
-    if max(widest) > limit:
+    if global_model_type != "None" and max(widest) > limit:
         raise SystemExit("run_zinc_gps: the largest graph has %d nodes, the attention kernels take at most %d at head_dim %d"
                          % (max(widest), limit, args.dim_hidden // args.n_heads))
     if args.load_model is not None:
