@@ -18,6 +18,7 @@
 // 1 KiB wave read.  x (N*C*4 = 2.4 MB @cfg1) stays L2-resident; e rows stream once.
 // Algorithmic bytes/launch: 2*E*C*4 + 2*N*C*4 + E*8 + (N+1)*4.
 #include "common.h"
+#include "sparse_plan.h"
 
 #include <cstdlib>
 
@@ -148,10 +149,8 @@ __global__ __launch_bounds__(256) void agg_fwd_wave(const float* __restrict__ x,
 // cold but 8.2 -> 9.3 with the operands the step has just produced: OFF (ESC_AGG_SPLIT_BWD=2 switches it on).  Non-temporal loads
 // of the once-streamed edge-term rows (so that they would not evict the gathered x rows from the L2) measured SLOWER
 // (cache-resident 6.4 -> 7.4 us, cold 6.5 -> 7.2) and were removed again.
-static int g_agg_split = getenv("ESC_AGG_SPLIT") ? atoi(getenv("ESC_AGG_SPLIT")) : 2;
-static int g_agg_split_bwd = getenv("ESC_AGG_SPLIT_BWD") ? atoi(getenv("ESC_AGG_SPLIT_BWD")) : 1;
-static inline int agg_split(int64_t C) { return (g_agg_split == 2 && C == 256) ? 2 : 1; }
-static inline int agg_split_bwd(int64_t C) { return (g_agg_split_bwd == 2 && C == 256) ? 2 : 1; }
+static const sparse::SparseKnobs g_knobs{getenv("ESC_AGG_SPLIT") ? atoi(getenv("ESC_AGG_SPLIT")) : 2,
+                                         getenv("ESC_AGG_SPLIT_BWD") ? atoi(getenv("ESC_AGG_SPLIT_BWD")) : 1, 0};
 
 // ---- narrow rows (C < 64, e.g. the 10-wide first layer): one thread per (node, channel) ----------
 __global__ __launch_bounds__(256) void agg_fwd_elem(const float* __restrict__ x, int64_t ld_x,
@@ -407,6 +406,55 @@ __global__ __launch_bounds__(1024) void reduce_sum_jobs_kernel(SumJobs t) {
   }
 }
 
+// ---- host side: validate, plan (sparse_plan.h), launch --------------------------------------------------------------------
+// the arguments of agg_fwd_wave / agg_bwd_wave as the entries hold them: NULL where a form has none
+struct AggFwd {
+  const float* x; int64_t ld_x; const float* e; int64_t ld_e;
+  const int32_t *in_ptr, *in_edge, *in_src;
+  const float* eps; int64_t N, C; float* out; int64_t ld_out;
+  const float *x_scale, *x_shift; unsigned long long* span; void* stream;
+};
+struct AggBwd {
+  const float* x; int64_t ld_x; const float* e; int64_t ld_e; const float* g; int64_t ld_g;
+  const int32_t *out_ptr, *out_edge, *out_dst;
+  const float* eps; int64_t N, C; float* d_e; int64_t ld_de; float* dx; int64_t ld_dx; int accumulate_dx; float* deps_part;
+  const float *x_scale, *x_shift, *bn_mean, *bn_invstd; float* partial; void* stream;
+};
+
+template <int VEC, bool AFF = false, bool SPAN = false>
+static void launch_agg_fwd(const AggFwd& a, const sparse::Plan& p) {
+  launch(ESC_K_AGG_FWD, agg_fwd_wave<VEC, AFF, SPAN>, dim3(p.grid[0].x), dim3(256), 0, (hipStream_t)a.stream, a.x, a.ld_x, a.e, a.ld_e, a.in_ptr,
+         a.in_edge, a.in_src, a.eps, (int)a.N, (int)a.C, a.out, a.ld_out, a.x_scale, a.x_shift, p.split, SPAN ? a.span : (unsigned long long*)nullptr);
+}
+template <int VEC, bool AFF = false, bool BST = false>
+static void launch_agg_bwd(const AggBwd& a, const sparse::Plan& p) {
+  launch(ESC_K_AGG_BWD, agg_bwd_wave<VEC, AFF, BST>, dim3(p.grid[0].x), dim3(256), p.lds, (hipStream_t)a.stream, a.x, a.ld_x, a.e, a.ld_e, a.g, a.ld_g,
+         a.out_ptr, a.out_edge, a.out_dst, a.eps, (int)a.N, (int)a.C, a.d_e, a.ld_de, a.dx, a.ld_dx, a.accumulate_dx, a.deps_part, a.x_scale,
+         a.x_shift, p.split, a.bn_mean, a.bn_invstd, reinterpret_cast<float2*>(a.partial));
+}
+
+static void agg_fwd(const AggFwd& a, bool affine) {
+  const sparse::Plan p = sparse::plan_agg_fwd(g_knobs, sparse::mat(a.x, a.ld_x), sparse::mat(a.e, a.ld_e), sparse::mat(a.out, a.ld_out), a.N, a.C, affine,
+                                              a.span != nullptr);
+  switch (p.family) {
+    case sparse::F_WAVE2: p.span ? launch_agg_fwd<2, true, true>(a, p) : p.affine ? launch_agg_fwd<2, true>(a, p) : launch_agg_fwd<2>(a, p); break;
+    case sparse::F_WAVE4: p.affine ? launch_agg_fwd<4, true>(a, p) : launch_agg_fwd<4>(a, p); break;
+    case sparse::F_WAVE1: launch_agg_fwd<1>(a, p); break;             // (the affine entry has refused such operands)
+    default:
+      launch(-1, agg_fwd_elem, dim3(p.grid[0].x), dim3(256), 0, (hipStream_t)a.stream, a.x, a.ld_x, a.e, a.ld_e, a.in_ptr, a.in_edge, a.in_src, a.eps,
+             (int)a.N, (int)a.C, a.out, a.ld_out);
+  }
+}
+static void agg_bwd(const AggBwd& a, bool affine, bool stats) {
+  const sparse::Plan p = sparse::plan_agg_bwd(g_knobs, sparse::mat(a.x, a.ld_x), sparse::mat(a.e, a.ld_e), sparse::mat(a.g, a.ld_g),
+                                              sparse::mat(a.d_e, a.ld_de), sparse::mat(a.dx, a.ld_dx), a.N, a.C, affine, stats);
+  switch (p.family) {
+    case sparse::F_WAVE2: p.affine ? launch_agg_bwd<2, true>(a, p) : launch_agg_bwd<2>(a, p); break;
+    case sparse::F_WAVE4: p.stats ? launch_agg_bwd<4, true, true>(a, p) : p.affine ? launch_agg_bwd<4, true>(a, p) : launch_agg_bwd<4>(a, p); break;
+    default: launch_agg_bwd<1>(a, p);                                 // (the affine entries have refused such operands)
+  }
+}
+
 }  // namespace esc
 
 extern "C" {
@@ -420,27 +468,13 @@ int esc_gine_aggregate_fwd(const float* x, int64_t ld_x, const float* e, int64_t
   ESC_REQUIRE(N < (1LL << 31) / 64, "esc_gine_aggregate_fwd: N too large");
   if (N == 0) return ESC_OK;
   // (the edge arrays may be NULL: a batch of isolated nodes has none, and a row without edges never reads them)
-  hipStream_t s = (hipStream_t)stream;
-  if (C >= 64) {
-    const bool vec = (C % 4 == 0) && (ld_x % 4 == 0) && (!e || ld_e % 4 == 0) && (ld_out % 4 == 0) &&
-                     esc::aligned16(x) && (!e || esc::aligned16(e)) && esc::aligned16(out);
-    const int64_t blocks = esc::cdiv(N, 4);
-    if (vec && esc::agg_split(C) == 2)
-      esc::launch(ESC_K_AGG_FWD, esc::agg_fwd_wave<2, false>, dim3((unsigned)esc::cdiv(2 * N, 4)), dim3(256), 0, s, x, ld_x, e, ld_e, in_ptr, in_edge, in_src, eps, (int)N, (int)C, out, ld_out, (const float*)nullptr, (const float*)nullptr, 2, (unsigned long long*)nullptr);
-    else if (vec)
-      esc::launch(ESC_K_AGG_FWD, esc::agg_fwd_wave<4, false>, dim3(blocks), dim3(256), 0, s, x, ld_x, e, ld_e, in_ptr, in_edge, in_src, eps, (int)N, (int)C, out, ld_out, (const float*)nullptr, (const float*)nullptr, 1, (unsigned long long*)nullptr);
-    else
-      esc::launch(ESC_K_AGG_FWD, esc::agg_fwd_wave<1, false>, dim3(blocks), dim3(256), 0, s, x, ld_x, e, ld_e, in_ptr, in_edge, in_src, eps, (int)N, (int)C, out, ld_out, (const float*)nullptr, (const float*)nullptr, 1, (unsigned long long*)nullptr);
-  } else {
-    const int64_t blocks = esc::cdiv(N * C, 256);
-    esc::launch(-1, esc::agg_fwd_elem, dim3(blocks), dim3(256), 0, s, x, ld_x, e, ld_e, in_ptr, in_edge, in_src, eps, (int)N, (int)C, out, ld_out);
-  }
+  esc::agg_fwd(esc::AggFwd{x, ld_x, e, ld_e, in_ptr, in_edge, in_src, eps, N, C, out, ld_out, nullptr, nullptr, nullptr, stream}, false);
   ESC_CHECK_LAUNCH("esc_gine_aggregate_fwd");
   return ESC_OK;
 }
 
 /* deps_part entries per node the backward writes for rows of C floats (1, or 2 when the row is split over two waves) */
-int esc_gine_aggregate_bwd_deps_slots(int64_t C) { return esc::agg_split_bwd(C); }
+int esc_gine_aggregate_bwd_deps_slots(int64_t C) { return esc::sparse::deps_slots(esc::g_knobs, C); }
 
 int esc_gine_aggregate_bwd(const float* x, int64_t ld_x, const float* e, int64_t ld_e,
                            const float* g, int64_t ld_g, const int32_t* out_ptr,
@@ -453,17 +487,8 @@ int esc_gine_aggregate_bwd(const float* x, int64_t ld_x, const float* e, int64_t
               "esc_gine_aggregate_bwd: bad sizes");
   ESC_REQUIRE(N < (1LL << 31) / 64, "esc_gine_aggregate_bwd: N too large");
   if (N == 0) return ESC_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const bool vec = (C % 4 == 0) && (ld_x % 4 == 0) && (!e || ld_e % 4 == 0) && (ld_g % 4 == 0) && (!d_e || ld_de % 4 == 0) &&
-                   (!dx || ld_dx % 4 == 0) && esc::aligned16(x) && (!e || esc::aligned16(e)) && esc::aligned16(g) &&
-                   (!d_e || esc::aligned16(d_e)) && (!dx || esc::aligned16(dx));
-  const int64_t blocks = esc::cdiv(N, 4);
-  if (vec && esc_gine_aggregate_bwd_deps_slots(C) == 2)
-    esc::launch(ESC_K_AGG_BWD, esc::agg_bwd_wave<2, false>, dim3((unsigned)esc::cdiv(2 * N, 4)), dim3(256), 0, s, x, ld_x, e, ld_e, g, ld_g, out_ptr, out_edge, out_dst, eps, (int)N, (int)C, d_e, ld_de, dx, ld_dx, accumulate_dx, deps_part, (const float*)nullptr, (const float*)nullptr, 2, (const float*)nullptr, (const float*)nullptr, (float2*)nullptr);
-  else if (vec)
-    esc::launch(ESC_K_AGG_BWD, esc::agg_bwd_wave<4, false>, dim3(blocks), dim3(256), 0, s, x, ld_x, e, ld_e, g, ld_g, out_ptr, out_edge, out_dst, eps, (int)N, (int)C, d_e, ld_de, dx, ld_dx, accumulate_dx, deps_part, (const float*)nullptr, (const float*)nullptr, 1, (const float*)nullptr, (const float*)nullptr, (float2*)nullptr);
-  else
-    esc::launch(ESC_K_AGG_BWD, esc::agg_bwd_wave<1, false>, dim3(blocks), dim3(256), 0, s, x, ld_x, e, ld_e, g, ld_g, out_ptr, out_edge, out_dst, eps, (int)N, (int)C, d_e, ld_de, dx, ld_dx, accumulate_dx, deps_part, (const float*)nullptr, (const float*)nullptr, 1, (const float*)nullptr, (const float*)nullptr, (float2*)nullptr);
+  esc::agg_bwd(esc::AggBwd{x, ld_x, e, ld_e, g, ld_g, out_ptr, out_edge, out_dst, eps, N, C, d_e, ld_de, dx, ld_dx, accumulate_dx, deps_part, nullptr,
+                           nullptr, nullptr, nullptr, nullptr, stream}, false, false);
   ESC_CHECK_LAUNCH("esc_gine_aggregate_bwd");
   return ESC_OK;
 }
@@ -480,15 +505,7 @@ int esc_gine_aggregate_fwd_affine(const float* x, int64_t ld_x, const float* x_s
   ESC_REQUIRE(esc::aligned16(x) && (!e || esc::aligned16(e)) && esc::aligned16(out), "esc_gine_aggregate_fwd_affine: pointers must be 16-byte aligned");
   if (N == 0) return ESC_OK;
   unsigned long long* span = esc::prof_span_next(ESC_K_AGG_FWD);      // non-NULL only for launches armed by esc_prof_span_arm
-  if (esc::agg_split(C) == 2 && span != nullptr)
-    esc::launch(ESC_K_AGG_FWD, esc::agg_fwd_wave<2, true, true>, dim3((unsigned)esc::cdiv(2 * N, 4)), dim3(256), 0, (hipStream_t)stream, x, ld_x, e, ld_e, in_ptr,
-                in_edge, in_src, eps, (int)N, (int)C, out, ld_out, x_scale, x_shift, 2, span);
-  else if (esc::agg_split(C) == 2)
-    esc::launch(ESC_K_AGG_FWD, esc::agg_fwd_wave<2, true>, dim3((unsigned)esc::cdiv(2 * N, 4)), dim3(256), 0, (hipStream_t)stream, x, ld_x, e, ld_e, in_ptr,
-                in_edge, in_src, eps, (int)N, (int)C, out, ld_out, x_scale, x_shift, 2, (unsigned long long*)nullptr);
-  else
-    esc::launch(ESC_K_AGG_FWD, esc::agg_fwd_wave<4, true>, dim3((unsigned)esc::cdiv(N, 4)), dim3(256), 0, (hipStream_t)stream, x, ld_x, e, ld_e, in_ptr,
-                in_edge, in_src, eps, (int)N, (int)C, out, ld_out, x_scale, x_shift, 1, (unsigned long long*)nullptr);
+  esc::agg_fwd(esc::AggFwd{x, ld_x, e, ld_e, in_ptr, in_edge, in_src, eps, N, C, out, ld_out, x_scale, x_shift, span, stream}, true);
   ESC_CHECK_LAUNCH("esc_gine_aggregate_fwd_affine");
   return ESC_OK;
 }
@@ -505,12 +522,8 @@ int esc_gine_aggregate_bwd_affine(const float* x, int64_t ld_x, const float* x_s
   ESC_REQUIRE(esc::aligned16(x) && (!e || esc::aligned16(e)) && esc::aligned16(g) && (!d_e || esc::aligned16(d_e)) && (!dx || esc::aligned16(dx)),
               "esc_gine_aggregate_bwd_affine: pointers must be 16-byte aligned");
   if (N == 0) return ESC_OK;
-  if (esc_gine_aggregate_bwd_deps_slots(C) == 2)
-    esc::launch(ESC_K_AGG_BWD, esc::agg_bwd_wave<2, true>, dim3((unsigned)esc::cdiv(2 * N, 4)), dim3(256), 0, (hipStream_t)stream, x, ld_x, e, ld_e, g, ld_g,
-                out_ptr, out_edge, out_dst, eps, (int)N, (int)C, d_e, ld_de, dx, ld_dx, accumulate_dx, deps_part, x_scale, x_shift, 2, (const float*)nullptr, (const float*)nullptr, (float2*)nullptr);
-  else
-    esc::launch(ESC_K_AGG_BWD, esc::agg_bwd_wave<4, true>, dim3((unsigned)esc::cdiv(N, 4)), dim3(256), 0, (hipStream_t)stream, x, ld_x, e, ld_e, g, ld_g,
-                out_ptr, out_edge, out_dst, eps, (int)N, (int)C, d_e, ld_de, dx, ld_dx, accumulate_dx, deps_part, x_scale, x_shift, 1, (const float*)nullptr, (const float*)nullptr, (float2*)nullptr);
+  esc::agg_bwd(esc::AggBwd{x, ld_x, e, ld_e, g, ld_g, out_ptr, out_edge, out_dst, eps, N, C, d_e, ld_de, dx, ld_dx, accumulate_dx, deps_part, x_scale,
+                           x_shift, nullptr, nullptr, nullptr, stream}, true, false);
   ESC_CHECK_LAUNCH("esc_gine_aggregate_bwd_affine");
   return ESC_OK;
 }
@@ -518,7 +531,7 @@ int esc_gine_aggregate_bwd_affine(const float* x, int64_t ld_x, const float* x_s
 /* esc_gine_aggregate_bwd_affine that also leaves the column sums of the BatchNorm backward in front of it: dx (required) is
  * then the complete gradient of x' = relu(BN(x)), and partial[slot][C] (float2, slot = 4 consecutive source rows,
  * esc_gine_aggregate_bwd_stats_slots(N) of them) holds (sum g, sum g*xhat) for esc_bn_bwd_coef_from_partials. */
-int64_t esc_gine_aggregate_bwd_stats_slots(int64_t N) { return esc::cdiv(N, 4); }
+int64_t esc_gine_aggregate_bwd_stats_slots(int64_t N) { return esc::sparse::stats_slots(N); }
 
 int esc_gine_aggregate_bwd_affine_stats(const float* x, int64_t ld_x, const float* x_scale, const float* x_shift, const float* bn_mean,
                                         const float* bn_invstd, const float* e, int64_t ld_e, const float* g, int64_t ld_g,
@@ -533,9 +546,8 @@ int esc_gine_aggregate_bwd_affine_stats(const float* x, int64_t ld_x, const floa
   ESC_REQUIRE(esc::aligned16(x) && (!e || esc::aligned16(e)) && esc::aligned16(g) && (!d_e || esc::aligned16(d_e)) && esc::aligned16(dx) && esc::aligned16(partial),
               "esc_gine_aggregate_bwd_affine_stats: pointers must be 16-byte aligned");
   if (N == 0) return ESC_OK;
-  esc::launch(ESC_K_AGG_BWD, esc::agg_bwd_wave<4, true, true>, dim3((unsigned)esc::cdiv(N, 4)), dim3(256), (size_t)4 * C * sizeof(float2), (hipStream_t)stream,
-              x, ld_x, e, ld_e, g, ld_g, out_ptr, out_edge, out_dst, eps, (int)N, (int)C, d_e, ld_de, dx, ld_dx, accumulate_dx, deps_part, x_scale,
-              x_shift, 1, bn_mean, bn_invstd, reinterpret_cast<float2*>(partial));
+  esc::agg_bwd(esc::AggBwd{x, ld_x, e, ld_e, g, ld_g, out_ptr, out_edge, out_dst, eps, N, C, d_e, ld_de, dx, ld_dx, accumulate_dx, deps_part, x_scale,
+                           x_shift, bn_mean, bn_invstd, partial, stream}, true, true);
   ESC_CHECK_LAUNCH("esc_gine_aggregate_bwd_affine_stats");
   return ESC_OK;
 }
@@ -544,9 +556,9 @@ int esc_segment_pool_fwd(const float* x, int64_t ld_x, const int32_t* seg_ptr, i
                          float* out, int64_t ld_out, void* stream) {
   ESC_REQUIRE(x && seg_ptr && out, "esc_segment_pool_fwd: null pointer");
   ESC_REQUIRE(G > 0 && C > 0 && ld_x >= C && ld_out >= C && G < (1LL << 31) / 64, "esc_segment_pool_fwd: bad sizes");
-  const bool vec = (C % 4 == 0) && (ld_x % 4 == 0) && (ld_out % 4 == 0) && esc::aligned16(x) && esc::aligned16(out);
-  if (vec) esc::launch(-1, esc::segment_pool_fwd<4>, dim3((unsigned)esc::cdiv(G, 4)), dim3(256), 0, (hipStream_t)stream, x, ld_x, seg_ptr, (int)G, (int)C, mean, out, ld_out);
-  else     esc::launch(-1, esc::segment_pool_fwd<1>, dim3((unsigned)esc::cdiv(G, 4)), dim3(256), 0, (hipStream_t)stream, x, ld_x, seg_ptr, (int)G, (int)C, mean, out, ld_out);
+  const esc::sparse::Plan p = esc::sparse::plan_segment_pool(esc::sparse::Op{x, ld_x}, esc::sparse::Op{out, ld_out}, G, C);
+  esc::launch(-1, p.family == esc::sparse::F_V4 ? esc::segment_pool_fwd<4> : esc::segment_pool_fwd<1>, dim3(p.grid[0].x), dim3(256), 0, (hipStream_t)stream,
+              x, ld_x, seg_ptr, (int)G, (int)C, mean, out, ld_out);
   ESC_CHECK_LAUNCH("esc_segment_pool_fwd");
   return ESC_OK;
 }
@@ -555,9 +567,9 @@ int esc_segment_pool_bwd(const float* g, int64_t ld_g, const int32_t* seg_ptr, i
                          float* dx, int64_t ld_dx, void* stream) {
   ESC_REQUIRE(g && seg_ptr && dx, "esc_segment_pool_bwd: null pointer");
   ESC_REQUIRE(G > 0 && C > 0 && ld_g >= C && ld_dx >= C && G < (1LL << 31) / 64, "esc_segment_pool_bwd: bad sizes");
-  const bool vec = (C % 4 == 0) && (ld_g % 4 == 0) && (ld_dx % 4 == 0) && esc::aligned16(g) && esc::aligned16(dx);
-  if (vec) esc::launch(-1, esc::segment_pool_bwd<4>, dim3((unsigned)esc::cdiv(G, 4)), dim3(256), 0, (hipStream_t)stream, g, ld_g, seg_ptr, (int)G, (int)C, mean, dx, ld_dx);
-  else     esc::launch(-1, esc::segment_pool_bwd<1>, dim3((unsigned)esc::cdiv(G, 4)), dim3(256), 0, (hipStream_t)stream, g, ld_g, seg_ptr, (int)G, (int)C, mean, dx, ld_dx);
+  const esc::sparse::Plan p = esc::sparse::plan_segment_pool(esc::sparse::Op{g, ld_g}, esc::sparse::Op{dx, ld_dx}, G, C);
+  esc::launch(-1, p.family == esc::sparse::F_V4 ? esc::segment_pool_bwd<4> : esc::segment_pool_bwd<1>, dim3(p.grid[0].x), dim3(256), 0, (hipStream_t)stream,
+              g, ld_g, seg_ptr, (int)G, (int)C, mean, dx, ld_dx);
   ESC_CHECK_LAUNCH("esc_segment_pool_bwd");
   return ESC_OK;
 }

@@ -11,6 +11,7 @@
 // row (an edge): the entry list of the row is wave-uniform, so indices/counts travel through the
 // scalar unit and every table row is one coalesced 16 B/lane read (H=256 => exactly 1 KiB/wave).
 #include "common.h"
+#include "sparse_plan.h"
 
 #include <cstdlib>
 
@@ -124,7 +125,7 @@ __global__ __launch_bounds__(256) void bag_fwd_kernel(const float* __restrict__ 
 constexpr int BAG_EB = 128;          // edges per workgroup (32 per wave, 4 at a time)
 constexpr int BAG_CAP = 192;         // table rows a workgroup can stage: 192 x 256 B = 48 KB
 constexpr int BAG_ENT = 6144;        // entries a workgroup can keep in LDS (4 bytes each: slot | count << 16)
-constexpr int BAG_MAXROWS = 4096;    // table height the row map serves
+static_assert(BAG_EB == sparse::BAG_EB && BAG_CAP == sparse::BAG_CAP && BAG_ENT == sparse::BAG_ENT, "sparse_plan.h sizes the grid and the LDS by these");
 
 template <bool ACC, bool STATS>
 __global__ __launch_bounds__(256) void bag_fwd_tiled(const float* __restrict__ table, int rows, int H,
@@ -273,6 +274,7 @@ __global__ __launch_bounds__(256) void bag_fwd_tiled(const float* __restrict__ t
 // Pass 2: one wave per column sums its partials in chunk order (=> bitwise reproducible) and
 // zero-fills columns without entries.
 constexpr int BAG_CH = 64;
+static_assert(BAG_CH == sparse::BAG_CH, "sparse_plan.h counts the chunks");
 
 template <int VEC>
 __device__ __forceinline__ void bag_chunk(int chunk, const float* __restrict__ dz, int64_t ld_dz, int H,
@@ -461,6 +463,32 @@ __global__ __launch_bounds__(256) void bag_bwd_pass2(int H, const int* __restric
   }
 }
 
+// ---- host side: validate, plan (sparse_plan.h), launch --------------------------------------------------------------------
+struct BagFwd {
+  const float* table; int64_t rows, H; const int32_t *row_ptr, *idx, *val; int64_t E; float* out; int64_t ld_out; float* stats; void* stream;
+};
+// the wave-per-row kernel, adding onto `out` or not (esc_bag_fwd / esc_bag_fwd_acc: rows = 0, they never tile)
+template <bool ACC>
+static void bag_fwd_rows(const BagFwd& a) {
+  const sparse::Plan p = sparse::plan_bag_fwd(sparse::SparseKnobs{}, a.table, 0, a.H, sparse::Op{a.out, a.ld_out}, a.E, ACC, nullptr, false);
+  launch(ESC_K_BAG_FWD, p.family == sparse::F_ROW4 ? bag_fwd_kernel<4, ACC> : bag_fwd_kernel<1, ACC>, dim3(p.grid[0].x), dim3(256), 0, (hipStream_t)a.stream,
+         a.table, (int)a.H, a.row_ptr, a.idx, a.val, (int)a.E, a.out, a.ld_out);
+}
+template <bool ACC, bool STATS>
+static void bag_fwd_tiled_launch(const BagFwd& a, const sparse::Plan& p) {
+  launch(ESC_K_BAG_FWD, bag_fwd_tiled<ACC, STATS>, dim3(p.grid[0].x, p.grid[0].y), dim3(256), p.lds, (hipStream_t)a.stream, a.table, (int)a.rows, (int)a.H,
+         a.row_ptr, a.idx, a.val, (int)a.E, a.out, a.ld_out, reinterpret_cast<float2*>(a.stats));
+}
+// ESC_BAG_TILED is read once, by the first call that asks for the tiled forward.  Measured on a config-1 batch
+// (profiles/r03_kernel_roofline.txt): 70.9 us against 22.7 us of the wave-per-row kernel — 1 904 waves walking 32 edges each through
+// dependent entry-list loads cannot hide what 15 200 one-row waves hide by sheer numbers, and every workgroup pays the row map.
+// OFF by default (ESC_BAG_TILED=1 enables it for experiments); what it would take to win — the workgroup's entry lists staged in
+// LDS too, batched reads — is in DESIGN.md.
+static const sparse::SparseKnobs& bag_knobs() {
+  static const sparse::SparseKnobs k{2, 1, getenv("ESC_BAG_TILED") ? atoi(getenv("ESC_BAG_TILED")) : 0};
+  return k;
+}
+
 }  // namespace esc
 
 extern "C" {
@@ -471,13 +499,7 @@ int esc_bag_fwd(const float* table, int64_t H, const int32_t* row_ptr, const int
   ESC_REQUIRE(H > 0 && E >= 0 && ld_out >= H, "esc_bag_fwd: bad sizes H=%ld E=%ld ld=%ld", (long)H, (long)E, (long)ld_out);
   ESC_REQUIRE(E < (1LL << 31) / 64, "esc_bag_fwd: E too large");
   if (E == 0) return ESC_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const bool vec = (H % 4 == 0) && (ld_out % 4 == 0) && esc::aligned16(table) && esc::aligned16(out);
-  const int64_t blocks = esc::cdiv(E, 4);
-  if (vec)
-    esc::launch(ESC_K_BAG_FWD, esc::bag_fwd_kernel<4>, dim3(blocks), dim3(256), 0, s, table, (int)H, row_ptr, idx32, val32, (int)E, out, ld_out);
-  else
-    esc::launch(ESC_K_BAG_FWD, esc::bag_fwd_kernel<1>, dim3(blocks), dim3(256), 0, s, table, (int)H, row_ptr, idx32, val32, (int)E, out, ld_out);
+  esc::bag_fwd_rows<false>(esc::BagFwd{table, 0, H, row_ptr, idx32, val32, E, out, ld_out, nullptr, stream});
   ESC_CHECK_LAUNCH("esc_bag_fwd");
   return ESC_OK;
 }
@@ -487,48 +509,29 @@ int esc_bag_fwd_acc(const float* table, int64_t H, const int32_t* row_ptr, const
   ESC_REQUIRE(table && row_ptr && out && idx32 && val32, "esc_bag_fwd_acc: null pointer");
   ESC_REQUIRE(H > 0 && E >= 0 && ld_out >= H && E < (1LL << 31) / 64, "esc_bag_fwd_acc: bad sizes H=%ld E=%ld ld=%ld", (long)H, (long)E, (long)ld_out);
   if (E == 0) return ESC_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const bool vec = (H % 4 == 0) && (ld_out % 4 == 0) && esc::aligned16(table) && esc::aligned16(out);
-  const int64_t blocks = esc::cdiv(E, 4);
-  if (vec)
-    esc::launch(ESC_K_BAG_FWD, esc::bag_fwd_kernel<4, true>, dim3(blocks), dim3(256), 0, s, table, (int)H, row_ptr, idx32, val32, (int)E, out, ld_out);
-  else
-    esc::launch(ESC_K_BAG_FWD, esc::bag_fwd_kernel<1, true>, dim3(blocks), dim3(256), 0, s, table, (int)H, row_ptr, idx32, val32, (int)E, out, ld_out);
+  esc::bag_fwd_rows<true>(esc::BagFwd{table, 0, H, row_ptr, idx32, val32, E, out, ld_out, nullptr, stream});
   ESC_CHECK_LAUNCH("esc_bag_fwd_acc");
   return ESC_OK;
 }
 
-
-/* the LDS-staged forward: needs the table height (rows), H % 4 == 0, 16-byte aligned table / out, ld_out % 4 == 0 */
-static bool bag_tiled_ok(const float* table, int64_t rows, int64_t H, const float* out, int64_t ld_out, int64_t E) {
-  // Measured on a config-1 batch (profiles/r03_kernel_roofline.txt): 70.9 us against 22.7 us of the wave-per-row kernel — 1 904
-  // waves walking 32 edges each through dependent entry-list loads cannot hide what 15 200 one-row waves hide by sheer
-  // numbers, and every workgroup pays the row map.  OFF by default (ESC_BAG_TILED=1 enables it for experiments); what it
-  // would take to win — the workgroup's entry lists staged in LDS too, batched reads — is in DESIGN.md.
-  static const int on = getenv("ESC_BAG_TILED") ? atoi(getenv("ESC_BAG_TILED")) : 0;
-  return on && rows > 0 && rows <= esc::BAG_MAXROWS && H % 4 == 0 && ld_out % 4 == 0 && esc::aligned16(table) && esc::aligned16(out) &&
-         E >= 4 * esc::BAG_EB && esc::cdiv(H, 64) <= 65535;
-}
-static size_t bag_tiled_lds(int64_t rows) { return (size_t)esc::BAG_CAP * 256 + (size_t)esc::BAG_ENT * 4 + (size_t)((rows + 7) & ~7) * 2 + (size_t)esc::BAG_CAP * 2 + 64; }
-
+/* the LDS-staged forward where sparse::bag_tiled_ok serves the shape (the table height given, float4 access, ESC_BAG_TILED=1), else
+ * esc_bag_fwd / esc_bag_fwd_acc */
 int esc_bag_fwd_rows(const float* table, int64_t rows, int64_t H, const int32_t* row_ptr, const int32_t* idx32, const int32_t* val32,
                      int64_t E, float* out, int64_t ld_out, int accumulate, float* stats, void* stream) {
   ESC_REQUIRE(table && row_ptr && out && idx32 && val32, "esc_bag_fwd_rows: null pointer");
   ESC_REQUIRE(H > 0 && E >= 0 && ld_out >= H && rows > 0 && E < (1LL << 31) / 64, "esc_bag_fwd_rows: bad sizes H=%ld E=%ld ld=%ld rows=%ld", (long)H, (long)E, (long)ld_out, (long)rows);
-  ESC_REQUIRE(stats == nullptr || (bag_tiled_ok(table, rows, H, out, ld_out, E) && !accumulate && esc::aligned16(stats)),
+  const esc::sparse::Plan p = esc::sparse::plan_bag_fwd(esc::bag_knobs(), table, rows, H, esc::sparse::Op{out, ld_out}, E, accumulate != 0, stats, stats != nullptr);
+  ESC_REQUIRE(!p.refused,
               "esc_bag_fwd_rows: the statistics epilogue needs the tiled kernel (esc_bag_fwd_stats_block_rows() != 0) and no accumulation");
   if (E == 0) return ESC_OK;
-  if (!bag_tiled_ok(table, rows, H, out, ld_out, E))
+  if (p.family == esc::sparse::F_ROW4 || p.family == esc::sparse::F_ROW1)
     return accumulate ? esc_bag_fwd_acc(table, H, row_ptr, idx32, val32, E, out, ld_out, stream)
                       : esc_bag_fwd(table, H, row_ptr, idx32, val32, E, out, ld_out, stream);
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((unsigned)esc::cdiv(H, 64), (unsigned)esc::cdiv(E, esc::BAG_EB));
-  const size_t lds = bag_tiled_lds(rows);
-  float2* st = reinterpret_cast<float2*>(stats);
+  const esc::BagFwd a{table, rows, H, row_ptr, idx32, val32, E, out, ld_out, stats, stream};
   {      // more than the default 64 KB of dynamic LDS: raise the limit once per kernel
     static bool raised = false;
     if (!raised) {
-      const int want = (int)bag_tiled_lds(esc::BAG_MAXROWS);
+      const int want = (int)esc::sparse::bag_tiled_lds(esc::sparse::BAG_MAXROWS);
       bool ok = hipFuncSetAttribute((const void*)esc::bag_fwd_tiled<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, want) == hipSuccess;
       ok = ok && hipFuncSetAttribute((const void*)esc::bag_fwd_tiled<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, want) == hipSuccess;
       ok = ok && hipFuncSetAttribute((const void*)esc::bag_fwd_tiled<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, want) == hipSuccess;
@@ -536,30 +539,27 @@ int esc_bag_fwd_rows(const float* table, int64_t rows, int64_t H, const int32_t*
       raised = true;
     }
   }
-  if (accumulate)      esc::launch(ESC_K_BAG_FWD, esc::bag_fwd_tiled<true, false>, grid, dim3(256), lds, s, table, (int)rows, (int)H, row_ptr, idx32, val32, (int)E, out, ld_out, st);
-  else if (stats)      esc::launch(ESC_K_BAG_FWD, esc::bag_fwd_tiled<false, true>, grid, dim3(256), lds, s, table, (int)rows, (int)H, row_ptr, idx32, val32, (int)E, out, ld_out, st);
-  else                 esc::launch(ESC_K_BAG_FWD, esc::bag_fwd_tiled<false, false>, grid, dim3(256), lds, s, table, (int)rows, (int)H, row_ptr, idx32, val32, (int)E, out, ld_out, st);
+  switch (p.family) {
+    case esc::sparse::F_TILED_ACC: esc::bag_fwd_tiled_launch<true, false>(a, p); break;
+    case esc::sparse::F_TILED_STATS: esc::bag_fwd_tiled_launch<false, true>(a, p); break;
+    default: esc::bag_fwd_tiled_launch<false, false>(a, p);
+  }
   ESC_CHECK_LAUNCH("esc_bag_fwd_rows");
   return ESC_OK;
 }
 
 /* rows per BatchNorm partial the statistics epilogue of esc_bag_fwd_rows leaves (0: this shape is not served by it) */
 int64_t esc_bag_fwd_stats_block_rows(const float* table, int64_t rows, int64_t H, const float* out, int64_t ld_out, int64_t E) {
-  return bag_tiled_ok(table, rows, H, out, ld_out, E) ? esc::BAG_EB : 0;
+  return esc::sparse::bag_stats_block_rows(esc::bag_knobs(), table, rows, H, esc::sparse::Op{out, ld_out}, E);
 }
 
 int64_t esc_bag_bwd_scratch(int64_t Z, int64_t H) {      // chunk partials + (chunk order, bucket starts) of the local schedule
-  return 2 * esc::cdiv(Z, esc::BAG_CH) * H + 8 * esc::cdiv(Z, esc::BAG_CH) + 64;
+  return esc::sparse::scratch_floats(Z, H);
 }
 
 static int bag_bwd_impl(const float* dz, int64_t ld_dz, int64_t H, const int32_t* col_ptr,
                         const int32_t* c_row, const int32_t* c_val, const int32_t* c_col, int64_t Z,
                         int64_t n_cols, int64_t rows, int classified, float* dtable, float* partials, void* stream);
-
-static inline bool bag_local_schedule(int64_t Z, int64_t H, int64_t rows) {
-  // rows given, the gradient matrix larger than one XCD's L2, enough chunks to spread over 8 groups
-  return rows > 0 && rows * H * (int64_t)sizeof(float) > (4 << 20) && esc::cdiv(Z, esc::BAG_CH) >= 64;
-}
 
 }  // extern "C"
 
@@ -570,18 +570,17 @@ int esc::bag_bwd_classify_counted(const int32_t* c_row, int64_t Z, int64_t H, in
   ESC_REQUIRE(Z == 0 || (c_row && partials), "esc_bag_bwd_classify: null pointer");
   ESC_REQUIRE(H > 0 && Z >= 0 && rows >= 0 && rows < (1LL << 28) && Z < (1LL << 31) - 64, "esc_bag_bwd_classify: bad sizes");
   ESC_REQUIRE(cnt.n >= 0 && cnt.n <= ESC_MAX_BN_COUNTERS, "esc_bag_bwd_classify: bad counter list");
-  const bool sched = bag_local_schedule(Z, H, rows);
-  if (!sched && cnt.n == 0) return ESC_OK;                   // esc_bag_bwd_table_rows will not use a schedule either
+  const sparse::Plan p = sparse::plan_bag_classify(Z, H, rows, cnt.n);
+  if (p.family == sparse::F_NONE) return ESC_OK;             // esc_bag_bwd_table_rows will not use a schedule either
   hipStream_t s = (hipStream_t)stream;
-  const int64_t chunks = sched ? esc::cdiv(Z, esc::BAG_CH) : 0;
-  int* order = sched ? reinterpret_cast<int*>(partials + 2 * chunks * H) : nullptr;       // [8][chunks]
-  int* bucket_cnt = sched ? order + 8 * chunks : nullptr;                                 // [8]
-  if (sched && hipMemsetAsync(bucket_cnt, 0, 8 * sizeof(int), s) != hipSuccess) {
+  const bool sched = p.classify;
+  int* order = sched ? reinterpret_cast<int*>(partials + p.order_offset) : nullptr;       // [8][chunks]
+  int* bucket_cnt = sched ? reinterpret_cast<int*>(partials + p.bucket_offset) : nullptr; // [8]
+  if (sched && hipMemsetAsync(bucket_cnt, 0, sparse::LOCAL_BUCKETS * sizeof(int), s) != hipSuccess) {
     esc::set_error("esc_bag_bwd_classify: memset failed");
     return ESC_ELAUNCH;
   }
-  const int64_t blocks = chunks > 0 ? esc::cdiv(chunks, 256) : 1;
-  esc::launch(ESC_K_BAG_BWD, esc::bag_bwd_classify, dim3((unsigned)blocks), dim3(256), 0, s, c_row, (int)Z, (int)rows, (int)chunks, order, bucket_cnt, cnt);
+  esc::launch(ESC_K_BAG_BWD, esc::bag_bwd_classify, dim3(p.grid[0].x), dim3(256), 0, s, c_row, (int)Z, (int)rows, (int)p.chunks, order, bucket_cnt, cnt);
   ESC_CHECK_LAUNCH("esc_bag_bwd_classify");
   return ESC_OK;
 }
@@ -614,35 +613,31 @@ static int bag_bwd_impl(const float* dz, int64_t ld_dz, int64_t H, const int32_t
   ESC_REQUIRE(H > 0 && Z >= 0 && n_cols > 0 && ld_dz >= H, "esc_bag_bwd_table: bad sizes");
   ESC_REQUIRE(Z < (1LL << 31) - 64, "esc_bag_bwd_table: Z too large");
   hipStream_t s = (hipStream_t)stream;
-  const bool vec = (H % 4 == 0) && (ld_dz % 4 == 0) && esc::aligned16(dz) && esc::aligned16(dtable) && esc::aligned16(partials);
-  if (Z > 0) {
-    const int64_t chunks = esc::cdiv(Z, esc::BAG_CH);
-    const int64_t blocks = esc::cdiv(chunks, 4);
-    if (bag_local_schedule(Z, H, rows)) {          // chunks bucketed by row eighth (see bag_bwd_classify)
-      if (!classified) {
+  const esc::sparse::Plan p = esc::sparse::plan_bag_bwd(esc::sparse::Op{dz, ld_dz}, dtable, partials, Z, H, n_cols, rows, classified != 0);
+  const esc::sparse::Grid& pass1 = p.grid[p.classify ? 1 : 0];
+  switch (p.family) {
+    case esc::sparse::F_LOCAL: {                   // chunks bucketed by row eighth (see bag_bwd_classify)
+      if (p.classify) {
         const int rc = esc_bag_bwd_classify(c_row, Z, H, rows, partials, stream);
         if (rc != ESC_OK) return rc;               // the message is already set
       }
-      int* order = reinterpret_cast<int*>(partials + 2 * chunks * H);
-      int* bucket_cnt = order + 8 * chunks;
-      const unsigned per_group = (unsigned)(esc::cdiv(esc::cdiv(chunks, 8) * 5 / 4 + 4, 4));   // 25 % slack; the kernel strides beyond
-      if (vec)
-        esc::launch(ESC_K_BAG_BWD, esc::bag_bwd_pass1_local<4>, dim3(per_group * 8), dim3(256), 0, s, dz, ld_dz, (int)H, col_ptr, c_row, c_val, c_col, (int)Z, dtable, partials, (const int*)order, (const int*)bucket_cnt, (int)chunks);
-      else
-        esc::launch(ESC_K_BAG_BWD, esc::bag_bwd_pass1_local<1>, dim3(per_group * 8), dim3(256), 0, s, dz, ld_dz, (int)H, col_ptr, c_row, c_val, c_col, (int)Z, dtable, partials, (const int*)order, (const int*)bucket_cnt, (int)chunks);
+      const int* order = reinterpret_cast<const int*>(partials + p.order_offset);
+      const int* bucket_cnt = reinterpret_cast<const int*>(partials + p.bucket_offset);
+      esc::launch(ESC_K_BAG_BWD, p.vec ? esc::bag_bwd_pass1_local<4> : esc::bag_bwd_pass1_local<1>, dim3(pass1.x), dim3(256), 0, s, dz, ld_dz, (int)H, col_ptr,
+                  c_row, c_val, c_col, (int)Z, dtable, partials, order, bucket_cnt, (int)p.chunks);
       ESC_CHECK_LAUNCH("esc_bag_bwd_table.pass1_local");
-    } else if (vec)
-      esc::launch(ESC_K_BAG_BWD, esc::bag_bwd_pass1<4>, dim3(blocks), dim3(256), 0, s, dz, ld_dz, (int)H, col_ptr, c_row, c_val, c_col, (int)Z, dtable, partials);
-    else
-      esc::launch(ESC_K_BAG_BWD, esc::bag_bwd_pass1<1>, dim3(blocks), dim3(256), 0, s, dz, ld_dz, (int)H, col_ptr, c_row, c_val, c_col, (int)Z, dtable, partials);
-    ESC_CHECK_LAUNCH("esc_bag_bwd_table.pass1");
+      break;
+    }
+    case esc::sparse::F_FLAT:
+      esc::launch(ESC_K_BAG_BWD, p.vec ? esc::bag_bwd_pass1<4> : esc::bag_bwd_pass1<1>, dim3(pass1.x), dim3(256), 0, s, dz, ld_dz, (int)H, col_ptr, c_row, c_val,
+                  c_col, (int)Z, dtable, partials);
+      ESC_CHECK_LAUNCH("esc_bag_bwd_table.pass1");
+      break;
+    default: break;                                // Z == 0: pass 2 zero-fills every column
   }
-  const size_t lds2 = (size_t)3 * H * sizeof(float);
-  ESC_REQUIRE(lds2 <= 64 * 1024, "esc_bag_bwd_table: H too large");
-  if (vec)
-    esc::launch(ESC_K_BAG_BWD, esc::bag_bwd_pass2<4>, dim3((unsigned)n_cols), dim3(256), lds2, s, (int)H, col_ptr, (int)n_cols, dtable, partials);
-  else
-    esc::launch(ESC_K_BAG_BWD, esc::bag_bwd_pass2<1>, dim3((unsigned)n_cols), dim3(256), lds2, s, (int)H, col_ptr, (int)n_cols, dtable, partials);
+  ESC_REQUIRE(!p.refused, "esc_bag_bwd_table: H too large");
+  esc::launch(ESC_K_BAG_BWD, p.vec ? esc::bag_bwd_pass2<4> : esc::bag_bwd_pass2<1>, dim3(p.grid[p.launches - 1].x), dim3(256), p.lds, s, (int)H, col_ptr, (int)n_cols,
+              dtable, partials);
   ESC_CHECK_LAUNCH("esc_bag_bwd_table.pass2");
   return ESC_OK;
 }

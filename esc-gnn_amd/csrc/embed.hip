@@ -3,6 +3,7 @@
 // here the table has few rows, so the gradient is one workgroup per TABLE ROW scanning the index vector — no sort,
 // no atomics, a fixed summation order (bitwise reproducible).
 #include "common.h"
+#include "sparse_plan.h"
 
 namespace esc {
 
@@ -272,20 +273,15 @@ int esc_embed_fwd(const float* table, int64_t rows, int64_t C, const int64_t* id
 int esc_embed_bwd(const float* g, int64_t ld_g, const int64_t* idx, int64_t M, int64_t rows, int64_t C, float* dtable,
                   void* stream) {
   ESC_REQUIRE(dtable && ((g && idx) || M == 0), "esc_embed_bwd: null pointer");
-  ESC_REQUIRE(rows > 0 && rows <= 4096 && C > 0 && ld_g >= C && M >= 0, "esc_embed_bwd: table of %ld rows x %ld is not a small one", (long)rows, (long)C);
-  if (rows == 1) {
-    esc::launch(ESC_K_BAG_BWD, embed_bwd_one_row_kernel, dim3((unsigned)cdiv(C, 64)), dim3(256), 0, (hipStream_t)stream, g, ld_g, M, C, dtable);
-    ESC_CHECK_LAUNCH("esc_embed_bwd");
-    return ESC_OK;
+  ESC_REQUIRE(rows > 0 && rows <= sparse::EMBED_MAX_ROWS && C > 0 && ld_g >= C && M >= 0, "esc_embed_bwd: table of %ld rows x %ld is not a small one", (long)rows, (long)C);
+  const sparse::Plan p = sparse::plan_embed_bwd(sparse::Op{g, ld_g}, dtable, rows, C);
+  const dim3 grid(p.grid[0].x);
+  hipStream_t s = (hipStream_t)stream;
+  switch (p.family) {
+    case sparse::F_ONE_ROW: esc::launch(ESC_K_BAG_BWD, embed_bwd_one_row_kernel, grid, dim3(256), 0, s, g, ld_g, M, C, dtable); break;
+    case sparse::F_V4: esc::launch(ESC_K_BAG_BWD, embed_bwd_kernel_v4, grid, dim3(256), 0, s, g, ld_g, idx, M, (int)C, dtable); break;
+    default: esc::launch(ESC_K_BAG_BWD, embed_bwd_kernel, grid, dim3(256), 0, s, g, ld_g, idx, M, C, p.cw, dtable);
   }
-  if (C % 4 == 0 && C <= 256 && ld_g % 4 == 0 && aligned16(g) && aligned16(dtable)) {
-    esc::launch(ESC_K_BAG_BWD, embed_bwd_kernel_v4, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, g, ld_g, idx, M, (int)C, dtable);
-    ESC_CHECK_LAUNCH("esc_embed_bwd");
-    return ESC_OK;
-  }
-  int CW = 1;
-  while (CW < C && CW < 256) CW <<= 1;
-  esc::launch(ESC_K_BAG_BWD, embed_bwd_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, g, ld_g, idx, M, C, CW, dtable);
   ESC_CHECK_LAUNCH("esc_embed_bwd");
   return ESC_OK;
 }

@@ -18,6 +18,7 @@
 // scheme: a short tail is padded by clamping the slot to the node's last edge and masking its contribution).
 // No atomics; every output element is written once.  Built with -ffp-contract=off (Makefile).
 #include "common.h"
+#include "sparse_plan.h"
 #include "../../include/escgnn_gatedgcn.h"
 
 namespace esc {
@@ -181,8 +182,6 @@ __global__ __launch_bounds__(256) void gated_bwd_src_kernel(const float* __restr
   }
 }
 
-static inline int gg_group(int64_t C) { return C <= 64 ? 16 : C <= 128 ? 32 : 64; }
-static inline dim3 gg_grid(int64_t N, int lg) { return dim3((unsigned)cdiv(N * lg, 256)); }
 
 // what both entries check before anything is launched; 0 or an error code with the message set
 static int gg_limits(const char* fn, int64_t N, int64_t E, int64_t C, const int64_t* ld, const char* const* ld_name, int n_ld,
@@ -219,11 +218,15 @@ int esc_gated_gcn_fwd(const float* Ax, int64_t ld_ax, const float* Bx, int64_t l
   ESC_REQUIRE(Ax && Bx && Dx && Ex && in_ptr && out && den, "%s: null pointer", fn);
   ESC_REQUIRE(!edges || (Ce && in_edge && in_src && e_out), "%s: null edge pointer with E=%ld", fn, (long)E);
   hipStream_t s = (hipStream_t)stream;
-  const int lg = gg_group(C);
-#define GG_FWD(LG) esc::launch(-1, gated_fwd_kernel<LG>, gg_grid(N, LG), dim3(256), 0, s, Ax, ld_ax, Bx, ld_bx, Dx, ld_dx, Ex, ld_ex, Ce, \
-                               ld_ce, in_ptr, in_edge, in_src, (int)N, (int)C, out, ld_out, e_out, ld_eo, den)
-  if (lg == 16) GG_FWD(16); else if (lg == 32) GG_FWD(32); else GG_FWD(64);
-#undef GG_FWD
+  const sparse::Plan p = sparse::plan_gated(N, C, false);
+  auto* fwd = gated_fwd_kernel<64>;
+  switch (p.family) {
+    case sparse::F_GROUP16: fwd = gated_fwd_kernel<16>; break;
+    case sparse::F_GROUP32: fwd = gated_fwd_kernel<32>; break;
+    default: break;
+  }
+  esc::launch(-1, fwd, dim3(p.grid[0].x), dim3(256), 0, s, Ax, ld_ax, Bx, ld_bx, Dx, ld_dx, Ex, ld_ex, Ce, ld_ce, in_ptr, in_edge, in_src, (int)N, (int)C, out,
+              ld_out, e_out, ld_eo, den);
   ESC_CHECK_LAUNCH(fn);
   return ESC_OK;
 }
@@ -243,16 +246,18 @@ int esc_gated_gcn_bwd(const float* g_out, int64_t ld_go, const float* g_e, int64
   ESC_REQUIRE(g_out && den && out && Ax && Bx && in_ptr && out_ptr && d_Dx && d_Ex && d_Bx, "%s: null pointer", fn);
   ESC_REQUIRE(!edges || (e_out && in_edge && in_src && out_edge && out_dst && d_Ce), "%s: null edge pointer with E=%ld", fn, (long)E);
   hipStream_t s = (hipStream_t)stream;
-  const int lg = gg_group(C);
-#define GG_BWD(LG)                                                                                                                   \
-  do {                                                                                                                               \
-    esc::launch(-1, gated_bwd_dst_kernel<LG>, gg_grid(N, LG), dim3(256), 0, s, g_out, ld_go, g_e, ld_ge, e_out, ld_eo, den, out, ld_out, Ax, \
-                ld_ax, Bx, ld_bx, in_ptr, in_edge, in_src, (int)N, (int)C, d_Ce, ld_dce, d_Dx, ld_ddx);                              \
-    esc::launch(-1, gated_bwd_src_kernel<LG>, gg_grid(N, LG), dim3(256), 0, s, g_out, ld_go, e_out, ld_eo, den, (const float*)d_Ce, ld_dce,  \
-                out_ptr, out_edge, out_dst, (int)N, (int)C, d_Ex, ld_dex, d_Bx, ld_dbx);                                             \
-  } while (0)
-  if (lg == 16) GG_BWD(16); else if (lg == 32) GG_BWD(32); else GG_BWD(64);
-#undef GG_BWD
+  const sparse::Plan p = sparse::plan_gated(N, C, true);
+  auto* dst = gated_bwd_dst_kernel<64>;
+  auto* src = gated_bwd_src_kernel<64>;
+  switch (p.family) {
+    case sparse::F_GROUP16: dst = gated_bwd_dst_kernel<16>; src = gated_bwd_src_kernel<16>; break;
+    case sparse::F_GROUP32: dst = gated_bwd_dst_kernel<32>; src = gated_bwd_src_kernel<32>; break;
+    default: break;
+  }
+  esc::launch(-1, dst, dim3(p.grid[0].x), dim3(256), 0, s, g_out, ld_go, g_e, ld_ge, e_out, ld_eo, den, out, ld_out, Ax, ld_ax, Bx, ld_bx, in_ptr, in_edge,
+              in_src, (int)N, (int)C, d_Ce, ld_dce, d_Dx, ld_ddx);
+  esc::launch(-1, src, dim3(p.grid[1].x), dim3(256), 0, s, g_out, ld_go, e_out, ld_eo, den, (const float*)d_Ce, ld_dce, out_ptr, out_edge, out_dst, (int)N,
+              (int)C, d_Ex, ld_dex, d_Bx, ld_dbx);
   ESC_CHECK_LAUNCH(fn);
   return ESC_OK;
 }

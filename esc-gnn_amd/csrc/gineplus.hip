@@ -18,6 +18,7 @@
 // relu(x_{d-1}[j]) * sum_i g[i]) and reduced per workgroup and then across workgroups in a fixed order: equal up to rounding,
 // bit-stable from run to run.
 #include "common.h"
+#include "sparse_plan.h"
 #include "../../include/escgnn_gineplus.h"
 
 namespace esc {
@@ -26,7 +27,7 @@ constexpr int GP_K_MAX = 4;
 constexpr int GP_FWD_BATCH = 8;         // rows in flight per wave, forward (as AGG_BATCH)
 constexpr int GP_BWD_BATCH = 4;         // ... backward: twice the live accumulators
 constexpr int GP_BWD_WAVES = 8;         // waves per workgroup of the backward: their d_eps partials are added in LDS
-constexpr int GP_BWD_MAX_BLOCKS = 512;  // each wave takes rows wave, wave + W, ...: the partials stay a few hundred rows
+static_assert(GP_K_MAX == sparse::GP_K_MAX && GP_BWD_WAVES == sparse::GP_BWD_WAVES, "sparse_plan.h sizes the backward's grid by these");
 
 template <int VEC> __device__ __forceinline__ void gp_load(const float* p, float (&v)[VEC]) {
   if constexpr (VEC == 4) { const float4 a = *reinterpret_cast<const float4*>(p); v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; }
@@ -275,12 +276,10 @@ __global__ __launch_bounds__(256) void gp_deps_reduce(const float* __restrict__ 
   if (grp == 0 && q < Q) d_eps[q] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
 }
 
-static inline int64_t gp_bwd_blocks(int64_t N) {
-  const int64_t b = cdiv(N, GP_BWD_WAVES);
-  return b < 1 ? 1 : (b > GP_BWD_MAX_BLOCKS ? GP_BWD_MAX_BLOCKS : b);
+// the operands both directions share, as the kernels are handed them (x_d for d > k: x0 again)
+static inline sparse::GpOps gp_ops(const GpArgs& a) {
+  return sparse::GpOps{sparse::mat(a.x0, a.ld0), sparse::mat(a.x1, a.ld1), sparse::mat(a.x2, a.ld2), sparse::mat(a.x3, a.ld3), sparse::mat(a.e, a.ld_e), a.eps};
 }
-
-static inline bool gp_vec_ok(const float* p, int64_t ld) { return p == nullptr || (aligned16(p) && ld % 4 == 0); }
 
 }  // namespace esc
 
@@ -288,7 +287,7 @@ using namespace esc;
 
 extern "C" {
 
-int64_t esc_gineplus_bwd_blocks(int64_t N) { return gp_bwd_blocks(N); }
+int64_t esc_gineplus_bwd_blocks(int64_t N) { return sparse::gp_bwd_blocks(N); }
 
 int esc_gineplus_aggregate_fwd(const float* x0, int64_t ld0, const float* x1, int64_t ld1, const float* x2, int64_t ld2,
                                const float* x3, int64_t ld3, const float* e, int64_t ld_e, const int32_t* in_ptr,
@@ -307,11 +306,8 @@ int esc_gineplus_aggregate_fwd(const float* x0, int64_t ld0, const float* x1, in
   a.ld0 = ld0; a.ld1 = k >= 2 ? ld1 : ld0; a.ld2 = k >= 3 ? ld2 : ld0; a.ld3 = k >= 4 ? ld3 : ld0;
   a.e = e; a.ld_e = ld_e; a.in_ptr = in_ptr; a.meta = in_meta; a.eps = eps; a.N = (int)N; a.C = (int)C; a.k = k; a.M1 = e ? M1 : 0;
   a.out = out; a.ld_out = ld_out;
-  const bool vec = C % 4 == 0 && gp_vec_ok(a.x0, a.ld0) && gp_vec_ok(a.x1, a.ld1) && gp_vec_ok(a.x2, a.ld2) && gp_vec_ok(a.x3, a.ld3) &&
-                   gp_vec_ok(e, ld_e) && gp_vec_ok(out, ld_out) && aligned16(eps);
-  hipStream_t s = (hipStream_t)stream;
-  if (vec) esc::launch(ESC_K_AGG_FWD, gp_fwd_wave<4>, dim3((unsigned)cdiv(N, 4)), dim3(256), 0, s, a);
-  else esc::launch(ESC_K_AGG_FWD, gp_fwd_wave<1>, dim3((unsigned)cdiv(N, 4)), dim3(256), 0, s, a);
+  const sparse::Plan p = sparse::plan_gineplus_fwd(gp_ops(a), sparse::mat(out, ld_out), N, C);
+  esc::launch(ESC_K_AGG_FWD, p.family == sparse::F_V4 ? gp_fwd_wave<4> : gp_fwd_wave<1>, dim3(p.grid[0].x), dim3(256), 0, (hipStream_t)stream, a);
   ESC_CHECK_LAUNCH("esc_gineplus_aggregate_fwd");
   return ESC_OK;
 }
@@ -341,15 +337,11 @@ int esc_gineplus_aggregate_bwd(const float* x0, int64_t ld0, const float* x1, in
   a.ld0 = ld0; a.ld1 = k >= 2 ? ld1 : ld0; a.ld2 = k >= 3 ? ld2 : ld0; a.ld3 = k >= 4 ? ld3 : ld0;
   a.e = e; a.ld_e = ld_e; a.g = g; a.ld_g = ld_g; a.out_ptr = out_ptr; a.meta = meta; a.eps = eps; a.N = (int)N; a.C = (int)C; a.k = k;
   a.M1 = e ? M1 : 0; a.dx = dx; a.d_e = d_e; a.deps_part = deps_part;
-  const bool vec = C % 4 == 0 && gp_vec_ok(a.x0, a.ld0) && gp_vec_ok(a.x1, a.ld1) && gp_vec_ok(a.x2, a.ld2) && gp_vec_ok(a.x3, a.ld3) &&
-                   gp_vec_ok(e, ld_e) && gp_vec_ok(g, ld_g) && gp_vec_ok(dx, C) && gp_vec_ok(d_e, C) && aligned16(eps);
-  const int64_t blocks = gp_bwd_blocks(N);
-  if (vec) esc::launch(ESC_K_AGG_BWD, gp_bwd_wave<4>, dim3((unsigned)blocks), dim3(GP_BWD_WAVES * 64), 0, s, a);
-  else esc::launch(ESC_K_AGG_BWD, gp_bwd_wave<1>, dim3((unsigned)blocks), dim3(GP_BWD_WAVES * 64), 0, s, a);
+  const sparse::Plan p = sparse::plan_gineplus_bwd(gp_ops(a), sparse::mat(g, ld_g), sparse::mat(dx, C), sparse::mat(d_e, C), N, C, k, d_eps != nullptr);
+  esc::launch(ESC_K_AGG_BWD, p.family == sparse::F_V4 ? gp_bwd_wave<4> : gp_bwd_wave<1>, dim3(p.grid[0].x), dim3(GP_BWD_WAVES * 64), 0, s, a);
   ESC_CHECK_LAUNCH("esc_gineplus_aggregate_bwd");
-  if (d_eps != nullptr) {
-    const int Q = (int)((k + 1) * C);
-    esc::launch(-1, gp_deps_reduce, dim3((unsigned)cdiv(Q, 64)), dim3(256), 0, s, (const float*)deps_part, (int)blocks, Q, d_eps);
+  if (p.launches == 2) {
+    esc::launch(-1, gp_deps_reduce, dim3(p.grid[1].x), dim3(256), 0, s, (const float*)deps_part, (int)p.slots, (int)((k + 1) * C), d_eps);
     ESC_CHECK_LAUNCH("esc_gineplus_aggregate_bwd.deps");
   }
   return ESC_OK;
