@@ -264,12 +264,14 @@ __device__ __forceinline__ void bn_fold_column(const BnFoldDev& f, int col, bool
 
 // BatchNorm(+ReLU) BACKWARD applied to the A operand while it is staged (PRO bit 2): A holds the gradient dOut of the
 // BatchNorm's output, `x` the rows the BatchNorm normalised (same shape as A), and the operand the MFMAs see is
-//   dY = scale * (g - k1 - (x - mean) * invstd * k2),   g = dOut * [fmaf(x, scale, shift) > 0]   (relu; g = dOut otherwise)
+//   dY = scale * (g - k1 - (x - mean) * invstd * k2),   g = dOut * [fmaf(x, scale, shift) > 0]   (relu; g = dOut otherwise;
+//                                                       ELU: g = dOut * (v > 0 ? 1 : exp(v)), v = (x - mean) * scale + beta)
 // with (k1, k2) = coef = (sum g, sum g*xhat) / rows — the value esc_bn_bwd_apply would have written to memory for the
 // GEMM to read back.  The elementwise launch between the finalize and the GEMM disappears from the dependent chain.
 struct BnbDev {
   const float* x; int ldx;
-  const float* mean; const float* invstd; const float* scale; const float* shift;
+  const float* mean; const float* invstd; const float* scale;
+  const float* shift;               // the pre-activation's offset: ReLU the forward's shift (on x), ELU the BatchNorm's beta (on x - mean)
   const float2* coef;
   int relu;                         // activation behind the BatchNorm: 0 none, 1 ReLU, 2 ELU (the fused-activation codes of norm.hip)
 };
@@ -278,7 +280,8 @@ struct BnbDev {
 struct BnStatDev {
   float2* partial;
   const float* x; int ldx;
-  const float* mean; const float* invstd; const float* scale; const float* shift;
+  const float* mean; const float* invstd; const float* scale;
+  const float* shift;               // as BnbDev::shift: beta when relu == 2
   int relu;
 };
 
@@ -288,10 +291,12 @@ __device__ __forceinline__ float bnb_apply(float gv, float xv, float mu, float a
   const float gm = fmaf(xv, ms, mh) > 0.f ? gv : 0.f;
   return a * fmaf(mu - xv, k2, gm - k1);                               // = a * (g - k1 - (x - mu) * invstd * k2)
 }
-// ... with ELU(alpha = 1) behind the BatchNorm (zinc_models.py:513-522): d act / d v = v > 0 ? 1 : exp(v), v = the pre-activation
-// the forward formed (fmaf(x, scale, shift)); `elu` is wave-uniform
+// ... with ELU(alpha = 1) behind the BatchNorm (zinc_models.py:513-522): d act / d v = v > 0 ? 1 : exp(v) at the CENTRED
+// pre-activation v = (x - mean) * scale + beta — ms = scale, mh = BETA here (BnbDev::shift).  The forward's fmaf(x, scale, shift)
+// loses u * |mean * scale| of v to cancellation and exp hands that on to the gradient (norm.hip pre_act_bwd has the same form);
+// a sign, which is all ReLU needs, does not care.  `elu` is wave-uniform
 __device__ __forceinline__ float bnb_apply_elu(float gv, float xv, float mu, float a, float ms, float mh, float k1, float k2) {
-  const float v = fmaf(xv, ms, mh);
+  const float v = fmaf(xv - mu, ms, mh);
   const float gm = v > 0.f ? gv : gv * expf(v);
   return a * fmaf(mu - xv, k2, gm - k1);
 }

@@ -185,8 +185,8 @@ static int linear_backward(const Ctx& c, const float* dY, int64_t ld_dy, const f
 static constexpr bool kBnBwdApplyInGemm = true;    // a BatchNorm backward's apply rides on the dY staging of the Linear backward behind it
 static constexpr bool kBnBwdSumsFromDx = true;     // its column sums come out of the dX epilogue of the Linear backward in front of it
 static constexpr bool kBnBwdSumsFromAgg = true;    // ... or out of the aggregate backward that completes its output gradient
-static esc_bn_bwd_fused bn_fused(const float* x, int64_t ld_x, const BnWs& w, int relu) {
-  return esc_bn_bwd_fused{x, ld_x, w.mean, w.invstd, w.scale, w.shift, w.coef, relu};
+static esc_bn_bwd_fused bn_fused(const float* x, int64_t ld_x, const BnWs& w, int relu, const float* beta) {
+  return esc_bn_bwd_fused{x, ld_x, w.mean, w.invstd, w.scale, w.shift, w.coef, relu, beta};
 }
 static int linear_backward_bn(const Ctx& c, const float* dOut, int64_t ld_dout, const esc_bn_bwd_fused& f, const float* X, int64_t ld_x,
                               const float* sc, const float* sh, const esc_linear_t& lin, int64_t M, float* dX, int64_t ld_dx,
@@ -460,8 +460,8 @@ static MlpFuse mlp_fuse_plan(const Ctx& c, const esc_mlp_t& p, const MlpWs& w, c
   MlpFuse f;
   if (!(kBnBwdApplyInGemm && c.train && !sync_on(c) && y.bst_part != nullptr && p.lin1.in_dim == H && p.lin1.out_dim == H)) return f;
   if (!(c.act == 1 && w.A1 == nullptr)) return f;     // (ELU models keep the elementwise launches: DESIGN.md *Retired step-engine switches*)
-  const esc_bn_bwd_fused f1 = bn_fused(pre_out ? out : w.Y1, pre_out ? ld_out : H, w.b1, c.act), f0 = bn_fused(w.Y0, H, w.b0, c.act);
-  const esc_bn_bwd_next n0{y.bst_part, w.Y0, H, w.b0.mean, w.b0.invstd, w.b0.scale, w.b0.shift, c.act};
+  const esc_bn_bwd_fused f1 = bn_fused(pre_out ? out : w.Y1, pre_out ? ld_out : H, w.b1, c.act, p.bn1.beta), f0 = bn_fused(w.Y0, H, w.b0, c.act, p.bn0.beta);
+  const esc_bn_bwd_next n0{y.bst_part, w.Y0, H, w.b0.mean, w.b0.invstd, w.b0.scale, w.b0.shift, c.act, p.bn0.beta};
   const float* slab_probe = c.jobs ? *c.slab_cursor : y.slabs;
   f.lin1 = esc_linear_bwd_both_bn_ok(dOut, ld_dout, &f1, w.Y0, H, p.lin1.w, H, M, H, H, y.dT2, H, slab_probe, &n0) != 0;   // (lin1's input: Y0's pre-BatchNorm rows)
   f.lin0 = f.lin1 && esc_linear_bwd_both_bn_ok(y.dT2, H, &f0, A, ld_a, p.lin0.w, p.lin0.in_dim, M, H, p.lin0.in_dim, dA, ld_da, slab_probe, nullptr) != 0;
@@ -483,8 +483,8 @@ static int mlp_backward(const Ctx& c, const esc_mlp_t& p, const MlpWs& w, const 
   if (fuse.lin1) {
     const float* x1 = pre_out ? out : w.Y1;                  // what BatchNorm 1 normalised
     const int64_t ld_x1 = pre_out ? ld_out : H;
-    const esc_bn_bwd_fused f1 = bn_fused(x1, ld_x1, w.b1, c.act), f0 = bn_fused(w.Y0, H, w.b0, c.act);
-    esc_bn_bwd_next n0{y.bst_part, w.Y0, H, w.b0.mean, w.b0.invstd, w.b0.scale, w.b0.shift, c.act};
+    const esc_bn_bwd_fused f1 = bn_fused(x1, ld_x1, w.b1, c.act, p.bn1.beta), f0 = bn_fused(w.Y0, H, w.b0, c.act, p.bn0.beta);
+    esc_bn_bwd_next n0{y.bst_part, w.Y0, H, w.b0.mean, w.b0.invstd, w.b0.scale, w.b0.shift, c.act, p.bn0.beta};
     // (activation derivatives are recomputed from the pre-BatchNorm rows everywhere — Y == NULL — so that the sums and the
     // fused apply see the same values)
     if (have_slots > 0)
@@ -730,12 +730,12 @@ static int backward(const Ctx& c, Pending* defer) {
   ESC_TRY(linear_backward(c, y.dpred, 1, y.Yl, H, y.bl.scale, y.bl.shift, m->lin2, N, y.dAl, H, 0));
   // bn_lin1 backward: folded into lin1's backward when the fused kernels serve its column blocks (see kBnBwdApplyInGemm)
   const bool split_lin1 = es.ok && c.jobs != nullptr && L >= 1;
-  const esc_bn_bwd_fused fl = bn_fused(y.Yl, H, y.bl, 1);
+  const esc_bn_bwd_fused fl = bn_fused(y.Yl, H, y.bl, 1, m->bn_lin1.beta);
   const bool fa_l = fuse_node_act(c);
   // the last layer's output gradient d(cat)[:, L*H:] is final once lin1's node-side block has written it: its dX tiles
   // leave the column sums of that layer's last BatchNorm backward (kBnBwdSumsFromDx)
   const MlpWs& wl = y.conv[L > 0 ? L - 1 : 0];
-  esc_bn_bwd_next nl{y.bst_part, y.cat + L * H, W, wl.b1.mean, wl.b1.invstd, wl.b1.scale, wl.b1.shift, 1};
+  esc_bn_bwd_next nl{y.bst_part, y.cat + L * H, W, wl.b1.mean, wl.b1.invstd, wl.b1.scale, wl.b1.shift, 1, nullptr};     // (ReLU: beta is not read)
   auto lin1_ok = [&](int64_t col0, int64_t ncols, const esc_bn_bwd_next* nx) {
     return esc_linear_bwd_both_bn_ok(y.dAl, H, &fl, y.cat + col0, W, m->lin1.w + col0, W, N, H, ncols, y.dcat + col0, W,
                                      c.jobs ? *c.slab_cursor : y.slabs, nx) != 0;
@@ -1323,7 +1323,7 @@ static int backward_ogb(const OgbCtx& z) {
     // column sums come out of lin1's dX epilogue (esc_linear_bwd_both_bn with bn == NULL), then finalize + apply
     bool hidden_done = false;
     if (kBnBwdSumsFromDx && !sync_on(c) && y.bst_part != nullptr) {
-      const esc_bn_bwd_next n0{y.bst_part, w.Y0, H2, w.b0.mean, w.b0.invstd, w.b0.scale, w.b0.shift, 1};
+      const esc_bn_bwd_next n0{y.bst_part, w.Y0, H2, w.b0.mean, w.b0.invstd, w.b0.scale, w.b0.shift, 1, nullptr};
       const float* slab_probe = c.jobs ? *c.slab_cursor : c.y.slabs;
       if (esc_linear_bwd_both_bn_ok(y.dT, H, nullptr, w.Y0, H2, q.lin1.w, H2, N, H, H2, y.dA1, H2, slab_probe, &n0)) {
         float* slabs = c.y.slabs;

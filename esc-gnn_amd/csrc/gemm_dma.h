@@ -321,7 +321,7 @@ __device__ __forceinline__ void gemm_body(const GArgs& g, float* __restrict__ ld
       const float2 kk = in ? g.bnb.coef[k] : make_float2(0.f, 0.f);
       bnbc[k] = in ? g.bnb.mean[k] : 0.f;
       bnbc[S + k] = sc;
-      bnbc[2 * S + k] = g.bnb.relu ? sc : 0.f;                           // mask: fmaf(x, msc, msh) > 0 (no activation: always)
+      bnbc[2 * S + k] = g.bnb.relu ? sc : 0.f;                           // mask: fmaf(x, msc, msh) > 0 (no activation: always); ELU: msh = beta on x - mean
       bnbc[3 * S + k] = g.bnb.relu ? (in ? g.bnb.shift[k] : 0.f) : 1.f;
       bnbc[4 * S + k] = kk.x;
       bnbc[5 * S + k] = in ? g.bnb.invstd[k] * kk.y : 0.f;
@@ -698,12 +698,14 @@ __device__ __forceinline__ void gemm_body(const GArgs& g, float* __restrict__ ld
             if constexpr (BSTAT) {
               if (bstat) {
                 const float4 y = ypre[it];
-                const float px = fmaf(y.x, e_ms.x, e_mh.x), py = fmaf(y.y, e_ms.y, e_mh.y), pz = fmaf(y.z, e_ms.z, e_mh.z), pw = fmaf(y.w, e_ms.w, e_mh.w);
                 float gx, gy, gz, gw;
-                if (g.bst.relu == 2) {                       // (workgroup-uniform) ELU: d act / d v = v > 0 ? 1 : exp(v)
+                if (g.bst.relu == 2) {                       // (workgroup-uniform) ELU: d act / d v = v > 0 ? 1 : exp(v), v centred (e_mh = beta)
+                  const float px = fmaf(y.x - e_mu.x, e_ms.x, e_mh.x), py = fmaf(y.y - e_mu.y, e_ms.y, e_mh.y),
+                              pz = fmaf(y.z - e_mu.z, e_ms.z, e_mh.z), pw = fmaf(y.w - e_mu.w, e_ms.w, e_mh.w);
                   gx = px > 0.f ? v.x : v.x * expf(px); gy = py > 0.f ? v.y : v.y * expf(py);
                   gz = pz > 0.f ? v.z : v.z * expf(pz); gw = pw > 0.f ? v.w : v.w * expf(pw);
                 } else {
+                  const float px = fmaf(y.x, e_ms.x, e_mh.x), py = fmaf(y.y, e_ms.y, e_mh.y), pz = fmaf(y.z, e_ms.z, e_mh.z), pw = fmaf(y.w, e_ms.w, e_mh.w);
                   gx = px > 0.f ? v.x : 0.f; gy = py > 0.f ? v.y : 0.f; gz = pz > 0.f ? v.z : 0.f; gw = pw > 0.f ? v.w : 0.f;
                 }
                 t1.x += gx; t1.y += gy; t1.z += gz; t1.w += gw;

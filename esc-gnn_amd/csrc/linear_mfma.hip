@@ -582,8 +582,8 @@ static Plan plan_both_bn(const float* dOut, int64_t ld_dout, const esc_bn_bwd_fu
                          const esc_bn_bwd_next* n) {
   plan::BnOps bo{};
   plan::NextOps no{};
-  if (b) bo = plan::BnOps{b->x, b->ld_x, b->mean, b->invstd, b->scale, b->shift, b->coef, b->relu};
-  if (n) no = plan::NextOps{n->partial, n->x, n->ld_x, n->mean, n->invstd, n->scale, n->shift, n->relu};
+  if (b) bo = plan::BnOps{b->x, b->ld_x, b->mean, b->invstd, b->scale, b->shift, b->coef, b->relu, b->beta};
+  if (n) no = plan::NextOps{n->partial, n->x, n->ld_x, n->mean, n->invstd, n->scale, n->shift, n->relu, n->beta};
   plan::PlanKnobs k = knobs();
   if (t_dual_split_on) k.dual_split = t_dual_split.dx_lds > 1 ? t_dual_split.dx_lds : 1;
   return plan::plan_both_bn(k, Op{dOut, ld_dout}, b ? &bo : nullptr, Op{X, ld_x}, Op{W, ld_w}, Op{dX, ld_dx}, slabs, n ? &no : nullptr,
@@ -608,7 +608,9 @@ int esc_linear_bwd_both_bn(const float* dOut, int64_t ld_dout, const esc_bn_bwd_
   const Plan p = plan_both_bn(dOut, ld_dout, bn, X, ld_x, W, ld_w, M, N, K, dX, ld_dx, slabs, next);
   ESC_REQUIRE(p.ok, "esc_linear_bwd_both_bn: shape / alignment not served (M=%ld N=%ld K=%ld) - use esc_bn_bwd + esc_linear_bwd_both", (long)M, (long)N, (long)K);
   hipStream_t s = (hipStream_t)stream;
-  const BnbDev bd = bn ? BnbDev{bn->x, (int)bn->ld_x, bn->mean, bn->invstd, bn->scale, bn->shift, reinterpret_cast<const float2*>(bn->coef), bn->relu}
+  // (ELU: the offset of the pre-activation is beta, on the centred rows — common.h BnbDev)
+  const BnbDev bd = bn ? BnbDev{bn->x, (int)bn->ld_x, bn->mean, bn->invstd, bn->scale, bn->relu == 2 ? bn->beta : bn->shift,
+                                reinterpret_cast<const float2*>(bn->coef), bn->relu}
                        : BnbDev{};
   if (p.family == plan::F_SMALL_BN) {
     const int act = bd.relu == 2 ? 2 : 1;
@@ -630,7 +632,8 @@ int esc_linear_bwd_both_bn(const float* dOut, int64_t ld_dout, const esc_bn_bwd_
   ev.dx_lds = (size_t)p.dx_lds;
   if (ev.split && t_dual_split_on) { ev.dx_done = t_dual_split.dx_done; ev.dw_done = t_dual_split.dw_done; (void)take_dual_split(); }
   if (next)
-    a.dx.bst = BnStatDev{reinterpret_cast<float2*>(next->partial), next->x, (int)next->ld_x, next->mean, next->invstd, next->scale, next->shift, next->relu};
+    a.dx.bst = BnStatDev{reinterpret_cast<float2*>(next->partial), next->x, (int)next->ld_x, next->mean, next->invstd, next->scale,
+                         next->relu == 2 ? next->beta : next->shift, next->relu};
   hipError_t e;
   // (the third operand image of the fused apply costs a ring stage: two stages keep the workgroup at 54 KB, which fits beside
   // an edge-stream GEMM on a CU; three stages — 78 KB — measured slower inside the two-stream step, and neutral (0.988 vs 0.985 ms)

@@ -308,17 +308,19 @@ inline Plan plan_both(const PlanKnobs& k, Op dY, Op X, Op W, Op dX, Op dW, const
 }
 
 // ---- both gradients with the BatchNorm(+ReLU) backward of dOut folded in (esc_linear_bwd_both_bn) ---------------------------
-struct BnOps { const void* x; int64_t ld_x; const void *mean, *invstd, *scale, *shift, *coef; int relu; };
-struct NextOps { const void* partial; const void* x; int64_t ld_x; const void *mean, *invstd, *scale, *shift; int relu; };
+// beta: read when relu == 2 (ELU: the derivative is taken at the centred pre-activation (x - mean) * scale + beta), else ignored
+struct BnOps { const void* x; int64_t ld_x; const void *mean, *invstd, *scale, *shift, *coef; int relu; const void* beta; };
+struct NextOps { const void* partial; const void* x; int64_t ld_x; const void *mean, *invstd, *scale, *shift; int relu; const void* beta; };
+inline bool elu_beta_ok(int relu, const void* beta) { return relu != 2 || (beta != nullptr && aligned16(beta)); }
 inline bool bn_ops_ok(const BnOps& b, int64_t M, int64_t N) {
   return b.x && b.mean && b.invstd && b.scale && b.shift && b.coef && b.relu >= 0 && b.relu <= 2 && b.ld_x >= N &&
          dma_ok(Op{b.x, b.ld_x}, M) && aligned16(b.mean) && aligned16(b.invstd) && aligned16(b.scale) && aligned16(b.shift) &&
-         aligned16(b.coef);
+         aligned16(b.coef) && elu_beta_ok(b.relu, b.beta);
 }
 inline bool next_ops_ok(const NextOps& n, Op dX, int64_t K) {
   return n.partial && n.x && n.mean && n.invstd && n.scale && n.shift && n.ld_x >= K && n.ld_x % 4 == 0 && aligned16(n.x) &&
          aligned16(n.mean) && aligned16(n.invstd) && aligned16(n.scale) && aligned16(n.shift) && aligned16(n.partial) && K % 4 == 0 &&
-         vec_ok(dX) && n.relu >= 0 && n.relu <= 2;
+         vec_ok(dX) && n.relu >= 0 && n.relu <= 2 && elu_beta_ok(n.relu, n.beta);
 }
 inline int64_t bwd_bn_block_rows(int64_t M, int64_t N, int64_t K) { return bwd_big(M, N, K) ? 128 : 64; }
 // bn / next: nullptr when the call has none (at least one is needed); dX.p may be nullptr on the tiny-K kernels only

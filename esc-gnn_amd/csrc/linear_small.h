@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void wgrad_small(const float* __restrict__ dY,
     if constexpr (BNB != 0) {
       const float2 kk = bnb.coef[t];
       b_mu = bnb.mean[t]; b_a = bnb.scale[t]; b_k1 = kk.x; b_k2 = bnb.invstd[t] * kk.y;
-      if (bnb.relu) { b_ms = b_a; b_mh = bnb.shift[t]; }
+      if (bnb.relu) { b_ms = b_a; b_mh = bnb.shift[t]; }          // (ELU: BnbDev::shift is beta, bnb_apply_elu centres x)
     }
 #pragma unroll 4
     for (int r = 0; r < rows; ++r) {
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256) void smalln_dx(const float* __restrict__ dY, i
       const float4 is = *reinterpret_cast<const float4*>(bnb.invstd + c);
       const float4 k01 = *reinterpret_cast<const float4*>(bnb.coef + c), k23 = *reinterpret_cast<const float4*>(bnb.coef + c + 2);
       float4 ms = make_float4(0.f, 0.f, 0.f, 0.f), mh = make_float4(1.f, 1.f, 1.f, 1.f);
-      if (bnb.relu) { ms = a; mh = *reinterpret_cast<const float4*>(bnb.shift + c); }
+      if (bnb.relu) { ms = a; mh = *reinterpret_cast<const float4*>(bnb.shift + c); }      // (ELU: beta)
       if constexpr (BNB == 2) {
         v.x = bnb_apply_elu(v.x, x.x, mu.x, a.x, ms.x, mh.x, k01.x, is.x * k01.y); v.y = bnb_apply_elu(v.y, x.y, mu.y, a.y, ms.y, mh.y, k01.z, is.y * k01.w);
         v.z = bnb_apply_elu(v.z, x.z, mu.z, a.z, ms.z, mh.z, k23.x, is.z * k23.y); v.w = bnb_apply_elu(v.w, x.w, mu.w, a.w, ms.w, mh.w, k23.z, is.w * k23.w);

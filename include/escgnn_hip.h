@@ -319,13 +319,20 @@ int esc_slab_reduce_jobs(const esc_reduce_job* jobs /* host array */, int count,
  *   dOut       gradient of the BatchNorm(+ReLU) OUTPUT [M, N]
  *   bn         its input rows, batch statistics, forward coefficients (scale = gamma*invstd, shift = beta - mean*scale, as
  *              esc_bn_stats writes them) and coef = float2[N] (sum g, sum g*xhat) / M from esc_bn_bwd_coef[_from_partials];
- *              relu = the activation behind the BatchNorm: 0 none, 1 ReLU, 2 ELU (its derivative is recomputed from the
- *              pre-activation fmaf(x, scale, shift), the forward's own expression: [v > 0], resp. v > 0 ? 1 : exp(v))
+ *              relu = the activation behind the BatchNorm: 0 none, 1 ReLU, 2 ELU.  The derivative is recomputed from the
+ *              pre-activation.  ReLU takes the forward's own expression, [fmaf(x, scale, shift) > 0]: a sign, which the
+ *              forward decided in the same arithmetic.  ELU takes v > 0 ? 1 : exp(v) at the CENTRED pre-activation
+ *              v = (x - mean) * scale + beta, the form of esc_bn_bwd (fmaf(x, scale, shift) loses u * |mean * scale| of v to
+ *              cancellation, which exp carries into the gradient of every column with |mean| >> sigma).  beta cannot be
+ *              recovered from shift without the same cancellation: `beta` is read when relu == 2 and only then, and
+ *              relu == 2 with beta == NULL is not served (esc_linear_bwd_both_bn_ok answers 0).
  *   next       optional: dX is itself the gradient of a BatchNorm(+ReLU) output over K channels whose input rows are
  *              next->x; the dX tiles then also write partial[row_block][K] = (sum g, sum g*xhat) of their rows
  *              (row blocks of esc_linear_bwd_bn_block_rows(M, N, K) rows) for esc_bn_bwd_coef_from_partials.
- * Result: dX / dW / db equal esc_bn_bwd_apply followed by esc_linear_bwd_both[_deferred] (same arithmetic per element;
- * the operand is never written to memory).  job == NULL reduces the slabs at once.
+ * Result: dX / dW / db are those of esc_bn_bwd_apply followed by esc_linear_bwd_both[_deferred] up to rounding: the operand
+ * is the same function of the same inputs in another association (one fmaf over (mean - x) * invstd * k2 instead of xhat * k2),
+ * and it is never written to memory.  The two sequences are not bit-equal; each holds the project's bound against fp64
+ * (tests/bnb_cases.py).  job == NULL reduces the slabs at once.
  * esc_linear_bwd_both_bn_ok tells whether a shape is served (node-sized rows, 16-byte aligned operands, N <= 640 on
  * the MFMA tiles or K <= 16 with N <= 848 on the narrow-input kernels); callers fall back to the unfused sequence otherwise.
  * bn == NULL (with next != NULL): dOut is a plain dY — only the next BatchNorm's column sums are folded in. */
@@ -334,12 +341,14 @@ typedef struct esc_bn_bwd_fused {
   const float* mean; const float* invstd; const float* scale; const float* shift;
   const float* coef;
   int32_t relu;
+  const float* beta;               /* relu == 2 only: the BatchNorm's beta[N] (may be NULL otherwise) */
 } esc_bn_bwd_fused;
 typedef struct esc_bn_bwd_next {
   float* partial;
   const float* x; int64_t ld_x;
   const float* mean; const float* invstd; const float* scale; const float* shift;
   int32_t relu;
+  const float* beta;               /* relu == 2 only: that BatchNorm's beta[K] */
 } esc_bn_bwd_next;
 int esc_linear_bwd_both_bn_ok(const float* dOut, int64_t ld_dout, const esc_bn_bwd_fused* bn, const float* X, int64_t ld_x,
                               const float* W, int64_t ld_w, int64_t M, int64_t N, int64_t K, const float* dX, int64_t ld_dx,

@@ -868,6 +868,7 @@ def test_linear_backward_with_batchnorm_backward_folded_in(E, M, N, K, relu, pro
 
     f = nv.BnBwdFused()
     f.x, f.ld_x, f.mean, f.invstd, f.scale, f.shift, f.coef, f.relu = xb.data_ptr(), N, mean.data_ptr(), invstd.data_ptr(), scale.data_ptr(), shift.data_ptr(), coef.data_ptr(), relu
+    f.beta = beta.data_ptr()                                     # read when relu == 2: the ELU derivative's centred pre-activation
     nx = None
     if nxt:
         rows = int(nv.lib().esc_linear_bwd_bn_block_rows(M, N, K))
@@ -875,6 +876,7 @@ def test_linear_backward_with_batchnorm_backward_folded_in(E, M, N, K, relu, pro
         partial = torch.full((slots, K, 2), float("nan"), device=dev)
         nx = nv.BnBwdNext()
         nx.partial, nx.x, nx.ld_x, nx.mean, nx.invstd, nx.scale, nx.shift, nx.relu = partial.data_ptr(), x2.data_ptr(), K, mean2.data_ptr(), invstd2.data_ptr(), scale2.data_ptr(), shift2.data_ptr(), (relu or 1)
+        nx.beta = b2.data_ptr()
     slabs = torch.empty(slab_n, device=dev)
     dX, dW, db = dx0.clone(), torch.full((N, K), float("nan"), device=dev), torch.full((N,), float("nan"), device=dev)
     assert nv.lib().esc_linear_bwd_both_bn_ok(nv.ptr(dOut), N, ctypes.byref(f), nv.ptr(X), ldx, nv.ptr(W), K, M, N, K, nv.ptr(dX), K, nv.ptr(slabs),
