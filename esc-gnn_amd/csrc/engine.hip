@@ -13,106 +13,13 @@
 // Model composition followed: /root/reference/run_graphcount.py:134-194 (graph_pred=False, dropout=0,
 // use_cycle=True — the configuration run_graphcount.py:465 instantiates).
 #include "common.h"
-#include "../../include/escgnn_step.h"
+#include "engine_plan.h"
 
 #include <map>
 #include <vector>
 #include <cstdlib>
 
 namespace esc {
-
-struct Arena {
-  float* base;
-  int64_t off;
-  float* take(int64_t n) {
-    float* p = base ? base + off : nullptr;
-    off += (n + 63) & ~63LL;          // 256-byte granules keep every buffer float4-aligned
-    return p;
-  }
-};
-
-struct BnWs { float *mean, *invstd, *scale, *shift, *nglob, *coef; };     // nglob: rows over all ranks (SyncBN); coef: float2[C] of the backward
-struct MlpWs { float *Y0, *Y1; BnWs b0, b1; float* A1 = nullptr; };   // A1: materialised hidden activation (ELU models)
-
-struct Layout {
-  int64_t N, E, Z, H, L, C0, W;   // W = (L+1)*H
-  // forward state
-  float *Zb, *Yz; BnWs zb0, zb1;
-  float *A0, *Zemb;               // relu(BN(Zb)) and z_emb = relu(BN(Yz)), materialised (see forward())
-  float* e[ESC_MAX_LAYERS]; float* agg[ESC_MAX_LAYERS]; MlpWs conv[ESC_MAX_LAYERS];
-  int64_t ld_e[ESC_MAX_LAYERS];   // leading dimension of e[l]: C, or (L-1)*H when the H-wide edge terms are column blocks of ONE matrix
-  float *e_cat, *w_cat;           // batched edge terms: [E, (L-1)*H] and the packed [(L-1)*H + (L-1), H] weights ++ biases
-  MlpWs xemb; float *cat, *Yl; BnWs bl; float *pred, *dpred;
-  // backward scratch
-  float *dcat, *dAl, *dT1, *dT2, *dagg, *dZemb, *dAz, *deps_part;
-  float* d_e[ESC_MAX_LAYERS];      // one per GINE layer: the edge stream consumes d_e[l] while the node chain moves on
-  float *bn_scratch, *bag_scratch, *slabs;
-  float *col_stats;               // GEMM-epilogue BatchNorm partials: float2[ceil(rows/32)][H]
-  float *bst_part;                // BatchNorm-backward column sums left by a dX epilogue / an aggregate backward: float2[slots][H]
-  float *bn_scratch_e, *col_stats_e;   // the edge stream's own BatchNorm scratch / GEMM-epilogue partials
-  // ZINC variant: node features from a table, [z_emb | edge type] edge-term input, pooled readout
-  float *cat_scale, *cat_shift;     // (scale, shift) of the BatchNorm that produced each H-wide slice of cat: [(L+1)*H]
-  float *X0, *dX0, *Zcat, *dZcat, *pooled, *dpool, *Al;
-  int64_t G, D, Wz;                 // graphs, type-embedding width, Wz = H + D
-  int64_t total;
-};
-
-static BnWs take_bn(Arena& a, int64_t C) { BnWs w; w.mean = a.take(C); w.invstd = a.take(C); w.scale = a.take(C); w.shift = a.take(C); w.nglob = a.take(16); w.coef = a.take(2 * C); return w; }
-
-static Layout plan_layout(const esc_nested_gin_t* m, int64_t N, int64_t E, int64_t Z, float* base, bool train) {
-  Layout y{};
-  Arena a{base, 0};
-  const int64_t H = m->hidden, L = m->num_layers, C0 = m->in_dim;
-  y.N = N; y.E = E; y.Z = Z; y.H = H; y.L = L; y.C0 = C0; y.W = (L + 1) * H;
-  y.Zb = a.take(E * H); y.Yz = a.take(E * H); y.zb0 = take_bn(a, H); y.zb1 = take_bn(a, H);
-  y.A0 = a.take(E * H); y.Zemb = a.take(E * H);
-  // the H-wide edge terms e_1 .. e_{L-1} = lin_l(z_emb) of ALL layers as ONE GEMM [E, H] x [H, (L-1)*H]
-  // over packed weights (one launch of 119 x 6 tiles instead of three of 119 x 2), their outputs column blocks of one matrix; see
-  // DESIGN.md for what it measured.
-  const bool batched = L >= 3;                              // (two or more H-wide edge terms)
-  if (batched) { y.e_cat = a.take(E * (L - 1) * H); y.w_cat = a.take(((L - 1) * H + (L - 1)) * H); }
-  for (int l = 0; l < L; ++l) {
-    const int64_t C = l == 0 ? C0 : H;
-    if (batched && l >= 1) { y.e[l] = base ? y.e_cat + (int64_t)(l - 1) * H : nullptr; y.ld_e[l] = (L - 1) * H; }
-    else { y.e[l] = a.take(E * C); y.ld_e[l] = C; }
-    y.agg[l] = a.take(N * C);
-    y.conv[l].Y0 = a.take(N * H); y.conv[l].Y1 = a.take(N * H);
-    y.conv[l].b0 = take_bn(a, H); y.conv[l].b1 = take_bn(a, H);
-  }
-  y.xemb.Y0 = a.take(N * H); y.xemb.Y1 = a.take(N * H); y.xemb.b0 = take_bn(a, H); y.xemb.b1 = take_bn(a, H);
-  y.cat = a.take(N * y.W); y.Yl = a.take(N * H); y.bl = take_bn(a, H);
-  y.cat_scale = a.take(y.W); y.cat_shift = a.take(y.W);       // the slices' BatchNorm coefficients side by side (readout prologue)
-  if (base) {
-    y.xemb.b1.scale = y.cat_scale; y.xemb.b1.shift = y.cat_shift;
-    for (int l = 0; l < L; ++l) { y.conv[l].b1.scale = y.cat_scale + (int64_t)(l + 1) * H; y.conv[l].b1.shift = y.cat_shift + (int64_t)(l + 1) * H; }
-  }
-  y.pred = a.take(N); y.dpred = a.take(N);
-  y.bn_scratch = a.take(esc_bn_scratch(H));
-  y.col_stats = a.take(2 * ((E > N ? E : N) / 32 + 1) * H);
-  y.bn_scratch_e = a.take(esc_bn_scratch(H));
-  y.col_stats_e = a.take(2 * (E / 32 + 1) * H);
-  if (train) {
-    y.bst_part = a.take(2 * (N / 4 + 2) * H);
-    y.dcat = a.take(N * y.W); y.dAl = a.take(N * H); y.dT1 = a.take(N * H); y.dT2 = a.take(N * H);
-    y.dagg = a.take(N * H); y.dZemb = a.take(E * H); y.dAz = a.take(E * H);
-    for (int l = 0; l < L; ++l) y.d_e[l] = a.take(E * (l == 0 ? C0 : H));
-    y.deps_part = a.take(2 * N * (L > 0 ? L : 1));        // one vector per GINE layer, summed together at the end
-    y.bag_scratch = a.take(esc_bag_bwd_scratch(Z, H));
-    // one private slab region per weight gradient: their ordered reduces are deferred to ONE launch at the end
-    int64_t sl = esc_linear_bwd_weight_scratch(E, H, H) + 64;                        // zlin
-    for (int l = 0; l < L; ++l) {
-      const int64_t C = l == 0 ? C0 : H;
-      sl += esc_linear_bwd_weight_scratch(E, C, H) + esc_linear_bwd_weight_scratch(N, H, H) +
-            esc_linear_bwd_weight_scratch(N, H, C) + 3 * 64;                           // conv.lin, nn.lin1, nn.lin0
-    }
-    sl += esc_linear_bwd_weight_scratch(N, H, H) + esc_linear_bwd_weight_scratch(N, H, C0) + 2 * 64;   // x_embedding
-    sl += esc_linear_bwd_weight_scratch(N, H, y.W) + esc_linear_bwd_weight_scratch(N, 1, H) + 2 * 64;  // lin1, lin2
-    sl += esc_linear_bwd_weight_scratch(N, H, 1) + 64;      // lin1 is reduced as two column blocks with a job each
-    y.slabs = a.take(sl);
-  }
-  y.total = a.off;
-  return y;
-}
 
 #define ESC_TRY(call)            \
   do {                           \
@@ -126,8 +33,8 @@ struct Ctx {
   Layout y;
   void* s;
   bool train;
-  std::vector<esc_reduce_job>* jobs = nullptr;   // deferred weight-gradient reduces (main chain only)
-  float** slab_cursor = nullptr;
+  std::vector<esc_reduce_job>* jobs = nullptr;   // deferred weight-gradient reduces (main chain only); null: each is reduced at once
+  SlabCursor* slabs = nullptr;                   // where the next weight gradient's slab region starts (every training entry)
   bool on_edge_stream = false;
   int act = 1;                                   // 1 ReLU (counting model), 2 ELU (ZINC): materialised activations
   const float* l1_target = nullptr;              // train_step: the prediction head also leaves d L1 / d pred (forward(), train_step_impl())
@@ -162,19 +69,40 @@ struct NodeFloorGuard {
   bool on_;
 };
 
+// The slab cursor and the deferred-reduction job list of a training entry: they live in the entry's frame, the Ctx points at
+// them.  The reduces are deferred when the step's `n_jobs` weight gradients fit one reduce launch (else each is reduced at once,
+// out of its own region all the same); the forward_train entries only mark the main chain (statistics from the GEMM
+// epilogues): n_jobs = 0.
+struct StepSlabs {
+  StepSlabs(Ctx& c, float* slabs, int64_t limit, int n_jobs) : cursor{slabs, 0, limit} {
+    if (n_jobs > 0) jobs.reserve(ESC_MAX_REDUCE_JOBS);
+    c.slabs = &cursor;
+    if (n_jobs <= ESC_MAX_REDUCE_JOBS) c.jobs = &jobs;
+  }
+  StepSlabs(const StepSlabs&) = delete;
+  SlabCursor cursor;
+  std::vector<esc_reduce_job> jobs;
+};
+// the private slab region of the next (M rows, N x K) weight gradient and, when reduces are deferred, its job
+struct Slab { float* p = nullptr; esc_reduce_job* job = nullptr; };
+static int take_slab(const Ctx& c, int64_t M, int64_t N, int64_t K, Slab* s) {
+  s->p = c.slabs ? c.slabs->take(M, N, K) : nullptr;
+  ESC_REQUIRE(s->p != nullptr, "esc_engine: no slab region left for a weight gradient of %ld rows, %ld x %ld", (long)M, (long)N, (long)K);
+  if (c.jobs) { c.jobs->emplace_back(); s->job = &c.jobs->back(); }
+  return ESC_OK;
+}
+
 // dX + dW tiles now, slab reduce deferred (or immediate when the context has no job list)
 static int linear_backward(const Ctx& c, const float* dY, int64_t ld_dy, const float* X, int64_t ld_x, const float* sc,
                            const float* sh, const esc_linear_t& lin, int64_t M, float* dX, int64_t ld_dx, int accumulate) {
   const LdsFloorGuard cap(c.on_edge_stream);
   const int64_t N = lin.out_dim, K = lin.in_dim;
-  if (c.jobs == nullptr)
-    return esc_linear_bwd_both(dY, ld_dy, X, ld_x, sc, sh, lin.w, K, M, N, K, dX, ld_dx, accumulate, lin.dw, K, lin.db,
-                               c.y.slabs, c.s);
-  float* slabs = *c.slab_cursor;
-  *c.slab_cursor += (esc_linear_bwd_weight_scratch(M, N, K) + 63) & ~63LL;
-  c.jobs->emplace_back();
+  Slab s;
+  ESC_TRY(take_slab(c, M, N, K, &s));
+  if (s.job == nullptr)
+    return esc_linear_bwd_both(dY, ld_dy, X, ld_x, sc, sh, lin.w, K, M, N, K, dX, ld_dx, accumulate, lin.dw, K, lin.db, s.p, c.s);
   return esc_linear_bwd_both_deferred(dY, ld_dy, X, ld_x, sc, sh, lin.w, K, M, N, K, dX, ld_dx, accumulate, lin.dw, K, lin.db,
-                                      slabs, &c.jobs->back(), c.s);
+                                      s.p, s.job, c.s);
 }
 
 // ---- BatchNorm(+ReLU) backward folded into the Linear backward behind it (r03; esc_linear_bwd_both_bn) ------------------
@@ -193,14 +121,10 @@ static int linear_backward_bn(const Ctx& c, const float* dOut, int64_t ld_dout, 
                               int accumulate, const esc_bn_bwd_next* next) {
   const LdsFloorGuard cap(c.on_edge_stream);
   const int64_t N = lin.out_dim, K = lin.in_dim;
-  if (c.jobs == nullptr)
-    return esc_linear_bwd_both_bn(dOut, ld_dout, &f, X, ld_x, sc, sh, lin.w, K, M, N, K, dX, ld_dx, accumulate, lin.dw, K, lin.db, c.y.slabs,
-                                  nullptr, next, c.s);
-  float* slabs = *c.slab_cursor;
-  *c.slab_cursor += (esc_linear_bwd_weight_scratch(M, N, K) + 63) & ~63LL;
-  c.jobs->emplace_back();
-  return esc_linear_bwd_both_bn(dOut, ld_dout, &f, X, ld_x, sc, sh, lin.w, K, M, N, K, dX, ld_dx, accumulate, lin.dw, K, lin.db, slabs,
-                                &c.jobs->back(), next, c.s);
+  Slab s;
+  ESC_TRY(take_slab(c, M, N, K, &s));
+  return esc_linear_bwd_both_bn(dOut, ld_dout, &f, X, ld_x, sc, sh, lin.w, K, M, N, K, dX, ld_dx, accumulate, lin.dw, K, lin.db, s.p,
+                                s.job, next, c.s);
 }
 
 // The edge-sized conv.lin GEMMs (e_l = lin_l(z_emb) forward; dX/dW of lin_l backward) depend on the node chain only
@@ -462,7 +386,7 @@ static MlpFuse mlp_fuse_plan(const Ctx& c, const esc_mlp_t& p, const MlpWs& w, c
   if (!(c.act == 1 && w.A1 == nullptr)) return f;     // (ELU models keep the elementwise launches: DESIGN.md *Retired step-engine switches*)
   const esc_bn_bwd_fused f1 = bn_fused(pre_out ? out : w.Y1, pre_out ? ld_out : H, w.b1, c.act, p.bn1.beta), f0 = bn_fused(w.Y0, H, w.b0, c.act, p.bn0.beta);
   const esc_bn_bwd_next n0{y.bst_part, w.Y0, H, w.b0.mean, w.b0.invstd, w.b0.scale, w.b0.shift, c.act, p.bn0.beta};
-  const float* slab_probe = c.jobs ? *c.slab_cursor : y.slabs;
+  const float* slab_probe = c.slabs->peek();
   f.lin1 = esc_linear_bwd_both_bn_ok(dOut, ld_dout, &f1, w.Y0, H, p.lin1.w, H, M, H, H, y.dT2, H, slab_probe, &n0) != 0;   // (lin1's input: Y0's pre-BatchNorm rows)
   f.lin0 = f.lin1 && esc_linear_bwd_both_bn_ok(y.dT2, H, &f0, A, ld_a, p.lin0.w, p.lin0.in_dim, M, H, p.lin0.in_dim, dA, ld_da, slab_probe, nullptr) != 0;
   return f;
@@ -738,7 +662,7 @@ static int backward(const Ctx& c, Pending* defer) {
   esc_bn_bwd_next nl{y.bst_part, y.cat + L * H, W, wl.b1.mean, wl.b1.invstd, wl.b1.scale, wl.b1.shift, 1, nullptr};     // (ReLU: beta is not read)
   auto lin1_ok = [&](int64_t col0, int64_t ncols, const esc_bn_bwd_next* nx) {
     return esc_linear_bwd_both_bn_ok(y.dAl, H, &fl, y.cat + col0, W, m->lin1.w + col0, W, N, H, ncols, y.dcat + col0, W,
-                                     c.jobs ? *c.slab_cursor : y.slabs, nx) != 0;
+                                     c.slabs->peek(), nx) != 0;
   };
   const bool fuse_l = kBnBwdApplyInGemm && c.act == 1 && !sync_on(c) && y.bst_part != nullptr &&
                       (split_lin1 ? (lin1_ok(0, L * H, nullptr) && lin1_ok(L * H, H, nullptr)) : lin1_ok(0, W, nullptr));
@@ -758,15 +682,14 @@ static int backward(const Ctx& c, Pending* defer) {
   if (split_lin1) {
     const int64_t K0 = L * H;                                 // columns [0, K0) go to the edge stream
     auto part = [&](void* stream, int64_t col0, int64_t ncols, float* db, const esc_bn_bwd_next* nx) -> int {
-      float* slabs = *c.slab_cursor;
-      *c.slab_cursor += (esc_linear_bwd_weight_scratch(N, H, ncols) + 63) & ~63LL;
-      c.jobs->emplace_back();
+      Slab s;
+      ESC_TRY(take_slab(c, N, H, ncols, &s));
       const bool fa = fa_l;
       if (fuse_l)
         return esc_linear_bwd_both_bn(y.dAl, H, &fl, y.cat + col0, W, fa ? y.cat_scale + col0 : nullptr, fa ? y.cat_shift + col0 : nullptr, m->lin1.w + col0, W,
-                                      N, H, ncols, y.dcat + col0, W, 0, m->lin1.dw + col0, W, db, slabs, &c.jobs->back(), nx, stream);
+                                      N, H, ncols, y.dcat + col0, W, 0, m->lin1.dw + col0, W, db, s.p, s.job, nx, stream);
       return esc_linear_bwd_both_deferred(y.dAl, H, y.cat + col0, W, fa ? y.cat_scale + col0 : nullptr, fa ? y.cat_shift + col0 : nullptr, m->lin1.w + col0, W, N, H, ncols,
-                                          y.dcat + col0, W, 0, m->lin1.dw + col0, W, db, slabs, &c.jobs->back(), stream);
+                                          y.dcat + col0, W, 0, m->lin1.dw + col0, W, db, s.p, s.job, stream);
     };
     if ((!fork_bound && hipEventRecord(es.lin1_fork, (hipStream_t)c.s) != hipSuccess) || hipStreamWaitEvent(es.stream, es.lin1_fork, 0) != hipSuccess) {
       set_error("esc_engine: stream event failed");
@@ -842,11 +765,10 @@ static int backward(const Ctx& c, Pending* defer) {
         const LdsFloorGuard cap(true);
         ESC_TRY(esc_linear_bwd_input(y.d_e[l], C, cv.lin.w, H, E, C, H, y.dZemb, H, l == (int)L - 1 ? 0 : 1, es.stream));
       }
-      float* slabs = *c.slab_cursor;
-      *c.slab_cursor += (esc_linear_bwd_weight_scratch(E, C, H) + 63) & ~63LL;
-      c.jobs->emplace_back();
+      Slab s;
+      ESC_TRY(take_slab(c, E, C, H, &s));
       ESC_TRY(esc_linear_bwd_both_deferred(y.d_e[l], C, zin, H, nullptr, nullptr, cv.lin.w, H, E, C, H, nullptr, 0, 0, cv.lin.dw, H, cv.lin.db,
-                                           slabs, &c.jobs->back(), c.s));
+                                           s.p, s.job, c.s));
     } else {
       ESC_TRY(linear_backward(ce, y.d_e[l], C, zin, H, nullptr, nullptr, cv.lin, E, y.dZemb, H, l == (int)L - 1 ? 0 : 1));
     }
@@ -898,56 +820,6 @@ static int backward(const Ctx& c, Pending* defer) {
 // ZINC variant (zinc_models.py:504-611): one stream, ELU, materialised activations.  Reuses the helpers above through a
 // Ctx whose count-model pointers are null.
 // =====================================================================================================================
-static Layout plan_layout_zinc(const esc_zinc_gin_t* m, int64_t N, int64_t E, int64_t Z, int64_t G, float* base, bool train) {
-  Layout y{};
-  Arena a{base, 0};
-  const int64_t H = m->hidden, L = m->num_layers, D = m->edge_emb.dim, C0 = m->node_emb.dim;
-  y.N = N; y.E = E; y.Z = Z; y.H = H; y.L = L; y.C0 = C0; y.W = L * H; y.G = G; y.D = D; y.Wz = H + D;
-  y.X0 = a.take(N * C0);
-  y.Zb = a.take(E * H); y.Yz = a.take(E * H); y.zb0 = take_bn(a, H); y.zb1 = take_bn(a, H);
-  y.A0 = a.take(E * H); y.Zcat = a.take(E * y.Wz);
-  const int64_t lb = C0 == H ? 0 : 1, nb = L - lb;            // the H-wide edge terms: layers lb .. L-1, batched into one GEMM (see plan_layout())
-  const bool batched = nb >= 2;
-  if (batched) { y.e_cat = a.take(E * nb * H); y.w_cat = a.take(nb * H * y.Wz + nb * H); }
-  for (int l = 0; l < L; ++l) {
-    const int64_t C = l == 0 ? C0 : H;
-    if (batched && l >= lb) { y.e[l] = base ? y.e_cat + (int64_t)(l - lb) * H : nullptr; y.ld_e[l] = nb * H; }
-    else { y.e[l] = a.take(E * C); y.ld_e[l] = C; }
-    y.agg[l] = a.take(N * C);
-    y.conv[l].Y0 = a.take(N * H); y.conv[l].Y1 = a.take(N * H); y.conv[l].A1 = a.take(N * H);
-    y.conv[l].b0 = take_bn(a, H); y.conv[l].b1 = take_bn(a, H);
-  }
-  // readout rows: the G pooled rows, or (node_readout) the N node rows of cat itself — no pooled / dpool then
-  const bool nodes = m->node_readout != 0;
-  const int64_t R = nodes ? N : G;
-  y.cat = a.take(N * y.W); y.pooled = nodes ? nullptr : a.take(G * y.W); y.Yl = a.take(R * H); y.Al = a.take(R * H);
-  y.bl = take_bn(a, H);
-  y.pred = a.take(R); y.dpred = a.take(R);
-  y.bn_scratch = a.take(esc_bn_scratch(H));
-  y.col_stats = a.take(2 * ((E > N ? E : N) / 32 + 1) * H);
-  y.bn_scratch_e = a.take(esc_bn_scratch(H));
-  y.col_stats_e = a.take(2 * (E / 32 + 1) * H);
-  if (train) {
-    y.dcat = a.take(N * y.W); y.dpool = nodes ? nullptr : a.take(G * y.W); y.dAl = a.take(R * H);
-    y.bst_part = a.take(2 * (N / 4 + E / 64 + 4) * H);
-    y.dT1 = a.take(N * H); y.dT2 = a.take(N * H); y.dagg = a.take(N * H); y.dX0 = a.take(N * C0);
-    y.dZcat = a.take(E * y.Wz); y.dZemb = a.take(E * H); y.dAz = a.take(E * H);
-    for (int l = 0; l < L; ++l) y.d_e[l] = a.take(E * (l == 0 ? C0 : H));
-    y.deps_part = a.take(2 * N * (L > 0 ? L : 1));
-    y.bag_scratch = a.take(esc_bag_bwd_scratch(Z, H));
-    int64_t sl = esc_linear_bwd_weight_scratch(E, H, H) + 64;                                    // zlin
-    for (int l = 0; l < L; ++l) {
-      const int64_t C = l == 0 ? C0 : H;
-      sl += esc_linear_bwd_weight_scratch(E, C, y.Wz) + esc_linear_bwd_weight_scratch(N, H, H) +
-            esc_linear_bwd_weight_scratch(N, H, C) + 3 * 64;                                       // conv.lin, nn.lin1, nn.lin0
-    }
-    sl += esc_linear_bwd_weight_scratch(R, H, y.W) + esc_linear_bwd_weight_scratch(R, 1, H) + 2 * 64;   // lin1, lin2
-    y.slabs = a.take(sl);
-  }
-  y.total = a.off;
-  return y;
-}
-
 struct ZincCtx {
   const esc_zinc_gin_t* m;
   const esc_mol_batch_t* b;
@@ -1114,100 +986,11 @@ static ZincCtx make_zinc(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, floa
 // OGB molecule variant (ogb_mol_gnn.py: GNN(gnn_type='gin_eff'), virtual node, JK last): one stream, ReLU,
 // materialised activations, dropout with its own counter-based stream.
 // =====================================================================================================================
-struct OgbLayer {
-  float *hin, *e, *agg, *Y0, *hc, *hb;            // hin = h + vn[batch]; Y0 [N,2H]; hc pre-BN; hb after BN(+ReLU)
-  BnWs b0, bn;
-  unsigned char* mask_h;
-  float *tmp, *V0, *VA, *V1, *VB, *vn;             // virtual-node update (rows G); vn = the embedding ENTERING layer l
-  BnWs vb0, vb1;
-  unsigned char* mask_v;
-  float* d_e;
-};
-struct OgbLayout {
-  int64_t N, E, Z, G, H, L, T;
-  float *Tcat, *dTcat, *h0, *hL;
-  float *Zb, *Zd, *A0, *Yz, *Yzd, *Zemb; BnWs zb0, zb1;
-  unsigned char *mask_z0, *mask_z1;
-  OgbLayer l[ESC_MAX_LAYERS];
-  float *h[ESC_MAX_LAYERS + 1];
-  float *pooled, *logits, *dlogits;
-  // backward
-  float *dpooled, *dHa, *dHb, *dT, *dA1, *dagg, *dZemb, *dYz, *dA0, *dvn_a, *dvn_b, *dG1, *dG2, *dtmp, *poolG;
-  float *deps_part, *bag_scratch, *emb_scratch, *emb_scratch_n, *slabs, *bn_scratch, *col_stats, *bn_scratch_e, *col_stats_e;
-  float *bst_part;                 // column sums of a node MLP's first BatchNorm backward, left by its second Linear's dX epilogue
-  int64_t total;
-};
-
-static unsigned char* take_bytes(Arena& a, int64_t n) { return reinterpret_cast<unsigned char*>(a.take((n + 3) / 4)); }
-
-static OgbLayout plan_layout_ogb(const esc_ogb_gnn_t* m, int64_t N, int64_t E, int64_t Z, int64_t G, int64_t atom_entries,
-                                 int64_t bond_entries, float* base, bool train) {
-  OgbLayout y{};
-  Arena a{base, 0};
-  const int64_t H = m->hidden, L = m->num_layers, T = m->num_tasks, H2 = 2 * H;
-  const bool drop = train && m->drop_ratio > 0.f;
-  y.N = N; y.E = E; y.Z = Z; y.G = G; y.H = H; y.L = L; y.T = T;
-  const int64_t rows_total = m->atom_rows + L * m->bond_rows;
-  y.Tcat = a.take(rows_total * H);
-  y.h0 = a.take(N * H); y.h[0] = y.h0;
-  y.Zb = a.take(E * H); y.Zd = drop ? a.take(E * H) : y.Zb; y.A0 = a.take(E * H);
-  y.Yz = a.take(E * H); y.Yzd = drop ? a.take(E * H) : y.Yz; y.Zemb = a.take(E * H);
-  y.zb0 = take_bn(a, H); y.zb1 = take_bn(a, H);
-  if (drop) { y.mask_z0 = take_bytes(a, E * H); y.mask_z1 = take_bytes(a, E * H); }
-  for (int l = 0; l < L; ++l) {
-    OgbLayer& q = y.l[l];
-    q.vn = a.take(G * H);
-    q.hin = a.take(N * H);
-    q.e = a.take(E * H);
-    q.agg = a.take(N * H);
-    q.Y0 = a.take(N * H2); q.hc = a.take(N * H); q.hb = nullptr;         // (hb is never materialised: BN -> ReLU -> dropout in one pass)
-    q.b0 = take_bn(a, H2); q.bn = take_bn(a, H);
-    y.h[l + 1] = a.take(N * H);
-    if (drop) q.mask_h = take_bytes(a, N * H);
-    if (l < L - 1) {
-      q.tmp = a.take(G * H); q.V0 = a.take(G * H2); q.VA = a.take(G * H2); q.V1 = a.take(G * H); q.VB = nullptr;
-      q.vb0 = take_bn(a, H2); q.vb1 = take_bn(a, H);
-      if (drop) q.mask_v = take_bytes(a, G * H);
-    }
-  }
-  y.hL = y.h[L];
-  y.pooled = a.take(G * H); y.logits = a.take(G * T); y.dlogits = a.take(G * T);
-  y.bn_scratch = a.take(esc_bn_scratch(H2));
-  y.col_stats = a.take(2 * ((E > N ? E : N) / 32 + 1) * H2);
-  y.bn_scratch_e = a.take(esc_bn_scratch(H2));               // the edge pipeline's own BatchNorm scratch / GEMM-epilogue partials
-  y.col_stats_e = a.take(2 * (E / 32 + 1) * H2);
-  if (train) {
-    y.dTcat = a.take(rows_total * H);
-    y.bst_part = a.take(2 * (N / 64 + 2) * H2);
-    y.dpooled = a.take(G * H); y.dHa = a.take(N * H); y.dHb = a.take(N * H); y.dT = a.take(N * H);
-    y.dA1 = a.take(N * H2); y.dagg = a.take(N * H);
-    y.dZemb = a.take(E * H); y.dYz = a.take(E * H); y.dA0 = a.take(E * H);
-    y.dvn_a = a.take(G * H); y.dvn_b = a.take(G * H); y.dG1 = a.take(G * H2); y.dG2 = a.take(G * H); y.dtmp = a.take(G * H);
-    y.poolG = a.take(G * H);
-    for (int l = 0; l < L; ++l) y.l[l].d_e = a.take(E * H);
-    y.deps_part = a.take(2 * N * (L > 0 ? L : 1));
-    y.bag_scratch = a.take(esc_bag_bwd_scratch(Z, H));
-    const int64_t ent = atom_entries > bond_entries ? atom_entries : bond_entries;
-    y.emb_scratch = a.take(esc_bag_bwd_scratch(ent, H));
-    y.emb_scratch_n = a.take(esc_bag_bwd_scratch(ent, H));
-    int64_t sl = esc_linear_bwd_weight_scratch(E, H, H) + 64;                                   // zlin
-    for (int l = 0; l < L; ++l) {
-      sl += esc_linear_bwd_weight_scratch(E, H, H) + esc_linear_bwd_weight_scratch(N, H2, H) +
-            esc_linear_bwd_weight_scratch(N, H, H2) + 3 * 64;                                     // pos, lin0, lin1
-      if (l < L - 1) sl += esc_linear_bwd_weight_scratch(G, H2, H) + esc_linear_bwd_weight_scratch(G, H, H2) + 2 * 64;
-    }
-    sl += esc_linear_bwd_weight_scratch(G, T, H) + 64;                                          // head
-    y.slabs = a.take(sl);
-  }
-  y.total = a.off;
-  return y;
-}
-
 struct OgbCtx {
   const esc_ogb_gnn_t* m;
   const esc_ogb_batch_t* b;
   OgbLayout o;
-  Ctx c;                // helpers' view (H, col_stats, bn_scratch, slabs, stream, jobs); act = ReLU
+  Ctx c;                // helpers' view (H, col_stats, bn_scratch, stream, slab cursor, jobs); act = ReLU
   float p;              // dropout probability of this call (0 in eval mode)
 };
 
@@ -1324,18 +1107,11 @@ static int backward_ogb(const OgbCtx& z) {
     bool hidden_done = false;
     if (kBnBwdSumsFromDx && !sync_on(c) && y.bst_part != nullptr) {
       const esc_bn_bwd_next n0{y.bst_part, w.Y0, H2, w.b0.mean, w.b0.invstd, w.b0.scale, w.b0.shift, 1, nullptr};
-      const float* slab_probe = c.jobs ? *c.slab_cursor : c.y.slabs;
-      if (esc_linear_bwd_both_bn_ok(y.dT, H, nullptr, w.Y0, H2, q.lin1.w, H2, N, H, H2, y.dA1, H2, slab_probe, &n0)) {
-        float* slabs = c.y.slabs;
-        esc_reduce_job* job = nullptr;
-        if (c.jobs) {
-          slabs = *c.slab_cursor;
-          *c.slab_cursor += (esc_linear_bwd_weight_scratch(N, H, H2) + 63) & ~63LL;
-          c.jobs->emplace_back();
-          job = &c.jobs->back();
-        }
+      if (esc_linear_bwd_both_bn_ok(y.dT, H, nullptr, w.Y0, H2, q.lin1.w, H2, N, H, H2, y.dA1, H2, c.slabs->peek(), &n0)) {
+        Slab s;
+        ESC_TRY(take_slab(c, N, H, H2, &s));
         ESC_TRY(esc_linear_bwd_both_bn(y.dT, H, nullptr, w.Y0, H2, w.b0.scale, w.b0.shift, q.lin1.w, H2, N, H, H2, y.dA1, H2, 0, q.lin1.dw, H2,
-                                       q.lin1.db, slabs, job, &n0, c.s));
+                                       q.lin1.db, s.p, s.job, &n0, c.s));
         ESC_TRY(esc_bn_bwd_coef_from_partials(y.bst_part, cdiv(N, esc_linear_bwd_bn_block_rows(N, H, H2)), N, H2, w.b0.coef, q.bn0.dgamma,
                                               q.bn0.dbeta, c.s));
         ESC_TRY(esc_bn_bwd_apply(w.Y0, H2, nullptr, 0, y.dA1, H2, N, H2, w.b0.mean, w.b0.invstd, q.bn0.gamma, q.bn0.beta, 1, w.b0.coef, y.dA1, H2, c.s));
@@ -1420,7 +1196,7 @@ static OgbCtx make_ogb(const esc_ogb_gnn_t* m, const esc_ogb_batch_t* b, float* 
   OgbCtx z{m, b, plan_layout_ogb(m, b->N, b->E, b->Z, b->G, b->atoms.n_entries, b->bonds.n_entries, ws, train),
            Ctx{nullptr, nullptr, Layout{}, stream, train}, train ? m->drop_ratio : 0.f};
   z.c.y.H = m->hidden; z.c.y.N = b->N; z.c.y.E = b->E;
-  z.c.y.col_stats = z.o.col_stats; z.c.y.bn_scratch = z.o.bn_scratch; z.c.y.slabs = z.o.slabs;
+  z.c.y.col_stats = z.o.col_stats; z.c.y.bn_scratch = z.o.bn_scratch;
   z.c.y.col_stats_e = z.o.col_stats_e; z.c.y.bn_scratch_e = z.o.bn_scratch_e;
   z.c.act = 1;
   return z;
@@ -1444,20 +1220,6 @@ static int copy_floats(float* dst, const float* src, int64_t n, void* stream, co
     return ESC_ELAUNCH;
   }
   return ESC_OK;
-}
-
-// The deferred-reduction job list of a training entry: it lives in the entry's frame, the Ctx points at it.  Armed when the
-// step's `budget` of jobs fits (else the reductions stay inline); the forward_train entries only mark the main chain
-// (statistics from the GEMM epilogues) and arm it whatever the budget (`always`).
-struct JobList {
-  std::vector<esc_reduce_job> jobs;
-  float* cursor = nullptr;
-};
-
-static void arm_jobs(Ctx& c, JobList& l, float* slabs, int64_t budget, bool always = false) {
-  if (!always) l.jobs.reserve(ESC_MAX_REDUCE_JOBS);
-  l.cursor = slabs;
-  if (always || budget <= ESC_MAX_REDUCE_JOBS) { c.jobs = &l.jobs; c.slab_cursor = &l.cursor; }
 }
 
 }  // namespace esc
@@ -1599,8 +1361,7 @@ static int train_step_impl(const esc_nested_gin_t* m, const esc_batch_t* b, floa
   if (rc) return rc;
   ESC_REQUIRE(loss, "esc_engine_train_step: null loss pointer");
   Ctx c{m, b, plan_layout(m, b->N, b->E, b->Z, workspace, true), stream, true};
-  JobList jobs;
-  arm_jobs(c, jobs, c.y.slabs, 3 * m->num_layers + 7);
+  StepSlabs slabs(c, c.y.slabs, c.y.slab_limit, c.y.n_wgrads);
   const int64_t denom = loss_denom > 0 ? loss_denom : b->N;
   EdgeStream& es = edge_stream_for(b->E);
   const bool head_l1 = es.ok && m->hidden <= 1024 &&
@@ -1634,8 +1395,7 @@ int esc_engine_forward_train(const esc_nested_gin_t* m, const esc_batch_t* b, fl
   if (rc) return rc;
   ESC_REQUIRE(pred, "esc_engine_forward_train: null output");
   Ctx c{m, b, plan_layout(m, b->N, b->E, b->Z, workspace, true), stream, true};
-  JobList jobs;
-  arm_jobs(c, jobs, c.y.slabs, 0, true);
+  StepSlabs slabs(c, c.y.slabs, c.y.slab_limit, 0);
   ESC_TRY(forward(c));
   return copy_floats(pred, c.y.pred, b->N, stream, "esc_engine_forward_train");
 }
@@ -1647,8 +1407,7 @@ int esc_engine_backward(const esc_nested_gin_t* m, const esc_batch_t* b, float* 
   if (rc) return rc;
   ESC_REQUIRE(dpred, "esc_engine_backward: null gradient");
   Ctx c{m, b, plan_layout(m, b->N, b->E, b->Z, workspace, true), stream, true};
-  JobList jobs;
-  arm_jobs(c, jobs, c.y.slabs, 3 * m->num_layers + 7);
+  StepSlabs slabs(c, c.y.slabs, c.y.slab_limit, c.y.n_wgrads);
   ESC_TRY(copy_floats(c.y.dpred, dpred, b->N, stream, "esc_engine_backward"));
   return backward(c, nullptr);
 }
@@ -1680,8 +1439,7 @@ int esc_zinc_train_step(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, float
   if (rc) return rc;
   ESC_REQUIRE(loss, "esc_zinc_train_step: null loss pointer");
   ZincCtx z = make_zinc(m, b, workspace, stream, true);
-  JobList jobs;
-  arm_jobs(z.c, jobs, z.c.y.slabs, 3 * m->num_layers + 3);
+  StepSlabs slabs(z.c, z.c.y.slabs, z.c.y.slab_limit, z.c.y.n_wgrads);
   const int64_t R = zinc_rows(m, b);
   ESC_TRY(forward_zinc(z));
   ESC_TRY(esc_l1_loss(z.c.y.pred, b->y, R, loss_denom > 0 ? loss_denom : R, 1.0f, loss, z.c.y.dpred, stream));
@@ -1695,8 +1453,7 @@ int esc_zinc_forward_train(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, fl
   if (rc) return rc;
   ESC_REQUIRE(pred, "esc_zinc_forward_train: null output");
   ZincCtx z = make_zinc(m, b, workspace, stream, true);
-  JobList jobs;
-  arm_jobs(z.c, jobs, z.c.y.slabs, 0, true);
+  StepSlabs slabs(z.c, z.c.y.slabs, z.c.y.slab_limit, 0);
   ESC_TRY(forward_zinc(z));
   return copy_floats(pred, z.c.y.pred, zinc_rows(m, b), stream, "esc_zinc_forward_train");
 }
@@ -1707,8 +1464,7 @@ int esc_zinc_backward(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, float* 
   if (rc) return rc;
   ESC_REQUIRE(dpred, "esc_zinc_backward: null gradient");
   ZincCtx z = make_zinc(m, b, workspace, stream, true);
-  JobList jobs;
-  arm_jobs(z.c, jobs, z.c.y.slabs, 3 * m->num_layers + 3);
+  StepSlabs slabs(z.c, z.c.y.slabs, z.c.y.slab_limit, z.c.y.n_wgrads);
   ESC_TRY(copy_floats(z.c.y.dpred, dpred, zinc_rows(m, b), stream, "esc_zinc_backward"));
   return backward_zinc(z);
 }
@@ -1737,8 +1493,7 @@ int esc_ogb_train_step(const esc_ogb_gnn_t* m, const esc_ogb_batch_t* b, float* 
   if (rc) return rc;
   ESC_REQUIRE(loss, "esc_ogb_train_step: null loss pointer");
   OgbCtx z = make_ogb(m, b, workspace, stream, true);
-  JobList jobs;
-  arm_jobs(z.c, jobs, z.o.slabs, 5 * m->num_layers + 2);
+  StepSlabs slabs(z.c, z.o.slabs, z.o.slab_limit, z.o.n_wgrads);
   ESC_TRY(forward_ogb(z));
   ESC_TRY(esc_bce_logits_loss(z.o.logits, b->y, b->G * m->num_tasks, loss_denom, loss, z.o.dlogits, stream));
   if (logits) ESC_TRY(copy_floats(logits, z.o.logits, b->G * m->num_tasks, stream, "esc_ogb_train_step"));
@@ -1751,8 +1506,7 @@ int esc_ogb_forward_train(const esc_ogb_gnn_t* m, const esc_ogb_batch_t* b, floa
   if (rc) return rc;
   ESC_REQUIRE(logits, "esc_ogb_forward_train: null output");
   OgbCtx z = make_ogb(m, b, workspace, stream, true);
-  JobList jobs;
-  arm_jobs(z.c, jobs, z.o.slabs, 0, true);
+  StepSlabs slabs(z.c, z.o.slabs, z.o.slab_limit, 0);
   ESC_TRY(forward_ogb(z));
   return copy_floats(logits, z.o.logits, b->G * m->num_tasks, stream, "esc_ogb_forward_train");
 }
@@ -1763,8 +1517,7 @@ int esc_ogb_backward(const esc_ogb_gnn_t* m, const esc_ogb_batch_t* b, float* wo
   if (rc) return rc;
   ESC_REQUIRE(dlogits, "esc_ogb_backward: null gradient");
   OgbCtx z = make_ogb(m, b, workspace, stream, true);
-  JobList jobs;
-  arm_jobs(z.c, jobs, z.o.slabs, 5 * m->num_layers + 2);
+  StepSlabs slabs(z.c, z.o.slabs, z.o.slab_limit, z.o.n_wgrads);
   ESC_TRY(copy_floats(z.o.dlogits, dlogits, b->G * m->num_tasks, stream, "esc_ogb_backward"));
   return backward_ogb(z);
 }

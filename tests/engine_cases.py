@@ -97,6 +97,17 @@ SELF_LOOP = {"count": True, "zinc": False, "ogb": True}          # run_graphcoun
 # (family, L, H): counting (3, 64) is the smallest shape on which every live fusion runs; (1, 32) has no hidden GINE layer, no
 # batched edge GEMM and H > 32 false; ZINC has its fixed width of 256
 MODELS = (("count", 3, 64), ("count", 1, 32), ("zinc", 2, 256), ("ogb", 2, 32))
+# (family, L, H, case): depths around the 48 weight-gradient reduces that one launch takes (csrc/engine_plan.h: 3L+6, 3L+3 and 5L
+# of them).  count 14 is the last depth whose reduces are deferred to the end of the step, the others reduce every weight gradient
+# at once; each on the ONE case named — not crossed with the table: the neighbours are not conditioned (count 15/32 `mixed` 7.6e-3,
+# zinc 16 `rows_64` 1.4e-2 against the cap below; tests/test_engine_cases_cpu.py holds these four to it).
+# The OGB model at depth 10 and width 32 is under the cap on seven cases of the table (`mixed` 7.7e-5) and exceeds B on the MI355X
+# on every one of them, by the same figure before and after the plan header and on the per-op path as well (`mixed`: per-op grad
+# convs.8.mlp.3.weight 1.80e-5 against 1.72e-5, e_ref 5.7e-6; `mixed_hub_last` 1.28 B; the G = 2 cases 6 .. 29 B in the two-row
+# BatchNorms of the virtual-node MLPs): ill-conditioned for the device's summation order where e_ref sits at the floor of B.  At
+# width 64 `mixed_hub_last` (worst e_ref 1.9e-4, the same on two host CPUs) is held at 0.73 B on both schedules.  Not a G = 2 case:
+# 10/64 `sparse_edges` is 8.8e-5 on one host CPU and 5.2e-2 on another (eval_pred, through the two-row BatchNorms' running variance).
+DEEP = (("count", 14, 64, "mixed"), ("count", 15, 64, "mixed_hub_last"), ("zinc", 16, 256, "rows_65"), ("ogb", 10, 64, "mixed_hub_last"))
 ZINC_NODE_TYPES, ZINC_EDGE_TYPES = 28, 4
 CAP = 1e-3                                                       # conditioning cap on the fp32 oracle's own error
 # Data seed of a (family, case) when it is not the default one: where the fp32 oracle exceeded the cap with the default seed.

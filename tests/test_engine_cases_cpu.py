@@ -88,6 +88,21 @@ def test_fp32_oracle_is_conditioned(model, case):
         assert e <= ec.CAP, (n, e)
 
 
+@pytest.mark.parametrize("deep", ec.DEEP, ids=lambda d: "%s-%s" % (ec.model_id(d[:3]), d[3]))
+def test_fp32_oracle_is_conditioned_on_the_deep_models(deep):
+    """ec.DEEP: the same cap for the models whose weight gradients do not fit one reduce launch (and the last one that does)"""
+    family, L, H, case = deep
+    step = ec.oracle_step(family, case, L, H)
+    e_ref = ec.reference_errors(step)
+    for side in ("fp32", "fp64"):
+        assert all(bool(torch.isfinite(t).all()) for n, t in ec.float_items(step[side])), side
+        assert len(step[side]["grads"]) == len(step["state"]) - len(step[side]["buffers"])
+    worst = max(e_ref, key=e_ref.get)
+    print("%s %s: worst e_ref %.2g (%s)" % (ec.model_id(deep[:3]), case, e_ref[worst], worst))
+    for n, e in e_ref.items():
+        assert e <= ec.CAP, (n, e)
+
+
 @pytest.mark.parametrize("family", ("zinc", "ogb"))
 def test_single_graph_boundary_oracle(family):
     """G = 1, one path(3): the ZINC reference skips bn_lin1 at one row and trains; the OGB reference cannot train (its

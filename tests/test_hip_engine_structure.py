@@ -98,6 +98,14 @@ def ops_loss(E, family, pred, b):
     return E.ops.l1_loss(pred, b.y)
 
 
+def reduces_deferred(family, L):
+    """Do the weight gradients of one step (csrc/engine_plan.h: 3L+6, 3L+3, 5L) fit the one reduce launch of 48 jobs?  Then
+    esc_*_train_step takes the BatchNorm statistics of the main chain from the GEMM epilogues, as esc_*_forward_train always does,
+    and the two forwards are the same launches.  Past it train_step takes them in passes of their own: another summation order,
+    and the node's predictions are held to B like everything else instead of bit for bit to train_step's."""
+    return {"count": 3 * L + 6, "zinc": 3 * L + 3, "ogb": 5 * L}[family] <= 48
+
+
 def is_engine_node(pred):
     return pred.grad_fn is not None and type(pred.grad_fn).__name__.startswith("_EngineNode")
 
@@ -192,9 +200,13 @@ def test_product_batch_equals_oracle_batch(E, family, case):
 
 
 # ---- every case, every family, both schedules ------------------------------------------------------------------------------
+# ec.MODELS on every case, and the deep models of ec.DEEP (reduce jobs at and past what one launch takes: the last depth that
+# defers its weight-gradient reduces, and the depths that reduce each at once out of its own slab region) on their one case each
+_ON_CASE = [(m, c) for c in ec.CASE_NAMES for m in ec.MODELS] + [(d[:3], d[3]) for d in ec.DEEP]
+
+
 @pytest.mark.parametrize("schedule", list(SCHEDULES))
-@pytest.mark.parametrize("case", ec.CASE_NAMES)
-@pytest.mark.parametrize("model", ec.MODELS, ids=ec.model_id)
+@pytest.mark.parametrize("model,case", _ON_CASE, ids=["%s-%s" % (ec.model_id(m), c) for m, c in _ON_CASE])
 def test_engine_on_case(E, schedule_knobs, model, case, schedule):
     """train_step, its repeat, predict, the per-op twin and the engine as an autograd node on one case: see the module
     docstring for the bound.  `zero_variance`: every BatchNorm column has zero batch variance and the fp32 oracle cannot
@@ -239,7 +251,11 @@ def test_engine_on_case(E, schedule_knobs, model, case, schedule):
     # 5. model(batch) in training mode: one autograd node on the engine, gradients through a torch loss
     pn = node(b)
     assert is_engine_node(pn)
-    assert torch.equal(pn.detach(), first[0])
+    if reduces_deferred(family, L):
+        assert torch.equal(pn.detach(), first[0])
+    else:
+        print("node predictions that differ from train_step's in some bit: %d of %d" % (int((pn.detach() != first[0]).sum()), pn.numel()))
+        held.check("node", "pred", pn)
     ln = torch_loss(family, pn, b)
     ln.backward()
     if with_grads:
