@@ -151,6 +151,7 @@ __global__ __launch_bounds__(256) void agg_fwd_wave(const float* __restrict__ x,
 // (cache-resident 6.4 -> 7.4 us, cold 6.5 -> 7.2) and were removed again.
 static const sparse::SparseKnobs g_knobs{getenv("ESC_AGG_SPLIT") ? atoi(getenv("ESC_AGG_SPLIT")) : 2,
                                          getenv("ESC_AGG_SPLIT_BWD") ? atoi(getenv("ESC_AGG_SPLIT_BWD")) : 1, 0};
+const sparse::SparseKnobs& aggregate_plan_knobs() { return g_knobs; }      // (the step engines' schedule plans with the same values: engine.hip)
 
 // ---- narrow rows (C < 64, e.g. the 10-wide first layer): one thread per (node, channel) ----------
 __global__ __launch_bounds__(256) void agg_fwd_elem(const float* __restrict__ x, int64_t ld_x,

@@ -488,6 +488,7 @@ static const sparse::SparseKnobs& bag_knobs() {
   static const sparse::SparseKnobs k{2, 1, getenv("ESC_BAG_TILED") ? atoi(getenv("ESC_BAG_TILED")) : 0};
   return k;
 }
+const sparse::SparseKnobs& bag_plan_knobs() { return bag_knobs(); }      // (the step engines' schedule plans with the same values: engine.hip)
 
 }  // namespace esc
 

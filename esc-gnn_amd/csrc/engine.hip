@@ -40,7 +40,12 @@ struct Ctx {
   const float* l1_target = nullptr;              // train_step: the prediction head also leaves d L1 / d pred (forward(), train_step_impl())
   int64_t l1_denom = 0;
   bool fast_seam = false;                        // the edge pipeline starts in edge-stream order, without the z_ready chain (see Seam)
+  Schedule sch;                                  // every decision of this call (engine_plan.h): set once by the entry, the bodies only read it
 };
+// the knob values the kernels' own plans are taken with (linear_mfma.hip, aggregate.hip, bag.hip): the schedule plans with the same
+const plan::PlanKnobs& linear_plan_knobs();
+const sparse::SparseKnobs& aggregate_plan_knobs();
+const sparse::SparseKnobs& bag_plan_knobs();
 
 struct LdsFloorGuard {            // occupancy cap for the GEMMs launched while it lives (edge stream only, forward and backward)
   explicit LdsFloorGuard(bool on) : on_(on && edge_lds_floor() > 0) { if (on_) set_gemm_lds_floor(edge_lds_floor()); }
@@ -55,12 +60,8 @@ struct LdsFloorGuard {            // occupancy cap for the GEMMs launched while 
 // step 0.995 -> 0.980 ms; bench 1.048 -> 1.031 ms); 60 000 bytes (still co-resident) changes nothing, 82 000 (one node workgroup per
 // CU) costs 50 us, and in the forward (152-workgroup launches) the same request costs 8 us: the backward only.
 static constexpr int kNodeLdsFloorBwd = 66 * 1024;      // bytes
-// The readout Linear's edge-stream block (backward(), lin1's columns [0, L*H)) goes out as two launches, the dX tiles first, and
-// the node chain waits for those only.  The dX launch asks for kReadoutDxLds: one workgroup per CU, and beside it the
-// kNodeLdsFloorBwd of a node tile still fits — two of its 54-KB workgroups on a CU shut the node chain's launches out of that CU
-// and the chain waited for slots (DESIGN.md *Step engine, readout backward*).  Bit 7 of esc_engine_set_side_stream (and bit 6,
+// (kReadoutDxLds, engine_plan.h: the readout Linear's edge-stream block as two launches.)  Bit 7 of esc_engine_set_side_stream (and bit 6,
 // the schedule of event records) keeps the block one launch with a record behind it: A/B runs.
-static constexpr int kReadoutDxLds = 84 * 1024;         // bytes: 2 x 84 > 160, 84 + 66 <= 160
 static_assert(2 * kReadoutDxLds > 160 * 1024 && kReadoutDxLds + kNodeLdsFloorBwd <= 160 * 1024, "one readout dX tile and one node tile per CU");
 static int g_readout_one_launch = 0;
 struct NodeFloorGuard {
@@ -105,17 +106,7 @@ static int linear_backward(const Ctx& c, const float* dY, int64_t ld_dy, const f
                                       s.p, s.job, c.s);
 }
 
-// ---- BatchNorm(+ReLU) backward folded into the Linear backward behind it (r03; esc_linear_bwd_both_bn) ------------------
-// The node chain's backward was, per Linear -> BatchNorm -> ReLU pair, partial -> finalize -> apply -> dX+dW: four dependent
-// launches.  The apply now happens while the GEMM stages its dY operand and the column sums of an MLP's FIRST BatchNorm come
-// out of the dX epilogue of its second Linear: partial/finalize -> dX+dW -> finalize -> dX+dW.  The three fusions in force
-// (the former ESC_BN_FUSE_BWD = 11, bits 0, 1, 3; the forms they replace stay for the shapes and modes they do not serve):
-static constexpr bool kBnBwdApplyInGemm = true;    // a BatchNorm backward's apply rides on the dY staging of the Linear backward behind it
-static constexpr bool kBnBwdSumsFromDx = true;     // its column sums come out of the dX epilogue of the Linear backward in front of it
-static constexpr bool kBnBwdSumsFromAgg = true;    // ... or out of the aggregate backward that completes its output gradient
-static esc_bn_bwd_fused bn_fused(const float* x, int64_t ld_x, const BnWs& w, int relu, const float* beta) {
-  return esc_bn_bwd_fused{x, ld_x, w.mean, w.invstd, w.scale, w.shift, w.coef, relu, beta};
-}
+// BatchNorm(+ReLU) backward folded into the Linear backward behind it (engine_plan.h: kBnBwdApplyInGemm and the schedule)
 static int linear_backward_bn(const Ctx& c, const float* dOut, int64_t ld_dout, const esc_bn_bwd_fused& f, const float* X, int64_t ld_x,
                               const float* sc, const float* sh, const esc_linear_t& lin, int64_t M, float* dX, int64_t ld_dx,
                               int accumulate, const esc_bn_bwd_next* next) {
@@ -177,13 +168,21 @@ static EdgeStream& edge_stream_for(int64_t edges) {
   static thread_local EdgeStream off;   // ok == false
   return edges >= g_two_stream_min_edges ? edge_stream() : off;
 }
-// `waiter` continues only after everything queued on `src` so far
-static int chain(hipEvent_t ev, hipStream_t src, hipStream_t waiter) {
-  if (hipEventRecord(ev, src) != hipSuccess || hipStreamWaitEvent(waiter, ev, 0) != hipSuccess) {
-    set_error("esc_engine: stream event failed");
-    return ESC_ELAUNCH;
-  }
+// The fork/join protocol: `ev` marks everything queued on `src` so far; `waiter` continues only behind it.  (ESC_TRACE_LAUNCH=1
+// announces both, between the launches they order.)
+static int record(hipEvent_t ev, hipStream_t src) {
+  if (trace_launch()) fprintf(stderr, "[esc] record event %p stream %p\n", (void*)ev, (void*)src);
+  if (hipEventRecord(ev, src) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
   return ESC_OK;
+}
+static int wait(hipStream_t waiter, hipEvent_t ev) {
+  if (trace_launch()) fprintf(stderr, "[esc] wait event %p stream %p\n", (void*)ev, (void*)waiter);
+  if (hipStreamWaitEvent(waiter, ev, 0) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
+  return ESC_OK;
+}
+static int chain(hipEvent_t ev, hipStream_t src, hipStream_t waiter) {
+  ESC_TRY(record(ev, src));
+  return wait(waiter, ev);
 }
 
 // The same dependency on the ONE kernel launched while an ArmedEvent lives.  hipEventRecord queues a marker packet behind the
@@ -207,11 +206,24 @@ struct ArmedLastEvent {
 };
 static int chain_armed(hipEvent_t ev, const ArmedEvent& arm, hipStream_t src, hipStream_t waiter) {
   const bool bound = arm.on_ && take_launch_event() == nullptr;
-  if ((!bound && hipEventRecord(ev, src) != hipSuccess) || (waiter != nullptr && hipStreamWaitEvent(waiter, ev, 0) != hipSuccess)) {
-    set_error("esc_engine: stream event failed");
-    return ESC_ELAUNCH;
-  }
+  if (!bound) ESC_TRY(record(ev, src));
+  return waiter != nullptr ? wait(waiter, ev) : ESC_OK;
+}
+
+// The schedule's edge-term walk (engine_plan.h EdgeTerms), the same in the three forwards: `term(l)` launches e_l on the edge
+// pipeline and records e_ready[l].  The terms that go out before the node pipeline starts ...
+template <class Term>
+static int edge_terms_up_front(const EdgeTerms& t, int64_t L, Term&& term) {
+  for (int l = 0; l < (int)L; ++l)
+    if (t.up_front[l]) ESC_TRY(term(l));
   return ESC_OK;
+}
+// ... and the one queued behind layer l's aggregate on the node stream
+template <class Term>
+static int edge_term_behind_agg(const EdgeTerms& t, int l, EdgeStream& es, void* node_stream, Term&& term) {
+  if (t.behind_agg[l] < 0) return ESC_OK;
+  ESC_TRY(chain(es.agg_done[l], (hipStream_t)node_stream, es.stream));
+  return term(t.behind_agg[l]);
 }
 
 static Ctx edge_ctx(const Ctx& c, hipStream_t edge) {       // same job list / slab cursor: host-side bookkeeping only
@@ -244,8 +256,7 @@ static void mark(int which, void* stream) {
 // The LAST BatchNorm+ReLU of every node MLP is not materialised: the Linear writes its pre-BatchNorm rows straight into the
 // concat slice and the consumers apply relu(x*scale+shift) as they read them — the next layer's aggregate (forward and
 // backward, esc_gine_aggregate_*_affine) and the readout GEMM (prologue over all (L+1)*H columns).  One elementwise launch
-// less per layer on the dependent node chain.
-static bool fuse_node_act(const Ctx& c) { return c.act == 1 && c.y.H >= 64 && c.y.H % 4 == 0 && c.y.cat_scale != nullptr; }
+// less per layer on the dependent node chain.  (Schedule::node_act: ReLU models, H >= 64.)
 
 // ---- SyncBN (esc_engine_set_collective): statistics over all ranks of a graph-sharded step ----------------------------
 struct Collective {
@@ -255,6 +266,15 @@ struct Collective {
 };
 static Collective g_coll;
 static bool sync_on(const Ctx& c) { return c.train && g_coll.fn != nullptr && g_coll.world > 1; }
+// what a schedule is planned from (engine_plan.h): the entry calls this once its context has its job list
+static RunMode run_mode(const Ctx& c, int64_t edges, const void* x = nullptr, bool l1_head = false) {
+  RunMode r;
+  r.train = c.train; r.two_stream = edge_stream_for(edges).ok; r.deferred = c.jobs != nullptr; r.sync = sync_on(c);
+  r.l1_head = l1_head; r.plain_events = g_plain_events != 0; r.readout_one_launch = g_readout_one_launch != 0;
+  r.x = x;
+  r.linear = linear_plan_knobs(); r.aggregate = aggregate_plan_knobs(); r.bag = bag_plan_knobs();
+  return r;
+}
 static float* sync_buf(const Ctx& c) {
   EdgeStream& es = edge_stream();
   return (es.ok && c.s == (void*)es.stream) ? g_coll.buf_edge : g_coll.buf_node;
@@ -290,18 +310,13 @@ static int bn_backward(const Ctx& c, const float* X, int64_t ldx, const float* Y
 }
 
 // BatchNorm(+ReLU) backward next to a dropout: on_output == 0: dY = grad of dropout(act(bn(X))) (mask applied to dY first);
-// on_output == 1: X = dropout(input) (mask applied to the result).  One fused sequence when the operands allow it
-// (esc_bn_bwd_dropout), else the dropout backward as its own pass.  ReLU / no activation only (c.act in {0, 1}).
-static int bn_backward_drop(const Ctx& c, const float* X, int64_t ldx, const float* dY, int64_t lddy, int64_t M, const BnWs& w,
+// on_output == 1: X = dropout(input) (mask applied to the result).  `fused` (OgbSchedule::drop_*): one fused sequence
+// (esc_bn_bwd_dropout), else the dropout backward as its own pass.  Dense rows (leading dimension C); ReLU / no activation only.
+static int bn_backward_drop(const Ctx& c, bool fused, const float* X, int64_t ldx, const float* dY, int64_t lddy, int64_t M, const BnWs& w,
                             const esc_bn_t& bn, const uint8_t* mask, float p, int on_output, float* dX, int64_t lddx,
                             float* scratch, int64_t width = 0) {
   const int64_t C = width > 0 ? width : c.y.H;
   if (p <= 0.f) return bn_backward(c, X, ldx, nullptr, 0, dY, lddy, M, w, bn, dX, lddx, scratch, width);
-  const bool fused = !sync_on(c) && c.act <= 1 && ldx == C && lddy == C && lddx == C && esc_bn_bwd_dropout_ok(C, ldx, lddy, lddx) &&
-                     ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(dY) | reinterpret_cast<uintptr_t>(dX) |
-                       reinterpret_cast<uintptr_t>(w.mean) | reinterpret_cast<uintptr_t>(w.invstd) | reinterpret_cast<uintptr_t>(bn.gamma) |
-                       reinterpret_cast<uintptr_t>(bn.beta) | reinterpret_cast<uintptr_t>(scratch)) & 15) == 0 &&
-                     (reinterpret_cast<uintptr_t>(mask) & 3) == 0;
   if (fused)
     return esc_bn_bwd_dropout(X, ldx, dY, lddy, M, C, w.mean, w.invstd, bn.gamma, bn.beta, c.act, mask, p, on_output, dX, lddx,
                               bn.dgamma, bn.dbeta, scratch, c.s);
@@ -313,16 +328,16 @@ static int bn_backward_drop(const Ctx& c, const float* X, int64_t ldx, const flo
   return esc_dropout_bwd(dX, lddx, M, C, p, mask, nullptr, 0, dX, lddx, c.s);
 }
 
-// Y = X*W^T + b followed by BatchNorm coefficient computation (training: batch statistics; eval: running ones)
-static int linear_bn(const Ctx& c, const float* X, int64_t ld_x, const esc_linear_t& lin, const float* sc, const float* sh,
+// Y = X*W^T + b followed by BatchNorm coefficient computation, in the pair's scheduled mode (engine_plan.h BnMode)
+static int linear_bn(const Ctx& c, BnMode mode, const float* X, int64_t ld_x, const esc_linear_t& lin, const float* sc, const float* sh,
                      int64_t M, float* Y, const esc_bn_t& bn, const BnWs& w, int64_t ld_y = 0) {
   const LdsFloorGuard cap(c.on_edge_stream);
   const int64_t H = lin.out_dim, K = lin.in_dim;          // (the BatchNorm is as wide as the Linear's output)
   if (ld_y <= 0) ld_y = H;
   const bool sync = sync_on(c);     // statistics over all ranks: local ones first (no running update, no coefficients), then the exchange
-  // BatchNorm statistics from the producing GEMM's epilogue (no extra pass over Y): main chain only (col_stats is shared scratch)
-  const bool fused = c.train && H > 32 && c.jobs != nullptr;
-  if (fused && M > 1 && !sync) {    // ... and their merge by the GEMM's last workgroup (no bn_finalize launch)
+  // BatchNorm statistics from the producing GEMM's epilogue (no extra pass over Y)
+  const bool fused = mode == BN_EPILOGUE_PARTIALS;
+  if (mode == BN_EPILOGUE_MERGED) {    // ... and their merge by the GEMM's last workgroup (no bn_finalize launch)
     esc_bn_fuse f{bn.eps, bn.momentum, w.mean, w.invstd, bn.running_mean, bn.running_var, bn.gamma, bn.beta, w.scale, w.shift};
     return esc_linear_bn_fwd(X, ld_x, lin.w, K, lin.b, sc, sh, M, H, K, Y, ld_y, c.y.col_stats, &f, c.s);
   }
@@ -334,7 +349,7 @@ static int linear_bn(const Ctx& c, const float* X, int64_t ld_x, const esc_linea
                                             sync ? nullptr : w.shift, c.s));
     return sync ? bn_sync_forward(c, M, bn, w, H) : ESC_OK;
   }
-  if (c.train) {
+  if (mode == BN_STATS_PASS) {
     ESC_TRY(esc_bn_stats(Y, ld_y, M, H, bn.eps, bn.momentum, w.mean, w.invstd, sync ? nullptr : bn.running_mean,
                          sync ? nullptr : bn.running_var, bn.gamma, bn.beta, sync ? nullptr : w.scale, sync ? nullptr : w.shift,
                          c.y.bn_scratch, c.s));
@@ -356,89 +371,62 @@ static int bn_coeffs(const Ctx& c, const float* X, int64_t ld, int64_t M, const 
 }
 
 // Linear, BN, ReLU, Linear, BN, ReLU  (reference :65-73, :78-87) -> out (materialised, ld_out)
-static int mlp_forward(const Ctx& c, const esc_mlp_t& p, const MlpWs& w, const float* A, int64_t ld_a, int64_t M,
+static int mlp_forward(const Ctx& c, const esc_mlp_t& p, const MlpWs& w, const BnMode (&mode)[2], const float* A, int64_t ld_a, int64_t M,
                        float* out, int64_t ld_out, bool pre_out = false) {
   const int64_t H = c.y.H;
-  if (pre_out) {                              // `out` receives the PRE-BatchNorm rows of lin1; w.b1 holds the coefficients
-    ESC_TRY(linear_bn(c, A, ld_a, p.lin0, nullptr, nullptr, M, w.Y0, p.bn0, w.b0));
-    return linear_bn(c, w.Y0, H, p.lin1, w.b0.scale, w.b0.shift, M, out, p.bn1, w.b1, ld_out);
-  }
-  ESC_TRY(linear_bn(c, A, ld_a, p.lin0, nullptr, nullptr, M, w.Y0, p.bn0, w.b0));
+  ESC_TRY(linear_bn(c, mode[0], A, ld_a, p.lin0, nullptr, nullptr, M, w.Y0, p.bn0, w.b0));
+  if (pre_out)                                // `out` receives the PRE-BatchNorm rows of lin1; w.b1 holds the coefficients
+    return linear_bn(c, mode[1], w.Y0, H, p.lin1, w.b0.scale, w.b0.shift, M, out, p.bn1, w.b1, ld_out);
   if (w.A1) {                                 // activation other than ReLU: the hidden activation is written once
     ESC_TRY(esc_affine_act(w.Y0, H, M, H, w.b0.scale, w.b0.shift, c.act, w.A1, H, c.s));
-    ESC_TRY(linear_bn(c, w.A1, H, p.lin1, nullptr, nullptr, M, w.Y1, p.bn1, w.b1));
+    ESC_TRY(linear_bn(c, mode[1], w.A1, H, p.lin1, nullptr, nullptr, M, w.Y1, p.bn1, w.b1));
     return esc_affine_act(w.Y1, H, M, H, w.b1.scale, w.b1.shift, c.act, out, ld_out, c.s);
   }
-  ESC_TRY(linear_bn(c, w.Y0, H, p.lin1, w.b0.scale, w.b0.shift, M, w.Y1, p.bn1, w.b1));
+  ESC_TRY(linear_bn(c, mode[1], w.Y0, H, p.lin1, w.b0.scale, w.b0.shift, M, w.Y1, p.bn1, w.b1));
   return esc_affine_act(w.Y1, H, M, H, w.b1.scale, w.b1.shift, 1, out, ld_out, c.s);
 }
 
-// given dOut (grad of the materialised output `out`), produce parameter grads and, if dA != NULL, dA
-// Which of an MLP's two Linear backwards take the fused form (see kBnBwdApplyInGemm)?  ReLU MLPs whose hidden activation was never
-// materialised (counting model), statistics of this rank only, shapes the fused kernels serve; lin0 only together with lin1.
-struct MlpFuse { bool lin1 = false, lin0 = false; };
-static MlpFuse mlp_fuse_plan(const Ctx& c, const esc_mlp_t& p, const MlpWs& w, const float* A, int64_t ld_a, int64_t M, const float* out,
-                             int64_t ld_out, const float* dOut, int64_t ld_dout, const float* dA, int64_t ld_da, bool pre_out) {
+// given o.dOut (grad of the MLP's output), produce parameter grads and, if o.dA != NULL, dA — in the form the schedule chose
+// (engine_plan.h MlpBwd; the fused entries refuse a call their plan does not serve)
+static int mlp_backward(const Ctx& c, const MlpOps& o, const MlpBwd& how) {
   const Layout& y = c.y;
-  const int64_t H = y.H;
-  MlpFuse f;
-  if (!(kBnBwdApplyInGemm && c.train && !sync_on(c) && y.bst_part != nullptr && p.lin1.in_dim == H && p.lin1.out_dim == H)) return f;
-  if (!(c.act == 1 && w.A1 == nullptr)) return f;     // (ELU models keep the elementwise launches: DESIGN.md *Retired step-engine switches*)
-  const esc_bn_bwd_fused f1 = bn_fused(pre_out ? out : w.Y1, pre_out ? ld_out : H, w.b1, c.act, p.bn1.beta), f0 = bn_fused(w.Y0, H, w.b0, c.act, p.bn0.beta);
-  const esc_bn_bwd_next n0{y.bst_part, w.Y0, H, w.b0.mean, w.b0.invstd, w.b0.scale, w.b0.shift, c.act, p.bn0.beta};
-  const float* slab_probe = c.slabs->peek();
-  f.lin1 = esc_linear_bwd_both_bn_ok(dOut, ld_dout, &f1, w.Y0, H, p.lin1.w, H, M, H, H, y.dT2, H, slab_probe, &n0) != 0;   // (lin1's input: Y0's pre-BatchNorm rows)
-  f.lin0 = f.lin1 && esc_linear_bwd_both_bn_ok(y.dT2, H, &f0, A, ld_a, p.lin0.w, p.lin0.in_dim, M, H, p.lin0.in_dim, dA, ld_da, slab_probe, nullptr) != 0;
-  return f;
-}
-// (callers that can leave BatchNorm 1's column sums ask whether they will be consumed)
-static bool mlp_backward_fused(const Ctx& c, const esc_mlp_t& p, const MlpWs& w, const float* A, int64_t ld_a, int64_t M, const float* out,
-                               int64_t ld_out, const float* dOut, int64_t ld_dout, const float* dA, int64_t ld_da, bool pre_out) {
-  return mlp_fuse_plan(c, p, w, A, ld_a, M, out, ld_out, dOut, ld_dout, dA, ld_da, pre_out).lin1;
-}
-// have_slots > 0: the column sums of BatchNorm 1's backward are already in c.y.bst_part (float2[have_slots][H], left by the
-// producer of dOut: the readout's dX epilogue or the next layer's aggregate backward)
-static int mlp_backward(const Ctx& c, const esc_mlp_t& p, const MlpWs& w, const float* A, int64_t ld_a, int64_t M,
-                        const float* out, int64_t ld_out, const float* dOut, int64_t ld_dout, float* dA,
-                        int64_t ld_da, bool pre_out = false, int64_t have_slots = 0) {
-  const Layout& y = c.y;
-  const int64_t H = y.H;
-  const MlpFuse fuse = mlp_fuse_plan(c, p, w, A, ld_a, M, out, ld_out, dOut, ld_dout, dA, ld_da, pre_out);
-  if (fuse.lin1) {
-    const float* x1 = pre_out ? out : w.Y1;                  // what BatchNorm 1 normalised
-    const int64_t ld_x1 = pre_out ? ld_out : H;
-    const esc_bn_bwd_fused f1 = bn_fused(x1, ld_x1, w.b1, c.act, p.bn1.beta), f0 = bn_fused(w.Y0, H, w.b0, c.act, p.bn0.beta);
-    esc_bn_bwd_next n0{y.bst_part, w.Y0, H, w.b0.mean, w.b0.invstd, w.b0.scale, w.b0.shift, c.act, p.bn0.beta};
+  const int64_t H = y.H, M = o.M;
+  const esc_mlp_t& p = *o.p;
+  const MlpWs& w = *o.w;
+  if (how.fuse.lin1) {
+    const esc_bn_bwd_fused f1 = mlp_fused1(y, o, c.act), f0 = mlp_fused0(y, o, c.act);
+    const esc_bn_bwd_next n0 = mlp_next(y, o, c.act);
     // (activation derivatives are recomputed from the pre-BatchNorm rows everywhere — Y == NULL — so that the sums and the
     // fused apply see the same values)
-    if (have_slots > 0)
-      ESC_TRY(esc_bn_bwd_coef_from_partials(y.bst_part, have_slots, M, H, w.b1.coef, p.bn1.dgamma, p.bn1.dbeta, c.s));
+    if (how.sums != SUMS_OWN_PASS)
+      ESC_TRY(esc_bn_bwd_coef_from_partials(y.bst_part, how.slots, M, H, w.b1.coef, p.bn1.dgamma, p.bn1.dbeta, c.s));
     else
-      ESC_TRY(esc_bn_bwd_coef(x1, ld_x1, nullptr, 0, dOut, ld_dout, M, H, w.b1.mean, w.b1.invstd, p.bn1.gamma, p.bn1.beta, c.act, w.b1.coef,
+      ESC_TRY(esc_bn_bwd_coef(f1.x, f1.ld_x, nullptr, 0, o.dOut, o.ld_dout, M, H, w.b1.mean, w.b1.invstd, p.bn1.gamma, p.bn1.beta, c.act, w.b1.coef,
                               p.bn1.dgamma, p.bn1.dbeta, y.bn_scratch, c.s));
-    ESC_TRY(linear_backward_bn(c, dOut, ld_dout, f1, w.Y0, H, w.b0.scale, w.b0.shift, p.lin1, M, y.dT2, H, 0, &n0));
-    ESC_TRY(esc_bn_bwd_coef_from_partials(y.bst_part, cdiv(M, esc_linear_bwd_bn_block_rows(M, H, H)), M, H, w.b0.coef, p.bn0.dgamma, p.bn0.dbeta, c.s));
-    if (fuse.lin0) return linear_backward_bn(c, y.dT2, H, f0, A, ld_a, nullptr, nullptr, p.lin0, M, dA, ld_da, 0, nullptr);
+    ESC_TRY(linear_backward_bn(c, o.dOut, o.ld_dout, f1, w.Y0, H, w.b0.scale, w.b0.shift, p.lin1, M, y.dT2, H, 0, &n0));
+    ESC_TRY(esc_bn_bwd_coef_from_partials(y.bst_part, cdiv(M, plan::bwd_bn_block_rows(M, H, H)), M, H, w.b0.coef, p.bn0.dgamma, p.bn0.dbeta, c.s));
+    if (how.fuse.lin0) return linear_backward_bn(c, y.dT2, H, f0, o.A, o.ld_a, nullptr, nullptr, p.lin0, M, o.dA, o.ld_da, 0, nullptr);
     // lin0's shape is not served by the fused kernels (e.g. a 32-wide input): the apply as its own pass, then the plain backward
     ESC_TRY(esc_bn_bwd_apply(w.Y0, H, nullptr, 0, y.dT2, H, M, H, w.b0.mean, w.b0.invstd, p.bn0.gamma, p.bn0.beta, c.act, w.b0.coef, y.dT2, H, c.s));
-    return linear_backward(c, y.dT2, H, A, ld_a, nullptr, nullptr, p.lin0, M, dA, ld_da, 0);
+    return linear_backward(c, y.dT2, H, o.A, o.ld_a, nullptr, nullptr, p.lin0, M, o.dA, o.ld_da, 0);
   }
-  if (pre_out) ESC_TRY(bn_backward(c, out, ld_out, nullptr, 0, dOut, ld_dout, M, w.b1, p.bn1, y.dT1, H, y.bn_scratch));   // `out` = pre-BN rows
-  else         ESC_TRY(bn_backward(c, w.Y1, H, out, ld_out, dOut, ld_dout, M, w.b1, p.bn1, y.dT1, H, y.bn_scratch));
+  if (o.pre_out) ESC_TRY(bn_backward(c, o.out, o.ld_out, nullptr, 0, o.dOut, o.ld_dout, M, w.b1, p.bn1, y.dT1, H, y.bn_scratch));   // `out` = pre-BN rows
+  else           ESC_TRY(bn_backward(c, w.Y1, H, o.out, o.ld_out, o.dOut, o.ld_dout, M, w.b1, p.bn1, y.dT1, H, y.bn_scratch));
   if (w.A1) {
     ESC_TRY(linear_backward(c, y.dT1, H, w.A1, H, nullptr, nullptr, p.lin1, M, y.dT2, H, 0));
     ESC_TRY(bn_backward(c, w.Y0, H, w.A1, H, y.dT2, H, M, w.b0, p.bn0, y.dT2, H, y.bn_scratch));
-    return linear_backward(c, y.dT2, H, A, ld_a, nullptr, nullptr, p.lin0, M, dA, ld_da, 0);
+    return linear_backward(c, y.dT2, H, o.A, o.ld_a, nullptr, nullptr, p.lin0, M, o.dA, o.ld_da, 0);
   }
   ESC_TRY(linear_backward(c, y.dT1, H, w.Y0, H, w.b0.scale, w.b0.shift, p.lin1, M, y.dT2, H, 0));
   ESC_TRY(bn_backward(c, w.Y0, H, nullptr, 0, y.dT2, H, M, w.b0, p.bn0, y.dT2, H, y.bn_scratch));
-  return linear_backward(c, y.dT2, H, A, ld_a, nullptr, nullptr, p.lin0, M, dA, ld_da, 0);
+  return linear_backward(c, y.dT2, H, o.A, o.ld_a, nullptr, nullptr, p.lin0, M, o.dA, o.ld_da, 0);
 }
 
 static int forward(const Ctx& c) {
   const esc_nested_gin_t* m = c.m;
   const esc_batch_t* b = c.b;
   const Layout& y = c.y;
+  const Schedule& sch = c.sch;
   const int64_t N = y.N, E = y.E, H = y.H, L = y.L, W = y.W;
   // ---- edge pipeline: ESC bag, z_embedding (reference :155-156) and the edge terms e_l = lin_l(z_emb) of ALL layers
   // (:161,:169 inside GINEConv).  It touches the node chain only through e_l, so it runs on the edge stream — for batches of at
@@ -458,7 +446,7 @@ static int forward(const Ctx& c) {
   }
   // ESC bag (esc_bag_fwd_rows; the LDS-staged table slices are an option that is off by default); in training mode its epilogue
   // leaves the BatchNorm partials of z_embedding's first BatchNorm, so the statistics pass over the E x H output is one finalize launch
-  const int64_t bag_block = (c.train && !sync_on(ce)) ? esc_bag_fwd_stats_block_rows(m->z_table, m->z_rows, H, y.Zb, H, E) : 0;
+  const int64_t bag_block = sch.bag_block;
   if (bag_block > 0) {
     ESC_TRY(esc_bag_fwd_rows(m->z_table, m->z_rows, H, b->row_ptr, b->bag_idx, b->bag_val, E, y.Zb, H, 0, ce.y.col_stats, ce.s));
     if (c.fast_seam) ESC_TRY(chain(es.z_ready, (hipStream_t)c.s, es.stream));       // seam_chain
@@ -472,15 +460,14 @@ static int forward(const Ctx& c) {
   // Edge-sized activations are materialised: the affine+ReLU prologue costs the edge-row GEMMs ~25 % (VALU-bound staging), more
   // than the two extra elementwise passes that write them once; node-sized MLP activations stay fused.
   ESC_TRY(esc_affine_act(y.Zb, H, E, H, y.zb0.scale, y.zb0.shift, 1, y.A0, H, ce.s));
-  ESC_TRY(linear_bn(ce, y.A0, H, m->zlin, nullptr, nullptr, E, y.Yz, m->zbn1, y.zb1));       // z_emb = relu(Yz*scale+shift)
+  ESC_TRY(linear_bn(ce, sch.zlin, y.A0, H, m->zlin, nullptr, nullptr, E, y.Yz, m->zbn1, y.zb1));       // z_emb = relu(Yz*scale+shift)
   // The first edge term is narrow (in_dim columns: a bandwidth pass over z_emb): it applies z_embedding's last BatchNorm+ReLU to
   // its operand itself and runs BEFORE the pass that materialises z_emb for the wide layers — the node chain's first
   // aggregate waits for e_0 only (same fmaf + max per element: e_0 is bit-identical either way).  It went there when node layer 0
   // was the later pipeline; since the batched launch below the two are level (layer 0 ends with the batched GEMM), and launching
   // e_0 from the node stream instead brings the GEMM forward by 10 us without moving the end of the forward (DESIGN.md *Step
   // engine, fork and join*): it stays here.
-  const bool e0_early = y.C0 <= 32 && L >= 1;
-  if (e0_early) {
+  if (sch.e0_early) {
     const LdsFloorGuard cap(ce.on_edge_stream);
     const ArmedEvent arm(es.e_ready[0], es.ok);
     ESC_TRY(esc_linear_fwd(y.Yz, H, m->conv[0].lin.w, H, m->conv[0].lin.b, y.zb1.scale, y.zb1.shift, E, y.C0, H, y.e[0], y.ld_e[0], nullptr, ce.s));
@@ -495,13 +482,12 @@ static int forward(const Ctx& c) {
     const esc_conv_t& cv = m->conv[l];
     const int64_t C = l == 0 ? y.C0 : H;
     ESC_TRY(esc_linear_fwd(y.Zemb, H, cv.lin.w, H, cv.lin.b, nullptr, nullptr, E, C, H, y.e[l], y.ld_e[l], nullptr, ce.s));
-    if (es.ok && hipEventRecord(es.e_ready[l], es.stream) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
-    return ESC_OK;
+    return es.ok ? record(es.e_ready[l], es.stream) : ESC_OK;
   };
   mark(PH_START, c.s);
-  const bool batched = y.e_cat != nullptr;
+  const bool batched = sch.terms.batched;
+  ESC_TRY(edge_terms_up_front(sch.terms, L, edge_term));
   if (batched) {                                            // e_1 .. e_{L-1} in one launch over the packed weights
-    if (!e0_early) ESC_TRY(edge_term(0));
     esc_table_list tl{};
     tl.count = 2 * ((int)L - 1);
     for (int l = 1; l < (int)L; ++l) {
@@ -516,10 +502,8 @@ static int forward(const Ctx& c) {
       if (es.ok) ESC_TRY(chain_armed(es.e_ready[1], arm, es.stream, nullptr));
     }
     for (int l = 2; l < (int)L; ++l)
-      if (es.ok && hipEventRecord(es.e_ready[l], es.stream) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
+      if (es.ok) ESC_TRY(record(es.e_ready[l], es.stream));
   }
-  const int ahead = batched ? 0 : (es.ok ? 1 : (int)L);          // one stream: all of them up front, in layer order
-  for (int l = e0_early ? 1 : 0; l < (int)L && l < ahead; ++l) ESC_TRY(edge_term(l));
   // ---- node pipeline (first, while it would otherwise wait for the first edge term: the chunk schedule of the bag
   // gradient, which depends on the batch's index arrays only)
   if (c.train) {                                             // ... and the BatchNorm step counters, in that same launch
@@ -529,7 +513,7 @@ static int forward(const Ctx& c) {
     ESC_TRY(bag_bwd_classify_counted(b->col_row, y.Z, H, E, y.bag_scratch, cnt, c.s));
   }
   // xs[0] = x_embedding(x) (reference :166)
-  ESC_TRY(mlp_forward(c, m->xemb, y.xemb, b->x, y.C0, N, y.cat, W, fuse_node_act(c)));
+  ESC_TRY(mlp_forward(c, m->xemb, y.xemb, sch.xemb, b->x, y.C0, N, y.cat, W, sch.node_act));
   // GINE layers (reference :161, :167-175): xs[l+1] -> cat[:, (l+1)H : (l+2)H]
   for (int l = 0; l < L; ++l) {
     const esc_conv_t& cv = m->conv[l];
@@ -537,26 +521,23 @@ static int forward(const Ctx& c) {
     const float* hin = l == 0 ? b->x : y.cat + (int64_t)l * H;
     const int64_t ld_h = l == 0 ? y.C0 : W;
     // (batched edge terms: e_1 .. e_{L-1} come out of one launch, the wait in front of layer 1 covers the later layers: -7 us of step time)
-    if (es.ok && !(batched && l >= 2) && hipStreamWaitEvent((hipStream_t)c.s, es.e_ready[l], 0) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
-    if (fuse_node_act(c) && l > 0)          // hin = pre-BatchNorm rows of the previous layer: relu(x*scale+shift) on the fly
+    if (es.ok && !(batched && l >= 2)) ESC_TRY(wait((hipStream_t)c.s, es.e_ready[l]));
+    if (sch.node_act && l > 0)          // hin = pre-BatchNorm rows of the previous layer: relu(x*scale+shift) on the fly
       ESC_TRY(esc_gine_aggregate_fwd_affine(hin, ld_h, y.cat_scale + (int64_t)l * H, y.cat_shift + (int64_t)l * H, y.e[l], y.ld_e[l], b->in_ptr,
                                             b->in_edge, b->in_src, cv.eps, N, C, y.agg[l], C, c.s));
     else
       ESC_TRY(esc_gine_aggregate_fwd(hin, ld_h, y.e[l], y.ld_e[l], b->in_ptr, b->in_edge, b->in_src, cv.eps, N, C, y.agg[l], C, c.s));
-    if (!batched && es.ok && l + ahead < (int)L) {
-      ESC_TRY(chain(es.agg_done[l], (hipStream_t)c.s, es.stream));
-      ESC_TRY(edge_term(l + ahead));
-    }
-    ESC_TRY(mlp_forward(c, cv.nn, y.conv[l], y.agg[l], C, N, y.cat + (int64_t)(l + 1) * H, W, fuse_node_act(c)));
+    ESC_TRY(edge_term_behind_agg(sch.terms, l, es, c.s, edge_term));
+    ESC_TRY(mlp_forward(c, cv.nn, y.conv[l], sch.conv[l], y.agg[l], C, N, y.cat + (int64_t)(l + 1) * H, W, sch.node_act));
   }
   if (c.train) mark(PH_EDGE_FWD_DONE, ce.s);
   // readout (reference :183-189)
-  const bool fa = fuse_node_act(c);       // cat holds pre-BatchNorm rows: the readout GEMM applies every slice's BatchNorm+ReLU itself
-  ESC_TRY(linear_bn(c, y.cat, W, m->lin1, fa ? y.cat_scale : nullptr, fa ? y.cat_shift : nullptr, N, y.Yl, m->bn_lin1, y.bl));
+  const bool fa = sch.node_act;           // cat holds pre-BatchNorm rows: the readout GEMM applies every slice's BatchNorm+ReLU itself
+  ESC_TRY(linear_bn(c, sch.readout, y.cat, W, m->lin1, fa ? y.cat_scale : nullptr, fa ? y.cat_shift : nullptr, N, y.Yl, m->bn_lin1, y.bl));
   // train_step: the head's launch leaves the L1 gradient of every prediction too, so the backward starts behind it and the loss
   // launch (a single workgroup walking all predictions, 5-7 us) leaves the chain: the edge stream continues behind the head
   // (train_step_impl() puts the loss value there)
-  if (c.l1_target != nullptr && esc_linear_fwd_l1_ok(y.Yl, H, m->lin2.w, H, y.bl.scale, y.bl.shift)) {
+  if (sch.l1_head) {
     const ArmedEvent arm(es.lin1_fork, es.ok);
     ESC_TRY(esc_linear_fwd_l1(y.Yl, H, m->lin2.w, m->lin2.b, y.bl.scale, y.bl.shift, N, H, c.l1_target, c.l1_denom, 1.0f, y.pred, y.dpred, c.s));
     return es.ok ? chain_armed(es.lin1_fork, arm, (hipStream_t)c.s, es.stream) : ESC_OK;
@@ -622,8 +603,8 @@ static int finish_pending(Pending& p) {
   p.open = false;
   EdgeStream& es = edge_stream();
   const bool edge_reduced = p.join && p.edge_jobs.empty();      // (backward(): the edge stream has run its last reduce itself)
-  if (p.join && p.halves && !g_legacy_seam && hipEventRecord(es.caller_done, p.stream) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
-  if (p.join && hipStreamWaitEvent(p.stream, es.joined, 0) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
+  if (p.join && p.halves && !g_legacy_seam) ESC_TRY(record(es.caller_done, p.stream));
+  if (p.join) ESC_TRY(wait(p.stream, es.joined));
   if (!p.edge_jobs.empty()) ESC_TRY(esc_slab_reduce_jobs(p.edge_jobs.data(), (int)p.edge_jobs.size(), p.stream));
   p.edge_jobs.clear();
   mark(PH_END, p.stream);
@@ -653,20 +634,9 @@ static int backward(const Ctx& c, Pending* defer) {
   // lin2 <- dpred
   ESC_TRY(linear_backward(c, y.dpred, 1, y.Yl, H, y.bl.scale, y.bl.shift, m->lin2, N, y.dAl, H, 0));
   // bn_lin1 backward: folded into lin1's backward when the fused kernels serve its column blocks (see kBnBwdApplyInGemm)
-  const bool split_lin1 = es.ok && c.jobs != nullptr && L >= 1;
-  const esc_bn_bwd_fused fl = bn_fused(y.Yl, H, y.bl, 1, m->bn_lin1.beta);
-  const bool fa_l = fuse_node_act(c);
-  // the last layer's output gradient d(cat)[:, L*H:] is final once lin1's node-side block has written it: its dX tiles
-  // leave the column sums of that layer's last BatchNorm backward (kBnBwdSumsFromDx)
-  const MlpWs& wl = y.conv[L > 0 ? L - 1 : 0];
-  esc_bn_bwd_next nl{y.bst_part, y.cat + L * H, W, wl.b1.mean, wl.b1.invstd, wl.b1.scale, wl.b1.shift, 1, nullptr};     // (ReLU: beta is not read)
-  auto lin1_ok = [&](int64_t col0, int64_t ncols, const esc_bn_bwd_next* nx) {
-    return esc_linear_bwd_both_bn_ok(y.dAl, H, &fl, y.cat + col0, W, m->lin1.w + col0, W, N, H, ncols, y.dcat + col0, W,
-                                     c.slabs->peek(), nx) != 0;
-  };
-  const bool fuse_l = kBnBwdApplyInGemm && c.act == 1 && !sync_on(c) && y.bst_part != nullptr &&
-                      (split_lin1 ? (lin1_ok(0, L * H, nullptr) && lin1_ok(L * H, H, nullptr)) : lin1_ok(0, W, nullptr));
-  int64_t last_slots = 0;          // > 0: slots of bst_part that hold the last layer's BatchNorm-backward sums
+  const Schedule& sch = c.sch;
+  const bool split_lin1 = sch.split_lin1, fuse_l = sch.fuse_lin1, fa_l = sch.node_act;
+  const esc_bn_bwd_fused fl = readout_fused(m, y);
   bool k0_split = false;           // the edge stream's lin1 block went out as two launches: its dW slabs are ready behind lin1_dw
   bool fork_bound = false;         // lin1_fork is the stop event of the coefficient call's last launch: no record in front of the H block
   if (fuse_l) {
@@ -691,27 +661,22 @@ static int backward(const Ctx& c, Pending* defer) {
       return esc_linear_bwd_both_deferred(y.dAl, H, y.cat + col0, W, fa ? y.cat_scale + col0 : nullptr, fa ? y.cat_shift + col0 : nullptr, m->lin1.w + col0, W, N, H, ncols,
                                           y.dcat + col0, W, 0, m->lin1.dw + col0, W, db, s.p, s.job, stream);
     };
-    if ((!fork_bound && hipEventRecord(es.lin1_fork, (hipStream_t)c.s) != hipSuccess) || hipStreamWaitEvent(es.stream, es.lin1_fork, 0) != hipSuccess) {
-      set_error("esc_engine: stream event failed");
-      return ESC_ELAUNCH;
-    }
+    if (!fork_bound) ESC_TRY(record(es.lin1_fork, (hipStream_t)c.s));
+    ESC_TRY(wait(es.stream, es.lin1_fork));
     // the node chain needs this block's dX (lin1_rest, in front of the last layer's aggregate backward) long before anyone needs
     // its dW slabs (lin1_dw, in front of the node-side slab reduce): two launches, the chain waits for the first only
     {
       const LdsFloorGuard cap(true);
-      const bool ask = fuse_l && !g_readout_one_launch && !g_plain_events;
-      if (ask) request_dual_split(DualSplit{es.lin1_rest, es.lin1_dw, kReadoutDxLds});
+      if (sch.ask_dx_split) request_dual_split(DualSplit{es.lin1_rest, es.lin1_dw, kReadoutDxLds});
       const int rc = part(es.stream, 0, K0, nullptr, nullptr);
-      k0_split = !take_dual_split() && ask;                                    // (a pending request: the call did not split)
+      k0_split = !take_dual_split() && sch.ask_dx_split;                       // (a pending request: the call did not split)
       ESC_TRY(rc);
+      ESC_REQUIRE(k0_split == sch.dx_split, "esc_engine: the readout block's launches disagree with the schedule");
     }
-    if (!k0_split && hipEventRecord(es.lin1_rest, es.stream) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
-    // (the last layer's MLP backward follows at once: does it take the fused form, and can this block leave its sums?)
-    const bool leave = fuse_l && fa_l && kBnBwdSumsFromDx && lin1_ok(K0, H, &nl) &&
-                       mlp_backward_fused(c, m->conv[L - 1].nn, y.conv[L - 1], y.agg[L - 1], L == 1 ? y.C0 : H, N, y.cat + L * H, W, y.dcat + L * H, W,
-                                          y.dagg, L == 1 ? y.C0 : H, true);
-    ESC_TRY(part(c.s, K0, H, m->lin1.db, leave ? &nl : nullptr));
-    if (leave) last_slots = cdiv(N, esc_linear_bwd_bn_block_rows(N, H, H));
+    if (!k0_split) ESC_TRY(record(es.lin1_rest, es.stream));
+    // (the last layer's MLP backward follows at once: it takes the sums this block's dX tiles leave)
+    const esc_bn_bwd_next nl = readout_next(y);
+    ESC_TRY(part(c.s, K0, H, m->lin1.db, sch.mlp[L - 1].sums == SUMS_READOUT ? &nl : nullptr));
   } else if (fuse_l) {
     ESC_TRY(linear_backward_bn(c, y.dAl, H, fl, y.cat, W, fa_l ? y.cat_scale : nullptr, fa_l ? y.cat_shift : nullptr, m->lin1, N, y.dcat, W, 0, nullptr));
   } else {
@@ -723,30 +688,22 @@ static int backward(const Ctx& c, Pending* defer) {
   edge_jobs.reserve(ESC_MAX_REDUCE_JOBS);    // the node pipeline's while the edge tail is still running
   if (es.ok && c.jobs) ce.jobs = &edge_jobs;
   std::vector<esc_sum_job> eps_jobs;
-  int64_t agg_slots = 0;            // > 0: the aggregate backward of the layer above left this layer's BatchNorm sums in bst_part
   for (int l = (int)L - 1; l >= 0; --l) {
     const esc_conv_t& cv = m->conv[l];
     const int64_t C = l == 0 ? y.C0 : H;
     const float* hin = l == 0 ? b->x : y.cat + (int64_t)l * H;
     const int64_t ld_h = l == 0 ? y.C0 : W;
-    ESC_TRY(mlp_backward(c, cv.nn, y.conv[l], y.agg[l], C, N, y.cat + (int64_t)(l + 1) * H, W,
-                         y.dcat + (int64_t)(l + 1) * H, W, y.dagg, C, fuse_node_act(c), l == (int)L - 1 ? last_slots : agg_slots));
-    agg_slots = 0;
+    ESC_TRY(mlp_backward(c, conv_mlp_ops(m, y, l, sch.node_act), sch.mlp[l]));
     float* dx = l == 0 ? nullptr : y.dcat + (int64_t)l * H;            // accumulate into the previous slice
-    if (split_lin1 && l == (int)L - 1 &&                               // ... which the edge stream's lin1 blocks fill
-        hipStreamWaitEvent((hipStream_t)c.s, es.lin1_rest, 0) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
+    if (split_lin1 && l == (int)L - 1) ESC_TRY(wait((hipStream_t)c.s, es.lin1_rest));      // ... which the edge stream's lin1 blocks fill
     // (kBnBwdSumsFromAgg) d(cat)[:, l*H:(l+1)*H] is final once this launch has added its share: it leaves the column sums of the PREVIOUS layer's
     // last BatchNorm backward, and that layer's MLP backward starts with the finalize
     const ArmedEvent arm(es.de_ready[l], es.ok);        // d_e[l] comes out of the aggregate backward: one launch, whichever form
-    const bool stats_here = fuse_node_act(c) && l > 0 && kBnBwdSumsFromAgg && esc_gine_aggregate_bwd_deps_slots(C) == 1 && C <= 2048 &&
-                            mlp_backward_fused(c, m->conv[l - 1].nn, y.conv[l - 1], y.agg[l - 1], l - 1 == 0 ? y.C0 : H, N, y.cat + (int64_t)l * H, W,
-                                               y.dcat + (int64_t)l * H, W, y.dagg, l - 1 == 0 ? y.C0 : H, true);
-    if (stats_here) {
+    if (sch.agg[l] == AGG_AFFINE_STATS) {
       ESC_TRY(esc_gine_aggregate_bwd_affine_stats(hin, ld_h, y.cat_scale + (int64_t)l * H, y.cat_shift + (int64_t)l * H, y.conv[l - 1].b1.mean,
                                                   y.conv[l - 1].b1.invstd, y.e[l], y.ld_e[l], y.dagg, C, b->out_ptr, b->out_edge, b->out_dst, cv.eps, N, C,
                                                   y.d_e[l], C, dx, W, 1, y.deps_part + (int64_t)l * 2 * N, y.bst_part, c.s));
-      agg_slots = esc_gine_aggregate_bwd_stats_slots(N);
-    } else if (fuse_node_act(c) && l > 0)
+    } else if (sch.agg[l] == AGG_AFFINE)
       ESC_TRY(esc_gine_aggregate_bwd_affine(hin, ld_h, y.cat_scale + (int64_t)l * H, y.cat_shift + (int64_t)l * H, y.e[l], y.ld_e[l], y.dagg, C,
                                             b->out_ptr, b->out_edge, b->out_dst, cv.eps, N, C, y.d_e[l], C, dx, W, 1,
                                             y.deps_part + (int64_t)l * 2 * N, c.s));
@@ -756,7 +713,7 @@ static int backward(const Ctx& c, Pending* defer) {
     eps_jobs.push_back(esc_sum_job{y.deps_part + (int64_t)l * 2 * N, N * esc_gine_aggregate_bwd_deps_slots(C), cv.deps});
     if (es.ok) ESC_TRY(chain_armed(es.de_ready[l], arm, (hipStream_t)c.s, es.stream));   // lin_l backward: edge stream
     const float* zin = y.Zemb;
-    if (l == 0 && es.ok && c.jobs) {
+    if (l == 0 && sch.last_dw_on_node) {
       // the LAST lin backward sits in the tail of the step: only its input gradient (which completes d(z_emb)) stays on
       // the edge stream; the weight gradient runs on the node stream, which has nothing left to do.  Measured neutral when it
       // went in (1.038 vs 1.031-1.044 ms by the phase marks): the node stream's own reductions then become the end of the
@@ -778,7 +735,7 @@ static int backward(const Ctx& c, Pending* defer) {
     }
   }
   // x_embedding backward (input x needs no gradient): only reads d(cat)[:, 0:H]
-  ESC_TRY(mlp_backward(c, m->xemb, y.xemb, b->x, y.C0, N, y.cat, W, y.dcat, W, nullptr, 0, fuse_node_act(c)));
+  ESC_TRY(mlp_backward(c, xemb_mlp_ops(m, y, b->x, sch.node_act), sch.xemb_bwd));
   // z_embedding + bag: the tail of the edge pipeline (d(z_emb) is complete in edge-stream order); it overlaps the
   // x_embedding backward queued above on the node stream
   // (the ReLU mask is recomputed from the pre-BN value even though the activation was materialised: one array less to read)
@@ -793,7 +750,7 @@ static int backward(const Ctx& c, Pending* defer) {
   mark(PH_EDGE_BWD_DONE, ce.s);
   // node-side reductions first (with an edge stream they overlap its tail), then join, then the edge-side ones
   if (!eps_jobs.empty()) ESC_TRY(esc_reduce_sum_jobs(eps_jobs.data(), (int)eps_jobs.size(), c.s));
-  if (k0_split && hipStreamWaitEvent((hipStream_t)c.s, es.lin1_dw, 0) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
+  if (k0_split) ESC_TRY(wait((hipStream_t)c.s, es.lin1_dw));
   if (c.jobs && !c.jobs->empty()) ESC_TRY(esc_slab_reduce_jobs(c.jobs->data(), (int)c.jobs->size(), c.s));
   if (es.ok) {
     if (!g_legacy_seam) {
@@ -805,7 +762,8 @@ static int backward(const Ctx& c, Pending* defer) {
       if (!edge_jobs.empty()) ESC_TRY(esc_slab_reduce_jobs(edge_jobs.data(), (int)edge_jobs.size(), es.stream));
       edge_jobs.clear();
       ESC_TRY(chain_armed(es.joined, arm, es.stream, nullptr));
-    } else if (hipEventRecord(es.joined, es.stream) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
+    } else
+      ESC_TRY(record(es.joined, es.stream));
     Pending local;
     Pending& p = defer ? *defer : local;
     p.open = true; p.join = true; p.halves = defer != nullptr; p.stream = (hipStream_t)c.s;
@@ -846,7 +804,7 @@ static int forward_zinc(const ZincCtx& z) {
   if (c.train) ESC_TRY(esc_bag_bwd_classify(b->col_row, y.Z, H, E, y.bag_scratch, ce.s));
   ESC_TRY(bn_coeffs(ce, y.Zb, H, E, m->zbn0, y.zb0));
   ESC_TRY(esc_affine_act(y.Zb, H, E, H, y.zb0.scale, y.zb0.shift, act, y.A0, H, ce.s));
-  ESC_TRY(linear_bn(ce, y.A0, H, m->zlin, nullptr, nullptr, E, y.Yz, m->zbn1, y.zb1));
+  ESC_TRY(linear_bn(ce, c.sch.zlin, y.A0, H, m->zlin, nullptr, nullptr, E, y.Yz, m->zbn1, y.zb1));
   ESC_TRY(esc_affine_act(y.Yz, H, E, H, y.zb1.scale, y.zb1.shift, act, y.Zcat, Wz, ce.s));
   ESC_TRY(esc_embed_fwd(m->edge_emb.w, m->edge_emb.rows, D, b->edge_type, E, y.Zcat + H, Wz, nullptr, ce.s));
   auto edge_term = [&](int l) -> int {
@@ -854,13 +812,12 @@ static int forward_zinc(const ZincCtx& z) {
     const esc_conv_t& cv = m->conv[l];
     const int64_t C = l == 0 ? C0 : H;
     ESC_TRY(esc_linear_fwd(y.Zcat, Wz, cv.lin.w, Wz, cv.lin.b, nullptr, nullptr, E, C, Wz, y.e[l], y.ld_e[l], nullptr, ce.s));
-    if (es.ok && hipEventRecord(es.e_ready[l], es.stream) != hipSuccess) { set_error("esc_zinc: stream event failed"); return ESC_ELAUNCH; }
-    return ESC_OK;
+    return es.ok ? record(es.e_ready[l], es.stream) : ESC_OK;
   };
-  const bool batched = y.e_cat != nullptr;
-  if (batched) {                      // every H-wide edge term in one launch over the packed weights (rows of Wz floats) ++ biases
+  const Schedule& sch = c.sch;
+  ESC_TRY(edge_terms_up_front(sch.terms, L, edge_term));
+  if (sch.terms.batched) {            // every H-wide edge term in one launch over the packed weights (rows of Wz floats) ++ biases
     const int lb = C0 == H ? 0 : 1, nb = (int)L - lb;
-    if (lb == 1) ESC_TRY(edge_term(0));
     // (two packs: the weight rows are Wz wide, the biases H wide)
     esc_table_list tw{}, tb{};
     tw.count = nb; tb.count = nb;
@@ -875,10 +832,8 @@ static int forward_zinc(const ZincCtx& z) {
       ESC_TRY(esc_linear_fwd(y.Zcat, Wz, y.w_cat, Wz, y.w_cat + (int64_t)nb * H * Wz, nullptr, nullptr, E, nb * H, Wz, y.e_cat, nb * H, nullptr, ce.s));
     }
     for (int l = lb; l < (int)L; ++l)
-      if (es.ok && hipEventRecord(es.e_ready[l], es.stream) != hipSuccess) { set_error("esc_zinc: stream event failed"); return ESC_ELAUNCH; }
+      if (es.ok) ESC_TRY(record(es.e_ready[l], es.stream));
   }
-  const int ahead = batched ? 0 : (es.ok ? 1 : (int)L);
-  for (int l = 0; l < (int)L && l < ahead; ++l) ESC_TRY(edge_term(l));
   // ---- node pipeline: x = node_type_embedding(data.x) (:581)
   ESC_TRY(esc_embed_fwd(m->node_emb.w, m->node_emb.rows, C0, b->node_type, N, y.X0, C0, nullptr, c.s));
   // GINE layers (:593-598): xs[l] -> cat[:, l*H : (l+1)*H]
@@ -887,13 +842,10 @@ static int forward_zinc(const ZincCtx& z) {
     const int64_t C = l == 0 ? C0 : H;
     const float* hin = l == 0 ? y.X0 : y.cat + (int64_t)(l - 1) * H;
     const int64_t ld_h = l == 0 ? C0 : W;
-    if (es.ok && hipStreamWaitEvent((hipStream_t)c.s, es.e_ready[l], 0) != hipSuccess) { set_error("esc_zinc: stream event failed"); return ESC_ELAUNCH; }
+    if (es.ok) ESC_TRY(wait((hipStream_t)c.s, es.e_ready[l]));
     ESC_TRY(esc_gine_aggregate_fwd(hin, ld_h, y.e[l], y.ld_e[l], b->in_ptr, b->in_edge, b->in_src, cv.eps, N, C, y.agg[l], C, c.s));
-    if (!batched && es.ok && l + ahead < (int)L) {
-      ESC_TRY(chain(es.agg_done[l], (hipStream_t)c.s, es.stream));
-      ESC_TRY(edge_term(l + ahead));
-    }
-    ESC_TRY(mlp_forward(c, cv.nn, y.conv[l], y.agg[l], C, N, y.cat + (int64_t)l * H, W));
+    ESC_TRY(edge_term_behind_agg(sch.terms, l, es, c.s, edge_term));
+    ESC_TRY(mlp_forward(c, cv.nn, y.conv[l], sch.conv[l], y.agg[l], C, N, y.cat + (int64_t)l * H, W));
   }
   // readout (:601-609): global_add_pool -> lin1 -> bn_lin1 -> ELU -> lin2; node_readout: lin1 reads the N rows of cat directly
   const int64_t R = m->node_readout ? N : G;
@@ -902,7 +854,7 @@ static int forward_zinc(const ZincCtx& z) {
     ESC_TRY(esc_segment_pool_fwd(y.cat, W, b->graph_ptr, G, W, 0, y.pooled, W, c.s));
     rin = y.pooled;
   }
-  ESC_TRY(linear_bn(c, rin, W, m->lin1, nullptr, nullptr, R, y.Yl, m->bn_lin1, y.bl));
+  ESC_TRY(linear_bn(c, sch.readout, rin, W, m->lin1, nullptr, nullptr, R, y.Yl, m->bn_lin1, y.bl));
   ESC_TRY(esc_affine_act(y.Yl, H, R, H, y.bl.scale, y.bl.shift, act, y.Al, H, c.s));
   ESC_TRY(esc_linear_fwd(y.Al, H, m->lin2.w, H, m->lin2.b, nullptr, nullptr, R, 1, H, y.pred, 1, nullptr, c.s));
   if (es.ok) ESC_TRY(chain(es.joined, es.stream, (hipStream_t)c.s));    // forward-only calls return ordered behind the edge stream
@@ -936,7 +888,7 @@ static int backward_zinc(const ZincCtx& z) {
     const int64_t C = l == 0 ? C0 : H;
     const float* hin = l == 0 ? y.X0 : y.cat + (int64_t)(l - 1) * H;
     const int64_t ld_h = l == 0 ? C0 : W;
-    ESC_TRY(mlp_backward(c, cv.nn, y.conv[l], y.agg[l], C, N, y.cat + (int64_t)l * H, W, y.dcat + (int64_t)l * H, W, y.dagg, C));
+    ESC_TRY(mlp_backward(c, MlpOps{&cv.nn, &y.conv[l], y.agg[l], C, N, y.cat + (int64_t)l * H, W, y.dcat + (int64_t)l * H, W, y.dagg, C, false}, c.sch.mlp[l]));
     float* dx = l == 0 ? y.dX0 : y.dcat + (int64_t)(l - 1) * H;
     ESC_TRY(esc_gine_aggregate_bwd(hin, ld_h, y.e[l], y.ld_e[l], y.dagg, C, b->out_ptr, b->out_edge, b->out_dst, cv.eps, N, C,
                                    y.d_e[l], C, dx, l == 0 ? C0 : W, l == 0 ? 0 : 1, y.deps_part + (int64_t)l * 2 * N, c.s));
@@ -992,6 +944,7 @@ struct OgbCtx {
   OgbLayout o;
   Ctx c;                // helpers' view (H, col_stats, bn_scratch, stream, slab cursor, jobs); act = ReLU
   float p;              // dropout probability of this call (0 in eval mode)
+  OgbSchedule sch;      // every decision of this call (engine_plan.h): set once by the entry
 };
 
 static uint64_t drop_seed(const OgbCtx& z, int which) { return z.b->seed * 0x2545F4914F6CDD1Dull + (uint64_t)(which + 1) * 0xD1342543DE82EF95ull; }
@@ -1023,7 +976,7 @@ static int forward_ogb(const OgbCtx& z) {
     ESC_TRY(esc_dropout_fwd(y.Yz, H, E, H, p, drop_seed(z, 1), nullptr, 0, y.Yzd, H, y.mask_z1, ce.s));
     ESC_TRY(bn_coeffs(ce, y.Yzd, H, E, m->zbn1, y.zb1));
   } else {
-    ESC_TRY(linear_bn(ce, y.A0, H, m->zlin, nullptr, nullptr, E, y.Yz, m->zbn1, y.zb1));
+    ESC_TRY(linear_bn(ce, z.sch.zlin, y.A0, H, m->zlin, nullptr, nullptr, E, y.Yz, m->zbn1, y.zb1));
   }
   ESC_TRY(esc_affine_act(y.Yzd, H, E, H, y.zb1.scale, y.zb1.shift, 1, y.Zemb, H, ce.s));
   // edge term of layer l = BondEncoder(edge_attr) + edge_encoder_pos(z_emb) (:352)
@@ -1032,12 +985,11 @@ static int forward_ogb(const OgbCtx& z) {
     const esc_ogb_layer_t& q = m->layer[l];
     ESC_TRY(esc_linear_fwd(y.Zemb, H, q.pos.w, H, q.pos.b, nullptr, nullptr, E, H, H, y.l[l].e, H, nullptr, ce.s));
     ESC_TRY(esc_bag_fwd_rows(y.Tcat + q.bond_row0 * H, m->bond_rows, H, b->bonds.row_ptr, b->bonds.idx, b->bonds.ones, E, y.l[l].e, H, 1, nullptr, ce.s));
-    if (es.ok && hipEventRecord(es.e_ready[l], es.stream) != hipSuccess) { set_error("esc_ogb: stream event failed"); return ESC_ELAUNCH; }
-    return ESC_OK;
+    return es.ok ? record(es.e_ready[l], es.stream) : ESC_OK;
   };
   // (per-layer launches, one layer ahead of the node chain as in forward(); one stream: all of them up front, in layer order)
-  const int ahead = es.ok ? 1 : (int)L;
-  for (int l = 0; l < (int)L && l < ahead; ++l) ESC_TRY(edge_term(l));
+  const OgbSchedule& sch = z.sch;
+  ESC_TRY(edge_terms_up_front(sch.terms, L, edge_term));
   // ---- node pipeline: h0 = AtomEncoder(x) (:264-282); vn_0 = virtualnode_embedding(0) per graph (:701)
   ESC_TRY(esc_bag_fwd_rows(y.Tcat, m->atom_rows, H, b->atoms.row_ptr, b->atoms.idx, b->atoms.ones, N, y.h0, H, 0, nullptr, c.s));
   ESC_TRY(esc_embed_fwd(m->vn_w, 1, H, b->zero_idx, G, y.l[0].vn, H, nullptr, c.s));
@@ -1045,24 +997,21 @@ static int forward_ogb(const OgbCtx& z) {
     const esc_ogb_layer_t& q = m->layer[l];
     const OgbLayer& w = y.l[l];
     ESC_TRY(esc_segment_broadcast_add(y.h[l], H, w.vn, H, b->graph_ptr, G, N, H, w.hin, H, c.s));                 // :739
-    if (es.ok && hipStreamWaitEvent((hipStream_t)c.s, es.e_ready[l], 0) != hipSuccess) { set_error("esc_ogb: stream event failed"); return ESC_ELAUNCH; }
+    if (es.ok) ESC_TRY(wait((hipStream_t)c.s, es.e_ready[l]));
     ESC_TRY(esc_gine_aggregate_fwd(w.hin, H, w.e, H, b->in_ptr, b->in_edge, b->in_src, q.eps, N, H, w.agg, H, c.s));
-    if (es.ok && l + ahead < (int)L) {
-      ESC_TRY(chain(es.agg_done[l], (hipStream_t)c.s, es.stream));
-      ESC_TRY(edge_term(l + ahead));
-    }
-    ESC_TRY(linear_bn(c, w.agg, H, q.lin0, nullptr, nullptr, N, w.Y0, q.bn0, w.b0));
+    ESC_TRY(edge_term_behind_agg(sch.terms, l, es, c.s, edge_term));
+    ESC_TRY(linear_bn(c, sch.lin0[l], w.agg, H, q.lin0, nullptr, nullptr, N, w.Y0, q.bn0, w.b0));
     // relu(bn(Y0)) is applied to the staged operand of lin1 (the hidden activation is never written); + batch_norms[l] statistics
-    ESC_TRY(linear_bn(c, w.Y0, H2, q.lin1, w.b0.scale, w.b0.shift, N, w.hc, q.bn, w.bn));
+    ESC_TRY(linear_bn(c, sch.lin1[l], w.Y0, H2, q.lin1, w.b0.scale, w.b0.shift, N, w.hc, q.bn, w.bn));
     // batch_norm -> ReLU (not after the last layer) -> dropout (+ residual), :744-755, as one pass over hc
     ESC_TRY(esc_affine_act_dropout_fwd(w.hc, H, N, H, w.bn.scale, w.bn.shift, l == (int)L - 1 ? 0 : 1, p, drop_seed(z, 2 + 2 * l),
                                        m->residual ? w.hin : nullptr, H, y.h[l + 1], H, w.mask_h, c.s));
     if (l < (int)L - 1) {                                                                                            // :757-783
       ESC_TRY(esc_segment_pool_fwd(w.hin, H, b->graph_ptr, G, H, 0, w.tmp, H, c.s));
       ESC_TRY(esc_dropout_fwd(w.tmp, H, G, H, 0.f, 0, w.vn, H, w.tmp, H, nullptr, c.s));                            // + vn
-      ESC_TRY(linear_bn(c, w.tmp, H, q.vlin0, nullptr, nullptr, G, w.V0, q.vbn0, w.vb0));
+      ESC_TRY(linear_bn(c, sch.vlin0[l], w.tmp, H, q.vlin0, nullptr, nullptr, G, w.V0, q.vbn0, w.vb0));
       ESC_TRY(esc_affine_act(w.V0, H2, G, H2, w.vb0.scale, w.vb0.shift, 1, w.VA, H2, c.s));
-      ESC_TRY(linear_bn(c, w.VA, H2, q.vlin1, nullptr, nullptr, G, w.V1, q.vbn1, w.vb1));
+      ESC_TRY(linear_bn(c, sch.vlin1[l], w.VA, H2, q.vlin1, nullptr, nullptr, G, w.V1, q.vbn1, w.vb1));
       ESC_TRY(esc_affine_act_dropout_fwd(w.V1, H, G, H, w.vb1.scale, w.vb1.shift, 1, p, drop_seed(z, 3 + 2 * l),
                                          m->residual ? w.vn : nullptr, H, y.l[l + 1].vn, H, w.mask_v, c.s));
     }
@@ -1079,6 +1028,7 @@ static int backward_ogb(const OgbCtx& z) {
   const esc_ogb_batch_t* b = z.b;
   const OgbLayout& y = z.o;
   const Ctx& c = z.c;
+  const OgbSchedule& sch = z.sch;
   Ctx c0 = c; c0.act = 0;                        // the last layer's batch_norm has no ReLU
   const int64_t N = y.N, E = y.E, H = y.H, L = y.L, G = y.G, T = y.T, H2 = 2 * H;
   const float p = z.p;
@@ -1101,24 +1051,16 @@ static int backward_ogb(const OgbCtx& z) {
     const OgbLayer& w = y.l[l];
     const bool last = l == (int)L - 1;
     // h_{l+1} = dropout(hb) (+ hin)
-    ESC_TRY(bn_backward_drop(last ? c0 : c, w.hc, H, dH, H, N, w.bn, q.bn, w.mask_h, p, 0, y.dT, H, y.bn_scratch));
-    // The hidden BatchNorm's backward loses its partial-sum pass (2H-wide rows: the most expensive of its three launches): the
-    // column sums come out of lin1's dX epilogue (esc_linear_bwd_both_bn with bn == NULL), then finalize + apply
-    bool hidden_done = false;
-    if (kBnBwdSumsFromDx && !sync_on(c) && y.bst_part != nullptr) {
-      const esc_bn_bwd_next n0{y.bst_part, w.Y0, H2, w.b0.mean, w.b0.invstd, w.b0.scale, w.b0.shift, 1, nullptr};
-      if (esc_linear_bwd_both_bn_ok(y.dT, H, nullptr, w.Y0, H2, q.lin1.w, H2, N, H, H2, y.dA1, H2, c.slabs->peek(), &n0)) {
-        Slab s;
-        ESC_TRY(take_slab(c, N, H, H2, &s));
-        ESC_TRY(esc_linear_bwd_both_bn(y.dT, H, nullptr, w.Y0, H2, w.b0.scale, w.b0.shift, q.lin1.w, H2, N, H, H2, y.dA1, H2, 0, q.lin1.dw, H2,
-                                       q.lin1.db, s.p, s.job, &n0, c.s));
-        ESC_TRY(esc_bn_bwd_coef_from_partials(y.bst_part, cdiv(N, esc_linear_bwd_bn_block_rows(N, H, H2)), N, H2, w.b0.coef, q.bn0.dgamma,
-                                              q.bn0.dbeta, c.s));
-        ESC_TRY(esc_bn_bwd_apply(w.Y0, H2, nullptr, 0, y.dA1, H2, N, H2, w.b0.mean, w.b0.invstd, q.bn0.gamma, q.bn0.beta, 1, w.b0.coef, y.dA1, H2, c.s));
-        hidden_done = true;
-      }
-    }
-    if (!hidden_done) {
+    ESC_TRY(bn_backward_drop(last ? c0 : c, sch.drop_h[l], w.hc, H, dH, H, N, w.bn, q.bn, w.mask_h, p, 0, y.dT, H, y.bn_scratch));
+    if (sch.hidden_from_dx[l]) {       // the hidden BatchNorm's column sums out of lin1's dX epilogue, then finalize + apply (OgbSchedule)
+      const esc_bn_bwd_next n0 = ogb_hidden_next(y, l);
+      Slab s;
+      ESC_TRY(take_slab(c, N, H, H2, &s));
+      ESC_TRY(esc_linear_bwd_both_bn(y.dT, H, nullptr, w.Y0, H2, w.b0.scale, w.b0.shift, q.lin1.w, H2, N, H, H2, y.dA1, H2, 0, q.lin1.dw, H2,
+                                     q.lin1.db, s.p, s.job, &n0, c.s));
+      ESC_TRY(esc_bn_bwd_coef_from_partials(y.bst_part, sch.hidden_slots, N, H2, w.b0.coef, q.bn0.dgamma, q.bn0.dbeta, c.s));
+      ESC_TRY(esc_bn_bwd_apply(w.Y0, H2, nullptr, 0, y.dA1, H2, N, H2, w.b0.mean, w.b0.invstd, q.bn0.gamma, q.bn0.beta, 1, w.b0.coef, y.dA1, H2, c.s));
+    } else {
       ESC_TRY(linear_backward(c, y.dT, H, w.Y0, H2, w.b0.scale, w.b0.shift, q.lin1, N, y.dA1, H2, 0));
       ESC_TRY(bn_backward(c, w.Y0, H2, nullptr, 0, y.dA1, H2, N, w.b0, q.bn0, y.dA1, H2, y.bn_scratch, H2));      // (ReLU mask from the pre-BatchNorm rows)
     }
@@ -1126,7 +1068,7 @@ static int backward_ogb(const OgbCtx& z) {
     // virtual-node update of this layer: vn_{l+1} = dropout(mlp(add_pool(hin) + vn_l)) (+ vn_l)
     bool have_dhin = false;
     if (!last) {
-      ESC_TRY(bn_backward_drop(c, w.V1, H, dvn_next, H, G, w.vb1, q.vbn1, w.mask_v, p, 0, y.dG2, H, y.bn_scratch));
+      ESC_TRY(bn_backward_drop(c, sch.drop_v[l], w.V1, H, dvn_next, H, G, w.vb1, q.vbn1, w.mask_v, p, 0, y.dG2, H, y.bn_scratch));
       ESC_TRY(linear_backward(c, y.dG2, H, w.VA, H2, nullptr, nullptr, q.vlin1, G, y.dG1, H2, 0));
       ESC_TRY(bn_backward(c, w.V0, H2, nullptr, 0, y.dG1, H2, G, w.vb0, q.vbn0, y.dG1, H2, y.bn_scratch, H2));
       ESC_TRY(linear_backward(c, y.dG1, H2, w.tmp, H, nullptr, nullptr, q.vlin0, G, y.dtmp, H, 0));
@@ -1146,7 +1088,7 @@ static int backward_ogb(const OgbCtx& z) {
     // bond tables: on the edge stream — except for the LAST layer processed (l == 0), whose edge-term backward opens the tail of
     // the step: there the table gradient runs on the node stream (d_e is its own product; it has the atom tables' scratch to
     // itself until the encoders below) and the edge stream goes straight to the Linear that completes d(z_emb): 4.34 -> 4.31 ms/step
-    const bool bonds_on_node = l == 0 && es.ok;
+    const bool bonds_on_node = l == 0 && sch.bonds_on_node;
     ESC_TRY(esc_bag_bwd_table(w.d_e, H, H, b->bonds.col_ptr, b->bonds.c_row, b->bonds.ones, b->bonds.c_col, b->bonds.n_entries,
                               m->bond_rows, y.dTcat + q.bond_row0 * H, bonds_on_node ? y.emb_scratch_n : y.emb_scratch,
                               bonds_on_node ? c.s : ce.s));
@@ -1163,9 +1105,9 @@ static int backward_ogb(const OgbCtx& z) {
                             m->atom_rows, y.dTcat, y.emb_scratch_n, c.s));
   ESC_TRY(esc_embed_bwd(dvn_next, H, b->zero_idx, G, 1, H, m->vn_dw, c.s));
   // z_embedding + bag: the tail of the edge pipeline (d(z_emb) is complete in edge-stream order)
-  ESC_TRY(bn_backward_drop(ce, y.Yzd, H, y.dZemb, H, E, y.zb1, m->zbn1, y.mask_z1, p, 1, y.dYz, H, ce.y.bn_scratch));
+  ESC_TRY(bn_backward_drop(ce, sch.drop_z1, y.Yzd, H, y.dZemb, H, E, y.zb1, m->zbn1, y.mask_z1, p, 1, y.dYz, H, ce.y.bn_scratch));
   ESC_TRY(linear_backward(ce, y.dYz, H, y.A0, H, nullptr, nullptr, m->zlin, E, y.dA0, H, 0));
-  ESC_TRY(bn_backward_drop(ce, y.Zd, H, y.dA0, H, E, y.zb0, m->zbn0, y.mask_z0, p, 1, y.dA0, H, ce.y.bn_scratch));
+  ESC_TRY(bn_backward_drop(ce, sch.drop_z0, y.Zd, H, y.dA0, H, E, y.zb0, m->zbn0, y.mask_z0, p, 1, y.dA0, H, ce.y.bn_scratch));
   ESC_TRY(esc_bag_bwd_table_rows(y.dA0, H, H, b->col_ptr, b->col_row, b->col_val, b->col_col, y.Z, m->z_rows, E, 1,
                                  m->dz_table, y.bag_scratch, ce.s));
   if (es.ok && !edge_jobs.empty()) ESC_TRY(esc_slab_reduce_jobs(edge_jobs.data(), (int)edge_jobs.size(), es.stream));
@@ -1261,7 +1203,7 @@ int esc_engine_adam_step(float* param, const float* grad, float* exp_avg, float*
   if (!es.ok) return adam_launch(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, nullptr, stream);
   // the late part on the edge stream, behind its last reduce and behind caller_done (the gradients of that part which the node
   // stream finishes: conv[0].lin's, reduced with the node-side jobs); late_done is the stop event of the launch
-  if (hipStreamWaitEvent(es.stream, es.caller_done, 0) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
+  ESC_TRY(wait(es.stream, es.caller_done));
   {
     const ArmedEvent arm(es.late_done, true);
     ESC_TRY(adam_launch(param + n_early, grad + n_early, exp_avg + n_early, exp_avg_sq + n_early, n - n_early, lr, beta1, beta2, eps, step,
@@ -1270,7 +1212,7 @@ int esc_engine_adam_step(float* param, const float* grad, float* exp_avg, float*
   }
   // ... the rest beside it; the caller's stream then holds every parameter in its order, as after one launch over all of them
   ESC_TRY(adam_launch(param, grad, exp_avg, exp_avg_sq, n_early, lr, beta1, beta2, eps, step, nullptr, stream));
-  if (hipStreamWaitEvent((hipStream_t)stream, es.late_done, 0) != hipSuccess) { set_error("esc_engine: stream event failed"); return ESC_ELAUNCH; }
+  ESC_TRY(wait((hipStream_t)stream, es.late_done));
   sm.stage = 2;
   sm.late_lo = param + n_early; sm.late_hi = param + n;
   ++sm.split_steps;
@@ -1362,10 +1304,10 @@ static int train_step_impl(const esc_nested_gin_t* m, const esc_batch_t* b, floa
   ESC_REQUIRE(loss, "esc_engine_train_step: null loss pointer");
   Ctx c{m, b, plan_layout(m, b->N, b->E, b->Z, workspace, true), stream, true};
   StepSlabs slabs(c, c.y.slabs, c.y.slab_limit, c.y.n_wgrads);
+  c.sch = plan_schedule(m, c.y, run_mode(c, b->E, b->x, true));
   const int64_t denom = loss_denom > 0 ? loss_denom : b->N;
   EdgeStream& es = edge_stream_for(b->E);
-  const bool head_l1 = es.ok && m->hidden <= 1024 &&
-                       esc_linear_fwd_l1_ok(c.y.Yl, m->hidden, m->lin2.w, m->hidden, c.y.bl.scale, c.y.bl.shift) != 0;
+  const bool head_l1 = c.sch.l1_head;
   if (head_l1) { c.l1_target = b->y; c.l1_denom = denom; }
   // the fast seam (see Seam): this call follows a split optimiser step at once, on the same stream and workspace, the caller has
   // claimed the batch, and the one parameter the ESC bag reads was updated on the edge stream
@@ -1396,6 +1338,7 @@ int esc_engine_forward_train(const esc_nested_gin_t* m, const esc_batch_t* b, fl
   ESC_REQUIRE(pred, "esc_engine_forward_train: null output");
   Ctx c{m, b, plan_layout(m, b->N, b->E, b->Z, workspace, true), stream, true};
   StepSlabs slabs(c, c.y.slabs, c.y.slab_limit, 0);
+  c.sch = plan_schedule(m, c.y, run_mode(c, b->E, b->x));
   ESC_TRY(forward(c));
   return copy_floats(pred, c.y.pred, b->N, stream, "esc_engine_forward_train");
 }
@@ -1408,6 +1351,7 @@ int esc_engine_backward(const esc_nested_gin_t* m, const esc_batch_t* b, float* 
   ESC_REQUIRE(dpred, "esc_engine_backward: null gradient");
   Ctx c{m, b, plan_layout(m, b->N, b->E, b->Z, workspace, true), stream, true};
   StepSlabs slabs(c, c.y.slabs, c.y.slab_limit, c.y.n_wgrads);
+  c.sch = plan_schedule(m, c.y, run_mode(c, b->E, b->x));
   ESC_TRY(copy_floats(c.y.dpred, dpred, b->N, stream, "esc_engine_backward"));
   return backward(c, nullptr);
 }
@@ -1419,6 +1363,7 @@ int esc_engine_predict(const esc_nested_gin_t* m, const esc_batch_t* b, float* w
   if (rc) return rc;
   ESC_REQUIRE(pred, "esc_engine_predict: null output");
   Ctx c{m, b, plan_layout(m, b->N, b->E, b->Z, workspace, false), stream, false};
+  c.sch = plan_schedule(m, c.y, run_mode(c, b->E, b->x));
   ESC_TRY(forward(c));
   return copy_floats(pred, c.y.pred, b->N, stream, "esc_engine_predict");
 }
@@ -1440,6 +1385,7 @@ int esc_zinc_train_step(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, float
   ESC_REQUIRE(loss, "esc_zinc_train_step: null loss pointer");
   ZincCtx z = make_zinc(m, b, workspace, stream, true);
   StepSlabs slabs(z.c, z.c.y.slabs, z.c.y.slab_limit, z.c.y.n_wgrads);
+  z.c.sch = plan_schedule_zinc(m, z.c.y, run_mode(z.c, b->E));
   const int64_t R = zinc_rows(m, b);
   ESC_TRY(forward_zinc(z));
   ESC_TRY(esc_l1_loss(z.c.y.pred, b->y, R, loss_denom > 0 ? loss_denom : R, 1.0f, loss, z.c.y.dpred, stream));
@@ -1454,6 +1400,7 @@ int esc_zinc_forward_train(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, fl
   ESC_REQUIRE(pred, "esc_zinc_forward_train: null output");
   ZincCtx z = make_zinc(m, b, workspace, stream, true);
   StepSlabs slabs(z.c, z.c.y.slabs, z.c.y.slab_limit, 0);
+  z.c.sch = plan_schedule_zinc(m, z.c.y, run_mode(z.c, b->E));
   ESC_TRY(forward_zinc(z));
   return copy_floats(pred, z.c.y.pred, zinc_rows(m, b), stream, "esc_zinc_forward_train");
 }
@@ -1465,6 +1412,7 @@ int esc_zinc_backward(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, float* 
   ESC_REQUIRE(dpred, "esc_zinc_backward: null gradient");
   ZincCtx z = make_zinc(m, b, workspace, stream, true);
   StepSlabs slabs(z.c, z.c.y.slabs, z.c.y.slab_limit, z.c.y.n_wgrads);
+  z.c.sch = plan_schedule_zinc(m, z.c.y, run_mode(z.c, b->E));
   ESC_TRY(copy_floats(z.c.y.dpred, dpred, zinc_rows(m, b), stream, "esc_zinc_backward"));
   return backward_zinc(z);
 }
@@ -1475,6 +1423,7 @@ int esc_zinc_predict(const esc_zinc_gin_t* m, const esc_mol_batch_t* b, float* w
   if (rc) return rc;
   ESC_REQUIRE(pred, "esc_zinc_predict: null output");
   ZincCtx z = make_zinc(m, b, workspace, stream, false);
+  z.c.sch = plan_schedule_zinc(m, z.c.y, run_mode(z.c, b->E));
   ESC_TRY(forward_zinc(z));
   return copy_floats(pred, z.c.y.pred, zinc_rows(m, b), stream, "esc_zinc_predict");
 }
@@ -1494,6 +1443,7 @@ int esc_ogb_train_step(const esc_ogb_gnn_t* m, const esc_ogb_batch_t* b, float* 
   ESC_REQUIRE(loss, "esc_ogb_train_step: null loss pointer");
   OgbCtx z = make_ogb(m, b, workspace, stream, true);
   StepSlabs slabs(z.c, z.o.slabs, z.o.slab_limit, z.o.n_wgrads);
+  z.sch = plan_schedule_ogb(m, z.o, run_mode(z.c, b->E));
   ESC_TRY(forward_ogb(z));
   ESC_TRY(esc_bce_logits_loss(z.o.logits, b->y, b->G * m->num_tasks, loss_denom, loss, z.o.dlogits, stream));
   if (logits) ESC_TRY(copy_floats(logits, z.o.logits, b->G * m->num_tasks, stream, "esc_ogb_train_step"));
@@ -1507,6 +1457,7 @@ int esc_ogb_forward_train(const esc_ogb_gnn_t* m, const esc_ogb_batch_t* b, floa
   ESC_REQUIRE(logits, "esc_ogb_forward_train: null output");
   OgbCtx z = make_ogb(m, b, workspace, stream, true);
   StepSlabs slabs(z.c, z.o.slabs, z.o.slab_limit, 0);
+  z.sch = plan_schedule_ogb(m, z.o, run_mode(z.c, b->E));
   ESC_TRY(forward_ogb(z));
   return copy_floats(logits, z.o.logits, b->G * m->num_tasks, stream, "esc_ogb_forward_train");
 }
@@ -1518,6 +1469,7 @@ int esc_ogb_backward(const esc_ogb_gnn_t* m, const esc_ogb_batch_t* b, float* wo
   ESC_REQUIRE(dlogits, "esc_ogb_backward: null gradient");
   OgbCtx z = make_ogb(m, b, workspace, stream, true);
   StepSlabs slabs(z.c, z.o.slabs, z.o.slab_limit, z.o.n_wgrads);
+  z.sch = plan_schedule_ogb(m, z.o, run_mode(z.c, b->E));
   ESC_TRY(copy_floats(z.o.dlogits, dlogits, b->G * m->num_tasks, stream, "esc_ogb_backward"));
   return backward_ogb(z);
 }
@@ -1528,6 +1480,7 @@ int esc_ogb_predict(const esc_ogb_gnn_t* m, const esc_ogb_batch_t* b, float* wor
   if (rc) return rc;
   ESC_REQUIRE(logits, "esc_ogb_predict: null output");
   OgbCtx z = make_ogb(m, b, workspace, stream, false);
+  z.sch = plan_schedule_ogb(m, z.o, run_mode(z.c, b->E));
   ESC_TRY(forward_ogb(z));
   return copy_floats(logits, z.o.logits, b->G * m->num_tasks, stream, "esc_ogb_predict");
 }

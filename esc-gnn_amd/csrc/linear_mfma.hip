@@ -51,6 +51,7 @@ static const plan::PlanKnobs& knobs() {
   (void)env_read;
   return g_plan;
 }
+const plan::PlanKnobs& linear_plan_knobs() { return knobs(); }      // (the step engines' schedule plans with the same values: engine.hip)
 
 // the plan's constants are the kernels' own
 using DmaBnCfg = dma::Cfg<64, 64, 32, 2, 2, 2, 2, false, true, 4, false, false>;
@@ -580,14 +581,9 @@ int esc_linear_bwd_both_deferred(const float* dY, int64_t ld_dy, const float* X,
 static Plan plan_both_bn(const float* dOut, int64_t ld_dout, const esc_bn_bwd_fused* b, const float* X, int64_t ld_x, const float* W,
                          int64_t ld_w, int64_t M, int64_t N, int64_t K, const float* dX, int64_t ld_dx, const float* slabs,
                          const esc_bn_bwd_next* n) {
-  plan::BnOps bo{};
-  plan::NextOps no{};
-  if (b) bo = plan::BnOps{b->x, b->ld_x, b->mean, b->invstd, b->scale, b->shift, b->coef, b->relu, b->beta};
-  if (n) no = plan::NextOps{n->partial, n->x, n->ld_x, n->mean, n->invstd, n->scale, n->shift, n->relu, n->beta};
   plan::PlanKnobs k = knobs();
   if (t_dual_split_on) k.dual_split = t_dual_split.dx_lds > 1 ? t_dual_split.dx_lds : 1;
-  return plan::plan_both_bn(k, Op{dOut, ld_dout}, b ? &bo : nullptr, Op{X, ld_x}, Op{W, ld_w}, Op{dX, ld_dx}, slabs, n ? &no : nullptr,
-                            M, N, K);
+  return plan::plan_both_bn(k, Op{dOut, ld_dout}, b, Op{X, ld_x}, Op{W, ld_w}, Op{dX, ld_dx}, slabs, n, M, N, K);
 }
 
 int esc_linear_bwd_both_bn_ok(const float* dOut, int64_t ld_dout, const esc_bn_bwd_fused* bn, const float* X, int64_t ld_x,

@@ -311,6 +311,10 @@ inline Plan plan_both(const PlanKnobs& k, Op dY, Op X, Op W, Op dX, Op dW, const
 // beta: read when relu == 2 (ELU: the derivative is taken at the centred pre-activation (x - mean) * scale + beta), else ignored
 struct BnOps { const void* x; int64_t ld_x; const void *mean, *invstd, *scale, *shift, *coef; int relu; const void* beta; };
 struct NextOps { const void* partial; const void* x; int64_t ld_x; const void *mean, *invstd, *scale, *shift; int relu; const void* beta; };
+// The C structs of include/escgnn_hip.h (esc_bn_bwd_fused, esc_bn_bwd_next: templates, so that this header needs neither) as plan
+// operands — the one translation, for esc_linear_bwd_both_bn (linear_mfma.hip) and for the step engines' schedule (engine_plan.h)
+template <class Fused> inline BnOps bn_ops(const Fused& b) { return BnOps{b.x, b.ld_x, b.mean, b.invstd, b.scale, b.shift, b.coef, b.relu, b.beta}; }
+template <class Next> inline NextOps next_ops(const Next& n) { return NextOps{n.partial, n.x, n.ld_x, n.mean, n.invstd, n.scale, n.shift, n.relu, n.beta}; }
 inline bool elu_beta_ok(int relu, const void* beta) { return relu != 2 || (beta != nullptr && aligned16(beta)); }
 inline bool bn_ops_ok(const BnOps& b, int64_t M, int64_t N) {
   return b.x && b.mean && b.invstd && b.scale && b.shift && b.coef && b.relu >= 0 && b.relu <= 2 && b.ld_x >= N &&
@@ -344,6 +348,16 @@ inline Plan plan_both_bn(const PlanKnobs& k, Op dOut, const BnOps* bn, Op X, Op 
   if (next != nullptr && !next_ops_ok(*next, dX, K)) return p;
   if (k.dual_split > 0) { p.launches = 2; p.dx_lds = k.dual_split > 1 ? (k.dual_split < LDS_BYTES ? k.dual_split : LDS_BYTES) : 0; }
   return dma_wgrad_splits(big ? with_family(p, F_DMA128_BN, 128, 128) : with_family(p, F_DMA64_BN, 64, 64), M, N, K);
+}
+// ... from the entry's own arguments (b, n: the C structs, or nullptr)
+template <class Fused, class Next>
+inline Plan plan_both_bn(const PlanKnobs& k, Op dOut, const Fused* b, Op X, Op W, Op dX, const void* slabs, const Next* n, int64_t M,
+                         int64_t N, int64_t K) {
+  BnOps bo{};
+  NextOps no{};
+  if (b) bo = bn_ops(*b);
+  if (n) no = next_ops(*n);
+  return plan_both_bn(k, dOut, b ? &bo : nullptr, X, W, dX, slabs, n ? &no : nullptr, M, N, K);
 }
 
 // ---- the scratch promise: an upper bound over every plan a knob setting can produce ----------------------------------------

@@ -103,6 +103,26 @@ def test_fp32_oracle_is_conditioned_on_the_deep_models(deep):
         assert e <= ec.CAP, (n, e)
 
 
+# tests/test_hip_engine_structure.py SCHEDULE_MODELS x SCHEDULE_CASES (that module needs the library: the pairs are repeated here)
+SCHEDULE_ON_CASE = ((("count", 2, 64), "mixed"), (("count", 2, 64), "minimal"), (("count", 2, 64), "rows_65"),
+                    (("ogb", 2, 64), "mixed"), (("ogb", 2, 64), "mixed_hub_last"))
+
+
+@pytest.mark.parametrize("model,case", SCHEDULE_ON_CASE, ids=["%s-%s" % (ec.model_id(m), c) for m, c in SCHEDULE_ON_CASE])
+def test_fp32_oracle_is_conditioned_on_the_schedule_models(model, case):
+    """the same cap for the models added for the step schedule's coverage, on the cases the device test runs them on"""
+    family, L, H = model
+    step = ec.oracle_step(family, case, L, H)
+    e_ref = ec.reference_errors(step)
+    for side in ("fp32", "fp64"):
+        assert all(bool(torch.isfinite(t).all()) for n, t in ec.float_items(step[side])), side
+        assert len(step[side]["grads"]) == len(step["state"]) - len(step[side]["buffers"])
+    worst = max(e_ref, key=e_ref.get)
+    print("%s %s: worst e_ref %.2g (%s)" % (ec.model_id(model), case, e_ref[worst], worst))
+    for n, e in e_ref.items():
+        assert e <= ec.CAP, (n, e)
+
+
 @pytest.mark.parametrize("family", ("zinc", "ogb"))
 def test_single_graph_boundary_oracle(family):
     """G = 1, one path(3): the ZINC reference skips bn_lin1 at one row and trains; the OGB reference cannot train (its
