@@ -18,6 +18,7 @@
 // scheme: a short tail is padded by clamping the slot to the node's last edge and masking its contribution).
 // No atomics; every output element is written once.  Built with -ffp-contract=off (Makefile).
 #include "common.h"
+#include "graph_wave.h"
 #include "sparse_plan.h"
 #include "../../include/escgnn_gatedgcn.h"
 
@@ -27,19 +28,7 @@ constexpr int GG_BATCH = 4;               // 3-4 float4 row reads per edge: 12-1
 constexpr int GG_MAX_C = 1024;
 constexpr float GG_EPS = 1e-6f;
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ float gg_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// the node of this lane's group and the first column of the lane; false: nothing to do
-template <int LG>
-__device__ __forceinline__ bool gg_locate(int N, int& node, int& c0) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t g = t / LG;
-  node = (int)g;
-  c0 = (int)(t - g * LG) * 4;
-  return g < N;
-}
 
 template <int LG>
 __global__ __launch_bounds__(256) void gated_fwd_kernel(const float* __restrict__ Ax, int64_t ld_ax, const float* __restrict__ Bx,
@@ -50,7 +39,7 @@ __global__ __launch_bounds__(256) void gated_fwd_kernel(const float* __restrict_
                                                         int64_t ld_out, float* __restrict__ e_out, int64_t ld_eo, float* __restrict__ den) {
   ESC_PRIO();
   int node, c0;
-  if (!gg_locate<LG>(N, node, c0)) return;
+  if (!group_locate<LG>(N, node, c0)) return;
   const int beg = in_ptr[node], end = in_ptr[node + 1];
   for (int c = c0; c < C; c += LG * 4) {
     const float4 dxi = ld4(Dx + (size_t)node * ld_dx + c);
@@ -100,7 +89,7 @@ __global__ __launch_bounds__(256) void gated_bwd_dst_kernel(const float* __restr
                                                             int64_t ld_dce, float* __restrict__ d_Dx, int64_t ld_ddx) {
   ESC_PRIO();
   int node, c0;
-  if (!gg_locate<LG>(N, node, c0)) return;
+  if (!group_locate<LG>(N, node, c0)) return;
   const int beg = in_ptr[node], end = in_ptr[node + 1];
   const bool has_ge = g_e != nullptr;
   for (int c = c0; c < C; c += LG * 4) {
@@ -150,7 +139,7 @@ __global__ __launch_bounds__(256) void gated_bwd_src_kernel(const float* __restr
                                                             int64_t ld_dex, float* __restrict__ d_Bx, int64_t ld_dbx) {
   ESC_PRIO();
   int node, c0;
-  if (!gg_locate<LG>(N, node, c0)) return;
+  if (!group_locate<LG>(N, node, c0)) return;
   const int beg = out_ptr[node], end = out_ptr[node + 1];
   for (int c = c0; c < C; c += LG * 4) {
     float4 ae = make_float4(0.f, 0.f, 0.f, 0.f), ab = ae;

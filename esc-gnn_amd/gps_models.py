@@ -26,7 +26,12 @@ GPSLayer / GPSModel(local_gnn_type='CustomGatedGCN') swaps the GINE layer for nn
 local type the fork implements: it also returns new edge attributes, which the next layer's ESC term is added to;
 global_model_type='None' drops the attention branch (self_attn None, no keys; norm1_attn stays, unused, as in the reference).
 
-Out of scope: BiasedTransformer / attn_bias, Performer and BigBird, the local GNN types GCN / GIN / GENConv / GAT / PNA, the
+local_gnn_type='PNA' swaps it for nn.PNAConv (PyG's PNAConv as gps_layer.py:78-93 constructs it: aggregators mean / max / sum,
+identity scaler, one tower, one pre- and one post-layer, edge_dim = min(128, dim_h)): treated as GINE is - dropout_local, the
+residual, norm1_local - and like GINE it leaves the edge attributes alone.
+
+Out of scope: BiasedTransformer / attn_bias, Performer and BigBird, the local GNN types GCN / GIN / GENConv / GAT, PNA's other
+aggregators (min, std), degree scalers, towers and deeper pre- / post-layers, the
 EquivStableLapPE gate of GINE and GatedGCN, a fused BatchNorm on GatedGCN's edge rows, layer_norm, the other positional
 encodings (SignNet, EquivStableLapPE, HKdiagSE, ElstaticSE) and LapPE's Transformer model, graphgym's config system and wandb,
 a whole-step engine, data parallelism."""
@@ -35,13 +40,14 @@ from torch.nn import Dropout, ModuleList, Sequential
 
 from . import nested
 from .nested import Z_TABLE_ROWS
-from .nn import BatchNorm1d, Embedding, GatedGCNLayer, GINEConv, GraphMultiheadAttention, LapPENodeEncoder, Linear, ReLU, RWSENodeEncoder, global_add_pool
+from .nn import BatchNorm1d, Embedding, GatedGCNLayer, GINEConv, GraphMultiheadAttention, LapPENodeEncoder, Linear, PNAConv, ReLU, RWSENodeEncoder, global_add_pool
 from .plan import graph_ptr_of, plan_of
 
 
 class GPSLayer(torch.nn.Module):
     """Local message passing + full graph attention + feed-forward (gps_layer.py:19-302 with act 'relu' and batch_norm).
-    local_gnn_type 'GINE' (the yaml's) or 'CustomGatedGCN' (gps_layer.py:94-99: nn.GatedGCNLayer with its own dropout and
+    local_gnn_type 'GINE' (the yaml's), 'PNA' (gps_layer.py:78-93: nn.PNAConv, handled as GINE is, :216-229) or
+    'CustomGatedGCN' (gps_layer.py:94-99: nn.GatedGCNLayer with its own dropout and
     residual, whose edge output becomes the layer's edge attributes, :197-208); global_model_type 'Transformer' or 'None'
     (self_attn None: the attention branch is skipped; norm1_attn exists all the same, :150-152)."""
 
@@ -50,6 +56,12 @@ class GPSLayer(torch.nn.Module):
         self.dim_h, self.num_heads = dim_h, num_heads
         if local_gnn_type == "GINE":
             self.local_model = GINEConv(Sequential(Linear(dim_h, dim_h), ReLU(), Linear(dim_h, dim_h)))  # constant eps = 0, no edge Linear
+        elif local_gnn_type == "PNA":
+            if dim_h > 128:                                   # edge_dim = min(128, dim_h): the reference would fail inside the encoder
+                raise ValueError("GPSLayer: local_gnn_type 'PNA' takes dim_h <= 128 (got %d): its edge_dim is min(128, dim_h), "
+                                 "and the edge attributes are dim_h wide" % dim_h)
+            self.local_model = PNAConv(dim_h, dim_h, aggregators=["mean", "max", "sum"], scalers=["identity"], deg=None,
+                                       edge_dim=min(128, dim_h), towers=1, pre_layers=1, post_layers=1, divide_input=False)
         elif local_gnn_type == "CustomGatedGCN":
             self.local_model = GatedGCNLayer(dim_h, dim_h, dropout=dropout, residual=True)
         else:

@@ -177,6 +177,54 @@ class GatedGCNLayer(torch.nn.Module):
         return h, e_ij
 
 
+class PNAConv(torch.nn.Module):
+    """PyG's PNAConv (Principal Neighbourhood Aggregation) as the reference's GPSLayer constructs it
+    (GraphGPS/graphgps/layer/gps_layer.py:78-93): aggregators ['mean', 'max', 'sum'], scaler 'identity', one tower, one pre-
+    and one post-layer.  The modules, their names and their construction order are PyG's - edge_encoder, pre_nns.0.0,
+    post_nns.0.0, lin (this module's Linear) - so equal seeds give equal weights and a state_dict in that layout loads; `deg`
+    only feeds the degree scalers, which are not selected: no buffer comes of it.
+
+        m_k = pre_nns.0.0(cat[x_i, x_j, edge_encoder(e_k)])       out = lin(post_nns.0.0(cat[x, mean, max, sum]))
+
+    pre_nns.0.0 is one Linear, so with its weight cut by input columns, W = [W_i | W_j | W_e], the message is
+    (P[i] + Q[j]) + R[k] with P = x W_i^T + b, Q = x W_j^T, R = edge_encoder(e) W_e^T: three GEMMs on slices of the one
+    parameter, then ops.pna_aggregate (one launch; csrc/pna.hip).  forward(x, edge_index, edge_attr, plan) -> [N, out]."""
+
+    def __init__(self, in_channels, out_channels, aggregators=("mean", "max", "sum"), scalers=("identity",), deg=None, edge_dim=None,
+                 towers=1, pre_layers=1, post_layers=1, divide_input=False):
+        super().__init__()
+        if list(aggregators) != ["mean", "max", "sum"]:
+            raise ValueError("PNAConv: aggregators %r: only ['mean', 'max', 'sum'], in this order, are supported" % (list(aggregators),))
+        if list(scalers) != ["identity"]:
+            raise ValueError("PNAConv: scalers %r: only ['identity'] is supported" % (list(scalers),))
+        if towers != 1:
+            raise ValueError("PNAConv: towers=%r: only one tower is supported" % (towers,))
+        if pre_layers != 1:
+            raise ValueError("PNAConv: pre_layers=%r: only one pre-layer is supported" % (pre_layers,))
+        if post_layers != 1:
+            raise ValueError("PNAConv: post_layers=%r: only one post-layer is supported" % (post_layers,))
+        if edge_dim is None:
+            raise ValueError("PNAConv: edge_dim=None: the layer is built for edge attributes (edge_dim is required)")
+        if in_channels != out_channels:
+            raise ValueError("PNAConv: in_channels=%d and out_channels=%d must be equal" % (in_channels, out_channels))
+        self.in_channels, self.out_channels, self.edge_dim = in_channels, out_channels, edge_dim
+        self.edge_encoder = Linear(edge_dim, in_channels)
+        self.pre_nns = torch.nn.ModuleList([torch.nn.Sequential(Linear(3 * in_channels, in_channels))])
+        self.post_nns = torch.nn.ModuleList([torch.nn.Sequential(Linear(4 * in_channels, out_channels))])
+        self.lin = Linear(out_channels, out_channels)
+
+    def forward(self, x, edge_index, edge_attr, plan=None):
+        if plan is None:
+            from .plan import BatchPlan
+            plan = BatchPlan.from_tensors(edge_index, x.size(0))
+        H, pre = self.in_channels, self.pre_nns[0][0]
+        P = ops.linear(x, pre.weight[:, :H], pre.bias)
+        Q = ops.linear(x, pre.weight[:, H:2 * H])
+        R = ops.linear(self.edge_encoder(edge_attr), pre.weight[:, 2 * H:])
+        agg = ops.pna_aggregate(P, Q, R, plan)                                       # [N, 3H]: mean | max | sum
+        return self.lin(self.post_nns[0][0](torch.cat([x, agg], 1)))
+
+
 def global_add_pool(x, batch, size=None):
     """PyG global_add_pool: segment sum by graph id (HIP segment_pool kernels)."""
     return ops.segment_pool(x, batch, size, mean=False)

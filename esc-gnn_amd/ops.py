@@ -242,6 +242,65 @@ def gated_gcn_aggregate(Ax, Bx, Dx, Ex, Ce, plan):
     return _GatedGCN.apply(Ax, Bx, Dx, Ex, Ce, plan)
 
 
+def pna_max_channels():
+    """the widest row esc_pna_aggregate_fwd / _bwd take (a multiple of 4 from 4 up to this)"""
+    return int(nv.lib().esc_pna_max_channels())
+
+
+class _PNAAggregate(Function):
+    """m_k = (P[i] + Q[j]) + R[k] over the edges k = (j -> i), and mean | max | sum of the messages of every node's in-edges in
+    one [N, 3C] tensor: message and aggregate of PyG's PNAConv with aggregators mean / max / sum and the identity scaler in
+    one launch, their backward in two (csrc/pna.hip).  Kept for the backward: arg [N, C] int32, the edge position of every
+    maximum - nothing of size [E, C]."""
+
+    @staticmethod
+    def forward(ctx, P, Q, R, plan):
+        _dev(P, Q, R)
+        _on(P.device, Q, R)
+        _plan_on(P.device, plan, "in_ptr", "in_edge", "in_src", "out_ptr", "out_edge", "out_dst")
+        (P, ldp), (Q, ldq), (R, ldr) = (_rows(t) for t in (P, Q, R))
+        N, C = P.shape
+        E = plan.num_edges
+        limit = pna_max_channels()
+        if C % 4 or not 4 <= C <= limit:
+            raise ValueError("pna_aggregate: width %d: the kernels take a multiple of 4 with 4 <= C <= %d" % (C, limit))
+        if tuple(Q.shape) != (N, C) or R.size(1) != C or N != plan.num_nodes:
+            raise ValueError("pna_aggregate: P %s, Q %s, R %s must share one width and the batch's %d nodes"
+                             % (tuple(P.shape), tuple(Q.shape), tuple(R.shape), plan.num_nodes))
+        if R.size(0) != E:
+            raise ValueError("pna_aggregate: R has %d rows, the batch has %d edges" % (R.size(0), E))
+        dev = P.device
+        agg, arg = _empty(dev, N, 3 * C), torch.empty((N, C), dtype=torch.int32, device=dev)
+        edge = (lambda t: nv.ptr(t)) if E else (lambda t: None)
+        nv.call("esc_pna_aggregate_fwd", nv.ptr(P), ldp, nv.ptr(Q), ldq, edge(R), ldr, nv.ptr(plan.in_ptr), edge(plan.in_edge),
+                edge(plan.in_src), N, E, C, nv.ptr(agg), 3 * C, nv.ptr(arg), nv.stream())
+        ctx.save_for_backward(arg)
+        ctx.plan = plan
+        return agg
+
+    @staticmethod
+    def backward(ctx, g):
+        arg, = ctx.saved_tensors
+        plan = ctx.plan
+        N, C = arg.shape
+        E, dev = plan.num_edges, arg.device
+        g, ldg = _rows(g)
+        d_R, d_P, d_Q = _empty(dev, E, C), _empty(dev, N, C), _empty(dev, N, C)
+        edge = (lambda t: nv.ptr(t)) if E else (lambda t: None)
+        nv.call("esc_pna_aggregate_bwd", nv.ptr(g), ldg, nv.ptr(arg), nv.ptr(plan.in_ptr), edge(plan.in_edge), edge(plan.in_src),
+                nv.ptr(plan.out_ptr), edge(plan.out_edge), edge(plan.out_dst), N, E, C, edge(d_R), C, nv.ptr(d_P), C, nv.ptr(d_Q), C,
+                nv.stream())
+        return d_P, d_Q, d_R, None
+
+
+def pna_aggregate(P, Q, R, plan):
+    """agg [N, 3C] = mean | max | sum of the messages (P[i] + Q[j]) + R[k] over every node's in-edges, in this column order: one
+    tensor, so the layer joins it to x with one cat and never cats the aggregates.  Differentiable in all three operands; the
+    gradient of a maximum goes to the lowest edge position that holds it.  ValueError: a width outside the kernels' limits,
+    operands of different widths, R rows != plan.num_edges."""
+    return _PNAAggregate.apply(P, Q, R, plan)
+
+
 class _Linear(Function):
     """torch.nn.Linear on the fp32 matrix cores (every Linear of run_graphcount.py:54-121,183-189)."""
 

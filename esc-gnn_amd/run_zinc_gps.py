@@ -21,13 +21,14 @@ or TypeDictNode+LapPE+RWSE with --posenc_LapPE 1 as well): one rwse.RWSETable pe
 RWSE: the posenc_RWSE_* defaults (20 steps, dim_pe 28, linear, BatchNorm on the raw statistics) are upstream GraphGPS's usual
 ZINC values, this project's choice.
 
---gt_layer_type picks the two halves of every layer as the yaml's gt.layer_type does: the local GNN is GINE (the yaml's) or
+--gt_layer_type picks the two halves of every layer as the yaml's gt.layer_type does: the local GNN is GINE (the yaml's),
 CustomGatedGCN (nn.GatedGCNLayer on the fused gate kernel, csrc/gatedgcn.hip; it also updates the edge attributes from layer to
-layer, so the ESC term of layer l is carried and re-gated), the global model Transformer or None (no attention branch).  A
+layer, so the ESC term of layer l is carried and re-gated) or PNA (nn.PNAConv on the fused mean | max | sum aggregate,
+csrc/pna.hip; the edge attributes pass through as with GINE), the global model Transformer or None (no attention branch).  A
 checkpoint of one layout is refused by another (load_state_dict's own error).
 
-Out of scope: BiasedTransformer / attn_bias, Performer and BigBird, the local GNN types GCN / GIN / GENConv / GAT / PNA, the
-EquivStableLapPE gate of GINE and GatedGCN, layer_norm, the other positional
+Out of scope: BiasedTransformer / attn_bias, Performer and BigBird, the local GNN types GCN / GIN / GENConv / GAT, PNA's other
+aggregators, degree scalers (pna_degrees) and towers, the EquivStableLapPE gate of GINE and GatedGCN, layer_norm, the other positional
 encodings (SignNet, EquivStableLapPE, HKdiagSE, ElstaticSE), graphgym's config system and wandb, a whole-step engine, and data
 parallelism (WORLD_SIZE > 1 is refused).
 
@@ -63,7 +64,7 @@ _FLAGS = [  # defaults: GraphGPS/configs/GPS/zinc-GPS.yaml (gt.*, train.batch_si
     ("--eval", dict(default=0, type=int)),
     ("--synthetic_graphs", dict(type=int, default=12000, help="train+val+test molecules (10:1:1 like ZINC-12k)")),
     ("--gt_layer_type", dict(default="GINE+Transformer", help="gt.layer_type, <local GNN>+<global model>: " + ", ".join(
-        ("GINE+Transformer", "CustomGatedGCN+Transformer", "GINE+None", "CustomGatedGCN+None")))),
+        ("GINE+Transformer", "CustomGatedGCN+Transformer", "GINE+None", "CustomGatedGCN+None", "PNA+Transformer", "PNA+None")))),
     ("--posenc_LapPE", dict(type=int, default=0, help="1: node encoder TypeDictNode+LapPE (the reference yaml), 0: TypeDictNode")),
     ("--posenc_LapPE_max_freqs", dict(type=int, default=8, help="posenc_LapPE.eigen.max_freqs")),
     ("--posenc_LapPE_dim_pe", dict(type=int, default=8, help="posenc_LapPE.dim_pe (model DeepSet, layers 2)")),
@@ -79,7 +80,7 @@ _FLAGS = [  # defaults: GraphGPS/configs/GPS/zinc-GPS.yaml (gt.*, train.batch_si
 ]
 
 
-LAYER_TYPES = ("GINE+Transformer", "CustomGatedGCN+Transformer", "GINE+None", "CustomGatedGCN+None")
+LAYER_TYPES = ("GINE+Transformer", "CustomGatedGCN+Transformer", "GINE+None", "CustomGatedGCN+None", "PNA+Transformer", "PNA+None")
 
 
 def build_parser():
