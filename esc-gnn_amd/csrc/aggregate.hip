@@ -18,6 +18,7 @@
 // 1 KiB wave read.  x (N*C*4 = 2.4 MB @cfg1) stays L2-resident; e rows stream once.
 // Algorithmic bytes/launch: 2*E*C*4 + 2*N*C*4 + E*8 + (N+1)*4.
 #include "common.h"
+#include "row_walk.h"
 #include "sparse_plan.h"
 
 #include <cstdlib>
@@ -29,23 +30,11 @@
 namespace esc {
 
 // ---- wide rows: one wave per node, VEC floats per lane per pass ---------------------------------
-// Edges are consumed in batches of AGG_BATCH with every row read of the batch issued before the first
-// use (2*AGG_BATCH loads in flight per wave); a short tail batch is padded by clamping the edge slot to
-// the node's last edge and masking its contribution, so the typical in-degree (6-7 for the counting
-// graphs) costs ONE round of memory latency instead of one per leftover edge.
-constexpr int AGG_BATCH = 8;
-
-// VEC consecutive floats of a row <-> registers (16-, 8- or 4-byte accesses)
-template <int VEC> __device__ __forceinline__ void row_load(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) { const float4 a = *reinterpret_cast<const float4*>(p); v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; }
-  else if constexpr (VEC == 2) { const float2 a = *reinterpret_cast<const float2*>(p); v[0] = a.x; v[1] = a.y; }
-  else v[0] = *p;
-}
-template <int VEC> __device__ __forceinline__ void row_store(float* p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else if constexpr (VEC == 2) *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
-  else *p = v[0];
-}
+// The two j loops below are row_walk.h's walk (segment_batches) written out, rule for rule: these are the kernels the training
+// step runs, tuned against measurements, and on the shared template every instantiation compiled to other instructions (the
+// loop test inverted, the operands of the accumulating v_add_f32 swapped, 2-10 instructions fewer in five of twelve;
+// profiles/row_walk_refactor.txt 0) - so they keep their text.  A change of the tail or the batch rule goes to both places.
+constexpr int AGG_BATCH = 8;              // 2 row reads per edge: 16 rows in flight per wave
 
 // AFF: x holds PRE-activation rows of a BatchNorm(+ReLU) whose output was never materialised; every row read applies
 // relu(x*xa_scale + xa_shift) on the fly (same fmaf + max as esc_affine_act, so the sums are bit-identical to the

@@ -18,25 +18,17 @@
 // relu(x_{d-1}[j]) * sum_i g[i]) and reduced per workgroup and then across workgroups in a fixed order: equal up to rounding,
 // bit-stable from run to run.
 #include "common.h"
+#include "row_walk.h"
 #include "sparse_plan.h"
 #include "../../include/escgnn_gineplus.h"
 
 namespace esc {
 
 constexpr int GP_K_MAX = 4;
-constexpr int GP_FWD_BATCH = 8;         // rows in flight per wave, forward (as AGG_BATCH)
+constexpr int GP_FWD_BATCH = 8;         // forward: 2 row reads per pair, 16 rows in flight per wave (as AGG_BATCH)
 constexpr int GP_BWD_BATCH = 4;         // ... backward: twice the live accumulators
 constexpr int GP_BWD_WAVES = 8;         // waves per workgroup of the backward: their d_eps partials are added in LDS
 static_assert(GP_K_MAX == sparse::GP_K_MAX && GP_BWD_WAVES == sparse::GP_BWD_WAVES, "sparse_plan.h sizes the backward's grid by these");
-
-template <int VEC> __device__ __forceinline__ void gp_load(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) { const float4 a = *reinterpret_cast<const float4*>(p); v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; }
-  else v[0] = *p;
-}
-template <int VEC> __device__ __forceinline__ void gp_store(float* p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else *p = v[0];
-}
 
 struct GpArgs {
   const float* x0; const float* x1; const float* x2; const float* x3;
@@ -72,56 +64,50 @@ __global__ __launch_bounds__(256) void gp_fwd_wave(GpArgs a) {
     for (int d = 0; d < GP_K_MAX; ++d)
 #pragma unroll
       for (int t = 0; t < VEC; ++t) acc[d][t] = 0.f;
-    gp_load<VEC>(a.x0 + (size_t)node * a.ld0 + c, self);
-    for (int j = beg; j < end; j += GP_FWD_BATCH) {
-      float xv[GP_FWD_BATCH][VEC], ev[GP_FWD_BATCH][VEC];
-      int dd[GP_FWD_BATCH];
+    row_load<VEC>(a.x0 + (size_t)node * a.ld0 + c, self);
+    float xv[GP_FWD_BATCH][VEC], ev[GP_FWD_BATCH][VEC];
+    int dd[GP_FWD_BATCH];
+    segment_batches<GP_FWD_BATCH, false>(beg, end, [&](int u, int jj, bool live) {
+      const int4 m = *reinterpret_cast<const int4*>(a.meta + 4 * (size_t)jj);
+      const int s = min(max(uniform(m.x), 0), a.N - 1);
+      const int d = uniform(m.z), rk = uniform(m.w);
+      dd[u] = (live && d >= 1 && d <= k) ? d : 0;           // distance 0 is the self term, read above
+      const int dsel = dd[u] ? d : 1;
+      row_load<VEC>(gp_row(a, dsel, s) + c, xv[u]);
+      if (dd[u] == 1 && rk >= 0 && rk < a.M1) row_load<VEC>(a.e + (size_t)rk * a.ld_e + c, ev[u]);
+      else {
 #pragma unroll
-      for (int u = 0; u < GP_FWD_BATCH; ++u) {
-        const int jj = min(j + u, end - 1);                 // wave-uniform clamp (tail padding)
-        const int4 m = *reinterpret_cast<const int4*>(a.meta + 4 * (size_t)jj);
-        const int s = min(max(uniform(m.x), 0), a.N - 1);
-        const int d = uniform(m.z), rk = uniform(m.w);
-        dd[u] = (j + u < end && d >= 1 && d <= k) ? d : 0;  // distance 0 is the self term, read above
-        const int dsel = dd[u] ? d : 1;
-        gp_load<VEC>(gp_row(a, dsel, s) + c, xv[u]);
-        if (dd[u] == 1 && rk >= 0 && rk < a.M1) gp_load<VEC>(a.e + (size_t)rk * a.ld_e + c, ev[u]);
-        else {
-#pragma unroll
-          for (int t = 0; t < VEC; ++t) ev[u][t] = 0.f;
-        }
+        for (int t = 0; t < VEC; ++t) ev[u][t] = 0.f;
       }
+    }, [&](int u) {
+      const int d = dd[u];                                  // wave-uniform: ascending-source order is kept inside every distance
+      if (d == 1) {
 #pragma unroll
-      for (int u = 0; u < GP_FWD_BATCH; ++u) {
-        const int d = dd[u];                                // wave-uniform: ascending-source order is kept inside every distance
-        if (d == 1) {
+        for (int t = 0; t < VEC; ++t) acc[0][t] = __fadd_rn(acc[0][t], fmaxf(__fadd_rn(xv[u][t], ev[u][t]), 0.f));
+      } else if (d == 2) {
 #pragma unroll
-          for (int t = 0; t < VEC; ++t) acc[0][t] = __fadd_rn(acc[0][t], fmaxf(__fadd_rn(xv[u][t], ev[u][t]), 0.f));
-        } else if (d == 2) {
+        for (int t = 0; t < VEC; ++t) acc[1][t] = __fadd_rn(acc[1][t], fmaxf(xv[u][t], 0.f));
+      } else if (d == 3) {
 #pragma unroll
-          for (int t = 0; t < VEC; ++t) acc[1][t] = __fadd_rn(acc[1][t], fmaxf(xv[u][t], 0.f));
-        } else if (d == 3) {
+        for (int t = 0; t < VEC; ++t) acc[2][t] = __fadd_rn(acc[2][t], fmaxf(xv[u][t], 0.f));
+      } else if (d == 4) {
 #pragma unroll
-          for (int t = 0; t < VEC; ++t) acc[2][t] = __fadd_rn(acc[2][t], fmaxf(xv[u][t], 0.f));
-        } else if (d == 4) {
-#pragma unroll
-          for (int t = 0; t < VEC; ++t) acc[3][t] = __fadd_rn(acc[3][t], fmaxf(xv[u][t], 0.f));
-        }
+        for (int t = 0; t < VEC; ++t) acc[3][t] = __fadd_rn(acc[3][t], fmaxf(xv[u][t], 0.f));
       }
-    }
+    });
     float res[VEC], ep[VEC];
-    gp_load<VEC>(a.eps + c, ep);
+    row_load<VEC>(a.eps + c, ep);
 #pragma unroll
     for (int t = 0; t < VEC; ++t) res[t] = __fmul_rn(__fadd_rn(1.0f, ep[t]), self[t]);
 #pragma unroll
     for (int d = 0; d < GP_K_MAX; ++d) {
       if (d < k) {
-        gp_load<VEC>(a.eps + (size_t)(d + 1) * C + c, ep);
+        row_load<VEC>(a.eps + (size_t)(d + 1) * C + c, ep);
 #pragma unroll
         for (int t = 0; t < VEC; ++t) res[t] = __fadd_rn(res[t], __fmul_rn(__fadd_rn(1.0f, ep[t]), acc[d][t]));
       }
     }
-    gp_store<VEC>(a.out + (size_t)node * a.ld_out + c, res);
+    row_store<VEC>(a.out + (size_t)node * a.ld_out + c, res);
   }
 }
 
@@ -148,7 +134,7 @@ __global__ __launch_bounds__(GP_BWD_WAVES * 64) void gp_bwd_wave(GpArgs a) {
       for (int d = 0; d <= GP_K_MAX; ++d) {
         if (d <= k) {
           float ep[VEC];
-          gp_load<VEC>(a.eps + (size_t)d * C + c, ep);
+          row_load<VEC>(a.eps + (size_t)d * C + c, ep);
 #pragma unroll
           for (int t = 0; t < VEC; ++t) ope[d][t] = __fadd_rn(1.0f, ep[t]);
         }
@@ -157,75 +143,69 @@ __global__ __launch_bounds__(GP_BWD_WAVES * 64) void gp_bwd_wave(GpArgs a) {
         const int beg = uniform((int)a.out_ptr[node]);
         const int end = uniform((int)a.out_ptr[node + 1]);
         float gi[VEC], xr[GP_K_MAX][VEC], accS[GP_K_MAX][VEC], accU[GP_K_MAX][VEC];
-        gp_load<VEC>(a.g + (size_t)node * a.ld_g + c, gi);
+        row_load<VEC>(a.g + (size_t)node * a.ld_g + c, gi);
 #pragma unroll
         for (int d = 0; d < GP_K_MAX; ++d) {
 #pragma unroll
           for (int t = 0; t < VEC; ++t) { xr[d][t] = 0.f; accS[d][t] = 0.f; accU[d][t] = 0.f; }
-          if (d < k) gp_load<VEC>(gp_row(a, d + 1, node) + c, xr[d]);
+          if (d < k) row_load<VEC>(gp_row(a, d + 1, node) + c, xr[d]);
         }
 #pragma unroll
         for (int t = 0; t < VEC; ++t) dep[0][t] = fmaf(gi[t], xr[0][t], dep[0][t]);
-        for (int j = beg; j < end; j += GP_BWD_BATCH) {     // the row reads of a batch in flight together
-          float gv[GP_BWD_BATCH][VEC], ev[GP_BWD_BATCH][VEC];
-          int dd[GP_BWD_BATCH], rr[GP_BWD_BATCH];
+        float gv[GP_BWD_BATCH][VEC], ev[GP_BWD_BATCH][VEC];
+        int dd[GP_BWD_BATCH], rr[GP_BWD_BATCH];
+        segment_batches<GP_BWD_BATCH, false>(beg, end, [&](int u, int jj, bool live) {
+          const int4 m = *reinterpret_cast<const int4*>(a.meta + 4 * (size_t)jj);
+          const int i = min(max(uniform(m.y), 0), N - 1);
+          const int d = uniform(m.z), rk = uniform(m.w);
+          dd[u] = (live && d >= 1 && d <= k) ? d : 0;
+          rr[u] = (dd[u] == 1 && rk >= 0 && rk < a.M1) ? rk : -1;
+          row_load<VEC>(a.g + (size_t)i * a.ld_g + c, gv[u]);
+          if (rr[u] >= 0) row_load<VEC>(a.e + (size_t)rr[u] * a.ld_e + c, ev[u]);
+          else {
 #pragma unroll
-          for (int u = 0; u < GP_BWD_BATCH; ++u) {
-            const int jj = min(j + u, end - 1);
-            const int4 m = *reinterpret_cast<const int4*>(a.meta + 4 * (size_t)jj);
-            const int i = min(max(uniform(m.y), 0), N - 1);
-            const int d = uniform(m.z), rk = uniform(m.w);
-            dd[u] = (j + u < end && d >= 1 && d <= k) ? d : 0;
-            rr[u] = (dd[u] == 1 && rk >= 0 && rk < a.M1) ? rk : -1;
-            gp_load<VEC>(a.g + (size_t)i * a.ld_g + c, gv[u]);
-            if (rr[u] >= 0) gp_load<VEC>(a.e + (size_t)rr[u] * a.ld_e + c, ev[u]);
-            else {
+            for (int t = 0; t < VEC; ++t) ev[u][t] = 0.f;
+          }
+        }, [&](int u) {
+          const int d = dd[u];
+          if (d == 1) {
+            float o[VEC];
 #pragma unroll
-              for (int t = 0; t < VEC; ++t) ev[u][t] = 0.f;
+            for (int t = 0; t < VEC; ++t) {
+              const float msg = __fadd_rn(xr[0][t], ev[u][t]);
+              o[t] = msg > 0.f ? __fmul_rn(gv[u][t], ope[1][t]) : 0.f;
+              accS[0][t] = __fadd_rn(accS[0][t], o[t]);
+              dep[1][t] = fmaf(gv[u][t], fmaxf(msg, 0.f), dep[1][t]);
+            }
+            if (a.d_e != nullptr && rr[u] >= 0) row_store<VEC>(a.d_e + (size_t)rr[u] * C + c, o);
+          } else if (d == 2) {
+#pragma unroll
+            for (int t = 0; t < VEC; ++t) {
+              accS[1][t] = __fadd_rn(accS[1][t], xr[1][t] > 0.f ? __fmul_rn(gv[u][t], ope[2][t]) : 0.f);
+              accU[1][t] += gv[u][t];
+            }
+          } else if (d == 3) {
+#pragma unroll
+            for (int t = 0; t < VEC; ++t) {
+              accS[2][t] = __fadd_rn(accS[2][t], xr[2][t] > 0.f ? __fmul_rn(gv[u][t], ope[3][t]) : 0.f);
+              accU[2][t] += gv[u][t];
+            }
+          } else if (d == 4) {
+#pragma unroll
+            for (int t = 0; t < VEC; ++t) {
+              accS[3][t] = __fadd_rn(accS[3][t], xr[3][t] > 0.f ? __fmul_rn(gv[u][t], ope[4][t]) : 0.f);
+              accU[3][t] += gv[u][t];
             }
           }
-#pragma unroll
-          for (int u = 0; u < GP_BWD_BATCH; ++u) {
-            const int d = dd[u];
-            if (d == 1) {
-              float o[VEC];
-#pragma unroll
-              for (int t = 0; t < VEC; ++t) {
-                const float msg = __fadd_rn(xr[0][t], ev[u][t]);
-                o[t] = msg > 0.f ? __fmul_rn(gv[u][t], ope[1][t]) : 0.f;
-                accS[0][t] = __fadd_rn(accS[0][t], o[t]);
-                dep[1][t] = fmaf(gv[u][t], fmaxf(msg, 0.f), dep[1][t]);
-              }
-              if (a.d_e != nullptr && rr[u] >= 0) gp_store<VEC>(a.d_e + (size_t)rr[u] * C + c, o);
-            } else if (d == 2) {
-#pragma unroll
-              for (int t = 0; t < VEC; ++t) {
-                accS[1][t] = __fadd_rn(accS[1][t], xr[1][t] > 0.f ? __fmul_rn(gv[u][t], ope[2][t]) : 0.f);
-                accU[1][t] += gv[u][t];
-              }
-            } else if (d == 3) {
-#pragma unroll
-              for (int t = 0; t < VEC; ++t) {
-                accS[2][t] = __fadd_rn(accS[2][t], xr[2][t] > 0.f ? __fmul_rn(gv[u][t], ope[3][t]) : 0.f);
-                accU[2][t] += gv[u][t];
-              }
-            } else if (d == 4) {
-#pragma unroll
-              for (int t = 0; t < VEC; ++t) {
-                accS[3][t] = __fadd_rn(accS[3][t], xr[3][t] > 0.f ? __fmul_rn(gv[u][t], ope[4][t]) : 0.f);
-                accU[3][t] += gv[u][t];
-              }
-            }
-          }
-        }
+        });
         if (a.dx != nullptr) {
           float o[VEC];
 #pragma unroll
           for (int t = 0; t < VEC; ++t) o[t] = __fadd_rn(__fmul_rn(gi[t], ope[0][t]), accS[0][t]);
-          gp_store<VEC>(a.dx + (size_t)node * C + c, o);
+          row_store<VEC>(a.dx + (size_t)node * C + c, o);
 #pragma unroll
           for (int d = 1; d < GP_K_MAX; ++d) {
-            if (d < k) gp_store<VEC>(a.dx + (size_t)d * plane + (size_t)node * C + c, accS[d]);
+            if (d < k) row_store<VEC>(a.dx + (size_t)d * plane + (size_t)node * C + c, accS[d]);
           }
         }
 #pragma unroll

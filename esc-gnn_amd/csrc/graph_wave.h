@@ -1,11 +1,12 @@
 // graph_wave.h — the wave-level primitives of the graph-structure kernels (features.hip, subgraphs.hip, multihop.hip, plan.hip;
-// DESIGN.md 6o): the segment search, the group of float4 lanes that owns a node (gatedgcn.hip, pna.hip), the ballot-prefix rank, the one-workgroup exclusive scan, the level-synchronous BFS in LDS
-// and what one root's wave of the rooted expansions does with it.  Every primitive is the text its callers used to carry, once.
+// DESIGN.md 6o): the segment search, the float4 accessors of pna.hip's lane groups, the ballot-prefix rank, the one-workgroup
+// exclusive scan, the level-synchronous BFS in LDS and what one root's wave of the rooted expansions does with it.  Every primitive is the text its callers used to carry, once.
 // Below them, the host side that subgraphs.hip and multihop.hip share: the argument check that every count / fill entry opens with
 // and the launchers of the per-graph validation and of the two-array scan (the kernels themselves live in subgraphs.hip: a
 // kernel has one translation unit).
 #pragma once
 #include "common.h"
+#include "row_walk.h"
 
 namespace esc {
 
@@ -22,19 +23,9 @@ __device__ __forceinline__ int find_segment(const int64_t* __restrict__ ptr, int
   return lo;
 }
 
-// ---- a group of LG float4 lanes per node (gatedgcn.hip, pna.hip) ------------------------------------------------------------------
+// ---- float4 rows of pna.hip's lane groups (group_locate: row_walk.h) -----------------------------------------------------------------
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
-// the node of this lane's group and the first column of the lane; false: nothing to do.  A wave holds 64 / LG groups.
-template <int LG>
-__device__ __forceinline__ bool group_locate(int N, int& node, int& c0) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t g = t / LG;
-  node = (int)g;
-  c0 = (int)(t - g * LG) * 4;
-  return g < N;
-}
 
 // ---- stable ballot-prefix compaction ------------------------------------------------------------------------------------------
 // number of set bits of a ballot below this lane: the lane's rank among the lanes that voted

@@ -38,6 +38,8 @@ constexpr int GP_K_MAX = 4;                   // GINE+: hops
 constexpr int GP_BWD_WAVES = 8;               // ... waves per workgroup of the backward: their d_eps partials are added in LDS
 constexpr int GP_BWD_MAX_BLOCKS = 512;        // ... each wave takes rows wave, wave + W, ...: the partials stay a few hundred rows
 constexpr int64_t GG_GROUP16_MAX_C = 64, GG_GROUP32_MAX_C = 128;      // GatedGCN: float4 lanes per node = 16 | 32 | 64
+constexpr int64_t GG_MAX_C = 1024;            // ... esc_gated_gcn_max_channels
+constexpr int GROUP_BLOCK = 256;              // ... threads of every workgroup of the lane-group kernels: four waves
 constexpr int64_t EMBED_V4_MAX_C = 256, EMBED_MAX_ROWS = 4096;       // esc_embed_bwd: float4 form up to here | "a small table"
 
 // ESC_AGG_SPLIT (default 2: the forward splits 256-wide rows over two waves; 1 switches it off), ESC_AGG_SPLIT_BWD (default 1;
@@ -238,7 +240,7 @@ inline Plan plan_gineplus_bwd(const GpOps& o, Op g, Op dx, Op d_e, int64_t N, in
 inline Plan plan_gated(int64_t N, int64_t C, bool backward) {
   Plan p = start(backward ? K_GATED_BWD : K_GATED_FWD, C <= GG_GROUP16_MAX_C ? F_GROUP16 : C <= GG_GROUP32_MAX_C ? F_GROUP32 : F_GROUP64, true);
   p.cw = p.family == F_GROUP16 ? 16 : p.family == F_GROUP32 ? 32 : 64;
-  p = with_launch(p, (unsigned)cdiv(N * p.cw, 256));
+  p = with_launch(p, (unsigned)cdiv(N * p.cw, GROUP_BLOCK));
   return backward ? with_launch(p, p.grid[0].x) : p;
 }
 

@@ -35,6 +35,22 @@ def _plan_on(dev, plan, *fields):
         _on(dev, getattr(plan, f))
 
 
+def _views_on(dev, plan):
+    """both sorted edge views of the plan, as the aggregate kernels walk them, on the operands' device"""
+    _plan_on(dev, plan, "in_ptr", "in_edge", "in_src", "out_ptr", "out_edge", "out_dst")
+
+
+def _edge_ptr(E):
+    """nv.ptr for what exists only where the batch has edges: a batch without any hands the kernels NULL instead"""
+    return nv.ptr if E else (lambda t: None)
+
+
+def _width_limit(op, C, limit):
+    """the width rule of the lane-group kernels, refused before anything is launched: a multiple of 4 from 4 up to `limit`"""
+    if C % 4 or not 4 <= C <= limit:
+        raise ValueError("%s: width %d: the kernels take a multiple of 4 with 4 <= C <= %d" % (op, C, limit))
+
+
 def _rows(t, width=None):
     """The row-operand rule, stated once: a 2-D tensor (of `width` columns when one is required) as a kernel reads it, and its
     leading dimension.  Unit inner stride with rows that do not overlap is taken in place (a column slice of wider rows keeps
@@ -134,7 +150,7 @@ class _Aggregate(Function):
     def forward(ctx, x, e, eps, plan, gine):
         _dev(x, e, eps)
         _on(x.device, e, eps)
-        _plan_on(x.device, plan, "in_ptr", "in_edge", "in_src", "out_ptr", "out_edge", "out_dst")
+        _views_on(x.device, plan)
         x, ldx = _rows(x)
         e, lde = _rows(e) if (gine or e is not None) else (None, 0)
         N, C = x.shape
@@ -195,13 +211,11 @@ class _GatedGCN(Function):
     def forward(ctx, Ax, Bx, Dx, Ex, Ce, plan):
         _dev(Ax, Bx, Dx, Ex, Ce)
         _on(Ax.device, Bx, Dx, Ex, Ce)
-        _plan_on(Ax.device, plan, "in_ptr", "in_edge", "in_src", "out_ptr", "out_edge", "out_dst")
+        _views_on(Ax.device, plan)
         (Ax, lda), (Bx, ldb), (Dx, ldd), (Ex, lde), (Ce, ldc) = (_rows(t) for t in (Ax, Bx, Dx, Ex, Ce))
         N, C = Ax.shape
         E = plan.num_edges
-        limit = gated_gcn_max_channels()
-        if C % 4 or not 4 <= C <= limit:
-            raise ValueError("gated_gcn_aggregate: width %d: the kernels take a multiple of 4 with 4 <= C <= %d" % (C, limit))
+        _width_limit("gated_gcn_aggregate", C, gated_gcn_max_channels())
         if any(tuple(t.shape) != (N, C) for t in (Bx, Dx, Ex)) or Ce.size(1) != C or N != plan.num_nodes:
             raise ValueError("gated_gcn_aggregate: Ax %s, Bx %s, Dx %s, Ex %s, Ce %s must share one width and the batch's %d nodes"
                              % (tuple(Ax.shape), tuple(Bx.shape), tuple(Dx.shape), tuple(Ex.shape), tuple(Ce.shape), plan.num_nodes))
@@ -209,7 +223,7 @@ class _GatedGCN(Function):
             raise ValueError("gated_gcn_aggregate: Ce has %d rows, the batch has %d edges" % (Ce.size(0), E))
         dev = Ax.device
         out, e_out, den = _empty(dev, N, C), _empty(dev, E, C), _empty(dev, N, C)
-        edge = (lambda t: nv.ptr(t)) if E else (lambda t: None)
+        edge = _edge_ptr(E)
         nv.call("esc_gated_gcn_fwd", nv.ptr(Ax), lda, nv.ptr(Bx), ldb, nv.ptr(Dx), ldd, nv.ptr(Ex), lde, edge(Ce), ldc,
                 nv.ptr(plan.in_ptr), edge(plan.in_edge), edge(plan.in_src), N, E, C, nv.ptr(out), C, edge(e_out), C, nv.ptr(den),
                 nv.stream())
@@ -228,7 +242,7 @@ class _GatedGCN(Function):
         g_out, ldg = _rows(g_out if g_out is not None else _zeros(dev, N, C))
         g_e, ldge = _rows(g_e) if g_e is not None else (None, 0)
         d_Ce, d_Dx, d_Ex, d_Bx = _empty(dev, E, C), _empty(dev, N, C), _empty(dev, N, C), _empty(dev, N, C)
-        edge = (lambda t: nv.ptr(t)) if E else (lambda t: None)
+        edge = _edge_ptr(E)
         nv.call("esc_gated_gcn_bwd", nv.ptr(g_out), ldg, edge(g_e), ldge, edge(e_out), C, nv.ptr(den), nv.ptr(out), C, nv.ptr(Ax), lda,
                 nv.ptr(Bx), ldb, nv.ptr(plan.in_ptr), edge(plan.in_edge), edge(plan.in_src), nv.ptr(plan.out_ptr),
                 edge(plan.out_edge), edge(plan.out_dst), N, E, C, edge(d_Ce), C, nv.ptr(d_Dx), C, nv.ptr(d_Ex), C, nv.ptr(d_Bx), C,
@@ -257,13 +271,11 @@ class _PNAAggregate(Function):
     def forward(ctx, P, Q, R, plan):
         _dev(P, Q, R)
         _on(P.device, Q, R)
-        _plan_on(P.device, plan, "in_ptr", "in_edge", "in_src", "out_ptr", "out_edge", "out_dst")
+        _views_on(P.device, plan)
         (P, ldp), (Q, ldq), (R, ldr) = (_rows(t) for t in (P, Q, R))
         N, C = P.shape
         E = plan.num_edges
-        limit = pna_max_channels()
-        if C % 4 or not 4 <= C <= limit:
-            raise ValueError("pna_aggregate: width %d: the kernels take a multiple of 4 with 4 <= C <= %d" % (C, limit))
+        _width_limit("pna_aggregate", C, pna_max_channels())
         if tuple(Q.shape) != (N, C) or R.size(1) != C or N != plan.num_nodes:
             raise ValueError("pna_aggregate: P %s, Q %s, R %s must share one width and the batch's %d nodes"
                              % (tuple(P.shape), tuple(Q.shape), tuple(R.shape), plan.num_nodes))
@@ -271,7 +283,7 @@ class _PNAAggregate(Function):
             raise ValueError("pna_aggregate: R has %d rows, the batch has %d edges" % (R.size(0), E))
         dev = P.device
         agg, arg = _empty(dev, N, 3 * C), torch.empty((N, C), dtype=torch.int32, device=dev)
-        edge = (lambda t: nv.ptr(t)) if E else (lambda t: None)
+        edge = _edge_ptr(E)
         nv.call("esc_pna_aggregate_fwd", nv.ptr(P), ldp, nv.ptr(Q), ldq, edge(R), ldr, nv.ptr(plan.in_ptr), edge(plan.in_edge),
                 edge(plan.in_src), N, E, C, nv.ptr(agg), 3 * C, nv.ptr(arg), nv.stream())
         ctx.save_for_backward(arg)
@@ -286,7 +298,7 @@ class _PNAAggregate(Function):
         E, dev = plan.num_edges, arg.device
         g, ldg = _rows(g)
         d_R, d_P, d_Q = _empty(dev, E, C), _empty(dev, N, C), _empty(dev, N, C)
-        edge = (lambda t: nv.ptr(t)) if E else (lambda t: None)
+        edge = _edge_ptr(E)
         nv.call("esc_pna_aggregate_bwd", nv.ptr(g), ldg, nv.ptr(arg), nv.ptr(plan.in_ptr), edge(plan.in_edge), edge(plan.in_src),
                 nv.ptr(plan.out_ptr), edge(plan.out_edge), edge(plan.out_dst), N, E, C, edge(d_R), C, nv.ptr(d_P), C, nv.ptr(d_Q), C,
                 nv.stream())

@@ -42,6 +42,16 @@ def _molecule():
     return 30, src, dst
 
 
+def _ladder():
+    """18 nodes, node i with the in-edges 0 .. i-1 -> i (153 edges): in-degrees 0 .. 17 and out-degrees 17 .. 0 in one launch - an
+    empty range, every tail length of a batch of 4 and of 8, exact multiples, two full batches and a tail, in both views"""
+    pairs = [(j, i) for i in range(18) for j in range(i)]
+    return 18, [p[0] for p in pairs], [p[1] for p in pairs]
+
+
+LADDER_WIDTH = 260    # beyond WIDTHS, on "degree-ladder" and "molecule-30" alone: 64 lanes cover 256 columns, so a second pass with one live lane
+
+
 def _cases():
     n, s, d = _star()
     out = {
@@ -66,15 +76,16 @@ def _cases():
 
 
 CASES, WHERE = _cases()           # WHERE[name] = (first node, end node, first edge, end edge) of the case inside "batch"
+LADDER = {"degree-ladder": _ladder()}     # beside CASES, not in them: the batch, every seed and every loop over CASES stay what they were
 
 
 def edges_of(name):
-    n, s, d = CASES[name]
+    n, s, d = CASES[name] if name in CASES else LADDER[name]
     return n, torch.tensor(s, dtype=torch.int64), torch.tensor(d, dtype=torch.int64)
 
 
 def _seed(name, C):
-    return 1000 * (list(CASES).index(name) + 1) + C
+    return 1000 * ((list(CASES) + list(LADDER)).index(name) + 1) + C
 
 
 def inputs_of(name, C, scale=1.0):

@@ -74,10 +74,10 @@ def test_oracle_agrees_with_gradcheck():
 
 
 # ---- conditioning of what the GPU tests assert -------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("C", gg.WIDTHS)
+@pytest.mark.parametrize("C", gg.WIDTHS + (gg.LADDER_WIDTH,))
 def test_every_asserted_case_is_within_the_conditioning_cap(C):
     worst = 0.0
-    for name in gg.CASES:
+    for name in (list(gg.CASES) + list(gg.LADDER) if C in gg.WIDTHS else ["degree-ladder", "molecule-30"]):
         for with_ge in (True, False):
             ref = gg.reference(name, C, with_ge)
             for k, want in ref[torch.float64].items():

@@ -127,6 +127,24 @@ def test_raw_abi_against_the_oracle(E):
     assert torch.equal(v["out"][zero_in].cpu(), ops[0][zero_in])                   # out = Ax exactly: 0 / 1e-6
 
 
+@pytest.mark.parametrize("name,C", [("degree-ladder", C) for C in gg.WIDTHS + (gg.LADDER_WIDTH,)] + [("molecule-30", gg.LADDER_WIDTH)])
+def test_every_tail_length_and_the_second_column_pass(E, name, C):
+    """the degree ladder (in- and out-degrees 0 .. 17: every tail of the batched walk) and width 260 (the first at which a group
+    of 64 lanes runs its column loop twice, with one live lane), through the op and through the C ABI, with and without g_e"""
+    ops, g_out, g_e = gg.inputs_of(name, C)
+    for with_ge in (True, False):
+        ref = gg.reference(name, C, with_ge)
+        out, e_out, x = run_op(E, name, C, with_ge)
+        got = dict(out=out, e_out=e_out, **{"d_" + k: t.grad for k, t in zip(OPERANDS, x)})
+        v, den, _ = raw_call(E, name, C, ops, g_out, g_e if with_ge else None, plan_of(E, name))
+        for how, tensors in (("op", got), ("raw", dict(v, den=den))):
+            for k, t in tensors.items():
+                check("%s %s C=%d %s %s" % (how, name, C, "g_e" if with_ge else "no-g_e", k), t, ref[F64][k], ref[F32][k],
+                      gg.scale_floor(name, C, with_ge, k))
+        for k in v:                                              # (d_Ax is g_out, formed by the op: the C ABI has no such output)
+            assert torch.equal(got[k], v[k]), "%s: the op and the C ABI differ" % k
+
+
 # ---- 2. column slices -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("C", [64, 68])
 def test_column_slices_of_wider_buffers(E, C):
