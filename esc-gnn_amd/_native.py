@@ -116,6 +116,14 @@ except OSError as exc:
     raise NativeLibraryError("esc_gnn_amd: cannot read the C header %s the binding is derived from (%s)" % (PNA_HEADER, exc)) from exc
 PNA_SIGNATURES = {name: args for name, (args, _) in _PNA.functions.items()}
 _RET.update({name: ret for name, (_, ret) in _PNA.functions.items()})
+# the tenth extension header (escgnn_spd.h: all-pairs shortest-path distances, their table gather and the biased ragged attention)
+SPD_HEADER = os.path.join(os.path.dirname(_abi.HEADER), "escgnn_spd.h")
+try:
+    _SPD = _abi.load(SPD_HEADER)
+except OSError as exc:
+    raise NativeLibraryError("esc_gnn_amd: cannot read the C header %s the binding is derived from (%s)" % (SPD_HEADER, exc)) from exc
+SPD_SIGNATURES = {name: args for name, (args, _) in _SPD.functions.items()}
+_RET.update({name: ret for name, (_, ret) in _SPD.functions.items()})
 KIND = {name[len("ESC_K_"):].lower(): v for name, v in _ABI.enum.items() if name != "ESC_K_COUNT"}
 
 CollateArgs = struct("esc_collate_args")
@@ -139,7 +147,7 @@ def lib():
             "esc_gnn_amd: %s not found. The HIP hot path has no fallback — build it with "
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C esc-gnn_amd/csrc`." % LIB_PATH)
     h = ctypes.CDLL(LIB_PATH)
-    for name, args in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()) + list(I2GNN_SIGNATURES.items()) + list(GINEPLUS_SIGNATURES.items()) + list(GPS_SIGNATURES.items()) + list(LAPPE_SIGNATURES.items()) + list(RWSE_SIGNATURES.items()) + list(STEP_SIGNATURES.items()) + list(GATEDGCN_SIGNATURES.items()) + list(PNA_SIGNATURES.items()):
+    for name, args in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()) + list(I2GNN_SIGNATURES.items()) + list(GINEPLUS_SIGNATURES.items()) + list(GPS_SIGNATURES.items()) + list(LAPPE_SIGNATURES.items()) + list(RWSE_SIGNATURES.items()) + list(STEP_SIGNATURES.items()) + list(GATEDGCN_SIGNATURES.items()) + list(PNA_SIGNATURES.items()) + list(SPD_SIGNATURES.items()):
         try:
             fn = getattr(h, name)
         except AttributeError as exc:

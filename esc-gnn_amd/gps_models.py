@@ -11,9 +11,15 @@ GINE layer and full self-attention over each graph's nodes side by side, adds th
 All arithmetic runs through the ops of this package (bag, GINE aggregate, Linear, BatchNorm, ReLU / ELU, embeddings, ragged
 attention, sum pooling); residual adds and the model-level Dropout stay torch ops as in the other models.  Per-op path only.
 
-`edge_attn_emb` and `edge_attn_linear` exist in the reference's state_dict although nothing uses them with `Transformer` (they
-feed the attn_bias of `BiasedTransformer`, which the reference's own collate leaves None); they are created here so that
-checkpoints load, and take no part in the forward.
+`edge_attn_emb` and `edge_attn_linear` exist in the reference's state_dict although nothing uses them with `Transformer`: they
+are created here so that checkpoints load, and take no part in that forward.  global_model_type='BiasedTransformer' is what
+they are for (gps_layer.py:237-239,273-278, Graphormer's spatial encoding): the batch's attn_bias - every graph's all-pairs
+shortest-path distances, 100 for no path (spd.add_spd, spd.SPDTable.attach) - goes through the embedding and the three Linears
+and is added to the attention scores per head.  The reference's own collate leaves the key None (loader/batch.py:132-141), and
+its dense form is a [B, n_max, n_max, heads] MLP per layer; here the bias depends on (distance, head) alone, so each layer
+evaluates edge_attn_linear(edge_attn_emb(arange(101))) once per forward - 101 x heads values of torch plumbing, through the
+Embedding lookup so that padding_idx keeps row 100's gradient zero - and the biased ragged attention reads that table
+(csrc/attention.hip).  The state_dict is the same under both types.
 
 The yaml's node encoder is TypeDictNode+LapPE.  GPSModel(lap_pe=True) builds it as the reference's Concat2NodeEncoder does:
 encoder1 = the type embedding at width dim_hidden - dim_pe, encoder2 = nn.LapPENodeEncoder over the batch's EigVals / EigVecs
@@ -30,7 +36,7 @@ local_gnn_type='PNA' swaps it for nn.PNAConv (PyG's PNAConv as gps_layer.py:78-9
 identity scaler, one tower, one pre- and one post-layer, edge_dim = min(128, dim_h)): treated as GINE is - dropout_local, the
 residual, norm1_local - and like GINE it leaves the edge attributes alone.
 
-Out of scope: BiasedTransformer / attn_bias, Performer and BigBird, the local GNN types GCN / GIN / GENConv / GAT, PNA's other
+Out of scope: Performer and BigBird, Graphormer's own encoders, log_attn_weights, edge-feature biases, the local GNN types GCN / GIN / GENConv / GAT, PNA's other
 aggregators (min, std), degree scalers, towers and deeper pre- / post-layers, the
 EquivStableLapPE gate of GINE and GatedGCN, a fused BatchNorm on GatedGCN's edge rows, layer_norm, the other positional
 encodings (SignNet, EquivStableLapPE, HKdiagSE, ElstaticSE) and LapPE's Transformer model, graphgym's config system and wandb,
@@ -48,8 +54,9 @@ class GPSLayer(torch.nn.Module):
     """Local message passing + full graph attention + feed-forward (gps_layer.py:19-302 with act 'relu' and batch_norm).
     local_gnn_type 'GINE' (the yaml's), 'PNA' (gps_layer.py:78-93: nn.PNAConv, handled as GINE is, :216-229) or
     'CustomGatedGCN' (gps_layer.py:94-99: nn.GatedGCNLayer with its own dropout and
-    residual, whose edge output becomes the layer's edge attributes, :197-208); global_model_type 'Transformer' or 'None'
-    (self_attn None: the attention branch is skipped; norm1_attn exists all the same, :150-152)."""
+    residual, whose edge output becomes the layer's edge attributes, :197-208); global_model_type 'Transformer',
+    'BiasedTransformer' (the same attention with the shortest-path bias of edge_attn_emb / edge_attn_linear on its scores,
+    :237-239,273-278) or 'None' (self_attn None: the attention branch is skipped; norm1_attn exists all the same, :150-152)."""
 
     def __init__(self, dim_h, num_heads, dropout=0.0, attn_dropout=0.0, local_gnn_type="GINE", global_model_type="Transformer"):
         super().__init__()
@@ -67,13 +74,13 @@ class GPSLayer(torch.nn.Module):
         else:
             raise ValueError(f"Unsupported local GNN model: {local_gnn_type}")
         self.local_gnn_type = local_gnn_type
-        self.edge_attn_emb = torch.nn.Embedding(101, num_heads, padding_idx=100)                         # unused: see the module docstring
+        self.edge_attn_emb = torch.nn.Embedding(101, num_heads, padding_idx=100)                         # BiasedTransformer's; else unused
         self.edge_attn_linear = Sequential(torch.nn.Linear(num_heads, num_heads), torch.nn.ReLU(),
                                            torch.nn.Linear(num_heads, num_heads), torch.nn.ReLU(),
                                            torch.nn.Linear(num_heads, num_heads))
         if global_model_type == "None":
             self.self_attn = None
-        elif global_model_type == "Transformer":
+        elif global_model_type in ("Transformer", "BiasedTransformer"):
             self.self_attn = GraphMultiheadAttention(dim_h, num_heads, dropout=attn_dropout)
         else:
             raise ValueError(f"Unsupported global x-former model: {global_model_type}")
@@ -91,6 +98,11 @@ class GPSLayer(torch.nn.Module):
         self.z_initial = torch.nn.Embedding(Z_TABLE_ROWS, dim_h)
         self.z_embedding = nested.z_embedding(dim_h, "elu", dropout)
 
+    def bias_table(self):
+        """[101, heads]: what the reference's MLP gives every pair at each distance (row 100: no path, the padding row)"""
+        index = torch.arange(101, device=self.edge_attn_emb.weight.device)
+        return self.edge_attn_linear(self.edge_attn_emb(index))
+
     def forward(self, h, edge_attr, data, plan, graph_ptr, max_nodes):
         """(node states, edge attributes) -> the same after this layer; the edge attributes carry this layer's ESC term on"""
         if "pos_index" in data:
@@ -102,7 +114,15 @@ class GPSLayer(torch.nn.Module):
             h_local = self.dropout_local(self.local_model(h, data.edge_index, edge_attr, plan))
             h_local = self.norm1_local(h + h_local)
         if self.self_attn is not None:
-            h_attn = self.dropout_attn(self.self_attn(h, graph_ptr, max_nodes))
+            if self.global_model_type == "BiasedTransformer":
+                spd = data["attn_bias"] if "attn_bias" in data else None
+                if spd is None:
+                    raise ValueError("GPSLayer: global_model_type 'BiasedTransformer' needs the batch's attn_bias (the graphs' "
+                                     "shortest-path distances): set it with spd.add_spd(batch) or spd.SPDTable(store).attach(batch, ids)")
+                h_attn = self.self_attn(h, graph_ptr, max_nodes, spd=spd, bias_table=self.bias_table())
+            else:
+                h_attn = self.self_attn(h, graph_ptr, max_nodes)
+            h_attn = self.dropout_attn(h_attn)
             h = h_local + self.norm1_attn(h + h_attn)
         else:
             h = h_local

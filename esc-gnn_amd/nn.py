@@ -257,9 +257,12 @@ class GraphMultiheadAttention(torch.nn.Module):
         torch.nn.init.constant_(self.in_proj_bias, 0.0)
         torch.nn.init.constant_(self.out_proj.bias, 0.0)
 
-    def forward(self, x, graph_ptr, max_nodes=None):
+    def forward(self, x, graph_ptr, max_nodes=None, spd=None, bias_table=None):
+        """spd (uint8, the batch's attn_bias) and bias_table [101, num_heads], both or neither: the float attn_mask of the
+        reference's BiasedTransformer as the table it collapses to (ops.graph_attention)"""
         qkv = ops.linear(x, self.in_proj_weight, self.in_proj_bias)
-        h = ops.graph_attention(qkv, graph_ptr, self.num_heads, p=self.dropout, training=self.training, max_nodes=max_nodes)
+        h = ops.graph_attention(qkv, graph_ptr, self.num_heads, p=self.dropout, training=self.training, max_nodes=max_nodes, spd=spd,
+                                bias_table=bias_table)
         return self.out_proj(h)
 
 

@@ -1292,15 +1292,79 @@ class _GraphAttention(Function):
         return d_qkv, None, None, None, None, None, None, None
 
 
-def graph_attention(qkv, graph_ptr, heads, p=0.0, training=False, max_nodes=None, seed=None, return_aux=False):
+def attention_bias_max_nodes(head_dim):
+    """the largest graph esc_graph_attention_bias_* take at this head_dim (0: no kernel for that head_dim): the unbiased limit
+    cut by the LDS the bias gradient's bins take (include/escgnn_spd.h states the formula)"""
+    return int(nv.lib().esc_graph_attention_bias_max_nodes(int(head_dim)))
+
+
+BIAS_ROWS = 101                   # rows of the bias table: distances 0..99, and 100 = no path (the reference's padding row)
+
+
+class _GraphAttentionBias(Function):
+    """_GraphAttention with table[min(spd_ij, 100), head] added to the scores: the reference's `BiasedTransformer`
+    (gps_layer.py:237-239,273-278), whose dense float attn_mask [B * heads, n_max, n_max] is never formed.  One launch forward,
+    two backward (the attention's, and the sum of the bias gradient's per-graph partials).  Gradients: qkv and the table; spd is
+    data."""
+
+    @staticmethod
+    def forward(ctx, qkv, table, spd, graph_ptr, pair_ptr, heads, head_dim, p, seed, max_nodes):
+        qkv, ld = _rows(qkv)
+        N, H = qkv.size(0), heads * head_dim
+        G, dev = graph_ptr.numel() - 1, qkv.device
+        out = _empty(dev, N, H)
+        lse = _empty(dev, heads, N)
+        mask_pairs = N * max_nodes if p > 0.0 else 0
+        mask = torch.empty(heads * mask_pairs, dtype=torch.uint8, device=dev) if p > 0.0 else None
+        nv.call("esc_graph_attention_bias_fwd", nv.ptr(qkv), ld, nv.ptr(graph_ptr), nv.ptr(pair_ptr), nv.ptr(spd), spd.numel(), nv.ptr(table),
+                G, N, mask_pairs, max_nodes, heads, head_dim, float(p), int(seed), nv.ptr(out), H, nv.ptr(lse), nv.ptr(mask), nv.stream())
+        ctx.save_for_backward(qkv, table, spd, lse, mask)
+        ctx.args = (graph_ptr, pair_ptr, G, N, mask_pairs, max_nodes, heads, head_dim, float(p))
+        ctx.mark_non_differentiable(lse)
+        ctx.set_materialize_grads(False)
+        return (out, lse) if mask is None else (out, lse, mask)
+
+    @staticmethod
+    def backward(ctx, d_out, *unused):
+        if d_out is None:
+            return (None,) * 10
+        qkv, table, spd, lse, mask = ctx.saved_tensors
+        graph_ptr, pair_ptr, G, N, mask_pairs, max_nodes, heads, head_dim, p = ctx.args
+        _dev(d_out)
+        qkv, ld = _rows(qkv)
+        d_out, ldg = _rows(d_out)
+        d_qkv = _empty(qkv.device, N, 3 * heads * head_dim)
+        d_table = _empty(qkv.device, BIAS_ROWS, heads)
+        need = int(nv.lib().esc_graph_attention_bias_scratch_floats(G, heads))
+        partial = _empty(qkv.device, max(need, 1))
+        nv.call("esc_graph_attention_bias_bwd", nv.ptr(qkv), ld, nv.ptr(d_out), ldg, nv.ptr(lse), nv.ptr(mask), nv.ptr(graph_ptr),
+                nv.ptr(pair_ptr), nv.ptr(spd), spd.numel(), nv.ptr(table), G, N, mask_pairs, max_nodes, heads, head_dim, p, nv.ptr(d_qkv),
+                nv.ptr(partial), need, nv.ptr(d_table), nv.stream())
+        return d_qkv, d_table, None, None, None, None, None, None, None, None
+
+
+def graph_attention(qkv, graph_ptr, heads, p=0.0, training=False, max_nodes=None, seed=None, return_aux=False, spd=None, bias_table=None):
     """Multi-head self-attention inside every graph of a ragged batch.  qkv: [N, 3H] rows [q | k | v] (a column slice of wider
     rows is read in place), graph_ptr: int32 [G+1] node ranges on the device, H = heads * head_dim.  Dropout with rate p on the
     attention weights when `training` (counter-based masks: `seed`, drawn from torch's generator when None).
     max_nodes: the largest graph of the batch as the HOST knows it (the device store's h_node_ptr) - given, nothing is read back;
     None costs one read-back of graph_ptr, cached on it.  Limits: head_dim a multiple of 4 and at most 64, max_nodes at most
     attention_max_nodes(head_dim); beyond them RuntimeError, raised before anything is launched.
-    return_aux: also (lse [heads, N], keep mask bytes or None; the mask's layout: include/escgnn_gps.h)."""
+    return_aux: also (lse [heads, N], keep mask bytes or None; the mask's layout: include/escgnn_gps.h).
+    spd, bias_table (both or neither): the shortest-path bias of the reference's BiasedTransformer - spd uint8, byte (i, j) of
+    graph g at pair_ptr[g] + i n + j (graph_spd, spd_gather; any byte matrix is legal, above 100 counts as 100), bias_table fp32
+    [101, heads], differentiable; the scores gain bias_table[min(spd_ij, 100), head] and lse includes it.  The node limit is then
+    attention_bias_max_nodes(head_dim).  Without them nothing changes."""
     _dev(qkv)
+    if (spd is None) != (bias_table is None):
+        raise ValueError("graph_attention: spd and bias_table come together (got %s)" % ("spd alone" if bias_table is None else "bias_table alone"))
+    if spd is not None:
+        _dev(bias_table)
+        _on(qkv.device, spd, bias_table)
+        if spd.dtype != torch.uint8 or spd.dim() != 1:
+            raise TypeError("graph_attention: spd must be a 1-D uint8 tensor (the graphs' flattened n x n distance matrices)")
+        if tuple(bias_table.shape) != (BIAS_ROWS, int(heads)):
+            raise ValueError("graph_attention: bias_table must be [%d, heads = %d], got %s" % (BIAS_ROWS, int(heads), tuple(bias_table.shape)))
     _on(qkv.device, graph_ptr)
     if graph_ptr.dtype != torch.int32 or graph_ptr.dim() != 1 or graph_ptr.numel() < 1:
         raise TypeError("graph_attention: graph_ptr must be a 1-D int32 tensor of G+1 node offsets")
@@ -1309,7 +1373,7 @@ def graph_attention(qkv, graph_ptr, heads, p=0.0, training=False, max_nodes=None
         raise RuntimeError("graph_attention: qkv %s is not [N, 3 * H] with heads * head_dim == H for %d heads"
                            % (tuple(qkv.shape), heads))
     head_dim = qkv.size(1) // (3 * heads)
-    limit = attention_max_nodes(head_dim)
+    limit = attention_max_nodes(head_dim) if spd is None else attention_bias_max_nodes(head_dim)
     if limit == 0:
         raise RuntimeError("graph_attention: head_dim %d must be a multiple of 4 and at most 64" % head_dim)
     graph_ptr = graph_ptr.contiguous()
@@ -1318,14 +1382,18 @@ def graph_attention(qkv, graph_ptr, heads, p=0.0, training=False, max_nodes=None
                             lambda: int((graph_ptr[1:] - graph_ptr[:-1]).max()) if graph_ptr.numel() > 1 else 0)
     max_nodes = int(max_nodes)
     if max_nodes > limit:
-        raise RuntimeError("graph_attention: a graph of %d nodes exceeds the limit of %d nodes per graph at head_dim %d"
-                           % (max_nodes, limit, head_dim))
+        raise RuntimeError("graph_attention: a graph of %d nodes exceeds the limit of %d nodes per graph at head_dim %d%s"
+                           % (max_nodes, limit, head_dim, "" if spd is None else " with the shortest-path bias"))
     p = float(p) if training else 0.0
     if not 0.0 <= p < 1.0:
         raise ValueError("graph_attention: dropout rate %g outside [0, 1)" % p)
     if p > 0.0 and seed is None:
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())      # host generator: seeded runs repeat, nothing waits for the device
-    res = _GraphAttention.apply(qkv, graph_ptr, _pair_ptr(graph_ptr), heads, head_dim, p, seed or 0, max_nodes)
+    if spd is None:
+        res = _GraphAttention.apply(qkv, graph_ptr, _pair_ptr(graph_ptr), heads, head_dim, p, seed or 0, max_nodes)
+    else:
+        res = _GraphAttentionBias.apply(qkv, bias_table.contiguous(), spd.contiguous(), graph_ptr, _pair_ptr(graph_ptr), heads, head_dim, p,
+                                        seed or 0, max_nodes)
     return (res[0], res[1], res[2] if len(res) > 2 else None) if return_aux else res[0]
 
 
@@ -1558,4 +1626,76 @@ def rwse_gather(table, node_ptr_all, graph_ids, graph_ptr, num_nodes):
         "rwse_gather", (table,), "the table must be a contiguous fp32 [N_all, K] tensor", node_ptr_all, graph_ids, graph_ptr, num_nodes)
     nv.call("esc_rwse_gather", nv.ptr(table), nv.ptr(node_ptr_all), G_all, N_all, nv.ptr(ids_d), nv.ptr(graph_ptr), B, N, K, nv.ptr(out), K,
             nv.stream())
+    return out
+
+
+# ---- shortest-path distances of the attention bias (csrc/spd.hip, include/escgnn_spd.h) ------------------------------------------
+def graph_spd_limits():
+    """(most nodes, most edges) of one graph esc_graph_spd takes, in the shape of rw_landing_limits(); the edges are not limited:
+    None"""
+    return int(nv.lib().esc_graph_spd_max_nodes()), None
+
+
+def _pairs_vector(pair_ptr, like, who):
+    pair_ptr = _index_vector(pair_ptr, "%s: pair_ptr" % who, torch.int64)
+    if pair_ptr.numel() != like.numel():
+        raise ValueError("%s: pair_ptr has %d entries, graph_ptr %d" % (who, pair_ptr.numel(), like.numel()))
+    return pair_ptr
+
+
+def graph_spd(edge_index, graph_ptr, edge_ptr, max_nodes=None, edges_local=False, num_nodes=None, num_pairs=None, pair_ptr=None):
+    """The all-pairs shortest-path distances of every graph of a ragged set, one workgroup per graph, one launch: the reference's
+    attn_bias key (GraphGPS/graphgps/loader/utils_escgnn.py:29-38: networkx on the undirected graph, 100 where there is no path).
+    edge_index, graph_ptr, edge_ptr, edges_local: as in laplacian_eig.  An edge listed in either direction connects both ends;
+    self-loops and duplicates change nothing.  Returns uint8 [sum n^2]: entry (i, j) of graph g at pair_ptr[g] + i n + j, the value
+    min(d, 100) - a true distance of 100 aliases "no path" as in the reference, and beyond 100 (where the reference's embedding
+    lookup raises) the pair reads the same row.  Not differentiable: the distances are data.
+    max_nodes, num_nodes, num_pairs (= sum n^2): as the HOST knows them; None costs one read-back each.  pair_ptr: the int64
+    scan of n^2 when the caller has it (default: the one cached on graph_ptr, which ops.graph_attention shares).
+    Limit: graph_spd_limits()[0] = 256 nodes per graph; beyond it RuntimeError, raised before anything is launched."""
+    src, dst, node_ptr, edge_ptr_, G, N, max_nodes = _ragged_graphs("graph_spd", graph_spd_limits()[0], edge_index, graph_ptr, edge_ptr,
+                                                                    max_nodes, num_nodes)
+    pair_ptr = _pair_ptr(graph_ptr) if pair_ptr is None else _pairs_vector(pair_ptr, graph_ptr, "graph_spd")
+    _on(src.device, pair_ptr)
+    if num_pairs is None:
+        num_pairs = int(pair_ptr[-1])
+    num_pairs = int(num_pairs)
+    out = torch.empty(max(num_pairs, 0), dtype=torch.uint8, device=src.device)
+    nv.call("esc_graph_spd", nv.ptr(src), nv.ptr(dst), src.numel(), nv.ptr(node_ptr), nv.ptr(edge_ptr_), nv.ptr(pair_ptr), G, N, num_pairs,
+            int(bool(edges_local)), max(max_nodes, 0), nv.ptr(out), nv.stream())
+    return out
+
+
+def spd_gather(table, pair_ptr_all, node_ptr_all, graph_ids, graph_ptr, num_pairs=None):
+    """The batch's bytes of a split's resident distance table (what the reference's collate would do to the attn_bias key), one
+    launch.  table uint8 [pairs_all] in pair_ptr_all's layout; pair_ptr_all, node_ptr_all int64 [G_all+1] (device); graph_ids: the
+    batch's graphs in batch order, a HOST int64 tensor or list - checked here, an id out of range raises IndexError before
+    anything is launched; graph_ptr int32 [B+1]: the batch's node ranges (its pair_ptr is the one cached on it); num_pairs: the
+    batch's sum of n^2 as the host knows it (None: one read-back).  Returns uint8 [num_pairs]."""
+    who = "spd_gather"
+    if not torch.is_tensor(table) or table.dtype != torch.uint8 or table.dim() != 1 or not table.is_contiguous():
+        raise TypeError("%s: the table must be a contiguous 1-D uint8 tensor" % who)
+    if not table.is_cuda:
+        raise RuntimeError("esc_gnn_amd: the hot path runs on the HIP device only (got a %s tensor); there is no CPU fallback" % table.device)
+    dev = table.device
+    node_ptr_all = _index_vector(node_ptr_all, "%s: node_ptr_all" % who, torch.int64)
+    pair_ptr_all = _pairs_vector(pair_ptr_all, node_ptr_all, who)
+    graph_ptr = _index_vector(graph_ptr, "%s: graph_ptr" % who, torch.int32)
+    _on(dev, node_ptr_all, pair_ptr_all, graph_ptr)
+    G_all, B = node_ptr_all.numel() - 1, graph_ptr.numel() - 1
+    if torch.is_tensor(graph_ids) and graph_ids.is_cuda:
+        raise RuntimeError("%s: graph_ids must live on the host (they are checked there, without a read-back)" % who)
+    ids_h = torch.as_tensor(graph_ids, dtype=torch.int64).reshape(-1)
+    if ids_h.numel() != B:
+        raise ValueError("%s: %d graph ids for a batch of %d graphs" % (who, ids_h.numel(), B))
+    if B and (int(ids_h.min()) < 0 or int(ids_h.max()) >= G_all):
+        raise IndexError("%s: graph id out of range (the table holds %d graphs)" % (who, G_all))
+    pair_ptr = _pair_ptr(graph_ptr)
+    if num_pairs is None:
+        num_pairs = int(pair_ptr[-1])
+    num_pairs = int(num_pairs)
+    ids_d = ids_h.to(dev, non_blocking=True)
+    out = torch.empty(max(num_pairs, 0), dtype=torch.uint8, device=dev)
+    nv.call("esc_spd_gather", nv.ptr(table), nv.ptr(pair_ptr_all), nv.ptr(node_ptr_all), G_all, table.numel(), nv.ptr(ids_d), nv.ptr(graph_ptr),
+            nv.ptr(pair_ptr), B, num_pairs, nv.ptr(out), nv.stream())
     return out

@@ -24,10 +24,15 @@ ZINC values, this project's choice.
 --gt_layer_type picks the two halves of every layer as the yaml's gt.layer_type does: the local GNN is GINE (the yaml's),
 CustomGatedGCN (nn.GatedGCNLayer on the fused gate kernel, csrc/gatedgcn.hip; it also updates the edge attributes from layer to
 layer, so the ESC term of layer l is carried and re-gated) or PNA (nn.PNAConv on the fused mean | max | sum aggregate,
-csrc/pna.hip; the edge attributes pass through as with GINE), the global model Transformer or None (no attention branch).  A
-checkpoint of one layout is refused by another (load_state_dict's own error).
+csrc/pna.hip; the edge attributes pass through as with GINE), the global model Transformer, BiasedTransformer or None (no
+attention branch).  A checkpoint of one layout is refused by another (load_state_dict's own error).
 
-Out of scope: BiasedTransformer / attn_bias, Performer and BigBird, the local GNN types GCN / GIN / GENConv / GAT, PNA's other
+<local GNN>+BiasedTransformer adds Graphormer's spatial encoding to the attention as the reference's fork defines it
+(gps_layer.py:237-239,273-278): every layer's edge_attn_emb / edge_attn_linear turn the shortest-path distance of a pair into a
+per-head bias on its score.  One spd.SPDTable per split - the all-pairs distances of every graph, one launch each
+(csrc/spd.hip) - and one more gather launch per batch; the attention reads the bytes in place.  Same state_dict as Transformer.
+
+Out of scope: Performer and BigBird, Graphormer's own encoders, log_attn_weights, edge-feature biases, the local GNN types GCN / GIN / GENConv / GAT, PNA's other
 aggregators, degree scalers (pna_degrees) and towers, the EquivStableLapPE gate of GINE and GatedGCN, layer_norm, the other positional
 encodings (SignNet, EquivStableLapPE, HKdiagSE, ElstaticSE), graphgym's config system and wandb, a whole-step engine, and data
 parallelism (WORLD_SIZE > 1 is refused).
@@ -64,7 +69,8 @@ _FLAGS = [  # defaults: GraphGPS/configs/GPS/zinc-GPS.yaml (gt.*, train.batch_si
     ("--eval", dict(default=0, type=int)),
     ("--synthetic_graphs", dict(type=int, default=12000, help="train+val+test molecules (10:1:1 like ZINC-12k)")),
     ("--gt_layer_type", dict(default="GINE+Transformer", help="gt.layer_type, <local GNN>+<global model>: " + ", ".join(
-        ("GINE+Transformer", "CustomGatedGCN+Transformer", "GINE+None", "CustomGatedGCN+None", "PNA+Transformer", "PNA+None")))),
+        ("GINE+Transformer", "CustomGatedGCN+Transformer", "GINE+None", "CustomGatedGCN+None", "PNA+Transformer", "PNA+None",
+         "GINE+BiasedTransformer", "CustomGatedGCN+BiasedTransformer", "PNA+BiasedTransformer")))),
     ("--posenc_LapPE", dict(type=int, default=0, help="1: node encoder TypeDictNode+LapPE (the reference yaml), 0: TypeDictNode")),
     ("--posenc_LapPE_max_freqs", dict(type=int, default=8, help="posenc_LapPE.eigen.max_freqs")),
     ("--posenc_LapPE_dim_pe", dict(type=int, default=8, help="posenc_LapPE.dim_pe (model DeepSet, layers 2)")),
@@ -81,6 +87,7 @@ _FLAGS = [  # defaults: GraphGPS/configs/GPS/zinc-GPS.yaml (gt.*, train.batch_si
 
 
 LAYER_TYPES = ("GINE+Transformer", "CustomGatedGCN+Transformer", "GINE+None", "CustomGatedGCN+None", "PNA+Transformer", "PNA+None")
+BIASED_LAYER_TYPES = ("GINE+BiasedTransformer", "CustomGatedGCN+BiasedTransformer", "PNA+BiasedTransformer")    # + the shortest-path bias
 
 
 def build_parser():
@@ -89,8 +96,8 @@ def build_parser():
 
 def layer_type_of(name):
     """gt.layer_type -> (local_gnn_type, global_model_type), split at '+' as graphgps/network/gps_model.py:72-76 does"""
-    if name not in LAYER_TYPES:
-        raise SystemExit("run_zinc_gps: --gt_layer_type %r is not supported; accepted: %s" % (name, ", ".join(LAYER_TYPES)))
+    if name not in LAYER_TYPES + BIASED_LAYER_TYPES:
+        raise SystemExit("run_zinc_gps: --gt_layer_type %r is not supported; accepted: %s" % (name, ", ".join(LAYER_TYPES + BIASED_LAYER_TYPES)))
     local_gnn_type, global_model_type = name.split("+")
     return local_gnn_type, global_model_type
 
@@ -141,16 +148,25 @@ def main(argv=None):
         if not 1 <= args.posenc_RWSE_ksteps <= 63:
             raise SystemExit("run_zinc_gps: --posenc_RWSE_ksteps %d outside 1..63" % args.posenc_RWSE_ksteps)
 
+    def spd_limits():
+        head_dim = args.dim_hidden // args.n_heads
+        node_limit, attn_limit = ops.graph_spd_limits()[0], ops.attention_bias_max_nodes(head_dim)
+        if max(widest) > min(node_limit, attn_limit):
+            raise SystemExit("run_zinc_gps: the largest graph has %d nodes, the shortest-path kernel takes at most %d nodes per graph and "
+                             "the biased attention kernels at most %d at head_dim %d" % (max(widest), node_limit, attn_limit, head_dim))
+
     from .lappe import LapPETable
     from .rwse import RWSETable
-    for name, on, cls, what, check in (("LapPE", args.posenc_LapPE, LapPETable, args.posenc_LapPE_max_freqs, lap_pe_limits),
-                                       ("RWSE", args.posenc_RWSE, RWSETable, list(range(1, args.posenc_RWSE_ksteps + 1)), rwse_limits)):
+    from .spd import SPDTable
+    for name, on, cls, what, check in (("LapPE", args.posenc_LapPE, LapPETable, (args.posenc_LapPE_max_freqs,), lap_pe_limits),
+                                       ("RWSE", args.posenc_RWSE, RWSETable, (list(range(1, args.posenc_RWSE_ksteps + 1)),), rwse_limits),
+                                       ("SPD", global_model_type == "BiasedTransformer", SPDTable, (), spd_limits)):
         if not on:
             continue
         check()
         t12 = time.time()
         for t, s in zip(tables, stores):
-            t.append(cls(s, what))
+            t.append(cls(s, *what))
         torch.cuda.synchronize()
         ctx.say("{} table build time cost: {}s,".format(name, time.time() - t12))
 
