@@ -124,6 +124,14 @@ except OSError as exc:
     raise NativeLibraryError("esc_gnn_amd: cannot read the C header %s the binding is derived from (%s)" % (SPD_HEADER, exc)) from exc
 SPD_SIGNATURES = {name: args for name, (args, _) in _SPD.functions.items()}
 _RET.update({name: ret for name, (_, ret) in _SPD.functions.items()})
+# the eleventh extension header (escgnn_layernorm.h: the per-graph LayerNorm of the GPS layer, forward and backward)
+LAYERNORM_HEADER = os.path.join(os.path.dirname(_abi.HEADER), "escgnn_layernorm.h")
+try:
+    _LN = _abi.load(LAYERNORM_HEADER)
+except OSError as exc:
+    raise NativeLibraryError("esc_gnn_amd: cannot read the C header %s the binding is derived from (%s)" % (LAYERNORM_HEADER, exc)) from exc
+LAYERNORM_SIGNATURES = {name: args for name, (args, _) in _LN.functions.items()}
+_RET.update({name: ret for name, (_, ret) in _LN.functions.items()})
 KIND = {name[len("ESC_K_"):].lower(): v for name, v in _ABI.enum.items() if name != "ESC_K_COUNT"}
 
 CollateArgs = struct("esc_collate_args")
@@ -147,7 +155,7 @@ def lib():
             "esc_gnn_amd: %s not found. The HIP hot path has no fallback — build it with "
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C esc-gnn_amd/csrc`." % LIB_PATH)
     h = ctypes.CDLL(LIB_PATH)
-    for name, args in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()) + list(I2GNN_SIGNATURES.items()) + list(GINEPLUS_SIGNATURES.items()) + list(GPS_SIGNATURES.items()) + list(LAPPE_SIGNATURES.items()) + list(RWSE_SIGNATURES.items()) + list(STEP_SIGNATURES.items()) + list(GATEDGCN_SIGNATURES.items()) + list(PNA_SIGNATURES.items()) + list(SPD_SIGNATURES.items()):
+    for name, args in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()) + list(I2GNN_SIGNATURES.items()) + list(GINEPLUS_SIGNATURES.items()) + list(GPS_SIGNATURES.items()) + list(LAPPE_SIGNATURES.items()) + list(RWSE_SIGNATURES.items()) + list(STEP_SIGNATURES.items()) + list(GATEDGCN_SIGNATURES.items()) + list(PNA_SIGNATURES.items()) + list(SPD_SIGNATURES.items()) + list(LAYERNORM_SIGNATURES.items()):
         try:
             fn = getattr(h, name)
         except AttributeError as exc:

@@ -36,9 +36,16 @@ local_gnn_type='PNA' swaps it for nn.PNAConv (PyG's PNAConv as gps_layer.py:78-9
 identity scaler, one tower, one pre- and one post-layer, edge_dim = min(128, dim_h)): treated as GINE is - dropout_local, the
 residual, norm1_local - and like GINE it leaves the edge attributes alone.
 
+layer_norm / batch_norm are the yaml's gt.layer_norm / gt.batch_norm (gps_layer.py:139-165): with layer_norm the three norms of
+a layer are nn.GraphLayerNorm - PyG's norm.LayerNorm in graph mode, one mean and one variance over all nodes and channels of
+each graph, state_dict keys weight and bias alone - and the residual add in front of each rides in the norm's launch
+(csrc/layernorm.hip); with neither, the layer has no norm modules and applies none; both is the reference's ValueError.  The
+BatchNorms inside GatedGCN and z_embedding stay what they are.  Unlike BatchNorm, a graph gets the same output alone and inside
+any batch, in training and in evaluation.
+
 Out of scope: Performer and BigBird, Graphormer's own encoders, log_attn_weights, edge-feature biases, the local GNN types GCN / GIN / GENConv / GAT, PNA's other
 aggregators (min, std), degree scalers, towers and deeper pre- / post-layers, the
-EquivStableLapPE gate of GINE and GatedGCN, a fused BatchNorm on GatedGCN's edge rows, layer_norm, the other positional
+EquivStableLapPE gate of GINE and GatedGCN, a fused BatchNorm on GatedGCN's edge rows, the other positional
 encodings (SignNet, EquivStableLapPE, HKdiagSE, ElstaticSE) and LapPE's Transformer model, graphgym's config system and wandb,
 a whole-step engine, data parallelism."""
 import torch
@@ -46,7 +53,7 @@ from torch.nn import Dropout, ModuleList, Sequential
 
 from . import nested
 from .nested import Z_TABLE_ROWS
-from .nn import BatchNorm1d, Embedding, GatedGCNLayer, GINEConv, GraphMultiheadAttention, LapPENodeEncoder, Linear, PNAConv, ReLU, RWSENodeEncoder, global_add_pool
+from .nn import BatchNorm1d, Embedding, GatedGCNLayer, GINEConv, GraphLayerNorm, GraphMultiheadAttention, LapPENodeEncoder, Linear, PNAConv, ReLU, RWSENodeEncoder, global_add_pool
 from .plan import graph_ptr_of, plan_of
 
 
@@ -56,10 +63,17 @@ class GPSLayer(torch.nn.Module):
     'CustomGatedGCN' (gps_layer.py:94-99: nn.GatedGCNLayer with its own dropout and
     residual, whose edge output becomes the layer's edge attributes, :197-208); global_model_type 'Transformer',
     'BiasedTransformer' (the same attention with the shortest-path bias of edge_attn_emb / edge_attn_linear on its scores,
-    :237-239,273-278) or 'None' (self_attn None: the attention branch is skipped; norm1_attn exists all the same, :150-152)."""
+    :237-239,273-278) or 'None' (self_attn None: the attention branch is skipped; norm1_attn exists all the same, :150-152).
+    layer_norm / batch_norm (:139-165): norm1_local, norm1_attn and norm2 are nn.GraphLayerNorm (each takes the residual add in
+    front of it into its launch), BatchNorm1d, or - with neither - absent; both raises as the reference does."""
 
-    def __init__(self, dim_h, num_heads, dropout=0.0, attn_dropout=0.0, local_gnn_type="GINE", global_model_type="Transformer"):
+    def __init__(self, dim_h, num_heads, dropout=0.0, attn_dropout=0.0, local_gnn_type="GINE", global_model_type="Transformer",
+                 layer_norm=False, batch_norm=True):
         super().__init__()
+        if layer_norm and batch_norm:
+            raise ValueError("Cannot apply two types of normalization together")
+        self.layer_norm, self.batch_norm = bool(layer_norm), bool(batch_norm)
+        norm = (lambda: GraphLayerNorm(dim_h)) if layer_norm else (lambda: BatchNorm1d(dim_h)) if batch_norm else None
         self.dim_h, self.num_heads = dim_h, num_heads
         if local_gnn_type == "GINE":
             self.local_model = GINEConv(Sequential(Linear(dim_h, dim_h), ReLU(), Linear(dim_h, dim_h)))  # constant eps = 0, no edge Linear
@@ -85,14 +99,16 @@ class GPSLayer(torch.nn.Module):
         else:
             raise ValueError(f"Unsupported global x-former model: {global_model_type}")
         self.global_model_type = global_model_type
-        self.norm1_local = BatchNorm1d(dim_h)
-        self.norm1_attn = BatchNorm1d(dim_h)
+        if norm is not None:
+            self.norm1_local = norm()
+            self.norm1_attn = norm()
         self.dropout_local = Dropout(dropout)
         self.dropout_attn = Dropout(dropout)
         self.ff_linear1 = Linear(dim_h, dim_h * 2)
         self.ff_linear2 = Linear(dim_h * 2, dim_h)
         self.act_fn_ff = ReLU()
-        self.norm2 = BatchNorm1d(dim_h)
+        if norm is not None:
+            self.norm2 = norm()
         self.ff_dropout1 = Dropout(dropout)
         self.ff_dropout2 = Dropout(dropout)
         self.z_initial = torch.nn.Embedding(Z_TABLE_ROWS, dim_h)
@@ -103,16 +119,25 @@ class GPSLayer(torch.nn.Module):
         index = torch.arange(101, device=self.edge_attn_emb.weight.device)
         return self.edge_attn_linear(self.edge_attn_emb(index))
 
+    def _normed(self, name, value, graph_ptr, residual=None):
+        """norm `name` of residual + value: the LayerNorm adds inside its launch, the BatchNorm behind a torch add; without norms
+        the sum alone (gps_layer.py:224-229,248-252,260-264)"""
+        if self.layer_norm:
+            return getattr(self, name)(value, graph_ptr, residual=residual)
+        if residual is not None:
+            value = residual + value
+        return getattr(self, name)(value) if self.batch_norm else value
+
     def forward(self, h, edge_attr, data, plan, graph_ptr, max_nodes):
         """(node states, edge attributes) -> the same after this layer; the edge attributes carry this layer's ESC term on"""
         if "pos_index" in data:
             edge_attr = edge_attr + self.z_embedding(nested.edge_term(self.z_initial, data, plan))
         if self.local_gnn_type == "CustomGatedGCN":          # it drops out and adds its residuals itself (gps_layer.py:206-208)
             h_local, edge_attr = self.local_model(h, edge_attr, plan)
-            h_local = self.norm1_local(h_local)
+            h_local = self._normed("norm1_local", h_local, graph_ptr)
         else:
             h_local = self.dropout_local(self.local_model(h, data.edge_index, edge_attr, plan))
-            h_local = self.norm1_local(h + h_local)
+            h_local = self._normed("norm1_local", h_local, graph_ptr, residual=h)
         if self.self_attn is not None:
             if self.global_model_type == "BiasedTransformer":
                 spd = data["attn_bias"] if "attn_bias" in data else None
@@ -123,12 +148,11 @@ class GPSLayer(torch.nn.Module):
             else:
                 h_attn = self.self_attn(h, graph_ptr, max_nodes)
             h_attn = self.dropout_attn(h_attn)
-            h = h_local + self.norm1_attn(h + h_attn)
+            h = h_local + self._normed("norm1_attn", h_attn, graph_ptr, residual=h)
         else:
             h = h_local
         ff = self.ff_dropout1(self.act_fn_ff(self.ff_linear1(h)))
-        h = h + self.ff_dropout2(self.ff_linear2(ff))
-        return self.norm2(h), edge_attr
+        return self._normed("norm2", self.ff_dropout2(self.ff_linear2(ff)), graph_ptr, residual=h), edge_attr
 
 
 class _TypeDict(torch.nn.Module):
@@ -202,16 +226,18 @@ class GPSModel(torch.nn.Module):
     (lappe.add_lap_pe, lappe.LapPETable.attach).  rwse=True: the node encoder gains nn.RWSENodeEncoder(rwse_dim_pe, rwse_steps,
     rwse_model, rwse_layers, rwse_raw_norm) as its last part and the batch must carry pestat_RWSE [N, rwse_steps]
     (rwse.add_rwse, rwse.RWSETable.attach); the rwse_* defaults are upstream GraphGPS's usual ZINC values - the reference ships
-    no configuration that enables RWSE."""
+    no configuration that enables RWSE.  layer_norm / batch_norm: gt.layer_norm / gt.batch_norm, handed to every GPSLayer."""
 
     def __init__(self, layers=10, dim_hidden=64, n_heads=4, dropout=0.0, attn_dropout=0.5, node_types=28, edge_types=4, dim_out=1,
                  lap_pe=False, dim_pe=8, max_freqs=8, rwse=False, rwse_dim_pe=28, rwse_steps=20, rwse_model="linear", rwse_layers=1,
-                 rwse_raw_norm="batchnorm", local_gnn_type="GINE", global_model_type="Transformer"):
+                 rwse_raw_norm="batchnorm", local_gnn_type="GINE", global_model_type="Transformer", layer_norm=False, batch_norm=True):
         super().__init__()
+        if layer_norm and batch_norm:
+            raise ValueError("Cannot apply two types of normalization together")
         self.lap_pe, self.rwse = bool(lap_pe), bool(rwse)
         rw = dict(dim_pe=rwse_dim_pe, num_steps=rwse_steps, model=rwse_model, layers=rwse_layers, raw_norm=rwse_raw_norm) if self.rwse else None
         self.encoder = FeatureEncoder(dim_hidden, node_types, edge_types, self.lap_pe, dim_pe, max_freqs, rw)
-        self.layers = Sequential(*[GPSLayer(dim_hidden, n_heads, dropout, attn_dropout, local_gnn_type, global_model_type)
+        self.layers = Sequential(*[GPSLayer(dim_hidden, n_heads, dropout, attn_dropout, local_gnn_type, global_model_type, layer_norm, batch_norm)
                                    for _ in range(layers)])
         self.has_attention = global_model_type != "None"
         self.post_mp = SANGraphHead(dim_hidden, dim_out)

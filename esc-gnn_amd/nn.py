@@ -266,6 +266,36 @@ class GraphMultiheadAttention(torch.nn.Module):
         return self.out_proj(h)
 
 
+class GraphLayerNorm(torch.nn.Module):
+    """PyG's norm.LayerNorm(in_channels) in graph mode - the reference's gt.layer_norm calls it as norm(h, batch.batch)
+    (gps_layer.py:226-227,249-250,261-262): one mean and one variance over all nodes and all channels of each graph.  The same
+    parameters, initial values and state_dict keys (weight: ones, bias: zeros; none with affine=False), computed by
+    ops.graph_layer_norm off graph_ptr: one launch forward, two backward.  forward(x, graph_ptr, residual=None) normalises
+    x + residual with the add folded into the launch.  No running statistics: train and eval are the same computation."""
+
+    def __init__(self, in_channels, eps=1e-5, affine=True):
+        super().__init__()
+        self.in_channels, self.eps = in_channels, eps
+        if affine:
+            self.weight = torch.nn.Parameter(torch.empty(in_channels))
+            self.bias = torch.nn.Parameter(torch.empty(in_channels))
+        else:
+            self.register_parameter("weight", None)
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        if self.weight is not None:
+            torch.nn.init.ones_(self.weight)
+            torch.nn.init.zeros_(self.bias)
+
+    def forward(self, x, graph_ptr, residual=None):
+        return ops.graph_layer_norm(x, graph_ptr, self.weight, self.bias, self.eps, residual)
+
+    def extra_repr(self):
+        return "%d, eps=%g, affine=%s" % (self.in_channels, self.eps, self.weight is not None)
+
+
 class LapPENodeEncoder(torch.nn.Module):
     """The reference's LapPENodeEncoder (GraphGPS/graphgps/encoder/laplace_pos_encoder.py) as zinc-GPS.yaml configures it and as
     Concat2NodeEncoder builds it (expand_x False): model DeepSet, `layers` 2, post_layers 0, raw_norm_type none.  The same

@@ -1699,3 +1699,83 @@ def spd_gather(table, pair_ptr_all, node_ptr_all, graph_ids, graph_ptr, num_pair
     nv.call("esc_spd_gather", nv.ptr(table), nv.ptr(pair_ptr_all), nv.ptr(node_ptr_all), G_all, table.numel(), nv.ptr(ids_d), nv.ptr(graph_ptr),
             nv.ptr(pair_ptr), B, num_pairs, nv.ptr(out), nv.stream())
     return out
+
+
+# ---- per-graph LayerNorm (csrc/layernorm.hip, include/escgnn_layernorm.h) ----------------------------------------------------------
+def graph_layer_norm_max_channels():
+    """the widest row esc_graph_layer_norm_fwd / _bwd take (a multiple of 4 from 4 up to this)"""
+    return int(nv.lib().esc_graph_layer_norm_max_channels())
+
+
+class _GraphLayerNorm(Function):
+    """PyG's norm.LayerNorm in graph mode (the reference's gt.layer_norm, gps_layer.py:143-145,161,226-227,249-250,261-262: one mean
+    and one variance over all nodes and channels of each graph) on x, or on x + residual with the add folded in: one launch
+    forward, two backward (one without an affine).  Saves x, the residual and stats [G, 2] = (mean, rstd); the backward
+    recomputes xhat from them.  d_x is also the residual's gradient: written once, returned for both."""
+
+    @staticmethod
+    def forward(ctx, x, residual, weight, bias, graph_ptr, eps):
+        x, ldx = _rows(x)
+        N, C = x.shape
+        G, dev = graph_ptr.numel() - 1, x.device
+        ldr = C
+        if residual is not None:
+            residual, ldr = _rows(residual, C)
+        y, stats = _empty(dev, N, C), _empty(dev, G, 2)
+        nv.call("esc_graph_layer_norm_fwd", nv.ptr(x), ldx, nv.ptr(residual), ldr, nv.ptr(graph_ptr), G, N, C, nv.ptr(weight), nv.ptr(bias),
+                float(eps), nv.ptr(y), C, nv.ptr(stats), nv.stream())
+        ctx.save_for_backward(x, residual, weight, stats)
+        ctx.graph_ptr = graph_ptr
+        ctx.mark_non_differentiable(stats)
+        ctx.set_materialize_grads(False)                       # no zero-filled gradient of stats: two launches per backward
+        return y, stats
+
+    @staticmethod
+    def backward(ctx, g, _unused):
+        if g is None:
+            return (None,) * 6
+        x, residual, weight, stats = ctx.saved_tensors
+        graph_ptr = ctx.graph_ptr
+        _dev(g)
+        x, ldx = _rows(x)
+        N, C = x.shape
+        G, dev = graph_ptr.numel() - 1, x.device
+        ldr = C
+        if residual is not None:
+            residual, ldr = _rows(residual, C)
+        g, ldg = _rows(g)
+        d_x = _empty(dev, N, C)
+        affine = weight is not None
+        d_weight, d_bias, partial = (_empty(dev, C), _empty(dev, C), _empty(dev, max(G, 1), 2, C)) if affine else (None, None, None)
+        nv.call("esc_graph_layer_norm_bwd", nv.ptr(x), ldx, nv.ptr(residual), ldr, nv.ptr(stats), nv.ptr(g), ldg, nv.ptr(graph_ptr), G, N, C,
+                nv.ptr(weight), nv.ptr(d_x), C, nv.ptr(d_weight), nv.ptr(d_bias), nv.ptr(partial), nv.stream())
+        return d_x, (d_x if residual is not None else None), d_weight, d_bias, None, None
+
+
+def graph_layer_norm(x, graph_ptr, weight, bias, eps=1e-5, residual=None, return_stats=False):
+    """y = LayerNorm over all nodes and channels of each graph (PyG norm.LayerNorm(C)(h, batch)) of h = x, or of h = x + residual
+    with the add folded into the launch (one fp32 addition per element: the same bits as adding beforehand).  x, residual: [N, C]
+    rows (a column slice of wider rows is read in place); graph_ptr: int32 [G+1] node ranges on the device; weight, bias: [C],
+    both or neither (None: no affine).  The variance is the centred second pass.  A graph's rows have the same bits alone and
+    inside any batch; an empty graph writes nothing.  Differentiable in x, residual, weight and bias.
+    return_stats: also stats [G, 2] = (mean, rstd) of every graph, what the backward reads.
+    Limits: C a multiple of 4 from 4 up to graph_layer_norm_max_channels() - ValueError before anything is launched; there is
+    no limit on the nodes of a graph."""
+    _dev(x, residual, weight, bias)
+    _on(x.device, residual, weight, bias, graph_ptr)
+    if x.dim() != 2:
+        raise ValueError("graph_layer_norm: expected a 2-D tensor, got shape %s" % (tuple(x.shape),))
+    C = x.size(1)
+    _width_limit("graph_layer_norm", C, graph_layer_norm_max_channels())
+    if residual is not None and tuple(residual.shape) != tuple(x.shape):
+        raise ValueError("graph_layer_norm: residual %s must have the shape of x %s" % (tuple(residual.shape), tuple(x.shape)))
+    if (weight is None) != (bias is None):
+        raise ValueError("graph_layer_norm: weight and bias come together (got %s)" % ("weight alone" if bias is None else "bias alone"))
+    if weight is not None and (tuple(weight.shape) != (C,) or tuple(bias.shape) != (C,)):
+        raise ValueError("graph_layer_norm: weight %s and bias %s must be [%d]" % (tuple(weight.shape), tuple(bias.shape), C))
+    if graph_ptr.dtype != torch.int32 or graph_ptr.dim() != 1 or graph_ptr.numel() < 1:
+        raise TypeError("graph_layer_norm: graph_ptr must be a 1-D int32 tensor of G+1 node offsets")
+    if weight is not None:
+        weight, bias = weight.contiguous(), bias.contiguous()
+    y, stats = _GraphLayerNorm.apply(x, residual, weight, bias, graph_ptr.contiguous(), eps)
+    return (y, stats) if return_stats else y

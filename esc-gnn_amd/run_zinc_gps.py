@@ -32,8 +32,14 @@ attention branch).  A checkpoint of one layout is refused by another (load_state
 per-head bias on its score.  One spd.SPDTable per split - the all-pairs distances of every graph, one launch each
 (csrc/spd.hip) - and one more gather launch per batch; the attention reads the bytes in place.  Same state_dict as Transformer.
 
+--gt_layer_norm 1 --gt_batch_norm 0 is the yaml's other normalisation (gt.layer_norm): the three norms of every layer become PyG's
+graph-mode LayerNorm - one mean and one variance over all nodes and channels of each graph, one launch forward and two backward
+with the residual add folded in (csrc/layernorm.hip) - the GPS recipe's choice for small batches and for inference one graph
+at a time.  Both 0 runs without the three norms; both 1 is refused, as the reference refuses it.  Either combines with every
+--gt_layer_type; a checkpoint of one normalisation is refused by another.
+
 Out of scope: Performer and BigBird, Graphormer's own encoders, log_attn_weights, edge-feature biases, the local GNN types GCN / GIN / GENConv / GAT, PNA's other
-aggregators, degree scalers (pna_degrees) and towers, the EquivStableLapPE gate of GINE and GatedGCN, layer_norm, the other positional
+aggregators, degree scalers (pna_degrees) and towers, the EquivStableLapPE gate of GINE and GatedGCN, the other positional
 encodings (SignNet, EquivStableLapPE, HKdiagSE, ElstaticSE), graphgym's config system and wandb, a whole-step engine, and data
 parallelism (WORLD_SIZE > 1 is refused).
 
@@ -71,6 +77,9 @@ _FLAGS = [  # defaults: GraphGPS/configs/GPS/zinc-GPS.yaml (gt.*, train.batch_si
     ("--gt_layer_type", dict(default="GINE+Transformer", help="gt.layer_type, <local GNN>+<global model>: " + ", ".join(
         ("GINE+Transformer", "CustomGatedGCN+Transformer", "GINE+None", "CustomGatedGCN+None", "PNA+Transformer", "PNA+None",
          "GINE+BiasedTransformer", "CustomGatedGCN+BiasedTransformer", "PNA+BiasedTransformer")))),
+    ("--gt_layer_norm", dict(type=int, default=0, choices=(0, 1), help="gt.layer_norm: 1: per-graph LayerNorm as the layers' three norms "
+                                                                       "(with --gt_batch_norm 0)")),
+    ("--gt_batch_norm", dict(type=int, default=1, choices=(0, 1), help="gt.batch_norm: 1: BatchNorm as the layers' three norms (the yaml's)")),
     ("--posenc_LapPE", dict(type=int, default=0, help="1: node encoder TypeDictNode+LapPE (the reference yaml), 0: TypeDictNode")),
     ("--posenc_LapPE_max_freqs", dict(type=int, default=8, help="posenc_LapPE.eigen.max_freqs")),
     ("--posenc_LapPE_dim_pe", dict(type=int, default=8, help="posenc_LapPE.dim_pe (model DeepSet, layers 2)")),
@@ -102,6 +111,14 @@ def layer_type_of(name):
     return local_gnn_type, global_model_type
 
 
+def norm_flags_of(args):
+    """(gt.layer_norm, gt.batch_norm); the two together are refused before anything is built (gps_layer.py:139-140)"""
+    if args.gt_layer_norm and args.gt_batch_norm:
+        raise SystemExit("run_zinc_gps: --gt_layer_norm 1 and --gt_batch_norm 1 cannot be applied together: "
+                         "pass --gt_batch_norm 0 with --gt_layer_norm 1")
+    return bool(args.gt_layer_norm), bool(args.gt_batch_norm)
+
+
 def _load_splits(args):
     from .datasets import build_feature_dataset, synthetic_zinc_graphs
     G = args.synthetic_graphs
@@ -118,6 +135,7 @@ def main(argv=None):
 
     args = build_parser().parse_args(argv)
     local_gnn_type, global_model_type = layer_type_of(args.gt_layer_type)
+    norm_flags_of(args)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("run_zinc_gps: data parallelism is out of scope for the graph transformer (WORLD_SIZE must be 1)")
     ctx = Context()
@@ -175,7 +193,8 @@ def main(argv=None):
                      lap_pe=bool(args.posenc_LapPE), dim_pe=args.posenc_LapPE_dim_pe, max_freqs=args.posenc_LapPE_max_freqs,
                      rwse=bool(args.posenc_RWSE), rwse_dim_pe=args.posenc_RWSE_dim_pe, rwse_steps=args.posenc_RWSE_ksteps,
                      rwse_model=args.posenc_RWSE_model, rwse_layers=args.posenc_RWSE_layers, rwse_raw_norm=args.posenc_RWSE_raw_norm_type,
-                     local_gnn_type=local_gnn_type, global_model_type=global_model_type)
+                     local_gnn_type=local_gnn_type, global_model_type=global_model_type, layer_norm=bool(args.gt_layer_norm),
+                     batch_norm=bool(args.gt_batch_norm))
     limit = ops.attention_max_nodes(args.dim_hidden // args.n_heads)
     if global_model_type != "None" and max(widest) > limit:
         raise SystemExit("run_zinc_gps: the largest graph has %d nodes, the attention kernels take at most %d at head_dim %d"
